@@ -15,14 +15,16 @@ float32 output.
 
 Order of work (so that the GPU is busy for seconds around the timed region and nothing long runs before it):
   warm-up (W steps, then more of the same until >= 1 s has passed: DVFS settles, the smi sampler sees the burst)
-  -> the timed K steps (barrier + synchronize on both sides, max over ranks) -> supplementary GPU records
-  -> the CPU baselines, LAST (announced on stderr; ~20 s of host work).
+  -> the timed K steps (barrier + synchronize on both sides, max over ranks) -> --dump-outputs DIR: the last step's output
+  -> the line.  That is all a plain run does.  With --full, before the line: the measured peaks of the roofline, the
+  supplementary GPU records, every gather mode side by side (N > 1), then the CPU baselines, LAST (announced on stderr;
+  ~20 s of host work).
 
 N > 1 (strong scaling, BASELINE.json configs[3]): rank r owns frequencies [r*256/N, (r+1)*256/N) of every gemm-unit; the
 only collective is the gather of the detected powers, through the C-ABI (bf_comm_create / bf_gather_detected: RCCL
 point-to-point over xGMI, include/dsabf.h).  `--gather` picks the headline mode (default alltoall = distributed owners);
-every mode -- none, root, alltoall, each in both layouts and transports -- is then timed side by side under "gather_modes",
-so a scaling run separates kernel scaling from xGMI.
+with --full every mode -- none, root, alltoall, each in both layouts and transports -- is then timed side by side under
+"gather_modes", so a scaling run separates kernel scaling from xGMI.
 
 N > 1 cannot fail softly:
   * a process-level deadline (class Deadline) is armed at the top of main(), before torch is imported, before the process
@@ -97,12 +99,21 @@ def parse():
                     help="limit of each stage that runs RCCL: communicator creation, and the warm-up / timed region / "
                          "verification of each gather mode")
     ap.add_argument("--no-verify", action="store_true", help="skip the checksum verification of the gather modes")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: the measured MFMA / HBM peaks of the roofline, the other "
+                         "kernels, detect modes, workloads and launch sizes, the streaming loop, the DM stage, the re-layout pass, "
+                         "every gather mode side by side (N > 1) and the CPU baselines.  Off: set up, warm up, time the steps, "
+                         "print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy: a fixed, seeded "
+                         "sample of its detected beam-blocks (float32, <= 32 MiB), their indices and every beam-block's sum "
+                         "(float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--budget-seconds", type=float, default=900.0,
                     help="wall-clock limit for everything AFTER the headline measurement (supplementary records, gather modes, "
                          "CPU baselines): when it expires the line is printed with what is there and the process exits 0")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the supplementary records: profiling passes see one kernel")
+                    help="with --full: skip the supplementary records (profiling passes see one kernel)")
     ap.add_argument("--min-warm-seconds", type=float, default=1.0)
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     return ap.parse_args()
@@ -955,6 +966,27 @@ def main():
             dist.all_reduce(flag, op=dist.ReduceOp.MIN)
         return bool(flag.item())
 
+    def dump_outputs(gm):
+        """--dump-outputs DIR (rank 0): what the LAST timed step handed its caller -- the step's detected beam-blocks (N > 1 with a
+        gather: the rows this rank holds after it) -- as DIR/<name>.npy: a fixed, seeded sample of whole beam-blocks (float32
+        [k][n_freq][n_beams], k such that it stays within 32 MiB), their indices in the step (float64 [k]) and the float64 sum of
+        every beam-block of the step ([rows]).  The inputs are seeded, so two builds run with the same arguments compare bit for bit."""
+        if not args.dump_outputs or rank != 0:
+            return
+        import numpy as np
+
+        slot = (args.steps - 1) & 1                  # step i wrote d_out[i & 1] (and the gather's full[i & 1])
+        flat, rows = (gm.full[slot], gm.held * world) if gm.held else (d_out[slot], n_rows)
+        x = flat.view(rows, row_floats)
+        k = max(1, min(rows, (32 << 20) // (4 * row_floats)))
+        pick = np.sort(np.random.default_rng(0xD5A).choice(rows, size=k, replace=False))
+        sample = x.index_select(0, torch.from_numpy(pick).to(x.device)).cpu().numpy().reshape(k, n_freq, cfg.n_beams)
+        sums = torch.cat([x[r0:r0 + 64].double().sum(dim=1) for r0 in range(0, rows, 64)]).cpu().numpy()
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "detected_sample.npy"), np.ascontiguousarray(sample, dtype=np.float32))
+        np.save(os.path.join(args.dump_outputs, "detected_sample_index.npy"), pick.astype(np.float64))
+        np.save(os.path.join(args.dump_outputs, "detected_block_sums.npy"), sums.astype(np.float64))
+
     info = bf.kernel_info(units)
     paired = "PAIRED" in info["kernel"]
     # the key a committed counter pass must carry to be quoted beside this run's timings: the device code the LIBRARY says it holds
@@ -993,6 +1025,9 @@ def main():
             try:
                 if "mfma" in peak_cache:
                     raise StopIteration
+                if not args.full:
+                    peak_cache["mfma"] = (None, "not measured: bench.py --full runs the micro-benchmark")
+                    raise StopIteration
                 d_sink = torch.empty(4 << 20, dtype=torch.uint8, device="cuda")
                 peak_ops = [0.0]
 
@@ -1023,6 +1058,9 @@ def main():
             # bf_expand_device (a1 alone: 1 byte in, 2 out per packed byte, whole 128-byte lines, nontemporal both ways)
             try:
                 if "hbm" in peak_cache:
+                    raise StopIteration
+                if not args.full:
+                    peak_cache["hbm"] = (None, "not measured: bench.py --full runs the micro-benchmark")
                     raise StopIteration
                 n_exp = 256 << 20      # 256 MiB in, 512 MiB out: well past the 256 MiB Infinity Cache
                 d_exp_in = torch.randint(0, 256, (n_exp,), dtype=torch.uint8, device="cuda")
@@ -1119,6 +1157,8 @@ def main():
     extra_warm = warm_up(none_mode, args.warmup, args.min_warm_seconds)
     deadline.stage("kernel-only timed region", stage_s)
     elapsed, events = timed_region(none_mode, args.steps, True)
+    if dist is None or args.gather == "none":
+        dump_outputs(none_mode)           # the kernel-only region IS the headline
     deadline.stage("record of the kernel-only region", stage_s)
     out = build_record(elapsed, events, extra_warm)
     deadline.adopt(out, "error")          # rank 0: the record the one line is printed from (None on the other ranks)
@@ -1198,6 +1238,7 @@ def main():
         tag = "gather '%s'" % headline_mode.key
         gather_stage(tag + ": warm-up", lambda: warm_up(headline_mode, args.warmup, 0.0))
         elapsed, events = gather_stage(tag + ": timed region", lambda: timed_region(headline_mode, args.steps, True))
+        dump_outputs(headline_mode)       # before verify(): its extra step overwrites slot 0
         verified = None if args.no_verify else gather_stage(tag + ": verification", lambda: verify(headline_mode))
         deadline.stage("record of the headline", stage_s)
         out = build_record(elapsed, events, extra_warm)
@@ -1220,7 +1261,8 @@ def main():
     deadline.stage("supplementary records")
 
     # ---- every gather mode side by side (N > 1) ----------------------------------------------------------------------------
-    if dist is not None and comm_box["comm"] is not None and not args.no_extras:
+    extras = args.full and not args.no_extras      # a plain run stops at the headline (and its outputs, --dump-outputs)
+    if dist is not None and comm_box["comm"] is not None and extras:
         n_side = max(5, min(args.steps, 50))
         for mode, layout, transport in (("root", "rank", "inplace"), ("root", "freq", "inplace"), ("root", "freq", "staged"),
                                         ("alltoall", "rank", "inplace"), ("alltoall", "freq", "inplace"),
@@ -1582,7 +1624,7 @@ def main():
                                               "written once, whole 128-byte lines, nontemporal; per step and receiver at N = 8; %d launches "
                                               "between each pair of HIP events" % REP}
 
-        if world == 1 and args.detect == "canonical" and args.workload in ("c3", "prod") and not args.no_extras:
+        if world == 1 and args.detect == "canonical" and args.workload in ("c3", "prod") and extras:
             guarded("general_kernel", extras_variants)
             guarded("gather_relayout", extras_relayout)
         def north_star_summary():
@@ -1605,14 +1647,14 @@ def main():
                                        "note": "algorithmic int8 ops / kernel time / 5.0 POP/s, this run, this box (boxes differ by ~2.5 %); "
                                                "canonical = the bit-exact reading of the CPU oracle (g++), contracted = nvcc's -fmad reading"}
 
-        if world == 1 and args.detect == "canonical" and args.workload in ("c3", "prod") and not args.no_extras:
+        if world == 1 and args.detect == "canonical" and args.workload in ("c3", "prod") and extras:
             guarded("north_star_check", north_star_summary)
-        if world == 1 and args.workload == "c3" and not args.no_extras:
+        if world == 1 and args.workload == "c3" and extras:
             guarded("debug_geometry", extras_geometries)
             guarded("streaming", extras_streaming)
             guarded("dedisperse_dm", extras_dm)
             guarded("dm_stage", extras_dm_stage)
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             # N = 1: the full set.  N > 1: the same key, the beamform port alone on a shorter sample (the other ranks have
             # finished; the whole-band beam-block is the unit at every N, so the number is comparable across the lines)
             secs = args.cpu_seconds if world == 1 else min(args.cpu_seconds, 5.0)

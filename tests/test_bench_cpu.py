@@ -23,6 +23,16 @@ def test_defaults_are_the_contract(monkeypatch):
     assert pos.shape == (100, 3) and dirs.shape == (512, 2)
 
 
+def test_a_plain_run_is_lean_unless_full_is_given(monkeypatch):
+    """Without --full the run stops at the headline (no supplementary records, no CPU baselines); --dump-outputs is opt-in."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 3)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out_dir"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "out_dir"
+
+
 def test_committed_pmc_summaries_give_the_quoted_traffic_and_mfma_busy():
     """roofline.traffic / mfma_busy_frac come from profiles/r06_*_pmc_summary.txt: the files must parse, and the derived
     numbers must be what DESIGN.md section 4 quotes (traffic within 1 % of the algorithmic bytes for C3 and C2)."""

@@ -168,7 +168,7 @@ def test_bench_with_two_ranks_on_one_gpu(fake_rccl, gather, n, wl):
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr",
                         "127.0.0.1", "--master-port", port, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "3",
                         "--warmup", "1", "--units", "2" if wl == "c5" else "4" if n == 2 else "8", "--workload", wl, "--gather", gather,
-                        "--dist-backend", "gloo", "--min-warm-seconds", "0.1", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env=env)
+                        "--dist-backend", "gloo", "--min-warm-seconds", "0.1", "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, (r.stdout + r.stderr)[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1                                   # rank 0 only
@@ -208,7 +208,7 @@ def test_bench_launches_its_own_ranks_when_called_plainly(fake_rccl):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
     env.update(DSABF_RCCL_LIB=fake_rccl, DSABF_BENCH_ONE_GPU="1", FAKERCCL_MAILBOX_MB="64")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--units", "4",
-                        "--dist-backend", "gloo", "--min-warm-seconds", "0.1", "--cpu-seconds", "1"],
+                        "--dist-backend", "gloo", "--min-warm-seconds", "0.1", "--cpu-seconds", "1", "--full"],
                        capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, (r.stdout + r.stderr)[-4000:]
     assert "without a launcher: starting -m torch.distributed.run" in r.stderr

@@ -987,7 +987,7 @@ def test_bench_rccl_gather_plumbing_on_one_gpu(mode, layout):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(29600 + (os.getpid() % 300)))
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--force-dist", "--gather", mode, "--layout", layout,
                         "--units", "4", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--min-warm-seconds", "0.1"] +
-                       ([] if LONG else ["--no-extras"]),      # (the side-by-side modes: the multi-rank tests and the LONG run)
+                       (["--full"] if LONG else ["--no-extras"]),      # (the side-by-side modes: the multi-rank tests and the LONG run)
                        capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
@@ -1012,7 +1012,7 @@ def test_bench_watchdog_prints_the_headline_when_the_supplementary_records_overr
 
     from conftest import ROOT
 
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "2", "--min-warm-seconds", "0.2",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "6", "--warmup", "2", "--min-warm-seconds", "0.2",
                         "--budget-seconds", "0.05"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -138,6 +138,48 @@ def test_plain_bench_prints_its_one_line(torch):
         assert roof["traffic"] is None and roof["mfma_busy_frac"] is None and roof["pmc_source"] is None and roof["from_committed_profile"] == []
 
 
+def test_plain_bench_dumps_the_last_timed_steps_output_bit_exact(torch, orc, tmp_path):
+    """bench.py --dump-outputs DIR: the LAST timed step's detected beam-blocks -- a seeded sample, their indices, every block's sum --
+    as .npy files; the sample is the oracle's beamform of that step's input (regenerated from the bench's seed), bit for bit.  A plain
+    run (no --full) carries the headline only: no supplementary record, no CPU baseline, no peak micro-benchmark."""
+    import json
+    import subprocess
+    import sys
+
+    import bench
+    import dsabeamformer_amd as bfm
+    from conftest import ROOT
+
+    units, steps = 4, 3
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", "1", "--units", str(units),
+                        "--min-warm-seconds", "0.2", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == steps and d["ms_per_step"] > 0 and d["value"] > 0 and d["higher_is_better"] is True
+    assert not {"cpu_baseline", "general_kernel", "debug_geometry", "streaming", "dm_stage", "launch_size", "gather_relayout"} & set(d)
+    assert d["roofline"]["peak_measured"] is None
+    sample = np.load(tmp_path / "detected_sample.npy")
+    rows = np.load(tmp_path / "detected_sample_index.npy")
+    sums = np.load(tmp_path / "detected_block_sums.npy")
+    n_rows = units * 16
+    assert sample.dtype == np.float32 and rows.dtype == np.float64 and sums.dtype == np.float64
+    assert sample.shape == (n_rows, 256, 256) and sums.shape == (n_rows,)       # 64 blocks of 256 KiB: all of them fit the sample
+    rows = rows.astype(np.int64)
+    assert np.array_equal(np.sort(rows), np.arange(n_rows))
+    assert np.allclose(sums[rows], sample.astype(np.float64).sum(axis=(1, 2)), rtol=1e-12, atol=0)
+    # the last step's input: step i reads step buffer i % 2, the buffers drawn in turn from one generator seeded 0xD5A (rank 0)
+    g = orc.Geom(n_avg=16, n_out_per_gemm=16)
+    cfg = bfm.production_config(n_avg=16, n_out_per_gemm=16, n_freq=256)
+    gen = torch.Generator(device="cuda").manual_seed(0xD5A)
+    bufs = [torch.randint(0, 256, (units * g.bytes_per_gemm,), dtype=torch.uint8, device="cuda", generator=gen) for _ in range(2)]
+    packed = bufs[(steps - 1) % 2].cpu().numpy().reshape(units, g.n_freq, g.n_time, g.n_ant)
+    with orc.detect_contract(orc.CONTRACT_NONE):
+        want = orc.beamform(g, bench.product_weights(cfg, 0), packed).reshape(n_rows, g.n_freq, g.n_beams)
+    assert np.array_equal(sample, want[rows])
+
+
 # ---- f4 as a pipeline stage (VERDICT r04 item 2): DM-trial dedispersion of the detected STREAM ---------------------------------
 def _pulse_delays(n_dm, n_f, d_max):
     """A fine, monotone ladder: delay[dm][f] grows with the trial and falls with f (channel 0 = the highest frequency)."""

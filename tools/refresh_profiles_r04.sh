@@ -4,9 +4,9 @@
 # separate PMC passes for the conjugate-pair AND the general kernel at C3, C5 and C2, stage kernels, interleaved mode A/B).
 set -x
 R=$PWD; O=$R/gpurun_out/r04p; mkdir -p $O
-python bench.py > $O/r04_c3_bench.json 2> $O/r04_c3_bench.err
-python bench.py --workload c5 --units 16 --no-cpu-baseline > $O/r04_c5_bench.json 2> $O/r04_c5_bench.err
-python bench.py --workload c2 --no-cpu-baseline > $O/r04_c2_bench.json 2> $O/r04_c2_bench.err
+python bench.py --full > $O/r04_c3_bench.json 2> $O/r04_c3_bench.err
+python bench.py --full --workload c5 --units 16 --no-cpu-baseline > $O/r04_c5_bench.json 2> $O/r04_c5_bench.err
+python bench.py --full --workload c2 --no-cpu-baseline > $O/r04_c2_bench.json 2> $O/r04_c2_bench.err
 python tools/ab_modes.py 5 > $O/r04_ab_modes.txt 2>&1
 python tools/bench_stages.py > $O/r04_stage_kernels.json 2> /dev/null
 cd /tmp; export TMPDIR=/tmp

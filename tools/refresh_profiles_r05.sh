@@ -6,9 +6,9 @@
 # the other kernels did not change since round 4 (profiles/r04_*).
 set -x
 R=$PWD; O=$R/gpurun_out/r05p; mkdir -p $O
-python bench.py > $O/r05_c3_bench.json 2> $O/r05_c3_bench.err
-python bench.py --workload c5 --units 16 --no-cpu-baseline > $O/r05_c5_bench.json 2> $O/r05_c5_bench.err
-python bench.py --workload c2 --no-cpu-baseline > $O/r05_c2_bench.json 2> $O/r05_c2_bench.err
+python bench.py --full > $O/r05_c3_bench.json 2> $O/r05_c3_bench.err
+python bench.py --full --workload c5 --units 16 --no-cpu-baseline > $O/r05_c5_bench.json 2> $O/r05_c5_bench.err
+python bench.py --full --workload c2 --no-cpu-baseline > $O/r05_c2_bench.json 2> $O/r05_c2_bench.err
 tools/ubench_k200 > $O/r05_ubench_k200.txt 2>&1
 cd /tmp; export TMPDIR=/tmp
 for V in paired general; do
@@ -34,10 +34,10 @@ rm -rf $O/prof_c5g
 unset DSABF_PAIRED
 # the auxiliary kernels of the round: the staged transport's re-layout pass (and the DM kernels beside it), from a bench run WITH its
 # supplementary records: kernel trace + HBM traffic counters
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_aux -- python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline > $O/prof_aux.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_aux -- python3 $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline > $O/prof_aux.log 2>&1
 find $O/prof_aux -name "*kernel_stats.csv" | head -1 | xargs -I{} sh -c "grep -E 'Name|gather_relayout|dedisperse' {} > $O/r05_aux_kernel_stats.csv"
 rm -rf $O/prof_aux
-(cd $R && PMC_FILTER="gather_relayout" PMC_BENCH_ARGS="--steps 3 --warmup 1 --no-cpu-baseline" bash tools/pmc.sh r05p/pmc_aux > /dev/null 2>&1 && cp $O/pmc_aux/summary.txt $O/r05_relayout_pmc_summary.txt; rm -rf $O/pmc_aux)
+(cd $R && PMC_FILTER="gather_relayout" PMC_BENCH_ARGS="--full --steps 3 --warmup 1 --no-cpu-baseline" bash tools/pmc.sh r05p/pmc_aux > /dev/null 2>&1 && cp $O/pmc_aux/summary.txt $O/r05_relayout_pmc_summary.txt; rm -rf $O/pmc_aux)
 cd $R
 SEED=51 CASES=300 python tools/fuzz_dm_stream.py > $O/r05_fuzz_dm_stream.txt 2>&1
 (SEED=2000 CASES=1200 python tools/fuzz_calls.py; SEED=10000 CASES=300 python tools/fuzz_calls.py; FUZZ=loops SEED=3000 CASES=150 python tools/fuzz_calls.py; FUZZ=debug SEED=4000 CASES=400 python tools/fuzz_calls.py; FUZZ=dmloops SEED=6000 CASES=200 python tools/fuzz_calls.py) 2>&1 | grep -v "obs Complete\|amdgpu.ids" > $O/r05_fuzz_calls.txt

@@ -4,9 +4,9 @@
 # bench.py quotes a summary beside its timings only when the key is its own run's.
 set -x
 R=$PWD; O=$R/gpurun_out/r06p; mkdir -p $O
-python bench.py > $O/r06_c3_bench.json 2> $O/r06_c3_bench.err
-python bench.py --workload c5 --units 16 --no-cpu-baseline > $O/r06_c5_bench.json 2> $O/r06_c5_bench.err
-python bench.py --workload c2 --no-cpu-baseline > $O/r06_c2_bench.json 2> $O/r06_c2_bench.err
+python bench.py --full > $O/r06_c3_bench.json 2> $O/r06_c3_bench.err
+python bench.py --full --workload c5 --units 16 --no-cpu-baseline > $O/r06_c5_bench.json 2> $O/r06_c5_bench.err
+python bench.py --full --workload c2 --no-cpu-baseline > $O/r06_c2_bench.json 2> $O/r06_c2_bench.err
 cd /tmp; export TMPDIR=/tmp
 for V in paired general; do
   if [ $V = general ]; then export DSABF_PAIRED=0; else unset DSABF_PAIRED; fi
@@ -34,7 +34,7 @@ cd $R
 for a in "64" "64 0 8" "64 0 1 4"; do python tools/dm_stage.py $a 2>/dev/null | tail -1; done > $O/r06_dm_stage.txt
 tools/pmc_hbm.sh r06p/dm_stage_pmc "dedisperse|copy|Copy" python3 $R/tools/dm_stage.py 64 > /dev/null 2>&1; cp $O/dm_stage_pmc/summary.txt $O/r06_dm_stage_pmc_summary.txt; rm -rf $O/dm_stage_pmc
 # the N = 8 line of BASELINE configs[4] in shape (eight rank processes on ONE GPU over the loopback stand-in: the numbers mean nothing)
-DSABF_BENCH_ONE_GPU=1 DSABF_RCCL_LIB=$R/tests/support/libfakerccl.so FAKERCCL_MAILBOX_MB=8 python bench.py --gpus 8 --workload c5 --units 16 --steps 3 --warmup 1 \
+DSABF_BENCH_ONE_GPU=1 DSABF_RCCL_LIB=$R/tests/support/libfakerccl.so FAKERCCL_MAILBOX_MB=8 python bench.py --full --gpus 8 --workload c5 --units 16 --steps 3 --warmup 1 \
   --dist-backend gloo --min-warm-seconds 0.1 --cpu-seconds 2 > $O/r06_bench_c5_n8_loopback.json 2> $O/r06_bench_c5_n8_loopback.err
 # parity at large: the census' own report, the fuzzers on the final build
 cp gpurun_out/census_gpu.txt $O/r06_census_gpu.txt 2>/dev/null
