@@ -81,6 +81,8 @@ def kernel_build_id() -> str:
     h = hashlib.sha256(_stamp().encode())
     for p in sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.hpp")) + glob.glob(os.path.join(CSRC, "*.h")) +
                     glob.glob(os.path.join(CSRC, "*.inc"))):
+        if os.path.basename(p) == "bf_runtime_internal.h":   # host-only: the runtime's .cpp files share it, no .hip file includes it
+            continue
         h.update(os.path.basename(p).encode())
         h.update(open(p, "rb").read())
     return h.hexdigest()[:16]

@@ -1,0 +1,406 @@
+// bf_dm_stream.cpp -- DM-trial dedispersion (include/dsabf.h): the caller-stream calls and the stage of the observation loop
+// (bf_dm_stream_*) with its twice-mapped ring.
+#include <algorithm>
+#include <mutex>
+#include <new>
+#include <numeric>
+
+#include "bf_runtime_internal.h"
+
+// ---- DM-trial dedispersion as a stage of the observation loop (include/dsabf.h) ---------------------------
+// The detected stream arrives block by block; out[dm][t][b] needs rows t .. t + max_delay.  The stream keeps the last
+// max_delay rows of what it has seen in front of the rows of the next push (one device buffer, slid back to its start when its
+// end is reached), so every push runs the SAME kernels over [carry | new rows] that bf_dedisperse_dm_device runs over a
+// whole series -- and emits exactly the output times that became complete.  Every (trial, time, beam) sum still runs over
+// ascending f in one register from +0: the concatenated chunks are bit-identical to one call over the whole series.
+struct bf_dm_stream {
+    bf_handle* h = nullptr;
+    int n_dm = 0, n_freq = 0, max_delay = 0, max_rows = 0;
+    size_t row_floats = 0;
+    // The rows live in a RING of cap_rows rows whose physical memory is mapped TWICE, back to back, into one virtual range (HIP's
+    // virtual-memory API): row i is also row i + cap_rows, so every window of <= cap_rows consecutive rows -- the carried-over
+    // delay window in front of a push's rows -- is contiguous for the kernels wherever it starts, and nothing ever moves.  (Rounds
+    // 5's linear buffer slid the carry back to its start every few pushes: at the production block, 31 MiB read and written again
+    // every 2.5 blocks.)  ring == false: that linear buffer -- for a device without VMM support, and bf_set_switch("dm_ring", 0).
+    bool ring = false;
+    size_t cap_rows = 0;          // ring: rows of physical memory (>= max_delay + 3 max_rows); linear: 2 (max_delay + max_rows)
+    size_t wpos = 0;              // ring: physical row the next pushed row goes to (< cap_rows)
+    size_t fill = 0;              // linear: rows of d_buf in use, [fill - carry, fill) are the newest rows of the series
+    hipMemGenericAllocationHandle_t phys{};
+    size_t phys_bytes = 0;
+    bool phys_created = false, mapped0 = false, mapped1 = false;
+    uint64_t pushed = 0;          // rows the stream has been given
+    uint64_t n_push = 0;          // pushes so far
+    float* d_buf = nullptr;       // ring: the double mapping (2 x phys_bytes of address space); linear: cap_rows x [freq][beam]
+    int32_t* d_delays = nullptr;  // [n_dm][freq]
+    // Three pushes may be in flight at once (a caller that alternates queues, as run_observation does: a production block is 64
+    // tiles of the shared-window kernel, a quarter of the chip -- the tiles of consecutive blocks run side by side).  Push j works
+    // in set j % 3: its chunk [n_dm][max_rows][beam] and the wide kernel's scratch (dsabf::kDmScratchBytes).
+    //   rows_ready[j % 3]: the rows of push j -- and of every push before it -- are in the buffer (recorded on push j's queue behind
+    //                      its producer and behind rows_ready of push j - 1): what push j + 1's kernels wait for, not push j's END;
+    //   done[j % 3]:       push j and every push before it are complete, host copy included (recorded behind done of push j - 1).
+    // Push j waits for done of push j - 3 (its set's previous user); so does the producer of push j's rows, which overwrites what
+    // only pushes <= j - 3 can still be reading (cap_rows >= max_delay + 3 max_rows).  The linear buffer keeps one push at a time.
+    float* d_out[3] = {nullptr, nullptr, nullptr};
+    int* d_flags[3] = {nullptr, nullptr, nullptr};
+    bool flags_zeroed[3] = {false, false, false};
+    hipEvent_t done[3] = {nullptr, nullptr, nullptr}, rows_ready[3] = {nullptr, nullptr, nullptr};
+    bool done_recorded[3] = {false, false, false}, rows_recorded[3] = {false, false, false};
+    float* reserved = nullptr;    // bf_dm_stream_reserve: where the NEXT push's rows are being written by their producer ...
+    int reserved_rows = 0;        // ... and how many (0: no reservation outstanding)
+};
+
+// device side of a DM stage (its handle's device must be current); the object itself stays, detached from the handle
+void dsabf::rt::dm_stream_release(bf_dm_stream* s)
+{
+    for (int k = 0; k < 3; k++) {
+        if (s->done[k]) {
+            if (s->done_recorded[k]) (void)hipEventSynchronize(s->done[k]);
+            (void)hipEventDestroy(s->done[k]);
+        }
+        if (s->rows_ready[k]) (void)hipEventDestroy(s->rows_ready[k]);
+        s->done[k] = s->rows_ready[k] = nullptr;
+        s->done_recorded[k] = s->rows_recorded[k] = false;
+    }
+    if (s->ring || s->phys_created) {
+        if (s->mapped0) (void)hipMemUnmap(s->d_buf, s->phys_bytes);
+        if (s->mapped1) (void)hipMemUnmap(reinterpret_cast<char*>(s->d_buf) + s->phys_bytes, s->phys_bytes);
+        if (s->phys_created) (void)hipMemRelease(s->phys);   // (the addresses go back to nobody: ring_address_space)
+        s->mapped0 = s->mapped1 = s->phys_created = false;
+    } else {
+        (void)hipFree(s->d_buf);
+    }
+    for (int k = 0; k < 3; k++) {
+        (void)hipFree(s->d_out[k]);
+        (void)hipFree(s->d_flags[k]);
+        s->d_out[k] = nullptr;
+        s->d_flags[k] = nullptr;
+    }
+    (void)hipFree(s->d_delays);
+    s->d_buf = nullptr;
+    s->d_delays = nullptr;
+    s->h = nullptr;
+}
+
+bool dsabf::rt::dm_stream_is_ring(const bf_dm_stream* s) { return s->ring; }
+
+// Address space for the rings: taken from arenas that are reserved once per process and NEVER given back or handed out twice.
+// On this stack (ROCm 7.2, gfx950) a virtual range that is unmapped and mapped again to other physical memory keeps stale
+// translations: kernels and copies then disagree about where the rows are (tools/vmm_probe.cpp modes 0-4: wrong from the second
+// ring on, whatever is freed, synchronised or allocated in between; modes 5-6, fresh addresses every time: always right --
+// profiles/r06_vmm_probe.txt).  Addresses cost nothing (47 bits of them); a stage takes 2 x its ring's bytes.
+static void* ring_address_space(size_t bytes, size_t gran)
+{
+    static std::mutex mu;
+    static char* base = nullptr;
+    static size_t size = 0, used = 0;
+    std::lock_guard<std::mutex> lock(mu);
+    used = (used + gran - 1) / gran * gran;
+    if (!base || used + bytes > size) {
+        void* va = nullptr;
+        for (size_t want : {(size_t)256 << 30, (size_t)32 << 30, (size_t)4 << 30, bytes}) {
+            if (want < bytes) continue;
+            if (hipMemAddressReserve(&va, want, gran, nullptr, 0) == hipSuccess && va) {
+                base = static_cast<char*>(va);
+                size = want;
+                used = 0;
+                break;
+            }
+            (void)hipGetLastError();
+            va = nullptr;
+        }
+        if (!va) return nullptr;
+    }
+    void* out = base + used;
+    used += bytes;
+    return out;
+}
+
+// The ring: one physical allocation, mapped at va and at va + phys_bytes.  False (and nothing left behind): no VMM here.
+static bool dm_ring_create(bf_dm_stream* s, int device, size_t want_rows)
+{
+    int vmm = 0;
+    if (hipDeviceGetAttribute(&vmm, hipDeviceAttributeVirtualMemoryManagementSupported, device) != hipSuccess || !vmm) return false;
+    hipMemAllocationProp prop{};
+    prop.type = hipMemAllocationTypePinned;
+    prop.location.type = hipMemLocationTypeDevice;
+    prop.location.id = device;
+    size_t gran = 0;
+    if (hipMemGetAllocationGranularity(&gran, &prop, hipMemAllocationGranularityRecommended) != hipSuccess || !gran) return false;
+    const size_t row_bytes = s->row_floats * sizeof(float);
+    const size_t step = gran / std::gcd(row_bytes, gran);   // rows per granule-aligned stretch
+    const size_t rows = (want_rows + step - 1) / step * step;
+    s->phys_bytes = rows * row_bytes;
+    void* va = ring_address_space(2 * s->phys_bytes, gran);
+    bool ok = va != nullptr && hipMemCreate(&s->phys, s->phys_bytes, &prop, 0) == hipSuccess;
+    s->phys_created = ok;
+    s->d_buf = static_cast<float*>(va);
+    ok = ok && (s->mapped0 = hipMemMap(va, s->phys_bytes, 0, s->phys, 0) == hipSuccess);
+    ok = ok && (s->mapped1 = hipMemMap(static_cast<char*>(va) + s->phys_bytes, s->phys_bytes, 0, s->phys, 0) == hipSuccess);
+    hipMemAccessDesc acc{};
+    acc.location = prop.location;
+    acc.flags = hipMemAccessFlagsProtReadWrite;
+    ok = ok && hipMemSetAccess(va, 2 * s->phys_bytes, &acc, 1) == hipSuccess;
+    if (!ok) {
+        if (s->mapped0) (void)hipMemUnmap(va, s->phys_bytes);
+        if (s->mapped1) (void)hipMemUnmap(static_cast<char*>(va) + s->phys_bytes, s->phys_bytes);
+        if (s->phys_created) (void)hipMemRelease(s->phys);
+        s->mapped0 = s->mapped1 = s->phys_created = false;
+        s->d_buf = nullptr;
+        (void)hipGetLastError();
+        return false;
+    }
+    s->ring = true;
+    s->cap_rows = rows;
+    return true;
+}
+
+// Scratch of the DM-trial dedispersion for calls on stream `s`: kDwMaxGroups flag ints + one 512-byte row of zeros
+// (dsabf::kDmScratchBytes), zeroed ON THAT STREAM when it is first used -- ordered before the kernels that read it, also on a
+// non-blocking stream (a memset on the null stream would not be).
+static hipError_t dm_scratch(bf_handle* h, hipStream_t s, int** out)
+{
+    for (auto& sc : h->dm_scratch)
+        if (sc.first == s) {
+            *out = sc.second;
+            return hipSuccess;
+        }
+    if (h->dm_scratch.size() >= 64) {   // a caller that keeps creating streams: nothing of ours may still be in flight
+        hipError_t e = hipDeviceSynchronize();
+        if (e != hipSuccess) return e;
+        for (auto& sc : h->dm_scratch) (void)hipFree(sc.second);   // (the handle's bf_dm_streams own their scratch: untouched)
+        h->dm_scratch.clear();
+    }
+    int* p = nullptr;
+    hipError_t e = hipMalloc((void**)&p, dsabf::kDmScratchBytes);
+    if (e != hipSuccess) return e;
+    e = hipMemsetAsync(p, 0, dsabf::kDmScratchBytes, s);
+    if (e != hipSuccess) {
+        (void)hipFree(p);
+        return e;
+    }
+    h->dm_scratch.emplace_back(s, p);
+    *out = p;
+    return hipSuccess;
+}
+
+extern "C" {
+
+int bf_dedisperse_dm_device(bf_handle* h, const float* d_series, int n_t, const int32_t* d_delays, int n_dm, int n_t_out,
+                            float* d_out, void* hip_stream)
+{
+    if (!h || !d_series || !d_delays || !d_out) return fail(BF_ERR_INVALID, "NULL argument");
+    if (n_t <= 0 || n_dm < 0 || n_t_out < 0 || n_t_out > n_t) return fail(BF_ERR_INVALID, "need 0 <= n_t_out <= n_t, n_dm >= 0");
+    return bf_dedisperse_dm_band_device(h, d_series, n_t, h->geom.n_freq, d_delays, n_dm, n_t_out, d_out, hip_stream);
+}
+
+int bf_dedisperse_dm_band_device(bf_handle* h, const float* d_series, int n_t, int n_freq_total, const int32_t* d_delays,
+                                 int n_dm, int n_t_out, float* d_out, void* hip_stream)
+{
+    if (!h || !d_series || !d_delays || !d_out) return fail(BF_ERR_INVALID, "NULL argument");
+    if (n_freq_total <= 0 || n_t <= 0 || n_dm < 0 || n_t_out < 0 || n_t_out > n_t)
+        return fail(BF_ERR_INVALID, "need n_freq_total > 0, 0 <= n_t_out <= n_t, n_dm >= 0");
+    ON_DEVICE(h);
+    dsabf::Geometry g = h->geom;
+    g.n_freq = n_freq_total;
+    int* flags = nullptr;
+    HIP_TRY(dm_scratch(h, as_stream(hip_stream), &flags));
+    HIP_TRY(dsabf::launch_dedisperse_dm(g, d_series, n_t, d_delays, n_dm, n_t_out, d_out, flags, as_stream(hip_stream)));
+    return BF_OK;
+}
+
+int bf_dm_stream_create(bf_handle* h, const int32_t* delays, int n_dm, int n_freq_total, int max_rows_per_push, bf_dm_stream** out)
+{
+    if (!out) return fail(BF_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (!h || !delays) return fail(BF_ERR_INVALID, "NULL argument");
+    if (n_dm <= 0 || n_freq_total <= 0 || max_rows_per_push <= 0) return fail(BF_ERR_INVALID, "need n_dm, n_freq_total, max_rows_per_push > 0");
+    int dmax = 0;
+    for (size_t i = 0; i < (size_t)n_dm * n_freq_total; i++) {
+        if (delays[i] < 0) return fail(BF_ERR_INVALID, "a streamed dedispersion needs delays >= 0 (delay[%zu] = %d)", i, delays[i]);
+        if (delays[i] > dmax) dmax = delays[i];
+    }
+    ON_DEVICE(h);
+    bf_dm_stream* s = new (std::nothrow) bf_dm_stream();
+    if (!s) return fail(BF_ERR_DEVICE, "out of host memory");
+    s->h = h;
+    s->n_dm = n_dm;
+    s->n_freq = n_freq_total;
+    s->max_delay = dmax;
+    s->max_rows = max_rows_per_push;
+    s->row_floats = (size_t)n_freq_total * h->cfg.n_beams;
+    hipError_t e = hipSuccess;
+    // the ring: the window of a push (<= max_delay + max_rows rows) + two more pushes' rows that may be written while it is read
+    if (!h->dm_ring || !dm_ring_create(s, h->device, (size_t)dmax + 3 * (size_t)max_rows_per_push)) {
+        // linear: room for the carry and a push twice over -- when the end is reached the carry moves to the start without overlapping itself
+        s->cap_rows = 2 * ((size_t)dmax + (size_t)max_rows_per_push);
+        e = hipMalloc((void**)&s->d_buf, s->cap_rows * s->row_floats * sizeof(float));
+    }
+    const int n_sets = s->ring ? 3 : 1;   // (the linear buffer keeps one push at a time: one chunk, one scratch)
+    for (int k = 0; k < n_sets && e == hipSuccess; k++) {
+        e = hipMalloc((void**)&s->d_out[k], (size_t)n_dm * max_rows_per_push * h->cfg.n_beams * sizeof(float));
+        if (e == hipSuccess) e = hipMalloc((void**)&s->d_flags[k], dsabf::kDmScratchBytes);
+    }
+    if (e == hipSuccess) e = hipMalloc((void**)&s->d_delays, (size_t)n_dm * n_freq_total * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMemcpy(s->d_delays, delays, (size_t)n_dm * n_freq_total * sizeof(int32_t), hipMemcpyHostToDevice);
+    for (int k = 0; k < 3 && e == hipSuccess; k++) {
+        e = hipEventCreateWithFlags(&s->done[k], hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&s->rows_ready[k], hipEventDisableTiming);
+    }
+    h->dm_streams.push_back(s);
+    if (e != hipSuccess) {
+        bf_dm_stream_destroy(s);
+        return fail(BF_ERR_DEVICE, "bf_dm_stream_create: %s", hipGetErrorString(e));
+    }
+    *out = s;
+    return BF_OK;
+}
+
+int bf_dm_stream_destroy(bf_dm_stream* s)
+{
+    if (!s) return BF_OK;
+    if (s->h) {   // (NULL: the handle went first and took the device memory with it)
+        bf_handle* h = s->h;
+        DeviceScope dev_scope_(h->device);
+        h->dm_streams.erase(std::remove(h->dm_streams.begin(), h->dm_streams.end(), s), h->dm_streams.end());
+        dm_stream_release(s);
+    }
+    delete s;
+    return BF_OK;
+}
+
+int bf_dm_stream_max_delay(const bf_dm_stream* s) { return s ? s->max_delay : BF_ERR_INVALID; }
+
+int bf_dm_stream_output_device(bf_dm_stream* s, float** d_out)
+{
+    if (!s || !d_out) return fail(BF_ERR_INVALID, "NULL argument");
+    if (!s->h) return fail(BF_ERR_STATE, "the handle of this DM stage has been destroyed");
+    *d_out = s->d_out[s->ring && s->n_push ? (s->n_push - 1) % 3 : 0];   // the most recent push's chunk
+    return BF_OK;
+}
+
+// Where the next n_rows rows go, with everything the writer of those rows must wait for queued on q first.
+//   ring: behind the previous rows, wherever that is -- they overwrite rows that only pushes <= j - 3 can still be reading;
+//   linear: behind the previous push, then behind the previous rows -- unless the buffer's end is reached: then the carry slides
+//           back to the start first.
+static int dm_place_rows(bf_dm_stream* s, int n_rows, hipStream_t q, float** dst)
+{
+    const size_t D = (size_t)s->max_delay;
+    const size_t carry = s->pushed < D ? (size_t)s->pushed : D;
+    if (s->ring) {
+        const int old = (int)(s->n_push % 3);        // the slot push j will record into: last recorded by push j - 3
+        if (s->done_recorded[old]) HIP_TRY(hipStreamWaitEvent(q, s->done[old], 0));
+        *dst = s->d_buf + s->wpos * s->row_floats;   // (wpos + n_rows may pass cap_rows: the second mapping continues the first)
+        return BF_OK;
+    }
+    // linear: the writer of the new rows runs behind the previous push, always -- after a slide the new rows walk into the area the
+    // pushes before it read (and an earlier, still pending slide copies from), and only the chain of pushes orders those
+    // (tools/fuzz_dm_stream.py without synchronisation between pushes found the version that waited only when sliding)
+    const int prev = (int)((s->n_push + 2) % 3);
+    if (s->n_push && s->done_recorded[prev]) HIP_TRY(hipStreamWaitEvent(q, s->done[prev], 0));
+    if (s->fill + (size_t)n_rows > s->cap_rows) {    // slide: fill - carry >= carry here (cap = 2 (D + max_rows))
+        if (carry)
+            HIP_TRY(hipMemcpyAsync(s->d_buf, s->d_buf + (s->fill - carry) * s->row_floats, carry * s->row_floats * sizeof(float),
+                                   hipMemcpyDeviceToDevice, q));
+        s->fill = carry;                              // (the carry HAS moved: committed here, not at the push)
+    }
+    *dst = s->d_buf + s->fill * s->row_floats;
+    return BF_OK;
+}
+
+// Zero-copy feed (round 6): the place of the next n_rows rows in the stage's own buffer, directly behind the carried-over window.
+// The producer -- bf_enqueue_block_to, bf_gather_detected -- writes them there, ordered on (or behind) hip_stream; the push that
+// follows finds them in place and only launches.  The reference's collapse sits directly behind detect, no copy in between
+// (src/beamformer.cu:492-511); round 5's push copied every row device-to-device first (64 MiB read + 64 MiB written per production
+// block).
+int bf_dm_stream_reserve(bf_dm_stream* s, int n_rows, float** d_dst, void* hip_stream)
+{
+    if (!s || !d_dst) return fail(BF_ERR_INVALID, "NULL argument");
+    *d_dst = nullptr;
+    if (n_rows <= 0 || n_rows > s->max_rows) return fail(BF_ERR_INVALID, "n_rows must be 1 .. %d (max_rows_per_push)", s->max_rows);
+    if (!s->h) return fail(BF_ERR_STATE, "the handle of this DM stage has been destroyed");
+    if (s->reserved_rows) return fail(BF_ERR_STATE, "bf_dm_stream_reserve: the previous reservation has not been pushed");
+    bf_handle* h = s->h;
+    ON_DEVICE(h);
+    float* dst = nullptr;
+    if (int rc = dm_place_rows(s, n_rows, as_stream(hip_stream), &dst)) return rc;
+    s->reserved = dst;
+    s->reserved_rows = n_rows;
+    *d_dst = dst;
+    return BF_OK;
+}
+
+int bf_dm_stream_push(bf_dm_stream* s, const float* d_rows, int n_rows, float* host_out, uint64_t* first_t, int* n_t_out,
+                      void* hip_stream)
+{
+    if (!s || !d_rows) return fail(BF_ERR_INVALID, "NULL argument");
+    if (n_rows <= 0 || n_rows > s->max_rows) return fail(BF_ERR_INVALID, "n_rows must be 1 .. %d (max_rows_per_push)", s->max_rows);
+    if (!s->h) return fail(BF_ERR_STATE, "the handle of this DM stage has been destroyed");
+    const bool in_place = s->reserved_rows != 0;
+    if (in_place && (d_rows != s->reserved || n_rows != s->reserved_rows))
+        return fail(BF_ERR_STATE, "bf_dm_stream_push: %d rows are reserved at %p (bf_dm_stream_reserve); push exactly those", s->reserved_rows,
+                    (void*)s->reserved);
+    bf_handle* h = s->h;
+    ON_DEVICE(h);
+    hipStream_t q = as_stream(hip_stream);
+    const int prev = (int)((s->n_push + 2) % 3), mine = (int)(s->n_push % 3);
+    const int set = s->ring ? mine : 0;                                   // chunk + scratch this push works in
+    if (s->ring) {
+        // this set's previous user is push j - 3 (the producer of in-place rows waited for it too, on the stream it was given)
+        if (s->done_recorded[mine]) HIP_TRY(hipStreamWaitEvent(q, s->done[mine], 0));
+    } else if (s->n_push && s->done_recorded[prev]) {
+        HIP_TRY(hipStreamWaitEvent(q, s->done[prev], 0));                 // linear: behind the previous push, whatever queue that ran on
+    }
+    if (!s->flags_zeroed[set]) {
+        HIP_TRY(hipMemsetAsync(s->d_flags[set], 0, dsabf::kDmScratchBytes, q));
+        s->flags_zeroed[set] = true;
+    }
+    // (the stream's bookkeeping -- wpos / fill, pushed -- is committed at the end: a call that fails on the way leaves it as it found it)
+    const size_t D = (size_t)s->max_delay;
+    const size_t carry = s->pushed < D ? (size_t)s->pushed : D;          // the rows in front of the new ones = series rows [pushed - carry, pushed)
+    if (!in_place) {                                                      // rows that live elsewhere: brought behind the carry first
+        float* dst = nullptr;
+        if (int rc = dm_place_rows(s, n_rows, q, &dst)) return rc;
+        HIP_TRY(hipMemcpyAsync(dst, d_rows, (size_t)n_rows * s->row_floats * sizeof(float), hipMemcpyDeviceToDevice, q));
+    }
+    if (s->ring) {
+        // the kernels read [carry | new rows]: the carry was written by the producers of the pushes before this one, possibly on
+        // other queues -- wait until THEIR rows are in place (not for their dedispersion), then say that ours are
+        if (s->n_push && s->rows_recorded[prev]) HIP_TRY(hipStreamWaitEvent(q, s->rows_ready[prev], 0));
+        HIP_TRY(hipEventRecord(s->rows_ready[mine], q));
+        s->rows_recorded[mine] = true;
+    }
+    const uint64_t emitted = s->pushed > D ? s->pushed - D : 0;          // output times [0, emitted) have been produced
+    const uint64_t after = s->pushed + (uint64_t)n_rows;
+    const uint64_t complete = after > D ? after - D : 0;                   // ... and [0, complete) can be now
+    const int n_out = (int)(complete - emitted);
+    const size_t n_t = carry + (size_t)n_rows;                            // the series the kernels see: starts at output time `emitted`
+    // first row of [carry | new rows]: linear: fill - carry; ring: wpos - carry, through the second mapping when that is negative
+    const size_t start = s->ring ? (s->wpos >= carry ? s->wpos - carry : s->wpos + s->cap_rows - carry) : s->fill - carry;
+    if (n_out > 0) {
+        dsabf::Geometry g = h->geom;
+        g.n_freq = s->n_freq;
+        HIP_TRY(dsabf::launch_dedisperse_dm(g, s->d_buf + start * s->row_floats, (int)n_t, s->d_delays, s->n_dm, n_out, s->d_out[set],
+                                            s->d_flags[set], q));
+        if (host_out)
+            HIP_TRY(hipMemcpyAsync(host_out, s->d_out[set], (size_t)s->n_dm * n_out * h->cfg.n_beams * sizeof(float), hipMemcpyDeviceToHost, q));
+    }
+    // the end of push j implies the end of every push before it (chunks leave in order; a producer that waits for push j - 3 knows
+    // that nothing older reads the rows it overwrites)
+    if (s->ring && s->n_push && s->done_recorded[prev]) HIP_TRY(hipStreamWaitEvent(q, s->done[prev], 0));
+    HIP_TRY(hipEventRecord(s->done[mine], q));
+    s->done_recorded[mine] = true;
+    if (s->ring)
+        s->wpos = (s->wpos + (size_t)n_rows) % s->cap_rows;
+    else
+        s->fill += (size_t)n_rows;
+    s->pushed = after;
+    s->n_push++;
+    s->reserved = nullptr;
+    s->reserved_rows = 0;
+    if (first_t) *first_t = emitted;
+    if (n_t_out) *n_t_out = n_out;
+    return BF_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,114 @@
+// bf_runtime_internal.h -- what the C-ABI runtime's translation units share (bf_runtime.cpp, bf_queues.cpp, bf_dm_stream.cpp,
+// bf_bench_abi.cpp): the handle, the error string, the device scope.  Host-only and not installed: no .hip / .hpp file includes it.
+#pragma once
+#include "../../include/dsabf.h"
+
+#include <hip/hip_runtime.h>
+
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "bf_kernels.h"
+
+struct bf_event {
+    hipEvent_t ev = nullptr;
+    bool recorded = false;
+};
+
+struct bf_handle {
+    bf_config cfg{};
+    dsabf::Geometry geom{};
+    int device = 0;
+    int n_cus = 256;
+    bool weights_set = false;
+    void* d_wimage = nullptr;     // MFMA fragment image of the weights
+    void* d_wimage_p = nullptr;   // conjugate-pair image (geometries with a paired kernel)
+    int* d_flag = nullptr;        // relayout flags: [0] weight out of range, [1] weights are not conjugate-paired
+    uint8_t* d_data = nullptr;    // ring: n_blocks_on_gpu x bytes_per_block
+    float* d_out = nullptr;       // n_streams x floats_per_detect
+    float* d_ded = nullptr;       // n_streams x n_beams
+    // Scratch of the DM-trial dedispersion, ONE PER STREAM the caller has used (kDmScratchBytes each: which trial groups the
+    // wide kernel takes + a 512-byte row of zeros).  The wide kernel writes the flags and the per-thread-window kernel reads
+    // them later on the same stream: calls on one stream are ordered by the stream, calls on different streams must not share.
+    std::vector<std::pair<hipStream_t, int*>> dm_scratch;
+    bool force_general = false;   // bf_set_switch("paired", 0): never select the conjugate-pair kernel
+    bool dm_ring = true;          // bf_set_switch("dm_ring", 0): the next bf_dm_stream_create takes the linear buffer (test switch)
+    // bf_enqueue_gemm_unit coalesces (see flush_units): the caller keeps the reference's one-unit-per-call loop
+    // (src/beamformer.cu:454-519), the device sees one launch per run of consecutive gemm-units.
+    struct pending_unit {
+        int stream_idx, slot, time_slice;
+        float* host_out;      // a4: D2H destination of the unit's detected powers (NULL: none)
+        float* ded_row;       // a8: D2H destination of its DM-0 row (bf_enqueue_dedisperse after the unit), NULL: none
+        bool ded;
+    };
+    std::vector<pending_unit> pending;
+    bool coalesce = true;         // DSABF_COALESCE=0 / bf_set_switch("coalesce", 0): one launch per call, the literal pattern
+    uint64_t flush_seq = 0;       // flushes alternate between the first two compute queues
+    hipEvent_t flush_done = nullptr;   // end of the previous flush's host copies: the next flush's copies queue behind it
+    bool flush_recorded = false;
+    uint64_t n_fused_launches = 0;        // fused-kernel launches this handle has issued (bf_get_counter)
+    std::vector<const float*> last_out;   // per caller-visible queue: where its most recent gemm-unit's powers are on the device ...
+    std::vector<int> last_q;              // ... and the queue that wrote them
+    // Per compute queue, device memory allocated at first use (bf_queues.cpp, ensure_buf); sized n_streams at bf_create.
+    struct queue_bufs {
+        float* out_blk = nullptr;     // n_gemms_per_block x floats_per_detect: bf_enqueue_block
+        float* ded_blk = nullptr;     // n_gemms_per_block x n_beams: bf_enqueue_block_dedisperse
+        float* full_blk = nullptr;    // the gathered block (world x as large): bf_block_gather_device
+        float* stage_blk = nullptr;   // the staged transport's landing area: bf_block_gather_stage_device
+        bool blk_ran = false;         // bf_enqueue_block has launched into out_blk
+    };
+    std::vector<queue_bufs> qbuf;
+    int full_world = 0;
+    std::vector<struct bf_dm_stream*> dm_streams;   // DM stages created on this handle: bf_destroy releases their device memory
+    hipStream_t h2d = nullptr;
+    std::vector<hipStream_t> streams;
+    std::vector<hipEvent_t> join;  // one per compute queue: queue_waits_for
+    hipEvent_t t0 = nullptr, t1 = nullptr;
+};
+
+// (hidden: shared by the runtime's translation units, not exported from libdsabf.so)
+#pragma GCC visibility push(hidden)
+namespace dsabf::rt {
+
+extern thread_local std::string g_err;   // bf_last_error(): ONE per thread for the whole library (defined in bf_runtime.cpp)
+int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+int supported_geom(const bf_config* c, dsabf::Geometry& g);   // check_cfg + make_geom + dsabf::fused_supported
+inline hipStream_t as_stream(void* s) { return static_cast<hipStream_t>(s); }
+inline int check_weights(const bf_handle* h) { return h->weights_set ? BF_OK : fail(BF_ERR_STATE, "bf_set_weights has not been called"); }
+int flush_units(bf_handle* h);                          // bf_queues.cpp
+void dm_stream_release(struct bf_dm_stream* s);         // bf_dm_stream.cpp
+bool dm_stream_is_ring(const struct bf_dm_stream* s);
+
+// Makes `device` current for the duration of one entry point and puts the caller's device back afterwards: a library
+// call must not change the current device of a multi-device host process (torch's included).
+struct DeviceScope {
+    int prev = -1;
+    hipError_t err = hipSuccess;
+    explicit DeviceScope(int device)
+    {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        if (prev != device) err = hipSetDevice(device);
+    }
+    ~DeviceScope()
+    {
+        int cur = -1;
+        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
+    }
+};
+
+}  // namespace dsabf::rt
+#pragma GCC visibility pop
+using namespace dsabf::rt;   // (the runtime's files and the macros below name these unqualified)
+
+#define HIP_TRY(expr)                                                                                       \
+    do {                                                                                                    \
+        hipError_t e_ = (expr);                                                                             \
+        if (e_ != hipSuccess)                                                                               \
+            return fail(BF_ERR_DEVICE, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
+    } while (0)
+#define ON_DEVICE(h_)                                                                                       \
+    DeviceScope dev_scope_((h_)->device);                                                                   \
+    if (dev_scope_.err != hipSuccess)                                                                       \
+        return fail(BF_ERR_DEVICE, "hipSetDevice(%d) failed: %s", (h_)->device, hipGetErrorString(dev_scope_.err))
+#define FLUSH_UNITS(h_) do { if (int rc_ = flush_units(h_)) return rc_; } while (0)

@@ -1,5 +1,6 @@
 #!/bin/bash
-# One-off sanitizer run of the host-side C++ (the host mirror, bf_runtime.cpp, bf_comm.cpp, bf_shmring.cpp) and of the oracle
+# One-off sanitizer run of the host-side C++ (the host mirror, the C-ABI runtime bf_runtime.cpp / bf_queues.cpp /
+# bf_dm_stream.cpp / bf_bench_abi.cpp, bf_comm.cpp, bf_shmring.cpp, bf_dada.cpp) and of the oracle
 # on the CPU (GPU AddressSanitizer is not available on this pool).  Temporarily swaps the built libraries; restores them
 # however the script ends, and exits with the tests' status.
 cd "$(dirname "$0")/.."
@@ -15,7 +16,8 @@ trap restore EXIT
 C=dsabeamformer_amd/csrc
 $CXX -O1 -g -std=c++17 -fPIC -ffp-contract=off -fsanitize=address,undefined -fno-omit-frame-pointer -Iinclude \
     -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -shared -o /tmp/libhost_asan.so $C/bf_geometry.cpp $C/bf_generator.cpp \
-    $C/bf_scheduler.cpp $C/bf_sinks.cpp $C/bf_host_c.cpp $C/bf_runtime.cpp $C/bf_comm.cpp $C/bf_shmring.cpp $C/bf_dada.cpp \
+    $C/bf_scheduler.cpp $C/bf_sinks.cpp $C/bf_host_c.cpp $C/bf_runtime.cpp $C/bf_queues.cpp $C/bf_dm_stream.cpp \
+    $C/bf_bench_abi.cpp $C/bf_comm.cpp $C/bf_shmring.cpp $C/bf_dada.cpp \
     dsabeamformer_amd/build/bf_kernels.hip.o dsabeamformer_amd/build/bf_dm_wide.hip.o dsabeamformer_amd/build/bf_fusedg.hip.o dsabeamformer_amd/build/bf_fused16_*.hip.o -lpthread -lrt -ldl || exit 1
 cp /tmp/libhost_asan.so dsabeamformer_amd/libdsabf.so
 status=0
