@@ -2,18 +2,13 @@
 // a C program binds.
 #include "../../include/dsabf_host.hpp"
 
-#include <algorithm>
-#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
-#include <functional>
 #include <iostream>
 #include <memory>
 #include <sstream>
-#include <thread>
-#include <unistd.h>
 
 #include "../../include/dsabf_host.h"
 #include "bf_host_internal.h"
@@ -30,6 +25,7 @@ struct bfh_obs {
 };
 
 namespace {
+
 // event_backend over a table of C callbacks (bfh_obs_create_custom)
 struct callback_backend : event_backend {
     bfh_event_ops ops;
@@ -40,6 +36,99 @@ struct callback_backend : event_backend {
     int record_analysis(void* ev) override { return ops.record_analysis(ops.user, ev); }
     int query(void* ev) override { return ops.query(ops.user, ev); }
 };
+
+// Keeps a wrapper caller's stdout clean for the scope's life: unless `verbose`, std::cout ("obs Complete" etc.) and log() go nowhere.
+struct quiet_cout {
+    std::ostringstream nowhere;
+    std::streambuf* const keep = std::cout.rdbuf();
+    const bool verbose;
+    explicit quiet_cout(bool v = false) : verbose(v) { if (!verbose) std::cout.rdbuf(nowhere.rdbuf()); }
+    ~quiet_cout() { std::cout.rdbuf(keep); }
+    std::ostream& log() { return verbose ? static_cast<std::ostream&>(std::cout) : nowhere; }
+};
+
+// the largest delay of trials [first_trial, first_trial + n_trials) of the [trial][n_freq] table
+int max_delay(const int32_t* delays, int first_trial, int n_trials, int n_freq)
+{
+    int dmax = 0;
+    for (size_t i = (size_t)first_trial * n_freq; i < (size_t)(first_trial + n_trials) * n_freq; i++) dmax = delays[i] > dmax ? delays[i] : dmax;
+    return dmax;
+}
+
+// The detected powers to a file; no path: no sink, which is fine.  false: it did not open.
+bool open_file_sink(const bf_config& cfg, const char* path, int gpu, std::unique_ptr<file_sink>* out)
+{
+    if (!path) return true;
+    out->reset(new file_sink(cfg, path, gpu));
+    if (!(*out)->ok() || !(*out)->is_open()) out->reset();
+    return *out != nullptr;
+}
+
+// The DM chunks to a file, or with ring_targets and "ring:<name>[:<blocks>]" to another process (dm_ring_sink).  NULL: it did not open.
+std::unique_ptr<dm_chunk_sink> open_dm_sink(const bf_config& cfg, const char* target, int n_freq_total, int n_dm, int dmax, int max_rows,
+                                            int gpu, int first_trial, bool ring_targets)
+{
+    if (ring_targets && !std::strncmp(target, "ring:", 5)) {
+        std::string nm(target + 5);
+        uint64_t blocks = 4;
+        const size_t colon = nm.find(':');
+        if (colon != std::string::npos) {
+            blocks = std::strtoull(nm.c_str() + colon + 1, nullptr, 10);
+            nm.resize(colon);
+        }
+        std::unique_ptr<dm_ring_sink> r(new dm_ring_sink(cfg, n_freq_total, n_dm, dmax, max_rows, nm.c_str(), blocks, gpu, first_trial));
+        if (!r->is_open()) return nullptr;
+        return r;
+    }
+    std::unique_ptr<dm_file_sink> f(new dm_file_sink(cfg, n_freq_total, n_dm, dmax, target, gpu, first_trial));
+    if (!f->is_open()) return nullptr;
+    return f;
+}
+
+// run_observation with the default geometry and the wrappers' common options; `opt` brings what only one entry point sets.
+int run_default_geometry(const bf_config& cfg, block_source& src, observation_options opt, int gpu, int device, int verbose,
+                         detected_sink* sink, const int32_t* delays, int n_dm, dm_chunk_sink* dm_sink, observation_result* res)
+{
+    std::vector<antenna> pos((size_t)cfg.n_ant);
+    std::vector<beam_direction> dir((size_t)cfg.n_beams);
+    default_positions(cfg.n_ant, pos.data());      // the reference's default geometry, src/beamformer.cu:135-147
+    default_directions(cfg.n_beams, dir.data());
+    opt.gpu = gpu;
+    opt.device = device;
+    opt.verbose = verbose != 0;
+    opt.sink = sink;
+    opt.dm_delays = delays;
+    opt.n_dm = delays ? n_dm : 0;
+    opt.dm_sink = dm_sink;
+    quiet_cout quiet(opt.verbose);
+    return run_observation(cfg, opt, src, pos.data(), dir.data(), res, quiet.log());
+}
+
+// The same from the junk source (every shard of a sharded run reads the same bytes with its local geometry).  A source that is not
+// there ends an unsharded run; a shard reports it to run_observation (local_setup_ok) and lets that tell the others.
+int run_junk(const bf_config& cfg, uint64_t n_blocks, int ring_blocks, uint64_t seed, observation_options opt, int gpu, int device,
+             int burn_in, int verbose, detected_sink* sink, const int32_t* delays, int n_dm, dm_chunk_sink* dm_sink, observation_result* res,
+             void* ring_copy)
+{
+    junk_block_source src(cfg, n_blocks, ring_blocks, seed);
+    if (!src.ok() && !opt.comm) return BF_ERR_DEVICE;
+    if (!src.ok()) opt.local_setup_ok = false;
+    opt.burn_in = burn_in;
+    const int rc = run_default_geometry(cfg, src, opt, gpu, device, verbose, sink, delays, n_dm, dm_sink, res);
+    if (rc == BF_OK && ring_copy) std::memcpy(ring_copy, src.ring_data(), (size_t)src.get_block_size() * src.get_ring_blocks());
+    return rc;
+}
+
+// the result fields a caller asked for
+void copy_result(const observation_result& res, float* observation_ms, uint64_t* dm_times = nullptr, float* beam_out = nullptr,
+                 long long* last_gemm = nullptr)
+{
+    if (observation_ms) *observation_ms = res.observation_time_ms;
+    if (dm_times) *dm_times = res.dm_times;
+    if (beam_out) std::memcpy(beam_out, res.beam_out.data(), res.beam_out.size() * sizeof(float));
+    if (last_gemm) std::memcpy(last_gemm, res.last_gemm.data(), res.last_gemm.size() * sizeof(long long));
+}
+
 }  // namespace
 
 static std::vector<antenna> to_antennas(const float* pos, int n)
@@ -232,12 +321,8 @@ int bfh_obs_check_ready_for_dh2_transfer(bfh_obs* o, int ts) { return o ? o->o->
 int bfh_obs_check_observations_complete(bfh_obs* o)
 {
     if (!o) return BF_ERR_INVALID;
-    std::streambuf* keep = std::cout.rdbuf();
-    std::ostringstream sink;  // the reference prints "obs Complete"; keep wrapper callers' stdout clean
-    std::cout.rdbuf(sink.rdbuf());
-    const bool r = o->o->check_observations_complete();
-    std::cout.rdbuf(keep);
-    return r;
+    quiet_cout quiet;  // the reference prints "obs Complete"
+    return o->o->check_observations_complete();
 }
 int bfh_obs_check_transfers_complete(bfh_obs* o) { return o ? o->o->check_transfers_complete() : BF_ERR_INVALID; }
 int bfh_obs_set_transfers_complete(bfh_obs* o, int v) { return o ? (o->o->set_transfers_complete(v != 0), BF_OK) : BF_ERR_INVALID; }
@@ -289,60 +374,28 @@ int bfh_run_debug_observation2(const bf_config* cfg, int gpu, const char* positi
     return BF_OK;
 }
 
-static int run_junk(const bf_config* cfg, uint64_t n_blocks, int ring_blocks, uint64_t seed, int gpu, int device,
-                    int burn_in, int verbose, detected_sink* sink, observation_result* res, void* ring_copy,
-                    const int32_t* dm_delays = nullptr, int n_dm = 0, dm_chunk_sink* dm_sink = nullptr)
-{
-    junk_block_source src(*cfg, n_blocks, ring_blocks, seed);
-    if (!src.ok()) return BF_ERR_DEVICE;
-    std::vector<antenna> pos((size_t)cfg->n_ant);
-    std::vector<beam_direction> dir((size_t)cfg->n_beams);
-    default_positions(cfg->n_ant, pos.data());
-    default_directions(cfg->n_beams, dir.data());
-    observation_options opt;
-    opt.gpu = gpu;
-    opt.device = device;
-    opt.burn_in = burn_in;
-    opt.verbose = verbose != 0;
-    opt.sink = sink;
-    opt.dm_delays = dm_delays;
-    opt.n_dm = n_dm;
-    opt.dm_sink = dm_sink;
-    std::ostringstream quiet;
-    std::streambuf* keep = std::cout.rdbuf();
-    if (!verbose) std::cout.rdbuf(quiet.rdbuf());  // "obs Complete" etc.
-    int rc = run_observation(*cfg, opt, src, pos.data(), dir.data(), res, verbose ? static_cast<std::ostream&>(std::cout) : quiet);
-    std::cout.rdbuf(keep);
-    if (rc == BF_OK && ring_copy) std::memcpy(ring_copy, src.ring_data(), (size_t)src.get_block_size() * src.get_ring_blocks());
-    return rc;
-}
-
 int bfh_run_observation_junk(const bf_config* cfg, uint64_t n_blocks, int ring_blocks, uint64_t seed, int gpu, int device,
                              int burn_in, int verbose, float* observation_ms, float* beam_out, long long* last_gemm,
                              void* ring_copy)
 {
     if (!cfg) return BF_ERR_INVALID;
     observation_result res;
-    int rc = run_junk(cfg, n_blocks, ring_blocks, seed, gpu, device, burn_in, verbose, nullptr, &res, ring_copy);
-    if (rc != BF_OK) return rc;
-    if (observation_ms) *observation_ms = res.observation_time_ms;
-    if (beam_out) std::memcpy(beam_out, res.beam_out.data(), res.beam_out.size() * sizeof(float));
-    if (last_gemm) std::memcpy(last_gemm, res.last_gemm.data(), res.last_gemm.size() * sizeof(long long));
-    return BF_OK;
+    const int rc = run_junk(*cfg, n_blocks, ring_blocks, seed, observation_options(), gpu, device, burn_in, verbose, nullptr, nullptr, 0, nullptr, &res, ring_copy);
+    if (rc == BF_OK) copy_result(res, observation_ms, nullptr, beam_out, last_gemm);
+    return rc;
 }
 
 int bfh_run_observation_junk_to_file(const bf_config* cfg, uint64_t n_blocks, int ring_blocks, uint64_t seed, int gpu,
                                      int device, int burn_in, int verbose, const char* path, float* observation_ms,
                                      uint64_t* gemms_written, void* ring_copy)
 {
-    if (!cfg || !path) return BF_ERR_INVALID;
-    file_sink sink(*cfg, path, gpu);
-    if (!sink.ok() || !sink.is_open()) return BF_ERR_INVALID;
+    std::unique_ptr<file_sink> sink;
+    if (!cfg || !path || !open_file_sink(*cfg, path, gpu, &sink)) return BF_ERR_INVALID;
     observation_result res;
-    int rc = run_junk(cfg, n_blocks, ring_blocks, seed, gpu, device, burn_in, verbose, &sink, &res, ring_copy);
+    const int rc = run_junk(*cfg, n_blocks, ring_blocks, seed, observation_options(), gpu, device, burn_in, verbose, sink.get(), nullptr, 0, nullptr, &res, ring_copy);
     if (rc != BF_OK) return rc;
-    if (observation_ms) *observation_ms = res.observation_time_ms;
-    if (gemms_written) *gemms_written = sink.get_delivered();
+    copy_result(res, observation_ms);
+    if (gemms_written) *gemms_written = sink->get_delivered();
     return BF_OK;
 }
 
@@ -351,111 +404,56 @@ int bfh_run_observation_junk_dm(const bf_config* cfg, uint64_t n_blocks, int rin
                                 const char* detected_path, float* observation_ms, uint64_t* dm_times, void* ring_copy)
 {
     if (!cfg || !delays || n_dm <= 0) return BF_ERR_INVALID;
-    int dmax = 0;
-    for (size_t i = 0; i < (size_t)n_dm * cfg->n_freq; i++) dmax = delays[i] > dmax ? delays[i] : dmax;
     std::unique_ptr<dm_chunk_sink> dms;
-    if (dm_path && !std::strncmp(dm_path, "ring:", 5)) {   // "ring:<name>[:<blocks>]": the chunks to another process (dm_ring_sink)
-        std::string nm(dm_path + 5);
-        uint64_t blocks = 4;
-        const size_t colon = nm.find(':');
-        if (colon != std::string::npos) {
-            blocks = std::strtoull(nm.c_str() + colon + 1, nullptr, 10);
-            nm.resize(colon);
-        }
-        dm_ring_sink* rs = new dm_ring_sink(*cfg, cfg->n_freq, n_dm, dmax, cfg->n_gemms_per_block * cfg->n_out_per_gemm, nm.c_str(), blocks, gpu);
-        dms.reset(rs);
-        if (!rs->is_open()) return BF_ERR_INVALID;
-    } else if (dm_path) {
-        dm_file_sink* fs2 = new dm_file_sink(*cfg, cfg->n_freq, n_dm, dmax, dm_path, gpu);
-        dms.reset(fs2);
-        if (!fs2->is_open()) return BF_ERR_INVALID;
+    if (dm_path) {
+        dms = open_dm_sink(*cfg, dm_path, cfg->n_freq, n_dm, max_delay(delays, 0, n_dm, cfg->n_freq), cfg->n_gemms_per_block * cfg->n_out_per_gemm,
+                           gpu, 0, /*ring_targets=*/true);
+        if (!dms) return BF_ERR_INVALID;
     }
     std::unique_ptr<file_sink> fs;
-    if (detected_path) {
-        fs.reset(new file_sink(*cfg, detected_path, gpu));
-        if (!fs->ok() || !fs->is_open()) return BF_ERR_INVALID;
-    }
+    if (!open_file_sink(*cfg, detected_path, gpu, &fs)) return BF_ERR_INVALID;
     observation_result res;
-    int rc = run_junk(cfg, n_blocks, ring_blocks, seed, gpu, device, burn_in, verbose, fs.get(), &res, ring_copy, delays, n_dm, dms.get());
-    if (rc != BF_OK) return rc;
-    if (observation_ms) *observation_ms = res.observation_time_ms;
-    if (dm_times) *dm_times = res.dm_times;
-    return BF_OK;
+    const int rc = run_junk(*cfg, n_blocks, ring_blocks, seed, observation_options(), gpu, device, burn_in, verbose, fs.get(), delays, n_dm, dms.get(), &res, ring_copy);
+    if (rc == BF_OK) copy_result(res, observation_ms, dm_times);
+    return rc;
 }
 
 // One frequency shard of a sharded observation (what `beam -R world -r rank` runs), with any geometry: communicator from the id,
-// the junk source (every shard reads the same bytes with its local geometry), the gather after every block in either transport,
-// to one root or to every rank, the DM stage on the root(s) or split by trials, file sinks where this rank holds the band.
+// the junk source, the gather after every block in either transport, to one root or to every rank, the DM stage on the root(s) or
+// split by trials, file sinks where this rank holds the band.
 int bfh_run_observation_junk_sharded(const bf_config* cfg, uint64_t n_blocks, int ring_blocks, uint64_t seed, int gpu, int device, int rank,
                                      int world, const void* id128, int gather_root, int staged, const int32_t* delays, int n_dm,
                                      int split_trials, const char* detected_path, const char* dm_path, float* observation_ms,
                                      uint64_t* dm_times, void* ring_copy)
 {
     if (!cfg || world < 1 || rank < 0 || rank >= world) return BF_ERR_INVALID;
-    bf_comm* comm = nullptr;
-    int rc = bf_comm_create(rank, world, id128, device, &comm);
+    observation_options opt;
+    int rc = bf_comm_create(rank, world, id128, device, &opt.comm);
     if (rc != BF_OK) return rc;
-    struct comm_guard {
-        bf_comm* c;
-        ~comm_guard() { bf_comm_destroy(c); }
-    } cg{comm};
+    const std::unique_ptr<bf_comm, int (*)(bf_comm*)> comm_guard(opt.comm, bf_comm_destroy);
+    opt.world = world;
+    opt.rank = rank;
+    opt.gather_root = gather_root;
+    opt.gather_staged = staged != 0;
+    opt.dm_split_trials = split_trials != 0;
     const bool holds_band = gather_root == BF_GATHER_ROOT_ALL || gather_root == rank;
     bf_config full = *cfg;
     full.n_freq = cfg->n_freq * world;
     // (a failed preparation of THIS rank does not return here: the other ranks would wait for it in the first gather.  It is
     //  reported to run_observation, which lets every shard know before anything starts -- observation_options::local_setup_ok)
-    bool setup_ok = true;
     std::unique_ptr<file_sink> fs;
-    if (detected_path && holds_band) {
-        fs.reset(new file_sink(full, detected_path, gpu));
-        if (!fs->ok() || !fs->is_open()) {
-            setup_ok = false;
-            fs.reset();
-        }
-    }
+    if (holds_band && !open_file_sink(full, detected_path, gpu, &fs)) opt.local_setup_ok = false;
     int first = 0, count = n_dm;
     if (split_trials) dm_trial_share(n_dm, world, rank, &first, &count);
-    std::unique_ptr<dm_file_sink> dms;
+    std::unique_ptr<dm_chunk_sink> dms;
     if (delays && dm_path && holds_band && count > 0) {
-        int dmax = 0;
-        for (size_t i = (size_t)first * full.n_freq; i < (size_t)(first + count) * full.n_freq; i++) dmax = delays[i] > dmax ? delays[i] : dmax;
-        dms.reset(new dm_file_sink(*cfg, full.n_freq, count, dmax, dm_path, gpu, first));
-        if (!dms->is_open()) {
-            setup_ok = false;
-            dms.reset();
-        }
+        dms = open_dm_sink(*cfg, dm_path, full.n_freq, count, max_delay(delays, first, count, full.n_freq), 0, gpu, first, /*ring_targets=*/false);
+        if (!dms) opt.local_setup_ok = false;
     }
-    junk_block_source src(*cfg, n_blocks, ring_blocks, seed);
-    if (!src.ok()) setup_ok = false;
-    std::vector<antenna> pos((size_t)cfg->n_ant);
-    std::vector<beam_direction> dir((size_t)cfg->n_beams);
-    default_positions(cfg->n_ant, pos.data());
-    default_directions(cfg->n_beams, dir.data());
-    observation_options opt;
-    opt.gpu = gpu;
-    opt.device = device;
-    opt.world = world;
-    opt.rank = rank;
-    opt.comm = comm;
-    opt.gather_root = gather_root;
-    opt.gather_staged = staged != 0;
-    opt.sink = fs.get();
-    opt.dm_delays = delays;
-    opt.n_dm = delays ? n_dm : 0;
-    opt.dm_split_trials = split_trials != 0;
-    opt.dm_sink = dms.get();
-    opt.local_setup_ok = setup_ok;
     observation_result res;
-    std::ostringstream quiet;
-    std::streambuf* keep = std::cout.rdbuf();
-    std::cout.rdbuf(quiet.rdbuf());
-    rc = run_observation(*cfg, opt, src, pos.data(), dir.data(), &res, quiet);
-    std::cout.rdbuf(keep);
-    if (rc != BF_OK) return rc;
-    if (ring_copy) std::memcpy(ring_copy, src.ring_data(), (size_t)src.get_block_size() * src.get_ring_blocks());
-    if (observation_ms) *observation_ms = res.observation_time_ms;
-    if (dm_times) *dm_times = res.dm_times;
-    return BF_OK;
+    rc = run_junk(*cfg, n_blocks, ring_blocks, seed, opt, gpu, device, 0, 0, fs.get(), delays, n_dm, dms.get(), &res, ring_copy);
+    if (rc == BF_OK) copy_result(res, observation_ms, dm_times);
+    return rc;
 }
 
 int bfh_dm_trials(double dm0, double dm_max, int nchan, double epsilon, double nu_ghz, double chan_bw_mhz, double ti_us,
@@ -564,44 +562,22 @@ int bfh_run_observation_shm_dm(const bf_config* cfg, const char* name, int core,
                                uint64_t* dm_times, int* pinned)
 {
     if (!cfg || !name) return BF_ERR_INVALID;
-    std::unique_ptr<dm_file_sink> dms;
+    std::unique_ptr<dm_chunk_sink> dms;
     if (delays && dm_path) {
-        int dmax = 0;
-        for (size_t i = 0; i < (size_t)n_dm * cfg->n_freq; i++) dmax = delays[i] > dmax ? delays[i] : dmax;
-        dms.reset(new dm_file_sink(*cfg, cfg->n_freq, n_dm, dmax, dm_path, gpu));
-        if (!dms->is_open()) return BF_ERR_INVALID;
+        dms = open_dm_sink(*cfg, dm_path, cfg->n_freq, n_dm, max_delay(delays, 0, n_dm, cfg->n_freq), 0, gpu, 0, /*ring_targets=*/false);
+        if (!dms) return BF_ERR_INVALID;
     }
     std::ostringstream quiet;
-    std::ostream& log = verbose ? static_cast<std::ostream&>(std::cout) : quiet;
-    shm_block_source src(name, core, /*pin=*/true, log);
+    shm_block_source src(name, core, /*pin=*/true, verbose ? static_cast<std::ostream&>(std::cout) : quiet);
     if (!src.ok()) return BF_ERR_STATE;
     src.expect_block_bytes(bf_bytes_per_block(cfg));
     if (pinned) *pinned = src.is_pinned() ? 1 : 0;
     std::unique_ptr<file_sink> sink;
-    if (path) {
-        sink.reset(new file_sink(*cfg, path, gpu));
-        if (!sink->ok() || !sink->is_open()) return BF_ERR_INVALID;
-    }
-    std::vector<antenna> pos((size_t)cfg->n_ant);
-    std::vector<beam_direction> dir((size_t)cfg->n_beams);
-    default_positions(cfg->n_ant, pos.data());
-    default_directions(cfg->n_beams, dir.data());
-    observation_options opt;
-    opt.gpu = gpu;
-    opt.device = device;
-    opt.verbose = verbose != 0;
-    opt.sink = sink.get();
-    opt.dm_delays = delays;
-    opt.n_dm = delays ? n_dm : 0;
-    opt.dm_sink = dms.get();
+    if (!open_file_sink(*cfg, path, gpu, &sink)) return BF_ERR_INVALID;
     observation_result res;
-    std::streambuf* keep = std::cout.rdbuf();
-    if (!verbose) std::cout.rdbuf(quiet.rdbuf());
-    int rc = run_observation(*cfg, opt, src, pos.data(), dir.data(), &res, log);
-    std::cout.rdbuf(keep);
+    const int rc = run_default_geometry(*cfg, src, observation_options(), gpu, device, verbose, sink.get(), delays, n_dm, dms.get(), &res);
     if (rc != BF_OK) return rc;
-    if (dm_times) *dm_times = res.dm_times;
-    if (observation_ms) *observation_ms = res.observation_time_ms;
+    copy_result(res, observation_ms, dm_times);
     if (gemms_written) *gemms_written = sink ? sink->get_delivered() : res.blocks * cfg->n_gemms_per_block;
     return BF_OK;
 }
@@ -614,9 +590,9 @@ int bfh_run_observation_junk_to_ring(const bf_config* cfg, uint64_t n_blocks, in
     ring_sink sink(*cfg, out_ring, out_ring_blocks, gpu);
     if (!sink.ok() || !sink.is_open()) return BF_ERR_INVALID;
     observation_result res;
-    int rc = run_junk(cfg, n_blocks, ring_blocks, seed, gpu, device, 0, 0, &sink, &res, ring_copy);
+    const int rc = run_junk(*cfg, n_blocks, ring_blocks, seed, observation_options(), gpu, device, 0, 0, &sink, nullptr, 0, nullptr, &res, ring_copy);
     if (rc != BF_OK) return rc;
-    if (observation_ms) *observation_ms = res.observation_time_ms;
+    copy_result(res, observation_ms);
     if (gemms_written) *gemms_written = sink.get_delivered();
     return BF_OK;
 }
@@ -670,28 +646,9 @@ int bfh_dm_sink_create(const bf_config* cfg, const char* target, int n_freq_tota
 {
     if (!cfg || !target || !out || n_dm <= 0 || max_rows <= 0) return BF_ERR_INVALID;
     *out = nullptr;
-    if (!std::strncmp(target, "ring:", 5)) {
-        std::string nm(target + 5);
-        uint64_t blocks = 4;
-        const size_t colon = nm.find(':');
-        if (colon != std::string::npos) {
-            blocks = std::strtoull(nm.c_str() + colon + 1, nullptr, 10);
-            nm.resize(colon);
-        }
-        dm_ring_sink* r = new dm_ring_sink(*cfg, n_freq_total, n_dm, max_delay, max_rows, nm.c_str(), blocks, 0, first_trial);
-        if (!r->is_open()) {
-            delete r;
-            return BF_ERR_INVALID;
-        }
-        *out = new bfh_dm_sink{r};
-        return BF_OK;
-    }
-    dm_file_sink* f = new dm_file_sink(*cfg, n_freq_total, n_dm, max_delay, target, 0, first_trial);
-    if (!f->is_open()) {
-        delete f;
-        return BF_ERR_INVALID;
-    }
-    *out = new bfh_dm_sink{f};
+    std::unique_ptr<dm_chunk_sink> s = open_dm_sink(*cfg, target, n_freq_total, n_dm, max_delay, max_rows, 0, first_trial, /*ring_targets=*/true);
+    if (!s) return BF_ERR_INVALID;
+    *out = new bfh_dm_sink{s.release()};
     return BF_OK;
 }
 int bfh_dm_sink_deliver(bfh_dm_sink* s, uint64_t first_t, int n_t, int n_dm, int n_beams, const float* data)

@@ -4,18 +4,11 @@
 #include "../../include/dsabf_host.hpp"
 
 #include <algorithm>
-#include <cmath>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <deque>
-#include <fstream>
 #include <functional>
 #include <iostream>
-#include <memory>
-#include <sstream>
-#include <thread>
-#include <unistd.h>
 
 #include "../../include/dsabf_host.h"
 #include "bf_host_internal.h"
@@ -81,60 +74,64 @@ observation_loop_state::~observation_loop_state()
     }
 }
 
+namespace {
+
+// generate_*_event (:71-81): records the next event of one direction; the queue counter moves only if the backend took the record.
+int record_next_event(event_backend* ev, const std::vector<void*>& sync, uint64_t& queued, int (event_backend::*record)(void*))
+{
+    void* e = sync[queued % sync.size()];
+    const int rc = e ? (ev->*record)(e) : BF_ERR_DEVICE;
+    if (rc == BF_OK) queued++;
+    return rc;
+}
+
+// check_*_events (:83-118): retires, in order, the events of [done, queued) that have fired, and stops at the first that has not.
+int retire_fired_events(event_backend* ev, std::vector<void*>& sync, uint64_t& done, uint64_t queued, const char* verbose_text)
+{
+    for (uint64_t event = done; event < queued; event++) {
+        void*& e = sync[event % sync.size()];
+        const int rc = ev->query(e);
+        if (rc < 0) return rc;   // the reference dies in gpuErrchk here; never treat an error as "not ready yet"
+        if (rc != BF_OK) break;  // :98, :116
+        done++;
+        if (verbose_text) std::cout << "Block " << event << verbose_text << std::endl;
+        ev->destroy(e);  // :95-96, :112-113 destroy and recreate
+        e = ev->create();
+        if (!e) return BF_ERR_DEVICE;
+    }
+    return BF_OK;
+}
+
+}  // namespace
+
 void observation_loop_state::generate_transfer_event()
 {
     if (error != BF_OK) return;
-    void* e = BlockTransferredSync[blocks_transfer_queue % n_events];
-    const int rc = e ? ev->record_transfer(e) : BF_ERR_DEVICE;  // :73
-    if (rc != BF_OK) return fail(rc);
-    blocks_transfer_queue++;
+    const int rc = record_next_event(ev, BlockTransferredSync, blocks_transfer_queue, &event_backend::record_transfer);  // :73
+    if (rc != BF_OK) fail(rc);
 }
 
 void observation_loop_state::generate_analysis_event()
 {
     if (error != BF_OK) return;
-    void* e = BlockAnalyzedSync[blocks_analysis_queue % n_events];
-    const int rc = e ? ev->record_analysis(e) : BF_ERR_DEVICE;  // :79
-    if (rc != BF_OK) return fail(rc);
-    blocks_analysis_queue++;
+    const int rc = record_next_event(ev, BlockAnalyzedSync, blocks_analysis_queue, &event_backend::record_analysis);  // :79
+    if (rc != BF_OK) fail(rc);
 }
 
 void observation_loop_state::check_transfer_events()
 {
     if (error != BF_OK) return;
-    for (uint64_t event = blocks_transferred; event < blocks_transfer_queue; event++) {  // :85
-        const int rc = ev->query(BlockTransferredSync[event % n_events]);
-        if (rc == BF_OK) {
-            if (verbose) std::cout << "Block " << event << " transfered to GPU" << std::endl;
-            blocks_transferred++;
-            ev->destroy(BlockTransferredSync[event % n_events]);  // :95-96 destroy and recreate
-            BlockTransferredSync[event % n_events] = ev->create();
-            if (!BlockTransferredSync[event % n_events]) return fail(BF_ERR_DEVICE);
-        } else if (rc < 0) {
-            return fail(rc);  // the reference dies in gpuErrchk here; never treat an error as "not ready yet"
-        } else {
-            break;  // :98
-        }
-    }
+    const int rc = retire_fired_events(ev, BlockTransferredSync, blocks_transferred, blocks_transfer_queue,  // :85
+                                       verbose ? " transfered to GPU" : nullptr);
+    if (rc != BF_OK) fail(rc);
 }
 
 void observation_loop_state::check_analysis_events()
 {
     if (error != BF_OK) return;
-    for (uint64_t event = blocks_analyzed; event < blocks_analysis_queue; event++) {  // :104
-        const int rc = ev->query(BlockAnalyzedSync[event % n_events]);
-        if (rc == BF_OK) {
-            blocks_analyzed++;
-            if (verbose) std::cout << "Block " << event << " Analyzed" << std::endl;
-            ev->destroy(BlockAnalyzedSync[event % n_events]);  // :112-113
-            BlockAnalyzedSync[event % n_events] = ev->create();
-            if (!BlockAnalyzedSync[event % n_events]) return fail(BF_ERR_DEVICE);
-        } else if (rc < 0) {
-            return fail(rc);
-        } else {
-            break;  // :116
-        }
-    }
+    const int rc = retire_fired_events(ev, BlockAnalyzedSync, blocks_analyzed, blocks_analysis_queue,  // :104
+                                       verbose ? " Analyzed" : nullptr);
+    if (rc != BF_OK) fail(rc);
 }
 
 uint64_t observation_loop_state::get_current_analysis_gemm(int time_slice)
@@ -161,18 +158,10 @@ bool observation_loop_state::check_ready_for_analysis() const { return (blocks_a
 
 bool observation_loop_state::check_observations_complete()
 {
-    if (debug_mode) {  // :146-151
-        if ((most_recent_gemm >= n_pt_sources - 1) && (blocks_analyzed == blocks_transfer_queue) && transfers_complete) {
-            std::cout << "obs Complete" << std::endl;
-            return true;
-        }
-        return false;
-    }
-    if ((blocks_analyzed == blocks_transfer_queue) && transfers_complete) {  // :153-157
-        std::cout << "obs Complete" << std::endl;
-        return true;
-    }
-    return false;
+    if (debug_mode && most_recent_gemm < n_pt_sources - 1) return false;               // :146-151: DEBUG also waits for the last source
+    if (blocks_analyzed != blocks_transfer_queue || !transfers_complete) return false;  // :153-157
+    std::cout << "obs Complete" << std::endl;
+    return true;
 }
 
 bool observation_loop_state::check_transfers_complete()
@@ -198,7 +187,103 @@ void dm_trial_share(int n_dm, int world, int rank, int* first, int* count)
     if (first) *first = rank * base + std::min(std::max(rank, 0), extra);
 }
 
+// ---- what the two loops share ----------------------------------------------------------------------------------------------
+namespace {
+
+// The reference dies inside gpuErrchk with this line (src/beamformer.cuh:19-29); the loops print it and return the code.
+int gpu_error(std::ostream& log, int rc)
+{
+    log << "GPUassert: " << bf_last_error() << std::endl;
+    return rc;
+}
+
+// What a run holds on the device and in pinned memory.  Released in this order: sync, the DM stream (before its handle), the pinned
+// buffers in the order they were allocated, the handle.
+struct run_resources {
+    bf_handle* h = nullptr;
+    bf_dm_stream* dm = nullptr;
+    std::vector<void*> pinned;
+    ~run_resources()
+    {
+        if (h) bf_stream_sync(h, -1);
+        bf_dm_stream_destroy(dm);
+        for (void* p : pinned) bf_free_pinned(p);
+        bf_destroy(h);
+    }
+    int alloc_pinned(size_t n_floats, float** out)
+    {
+        void* p = nullptr;
+        const int rc = bf_alloc_pinned(&p, n_floats * sizeof(float));
+        if (rc == BF_OK) pinned.push_back(p);
+        *out = static_cast<float*>(p);
+        return rc;
+    }
+};
+
+// The reference's launch pattern for one block (src/beamformer.cu:454-519): one gemm-unit per launch, round-robin over the compute
+// queues.  timeSlice[st] is the unit that stream st takes next (:319); it is back at st when the block is through.  dst(st, unit)
+// names the unit's D2H destination (nullptr, already logged: no destination, BF_ERR_STATE); after(st, unit), if any, is what
+// follows the enqueue on that stream.
+int enqueue_block_by_units(bf_handle* h, const bf_config& cfg, int gpu_block, std::vector<int>& timeSlice, std::ostream& log,
+                           const std::function<int(int st, int unit)>& after, const std::function<float*(int st, int unit)>& dst)
+{
+    const int n_streams = cfg.n_streams;
+    for (int part = 0; part < cfg.n_gemms_per_block / n_streams; part++) {
+        for (int st = 0; st < n_streams; st++) {
+            float* d = dst(st, timeSlice[st]);  // the reference's destination, :485-488
+            if (!d) return BF_ERR_STATE;
+            int rc = bf_enqueue_gemm_unit(h, st, gpu_block, timeSlice[st], d);  // :464-488
+            if (rc == BF_OK && after) rc = after(st, timeSlice[st]);
+            if (rc != BF_OK) return gpu_error(log, rc);
+            timeSlice[st] += n_streams;  // :515-519
+            if (timeSlice[st] >= cfg.n_gemms_per_block) timeSlice[st] -= cfg.n_gemms_per_block;
+        }
+    }
+    return BF_OK;
+}
+
+// The closing lines of both loops (src/beamformer.cu:540-562).  "Launch pattern" is not a line of the reference: it says which
+// caller-side loop the timing lines above it were measured with.
+void closing_report(std::ostream& log, float ms, uint64_t chunks, float ms_per_chunk, double gbytes_per_s, const char* launch_pattern)
+{
+    log << "Observation ran in " << ms << "milliseconds.\n";
+    log << "Code produced outputs for " << chunks << " data chunks.\n";
+    log << "Time per data chunk: " << ms_per_chunk << " milliseconds.\n";
+    log << "Approximate datarate: " << gbytes_per_s << "GB/s" << std::endl;
+    log << "Launch pattern: " << launch_pattern << std::endl;
+    log << "Synchronized" << std::endl;
+}
+const char* const kUnitLaunchPattern = "the reference's loop, one bf_enqueue_gemm_unit per gemm-unit (src/beamformer.cu:454-519)";
+
+// A failed record / query of the loop's events: the reference exits in gpuErrchk, never keep polling.
+int event_backend_error(std::ostream& log, const observation_loop_state& obs_state)
+{
+    log << "GPUassert: event backend failed: " << bf_last_error() << std::endl;
+    return obs_state.status();
+}
+
 // ---- the DEBUG main() flow (src/beamformer.cu:12-621 with -DDEBUG) ----------------------------------------------------
+// Block-granular analysis: one fused launch over the block's gemm-units, their detected powers to the host in ONE copy (a4: every
+// unit still travels, as src/beamformer.cu:485-488 has it), one DM-0 launch for all of them (a8).
+int debug_block_launch(bf_handle* h, const bf_config& cfg, int q, observation_loop_state& obs_state, int n_src, float* beam_out_blk,
+                       float* dedispersed_out, bool verbose, std::ostream& log)
+{
+    const int first_gemm = (int)obs_state.get_current_analysis_gemm(0);
+    if (verbose) log << "Queueing Beamforming. Start Dir = " << first_gemm << std::endl;
+    const size_t n_f_per_detect = bf_floats_per_detect(&cfg);
+    std::vector<float*> dst((size_t)cfg.n_gemms_per_block);
+    for (int u = 0; u < cfg.n_gemms_per_block; u++) dst[(size_t)u] = beam_out_blk + n_f_per_detect * (size_t)u;
+    int rc = bf_enqueue_block(h, q, (int)obs_state.get_next_gpu_analysis_block(), 0, cfg.n_gemms_per_block, dst.data());
+    const int n_valid = std::min(cfg.n_gemms_per_block, n_src - first_gemm);   // check_ready_for_dh2_transfer, :492
+    if (rc == BF_OK && n_valid > 0)
+        rc = bf_enqueue_block_dedisperse(h, q, 0, n_valid, &dedispersed_out[(size_t)first_gemm * cfg.n_beams]);
+    if (rc != BF_OK) return gpu_error(log, rc);
+    (void)obs_state.get_current_analysis_gemm(cfg.n_gemms_per_block - 1);   // most_recent_gemm = the block's last unit
+    return BF_OK;
+}
+
+}  // namespace
+
 int run_debug_observation(const bf_config& cfg, const debug_run_options& opt, debug_run_result* res,
                           std::vector<float>* dedispersed_result, std::ostream& log)
 {
@@ -213,63 +298,36 @@ int run_debug_observation(const bf_config& cfg, const debug_run_options& opt, de
     }
     std::vector<antenna> pos((size_t)cfg.n_ant);
     std::vector<beam_direction> dir((size_t)cfg.n_beams);
-    bool pos_set = false, dir_set = false;
-
     test_data_generator input_data_generator(cfg);
     if (!input_data_generator.get_data()) return BF_ERR_DEVICE;
     if (opt.sources && input_data_generator.read_in_source_directions(opt.sources) != 0) {
         log << "beam: could not read source direction file " << opt.sources << std::endl;
         return BF_ERR_INVALID;
     }
-    if (opt.positions) {
-        if (read_in_position_locations(opt.positions, cfg.n_ant, pos.data()) != 0) return BF_ERR_INVALID;
-        pos_set = true;
-    }
-    if (opt.directions) {
-        if (read_in_beam_directions(opt.directions, cfg.n_beams, dir.data()) != 0) return BF_ERR_INVALID;
-        dir_set = true;
-    }
-    if (!pos_set) default_positions(cfg.n_ant, pos.data());    // :135-140
-    if (!dir_set) default_directions(cfg.n_beams, dir.data());  // :142-147
+    if (opt.positions && read_in_position_locations(opt.positions, cfg.n_ant, pos.data()) != 0) return BF_ERR_INVALID;
+    if (opt.directions && read_in_beam_directions(opt.directions, cfg.n_beams, dir.data()) != 0) return BF_ERR_INVALID;
+    if (!opt.positions) default_positions(cfg.n_ant, pos.data());      // :135-140
+    if (!opt.directions) default_directions(cfg.n_beams, dir.data());  // :142-147
     if (opt.verbose) print_all_defines(cfg, log);
 
-    bf_handle* h = nullptr;
-    int rc = bf_create(&cfg, opt.device, &h);
-    if (rc != BF_OK) {
-        log << "GPUassert: " << bf_last_error() << std::endl;
-        return rc;
-    }
-    struct guard {
-        bf_handle* h;
-        std::vector<void*> pinned;
-        ~guard()
-        {
-            if (h) bf_stream_sync(h, -1);
-            for (void* p : pinned) bf_free_pinned(p);
-            bf_destroy(h);
-        }
-    } g{h, {}};
+    run_resources dev;
+    int rc = bf_create(&cfg, opt.device, &dev.h);
+    if (rc != BF_OK) return gpu_error(log, rc);
+    bf_handle* const h = dev.h;
 
     const int n_src = input_data_generator.get_n_pt_sources();
     const size_t n_f_per_detect = bf_floats_per_detect(&cfg);
+    const size_t n_dedispersed = (size_t)cfg.n_beams * std::max(n_src, 1);
     float *beam_out = nullptr, *dedispersed_out = nullptr;
-    void* p = nullptr;
-    if ((rc = bf_alloc_pinned(&p, n_f_per_detect * n_streams * sizeof(float))) != BF_OK) return rc;  // :249
-    g.pinned.push_back(p);
-    beam_out = static_cast<float*>(p);
-    if ((rc = bf_alloc_pinned(&p, (size_t)cfg.n_beams * std::max(n_src, 1) * sizeof(float))) != BF_OK) return rc;  // :212
-    g.pinned.push_back(p);
-    dedispersed_out = static_cast<float*>(p);
-    ::memset(dedispersed_out, 0, (size_t)cfg.n_beams * std::max(n_src, 1) * sizeof(float));
+    if ((rc = dev.alloc_pinned(n_f_per_detect * n_streams, &beam_out)) != BF_OK) return rc;  // :249
+    if ((rc = dev.alloc_pinned(n_dedispersed, &dedispersed_out)) != BF_OK) return rc;         // :212
+    ::memset(dedispersed_out, 0, n_dedispersed * sizeof(float));
 
     {  // :230-241, :251, :272
         std::vector<int8_t> fourier_coefficients((size_t)cfg.n_freq * cfg.n_ant * cfg.n_beams * 2);
         generate_fourier_coefficients(cfg.n_beams, cfg.n_ant, cfg.n_freq, 0, opt.gpu, pos.data(), dir.data(),
                                       fourier_coefficients.data());
-        if ((rc = bf_set_weights(h, fourier_coefficients.data())) != BF_OK) {
-            log << "GPUassert: " << bf_last_error() << std::endl;
-            return rc;
-        }
+        if ((rc = bf_set_weights(h, fourier_coefficients.data())) != BF_OK) return gpu_error(log, rc);
     }
 
     std::vector<int> timeSlice((size_t)n_streams);
@@ -277,10 +335,7 @@ int run_debug_observation(const bf_config& cfg, const debug_run_options& opt, de
     float* beam_out_blk[2] = {nullptr, nullptr};   // block_launch: a block's detected powers on the host, per alternating queue
     uint64_t block_launches = 0;
     for (int q = 0; q < 2 && opt.block_launch; q++) {   // (page-locking 2 x N_GEMMS_PER_BLOCK x 2 MiB is setup, like beam_out)
-        void* pb = nullptr;
-        if ((rc = bf_alloc_pinned(&pb, n_f_per_detect * (size_t)cfg.n_gemms_per_block * sizeof(float))) != BF_OK) return rc;
-        g.pinned.push_back(pb);
-        beam_out_blk[q] = static_cast<float*>(pb);
+        if ((rc = dev.alloc_pinned(n_f_per_detect * (size_t)cfg.n_gemms_per_block, &beam_out_blk[q])) != BF_OK) return rc;
         float* d_blk = nullptr;                        // and the queue's device-side block buffer (allocated at first use otherwise)
         if ((rc = bf_block_output_device(h, q % n_streams, &d_blk)) != BF_OK) return rc;
     }
@@ -301,10 +356,7 @@ int run_debug_observation(const bf_config& cfg, const debug_run_options& opt, de
     const size_t input_data_size = input_data_generator.input_data_size();
 
     while (!obs_state.check_observations_complete()) {  // :364
-        if (opt.verbose) {
-            log << "##########################################" << std::endl;
-            log << obs_state << std::endl;
-        }
+        if (opt.verbose) log << "##########################################" << std::endl << obs_state << std::endl;
         if (obs_state.check_ready_for_transfer()) {  // :378
             if (input_data_generator.check_need_to_generate_more_input_data((int)obs_state.get_blocks_transferred())) {
                 log << "Generating new source data" << std::endl;
@@ -319,84 +371,44 @@ int run_debug_observation(const bf_config& cfg, const debug_run_options& opt, de
                 rc = bf_submit_block(h, (int)obs_state.get_next_gpu_transfer_block(),
                                      &input_data[(block_bytes * obs_state.get_blocks_transfer_queue()) % input_data_size],
                                      block_bytes, nullptr);  // :425-429
-                if (rc != BF_OK) {
-                    log << "GPUassert: " << bf_last_error() << std::endl;
-                    return rc;
-                }
+                if (rc != BF_OK) return gpu_error(log, rc);
                 obs_state.generate_transfer_event();  // :431
             }
             obs_state.check_transfers_complete();  // :438
         }
         obs_state.check_transfer_events();  // :446
 
-        if (obs_state.check_ready_for_analysis() && opt.block_launch) {
-            // Block-granular analysis: one fused launch over the block's gemm-units, their detected powers to the host in
-            // ONE copy (a4: every unit still travels, as src/beamformer.cu:485-488 has it), one DM-0 launch for all of
-            // them (a8).  Two queues alternate so that block i+1's kernel overlaps block i's copy.
-            const int q = (int)(block_launches++ % 2) % n_streams;
-            const int first_gemm = (int)obs_state.get_current_analysis_gemm(0);
-            if (opt.verbose) log << "Queueing Beamforming. Start Dir = " << first_gemm << std::endl;
-            std::vector<float*> dst((size_t)cfg.n_gemms_per_block);
-            for (int u = 0; u < cfg.n_gemms_per_block; u++) dst[(size_t)u] = beam_out_blk[q] + n_f_per_detect * (size_t)u;
-            rc = bf_enqueue_block(h, q, (int)obs_state.get_next_gpu_analysis_block(), 0, cfg.n_gemms_per_block, dst.data());
-            const int n_valid = std::min(cfg.n_gemms_per_block, n_src - first_gemm);   // check_ready_for_dh2_transfer, :492
-            if (rc == BF_OK && n_valid > 0)
-                rc = bf_enqueue_block_dedisperse(h, q, 0, n_valid, &dedispersed_out[(size_t)first_gemm * cfg.n_beams]);
-            if (rc != BF_OK) {
-                log << "GPUassert: " << bf_last_error() << std::endl;
-                return rc;
+        if (obs_state.check_ready_for_analysis()) {  // :452
+            if (opt.block_launch) {
+                // Two queues alternate so that block i+1's kernel overlaps block i's copy.
+                const int q = (int)(block_launches++ % 2) % n_streams;
+                rc = debug_block_launch(h, cfg, q, obs_state, n_src, beam_out_blk[q], dedispersed_out, opt.verbose, log);
+            } else {
+                const auto dedisperse_unit = [&](int st, int unit) {
+                    if (!obs_state.check_ready_for_dh2_transfer(unit)) return (int)BF_OK;  // :492
+                    const int current_gemm = (int)obs_state.get_current_analysis_gemm(unit);
+                    if (opt.verbose) log << "Current GEMM: " << current_gemm << std::endl;
+                    return bf_enqueue_dedisperse(h, st, &dedispersed_out[(size_t)current_gemm * cfg.n_beams]);  // :498-510
+                };
+                rc = enqueue_block_by_units(h, cfg, (int)obs_state.get_next_gpu_analysis_block(), timeSlice, log, dedisperse_unit, [&](int st, int unit) {
+                    if (opt.verbose && st == 0) log << "Queueing Beamforming. Start Dir = " << obs_state.get_current_analysis_gemm(unit) << std::endl;
+                    return &beam_out[(size_t)st * n_f_per_detect];
+                });
             }
-            (void)obs_state.get_current_analysis_gemm(cfg.n_gemms_per_block - 1);   // most_recent_gemm = the block's last unit
-            obs_state.generate_analysis_event();  // :525
-        } else if (obs_state.check_ready_for_analysis()) {  // :452
-            for (int part = 0; part < cfg.n_gemms_per_block / n_streams; part++) {
-                if (opt.verbose)
-                    log << "Queueing Beamforming. Start Dir = " << obs_state.get_current_analysis_gemm(timeSlice[0])
-                        << std::endl;
-                for (int st = 0; st < n_streams; st++) {
-                    rc = bf_enqueue_gemm_unit(h, st, (int)obs_state.get_next_gpu_analysis_block(), timeSlice[st],
-                                              &beam_out[(size_t)st * n_f_per_detect]);  // :464-488
-                    if (rc != BF_OK) {
-                        log << "GPUassert: " << bf_last_error() << std::endl;
-                        return rc;
-                    }
-                    if (obs_state.check_ready_for_dh2_transfer(timeSlice[st])) {  // :492
-                        int current_gemm = (int)obs_state.get_current_analysis_gemm(timeSlice[st]);
-                        if (opt.verbose) log << "Current GEMM: " << current_gemm << std::endl;
-                        rc = bf_enqueue_dedisperse(h, st, &dedispersed_out[(size_t)current_gemm * cfg.n_beams]);  // :498-510
-                        if (rc != BF_OK) {
-                            log << "GPUassert: " << bf_last_error() << std::endl;
-                            return rc;
-                        }
-                    }
-                    timeSlice[st] += n_streams;  // :515
-                    if (timeSlice[st] >= cfg.n_gemms_per_block) timeSlice[st] -= cfg.n_gemms_per_block;
-                }
-            }
+            if (rc != BF_OK) return rc;
             obs_state.generate_analysis_event();  // :525
         }
         obs_state.check_analysis_events();  // :532
-        if (obs_state.status() != BF_OK) {  // a failed record / query: the reference exits in gpuErrchk, never keep polling
-            log << "GPUassert: event backend failed: " << bf_last_error() << std::endl;
-            return obs_state.status();
-        }
+        if (obs_state.status() != BF_OK) return event_backend_error(log, obs_state);
     }
 
     bf_timer_stop(h, &time_accumulator_ms);  // :540
     observation_time_ms += time_accumulator_ms;
     const long long chunks = (long long)n_src * cfg.n_out_per_gemm;
-    log << "Observation ran in " << observation_time_ms << "milliseconds.\n";
-    log << "Code produced outputs for " << chunks << " data chunks.\n";
-    log << "Time per data chunk: " << observation_time_ms / chunks << " milliseconds.\n";
-    log << "Approximate datarate: " << bf_bytes_per_gemm(&cfg) * (double)n_src / observation_time_ms / 1e6 << "GB/s"
-        << std::endl;
-    // (not a line of the reference: which caller-side loop the two timing lines above were measured with)
-    log << "Launch pattern: " << (opt.block_launch ? "one bf_enqueue_block per PSRDADA block"
-                                                    : "the reference's loop, one bf_enqueue_gemm_unit per gemm-unit (src/beamformer.cu:454-519)")
-        << std::endl;
-
+    const double rate = bf_bytes_per_gemm(&cfg) * (double)n_src / observation_time_ms / 1e6;
     bf_stream_sync(h, -1);  // :560-562
-    log << "Synchronized" << std::endl;
+    closing_report(log, observation_time_ms, (uint64_t)chunks, observation_time_ms / chunks, rate,
+                   opt.block_launch ? "one bf_enqueue_block per PSRDADA block" : kUnitLaunchPattern);
 
     if (opt.output && opt.output[0])
         if (write_array_to_disk_as_python_file(dedispersed_out, n_src, cfg.n_beams, opt.output) != 0)  // :568-571
@@ -411,43 +423,299 @@ int run_debug_observation(const bf_config& cfg, const debug_run_options& opt, de
 }
 
 // ---- production observation loop (src/beamformer.cu:364-534, #ifndef DEBUG branches) -------------------------------------
+namespace {
+
+// A sharded run enters its first collective -- the gather behind block 0 -- only if EVERY shard got through its setup: each rank
+// takes part in ONE exchange of "ready" flags before the loop, whichever way its setup went (a rank that bailed out alone would
+// leave the others waiting in that gather for ever: ADVICE r05).  The caller's own preparations count too (local_setup_ok).
+struct setup_gate {
+    bf_comm* comm;
+    bool done = false;
+    int fail(int rc)   // an early return of the setup: tell the other shards, once
+    {
+        if (comm && !done) {
+            done = true;
+            bool all = false;
+            (void)comm_all_ok(comm, false, &all);
+        }
+        return rc;
+    }
+    int pass(bool local_setup_ok)   // the end of the setup: BF_OK if every shard (and every caller) is ready
+    {
+        if (!comm)
+            return local_setup_ok ? BF_OK : set_error(BF_ERR_STATE, "run_observation: the caller reported a failed setup (local_setup_ok = false)");
+        done = true;
+        bool all = false;
+        const int rc = comm_all_ok(comm, local_setup_ok, &all);
+        if (rc != BF_OK || all) return rc;
+        return set_error(BF_ERR_STATE, local_setup_ok ? "run_observation: another shard of this run failed its setup; nothing was started"
+                                                      : "run_observation: this shard's caller reported a failed setup (local_setup_ok = false)");
+    }
+};
+
+// who holds the gathered band after every block: one rank, or (BF_GATHER_ROOT_ALL) every rank
+bool holds_band(const observation_options& opt) { return !opt.comm || opt.gather_root == BF_GATHER_ROOT_ALL || opt.rank == opt.gather_root; }
+
+// The option combinations run_observation refuses, before anything is read or created.
+int check_options(const bf_config& cfg, const observation_options& opt)
+{
+    const bool is_root = holds_band(opt);
+    if (cfg.n_gemms_per_block % cfg.n_streams) return BF_ERR_INVALID;
+    if (opt.world < 1 || opt.rank < 0 || opt.rank >= opt.world || opt.gather_root < BF_GATHER_ROOT_ALL || opt.gather_root >= opt.world)
+        return set_error(BF_ERR_INVALID, "run_observation: need 0 <= rank < world and gather_root a rank or BF_GATHER_ROOT_ALL");
+    if (opt.comm && (bf_comm_rank(opt.comm) != opt.rank || bf_comm_world(opt.comm) != opt.world))
+        return set_error(BF_ERR_INVALID, "run_observation: the communicator's rank / world differ from the options'");
+    if (opt.comm && !opt.block_launch) return set_error(BF_ERR_INVALID, "run_observation: the sharded gather needs block-granular launches");
+    if (opt.comm && opt.sink && !is_root) return set_error(BF_ERR_INVALID, "run_observation: only the gather root may have a sink");
+    if (opt.dm_delays && opt.n_dm <= 0) return set_error(BF_ERR_INVALID, "run_observation: dm_delays without n_dm");
+    if (opt.dm_sink && !opt.dm_delays) return set_error(BF_ERR_INVALID, "run_observation: a dm_sink needs dm_delays");
+    if (opt.comm && opt.dm_sink && !is_root) return set_error(BF_ERR_INVALID, "run_observation: only the gather root may have a dm_sink");
+    if (opt.dm_split_trials && (!opt.comm || opt.gather_root != BF_GATHER_ROOT_ALL))
+        return set_error(BF_ERR_INVALID, "run_observation: dm_split_trials needs a sharded run gathered to every rank (BF_GATHER_ROOT_ALL)");
+    return BF_OK;
+}
+
+// How the loop launches, resolved once from the options and the lab switches (DSABF_LAB=1).
+struct launch_plan {
+    bool block_launch = true;   // bf_enqueue_block launches, or the reference's per-gemm-unit pattern
+    int upl = 0;                // gemm-units per launch of the block path
+    int n_queues_used = 0;      // compute queues the block launches rotate over
+    bool staged = false;        // transport of the sharded gather
+    bool is_root = true;        // this rank holds the (gathered) band
+    int dm_first = 0, dm_count = 0;   // this rank's share of the DM ladder
+    int n_freq_band = 0;        // channels of the band the DM stage sees
+    int dm_rows = 0;            // beam-blocks per launch = rows per push
+    bool dm_run = false;        // this rank runs a DM stage
+};
+
+int resolve_plan(const bf_config& cfg, const observation_options& opt, launch_plan* plan)
+{
+    launch_plan& p = *plan;
+    const char* unit_env = lab_getenv("DSABF_UNIT_LAUNCH");   // measurement / test switch: the reference's per-gemm-unit launches
+    p.block_launch = opt.block_launch && !(unit_env && unit_env[0] == '1');
+    if (opt.comm && !p.block_launch) return set_error(BF_ERR_INVALID, "run_observation: the sharded gather needs block-granular launches");
+    p.upl = opt.units_per_launch;
+    if (const char* e = lab_getenv("DSABF_UNITS_PER_LAUNCH")) p.upl = atoi(e);
+    if (p.upl <= 0 || p.upl > cfg.n_gemms_per_block || opt.comm) p.upl = cfg.n_gemms_per_block;   // 0 / sharded: the whole block
+    while (cfg.n_gemms_per_block % p.upl) p.upl--;                                                  // whole launches only
+    // whole blocks alternate between TWO queues (block i + 1's kernel under block i's copies, as in the DEBUG flow):
+    // more queues only put more concurrent host copies beside the H2D stream (9.6 -> 9.2 us per beam-block, and
+    // 11.6 -> 9.x with other streams alive in the process: tools/stream_queues.py); sub-block launches rotate over all
+    p.n_queues_used = p.upl == cfg.n_gemms_per_block ? std::min(cfg.n_streams, 2) : cfg.n_streams;
+    p.staged = opt.gather_staged;
+    if (const char* e = lab_getenv("DSABF_GATHER_STAGED")) p.staged = e[0] == '1';
+    // ---- the DM stage (SURVEY.md 8f-4): where the reference's loop has its frequency collapse, src/beamformer.cu:492-511 ----
+    p.is_root = holds_band(opt);
+    // dm_split_trials: every rank holds the whole band (one all-gather instead of a gather) and takes ITS share of the trial ladder --
+    // the DM work scales with the GPUs, the path still has ONE collective; rank r: trials [r n / R, (r + 1) n / R), the first n % R
+    // ranks one more
+    p.dm_count = opt.n_dm;
+    if (opt.dm_split_trials) dm_trial_share(opt.n_dm, opt.world, opt.rank, &p.dm_first, &p.dm_count);
+    p.n_freq_band = cfg.n_freq * (opt.comm ? opt.world : 1);
+    p.dm_rows = p.upl * cfg.n_out_per_gemm;
+    if (opt.dm_delays && !p.block_launch) return set_error(BF_ERR_INVALID, "run_observation: the DM stage needs block-granular launches");
+    // a sharded run dedisperses the gathered band (more ranks than trials: the surplus ranks only beamform)
+    p.dm_run = opt.dm_delays && p.is_root && p.dm_count > 0;
+    return BF_OK;
+}
+
+struct dm_chunk {
+    uint64_t block, first_t;
+    int n_t;
+    float* host;
+};
+
+// One production run: its resources, its plan and what the steps of the loop hand to each other.
+struct production_run {
+    const bf_config& cfg;
+    const observation_options& opt;
+    std::ostream& log;
+    run_resources dev;
+    launch_plan plan;
+    // beam_out: the reference's pinned D2H destination (:249), [stream][beam_out_stride]; the root of a sharded run receives the whole band there
+    const size_t n_f_per_detect = bf_floats_per_detect(&cfg), beam_out_stride = n_f_per_detect * (size_t)(opt.comm ? opt.world : 1);
+    float* beam_out = nullptr;
+    std::vector<int> timeSlice = std::vector<int>((size_t)cfg.n_streams);              // :319
+    std::vector<long long> last_gemm = std::vector<long long>((size_t)cfg.n_streams, -1);   // the gemm-unit beam_out[q] ends up holding
+    std::vector<float*> unit_dst;         // the D2H destination of every unit of the block being launched
+    uint64_t launch_seq = 0, sink_committed = 0;
+    std::deque<dm_chunk> dm_pending;      // pushed, not yet delivered (their block's analysis event has not fired)
+    std::vector<float*> dm_host;          // pinned chunk buffers, used round robin
+    uint64_t dm_seq = 0, dm_times = 0, dm_chunks = 0;
+
+    int create_handle_and_weights(const antenna* pos, const beam_direction* dir)
+    {
+        int rc = bf_create(&cfg, opt.device, &dev.h);
+        if (rc != BF_OK) return gpu_error(log, rc);
+        if ((rc = dev.alloc_pinned(beam_out_stride * cfg.n_streams, &beam_out)) != BF_OK) return rc;
+        ::memset(beam_out, 0, beam_out_stride * cfg.n_streams * sizeof(float));
+        std::vector<int8_t> fourier_coefficients((size_t)cfg.n_freq * cfg.n_ant * cfg.n_beams * 2);
+        generate_fourier_coefficients(cfg.n_beams, cfg.n_ant, cfg.n_freq, opt.rank * cfg.n_freq, opt.gpu, pos, dir, fourier_coefficients.data());
+        return bf_set_weights(dev.h, fourier_coefficients.data());
+    }
+
+    int create_dm_stage_and_buffers()
+    {
+        int rc = BF_OK;
+        if (plan.dm_run) {
+            rc = bf_dm_stream_create(dev.h, opt.dm_delays + (size_t)plan.dm_first * plan.n_freq_band, plan.dm_count, plan.n_freq_band, plan.dm_rows, &dev.dm);
+            if (rc != BF_OK) return gpu_error(log, rc);
+            // chunks in flight: the launches of MAX_TOTAL_SEP blocks queued + the one being delivered
+            const size_t n_buf = (size_t)(kMaxTotalSep + 2) * (size_t)(cfg.n_gemms_per_block / plan.upl);
+            for (size_t i = 0; i < n_buf; i++) {
+                float* chunk = nullptr;
+                if ((rc = dev.alloc_pinned((size_t)plan.dm_count * plan.dm_rows * cfg.n_beams, &chunk)) != BF_OK) return rc;
+                dm_host.push_back(chunk);
+            }
+        }
+        if (plan.block_launch)   // the per-queue block buffers are allocated on first use: do that here, not inside the timed loop
+            for (int q = 0; q < plan.n_queues_used; q++) {
+                float* unused = nullptr;
+                if ((!plan.dm_run || opt.comm) && (rc = bf_block_output_device(dev.h, q, &unused)) != BF_OK) return rc;   // (a DM stage takes the rows itself)
+                if (opt.comm && plan.is_root && !plan.dm_run && (rc = bf_block_gather_device(dev.h, q, opt.world, &unused)) != BF_OK) return rc;
+                if (opt.comm && plan.staged && plan.is_root && (rc = bf_block_gather_stage_device(dev.h, q, opt.world, &unused)) != BF_OK) return rc;
+            }
+        return BF_OK;
+    }
+
+    // :378-401: the next block of the source to its slot of the device ring, or the end of the observation
+    int transfer_block(observation_loop_state& obs_state, block_source& source, size_t block_bytes)
+    {
+        char* block = source.read();             // :384
+        if (!source.check_transfers_complete()) {  // :386
+            const int rc = bf_submit_block(dev.h, (int)obs_state.get_next_gpu_transfer_block(), block, block_bytes, nullptr);  // :389-393
+            if (rc != BF_OK) return gpu_error(log, rc);
+            obs_state.generate_transfer_event();  // :396
+            if (source.close_releases_block())      // not in the reference: see block_source::close_releases_block
+                while (obs_state.status() == BF_OK && obs_state.get_blocks_transferred() < obs_state.get_blocks_transfer_queue())
+                    obs_state.check_transfer_events();
+        } else {
+            obs_state.set_transfers_complete(true);  // :398
+        }
+        source.close();  // :401
+        return BF_OK;
+    }
+
+    // unit gemm_index's powers go to its sink slot, or to `fallback`; nullptr (logged): the sink is full
+    float* unit_destination(float* fallback, uint64_t gemm_index)
+    {
+        if (!opt.sink) return fallback;
+        float* slot = opt.sink->acquire(gemm_index);
+        if (!slot) log << "ERROR: detected sink has no free slot" << std::endl;
+        return slot;
+    }
+
+    // :452-519: the launches of the block at the head of the analysis queue, in the plan's pattern
+    int analyse_block(const observation_loop_state& obs_state)
+    {
+        const int n_units = cfg.n_gemms_per_block;
+        const long long block_index = (long long)obs_state.get_blocks_analysis_queue();
+        const int gpu_block = (int)obs_state.get_next_gpu_analysis_block();
+        if (!plan.block_launch)   // the reference's launch pattern; beam_out[st] is the reference's destination, :485-488
+            return enqueue_block_by_units(dev.h, cfg, gpu_block, timeSlice, log, nullptr, [&](int st, int unit) {
+                last_gemm[st] = block_index * n_units + unit;
+                return unit_destination(&beam_out[(size_t)st * n_f_per_detect], (uint64_t)last_gemm[st]);
+            });
+        unit_dst.assign((size_t)n_units, nullptr);
+        for (int first = 0; first < n_units; first += plan.upl)
+            if (const int rc = launch_units(block_index, gpu_block, first)) return rc;
+        return BF_OK;
+    }
+
+    // One block launch over the gemm-units [first, first + upl) of the block, with everything that follows it on its queue.
+    int launch_units(long long block_index, int gpu_block, int first)
+    {
+        const int n_units = cfg.n_gemms_per_block, upl = plan.upl;
+        const int q = (int)(launch_seq++ % (uint64_t)plan.n_queues_used);   // (why these queues: resolve_plan)
+        // unit u's powers go to its sink slot, or to beam_out[queue of its launch] (later units on that queue
+        // overwrite earlier ones, in order: beam_out[q] ends up holding gemm-unit last_gemm[q])
+        for (int u = first; u < first + upl; u++) {
+            unit_dst[u] = unit_destination(&beam_out[(size_t)q * beam_out_stride], (uint64_t)block_index * n_units + u);
+            if (!unit_dst[u]) return BF_ERR_STATE;
+            last_gemm[q] = block_index * n_units + u;
+        }
+        // The DM stage owns the place its rows belong in -- directly behind its carried-over delay window: the beamformer
+        // (one GPU) or the gather (a holder of a sharded run) writes them THERE, and the push below only launches.  The
+        // reference's collapse reads what detect wrote, no copy in between (src/beamformer.cu:481,492-511).
+        float* d_rows = nullptr;     // where this launch's beam-blocks are on the device, [row][freq (over the band)][beam]
+        void* dm_qs = nullptr;
+        int rc = BF_OK;
+        if (plan.dm_run && (rc = bf_queue_stream(dev.h, q, &dm_qs)) == BF_OK) rc = bf_dm_stream_reserve(dev.dm, plan.dm_rows, &d_rows, dm_qs);
+        if (rc == BF_OK)
+            rc = (plan.dm_run && !opt.comm) ? bf_enqueue_block_to(dev.h, q, gpu_block, first, upl, d_rows, &unit_dst[first])
+                                            : bf_enqueue_block(dev.h, q, gpu_block, first, upl, opt.comm ? nullptr : &unit_dst[first]);
+        if (rc == BF_OK && opt.comm) rc = gather_block(q, d_rows);
+        if (rc == BF_OK && plan.dm_run) rc = push_dm_rows(block_index, d_rows, dm_qs);
+        return rc == BF_OK ? BF_OK : gpu_error(log, rc);
+    }
+
+    // sharded (upl == n_units): bring the shards' powers together on the root, in [unit][o][f over the band][b], behind the launch on
+    // the same queue; only the root copies to the host
+    int gather_block(int q, float* d_rows)
+    {
+        const int n_units = cfg.n_gemms_per_block;
+        float *d_blk = nullptr, *d_full = nullptr, *d_stage = nullptr;
+        void* qs = nullptr;
+        const size_t full_det = n_f_per_detect * (size_t)opt.world;
+        const size_t rows = (size_t)n_units * cfg.n_out_per_gemm, row_floats = (size_t)cfg.n_freq * cfg.n_beams;
+        const bool root = plan.is_root;
+        if (plan.dm_run) d_full = d_rows;     // (a holder with a DM stage receives straight into the stage's buffer)
+        int rc = bf_block_output_device(dev.h, q, &d_blk);
+        if (rc == BF_OK) rc = bf_queue_stream(dev.h, q, &qs);
+        if (rc == BF_OK && root && !plan.dm_run) rc = bf_block_gather_device(dev.h, q, opt.world, &d_full);
+        if (rc == BF_OK && root && plan.staged) rc = bf_block_gather_stage_device(dev.h, q, opt.world, &d_stage);
+        if (rc == BF_OK)
+            rc = plan.staged ? bf_gather_detected_staged(opt.comm, d_blk, rows, row_floats, opt.gather_root, d_full, d_stage, qs)
+                             : bf_gather_detected(opt.comm, d_blk, rows, row_floats, opt.gather_root, BF_GATHER_LAYOUT_FREQ_MAJOR, d_full, qs);
+        for (int u = 0; rc == BF_OK && root && u < n_units; u++)
+            rc = bf_enqueue_d2h(dev.h, q, d_full + full_det * (size_t)u, unit_dst[u], full_det);
+        return rc;
+    }
+
+    // the DM stage, where the reference's loop collapses frequency (src/beamformer.cu:492-511): this launch's rows are in the stream's
+    // buffer already; its kernels run on the launch's own queue, the chunk that becomes complete travels to a pinned buffer
+    int push_dm_rows(long long block_index, float* d_rows, void* dm_qs)
+    {
+        uint64_t first_t = 0;
+        int n_t = 0;
+        float* chunk = dm_host[(size_t)(dm_seq++ % dm_host.size())];
+        const int rc = bf_dm_stream_push(dev.dm, d_rows, plan.dm_rows, chunk, &first_t, &n_t, dm_qs);
+        if (rc == BF_OK && n_t > 0) dm_pending.push_back({(uint64_t)block_index, first_t, n_t, chunk});
+        return rc;
+    }
+
+    // What the blocks analysed so far finished: their DM chunks have landed (their copies sit on the queues the analysis event joins),
+    // and so has every D2H copy of their gemm-units: hand those over, in order.
+    int deliver(uint64_t blocks_analyzed)
+    {
+        while (!dm_pending.empty() && dm_pending.front().block < blocks_analyzed) {
+            const dm_chunk c = dm_pending.front();
+            dm_pending.pop_front();
+            dm_times += (uint64_t)c.n_t;
+            if (!opt.dm_sink) continue;
+            dm_chunks++;
+            if (!opt.dm_sink->deliver(c.first_t, c.n_t, plan.dm_count, cfg.n_beams, c.host)) {
+                log << "ERROR: DM sink failed at output time " << c.first_t << std::endl;
+                return BF_ERR_STATE;
+            }
+        }
+        for (; opt.sink && sink_committed < blocks_analyzed * (uint64_t)cfg.n_gemms_per_block; sink_committed++)
+            if (!opt.sink->commit(sink_committed)) {
+                log << "ERROR: detected sink failed at gemm-unit " << sink_committed << std::endl;
+                return BF_ERR_STATE;
+            }
+        return BF_OK;
+    }
+};
+
+}  // namespace
+
 int run_observation(const bf_config& cfg, const observation_options& opt, block_source& source, const antenna* pos,
                     const beam_direction* dir, observation_result* res, std::ostream& log)
 {
-    // A sharded run enters its first collective -- the gather behind block 0 -- only if EVERY shard got through its setup: each rank
-    // takes part in ONE exchange of "ready" flags before the loop, whichever way its setup went (a rank that bailed out alone would
-    // leave the others waiting in that gather for ever: ADVICE r05).  The caller's own preparations count too (local_setup_ok).
-    struct setup_gate {
-        bf_comm* comm;
-        bool done = false;
-        int fail(int rc)
-        {
-            if (comm && !done) {
-                done = true;
-                bool all = false;
-                (void)comm_all_ok(comm, false, &all);
-            }
-            return rc;
-        }
-    } gate{opt.comm};
-    const int n_streams = cfg.n_streams;
-    if (cfg.n_gemms_per_block % n_streams) return gate.fail(BF_ERR_INVALID);
-    if (opt.world < 1 || opt.rank < 0 || opt.rank >= opt.world || opt.gather_root < BF_GATHER_ROOT_ALL || opt.gather_root >= opt.world)
-        return gate.fail(set_error(BF_ERR_INVALID, "run_observation: need 0 <= rank < world and gather_root a rank or BF_GATHER_ROOT_ALL"));
-    // who holds the gathered band after every block: one rank, or (BF_GATHER_ROOT_ALL) every rank
-    const bool is_root = !opt.comm || opt.gather_root == BF_GATHER_ROOT_ALL || opt.rank == opt.gather_root;
-    if (opt.comm && (bf_comm_rank(opt.comm) != opt.rank || bf_comm_world(opt.comm) != opt.world))
-        return gate.fail(set_error(BF_ERR_INVALID, "run_observation: the communicator's rank / world differ from the options'"));
-    if (opt.comm && !opt.block_launch)
-        return gate.fail(set_error(BF_ERR_INVALID, "run_observation: the sharded gather needs block-granular launches"));
-    if (opt.comm && opt.sink && !is_root)
-        return gate.fail(set_error(BF_ERR_INVALID, "run_observation: only the gather root may have a sink"));
-    if (opt.dm_delays && opt.n_dm <= 0) return gate.fail(set_error(BF_ERR_INVALID, "run_observation: dm_delays without n_dm"));
-    if (opt.dm_sink && !opt.dm_delays) return gate.fail(set_error(BF_ERR_INVALID, "run_observation: a dm_sink needs dm_delays"));
-    if (opt.comm && opt.dm_sink && !is_root)
-        return gate.fail(set_error(BF_ERR_INVALID, "run_observation: only the gather root may have a dm_sink"));
-    if (opt.dm_split_trials && (!opt.comm || opt.gather_root != BF_GATHER_ROOT_ALL))
-        return gate.fail(set_error(BF_ERR_INVALID, "run_observation: dm_split_trials needs a sharded run gathered to every rank (BF_GATHER_ROOT_ALL)"));
+    setup_gate gate{opt.comm};
+    int rc = check_options(cfg, opt);
+    if (rc != BF_OK) return gate.fail(rc);
     source.read_headers();  // :334 (before the device exists here: the block-size check below needs no GPU)
     const size_t block_bytes = bf_bytes_per_block(&cfg);
     if (source.get_block_size() != block_bytes) {
@@ -458,44 +726,10 @@ int run_observation(const bf_config& cfg, const observation_options& opt, block_
         return gate.fail(set_error(BF_ERR_INVALID, "run_observation: the source's block size does not match bf_bytes_per_block(cfg)"));
     }
 
-    bf_handle* h = nullptr;
-    int rc = bf_create(&cfg, opt.device, &h);
-    if (rc != BF_OK) {
-        log << "GPUassert: " << bf_last_error() << std::endl;
-        return gate.fail(rc);
-    }
-    struct guard {
-        bf_handle* h;
-        void* pinned;
-        bf_dm_stream* dm = nullptr;
-        std::vector<void*> more_pinned;
-        ~guard()
-        {
-            if (h) bf_stream_sync(h, -1);
-            bf_dm_stream_destroy(dm);   // (before its handle)
-            bf_free_pinned(pinned);
-            for (void* p : more_pinned) bf_free_pinned(p);
-            bf_destroy(h);
-        }
-    } g{h, nullptr};
-
-    const size_t n_f_per_detect = bf_floats_per_detect(&cfg);
-    // beam_out: the reference's pinned D2H destination (:249); the root of a sharded run receives the whole band there
-    const size_t beam_out_stride = n_f_per_detect * (size_t)(opt.comm ? opt.world : 1);
-    if ((rc = bf_alloc_pinned(&g.pinned, beam_out_stride * n_streams * sizeof(float))) != BF_OK) return gate.fail(rc);
-    float* beam_out = static_cast<float*>(g.pinned);
-    ::memset(beam_out, 0, beam_out_stride * n_streams * sizeof(float));
-    {
-        std::vector<int8_t> fourier_coefficients((size_t)cfg.n_freq * cfg.n_ant * cfg.n_beams * 2);
-        generate_fourier_coefficients(cfg.n_beams, cfg.n_ant, cfg.n_freq, opt.rank * cfg.n_freq, opt.gpu, pos, dir,
-                                      fourier_coefficients.data());
-        if ((rc = bf_set_weights(h, fourier_coefficients.data())) != BF_OK) return gate.fail(rc);
-    }
-    std::vector<int> timeSlice((size_t)n_streams);
-    for (int i = 0; i < n_streams; i++) timeSlice[i] = i;  // :319
-    std::vector<long long> last_gemm((size_t)n_streams, -1);
-    std::vector<float*> unit_dst;
-
+    production_run run{cfg, opt, log};
+    for (int i = 0; i < cfg.n_streams; i++) run.timeSlice[i] = i;  // :319
+    if ((rc = run.create_handle_and_weights(pos, dir)) != BF_OK) return gate.fail(rc);
+    bf_handle* const h = run.dev.h;
     hip_backend backend(h);
     observation_loop_state obs_state(kMaxTransferSep, kMaxTotalSep, cfg, &backend, /*debug_mode=*/false);  // :322
     if (opt.burn_in > 0) {  // :348-355
@@ -506,240 +740,46 @@ int run_observation(const bf_config& cfg, const observation_options& opt, block_
         }
         log << "Done Burn in" << std::endl;
     }
-    uint64_t sink_committed = 0;
-    const char* unit_env = lab_getenv("DSABF_UNIT_LAUNCH");   // measurement / test switch (DSABF_LAB=1): the reference's per-gemm-unit launches
-    const bool block_launch = opt.block_launch && !(unit_env && unit_env[0] == '1');
-    if (opt.comm && !block_launch) return gate.fail(set_error(BF_ERR_INVALID, "run_observation: the sharded gather needs block-granular launches"));
-    int upl = opt.units_per_launch;                                // gemm-units per launch of the block path
-    if (const char* e = lab_getenv("DSABF_UNITS_PER_LAUNCH")) upl = atoi(e);
-    if (upl <= 0 || upl > cfg.n_gemms_per_block || opt.comm) upl = cfg.n_gemms_per_block;   // 0 / sharded: the whole block
-    while (cfg.n_gemms_per_block % upl) upl--;                    // whole launches only
-    uint64_t launch_seq = 0;
-    const int n_queues_used = upl == cfg.n_gemms_per_block ? std::min(n_streams, 2) : n_streams;   // (the rotation below)
-    bool staged = opt.gather_staged;
-    if (const char* e = lab_getenv("DSABF_GATHER_STAGED")) staged = e[0] == '1';
-    // ---- the DM stage (SURVEY.md 8f-4): where the reference's loop has its frequency collapse, src/beamformer.cu:492-511 ----
-    const bool dm_here = opt.dm_delays && is_root;   // a sharded run dedisperses the gathered band
-    // dm_split_trials: every rank holds the whole band (one all-gather instead of a gather) and takes ITS share of the trial ladder --
-    // the DM work scales with the GPUs, the path still has ONE collective; rank r: trials [r n / R, (r + 1) n / R), the first n % R
-    // ranks one more
-    int dm_first = 0, dm_count = opt.n_dm;
-    if (opt.dm_split_trials) dm_trial_share(opt.n_dm, opt.world, opt.rank, &dm_first, &dm_count);
-    const int n_freq_band = cfg.n_freq * (opt.comm ? opt.world : 1);
-    const int dm_rows = upl * cfg.n_out_per_gemm;                                       // beam-blocks per launch = rows per push
-    struct dm_chunk {
-        uint64_t block, first_t;
-        int n_t;
-        float* host;
-    };
-    std::deque<dm_chunk> dm_pending;            // pushed, not yet delivered (their block's analysis event has not fired)
-    std::vector<float*> dm_host;                // pinned chunk buffers, used round robin
-    uint64_t dm_seq = 0, dm_times = 0, dm_chunks = 0;
-    if (opt.dm_delays && !block_launch) return gate.fail(set_error(BF_ERR_INVALID, "run_observation: the DM stage needs block-granular launches"));
-    const bool dm_run = dm_here && dm_count > 0;      // (more ranks than trials: the surplus ranks only beamform)
-    if (dm_run) {
-        if ((rc = bf_dm_stream_create(h, opt.dm_delays + (size_t)dm_first * n_freq_band, dm_count, n_freq_band, dm_rows, &g.dm)) != BF_OK) {
-            log << "GPUassert: " << bf_last_error() << std::endl;
-            return gate.fail(rc);
-        }
-        // chunks in flight: the launches of MAX_TOTAL_SEP blocks queued + the one being delivered
-        const size_t n_buf = (size_t)(kMaxTotalSep + 2) * (size_t)(cfg.n_gemms_per_block / upl);
-        for (size_t i = 0; i < n_buf; i++) {
-            void* pb = nullptr;
-            if ((rc = bf_alloc_pinned(&pb, (size_t)dm_count * dm_rows * cfg.n_beams * sizeof(float))) != BF_OK) return gate.fail(rc);
-            g.more_pinned.push_back(pb);
-            dm_host.push_back(static_cast<float*>(pb));
-        }
-    }
+    if ((rc = resolve_plan(cfg, opt, &run.plan)) != BF_OK) return gate.fail(rc);
+    if ((rc = run.create_dm_stage_and_buffers()) != BF_OK) return gate.fail(rc);
+    if ((rc = gate.pass(opt.local_setup_ok)) != BF_OK) return rc;
 
-    if (block_launch)   // the per-queue block buffers are allocated on first use: do that here, not inside the timed loop
-        for (int q = 0; q < n_queues_used; q++) {
-            float* unused = nullptr;
-            if ((!dm_run || opt.comm) && (rc = bf_block_output_device(h, q, &unused)) != BF_OK) return gate.fail(rc);   // (a DM stage takes the rows itself)
-            if (opt.comm && is_root && !dm_run && (rc = bf_block_gather_device(h, q, opt.world, &unused)) != BF_OK) return gate.fail(rc);
-            if (opt.comm && staged && is_root && (rc = bf_block_gather_stage_device(h, q, opt.world, &unused)) != BF_OK) return gate.fail(rc);
-        }
-    if (opt.comm) {
-        gate.done = true;
-        bool all = false;
-        if ((rc = comm_all_ok(opt.comm, opt.local_setup_ok, &all)) != BF_OK) return rc;
-        if (!all)
-            return set_error(BF_ERR_STATE, opt.local_setup_ok ? "run_observation: another shard of this run failed its setup; nothing was started"
-                                                              : "run_observation: this shard's caller reported a failed setup (local_setup_ok = false)");
-    } else if (!opt.local_setup_ok) {
-        return set_error(BF_ERR_STATE, "run_observation: the caller reported a failed setup (local_setup_ok = false)");
-    }
     bf_timer_start(h);  // :358
     while (!obs_state.check_observations_complete()) {  // :364
-        if (opt.verbose) {
-            log << "##########################################" << std::endl;
-            log << obs_state << std::endl;
-        }
-        if (obs_state.check_ready_for_transfer()) {  // :378
-            char* block = source.read();             // :384
-            if (!source.check_transfers_complete()) {  // :386
-                rc = bf_submit_block(h, (int)obs_state.get_next_gpu_transfer_block(), block, block_bytes, nullptr);  // :389-393
-                if (rc != BF_OK) {
-                    log << "GPUassert: " << bf_last_error() << std::endl;
-                    return rc;
-                }
-                obs_state.generate_transfer_event();  // :396
-                if (source.close_releases_block())      // not in the reference: see block_source::close_releases_block
-                    while (obs_state.status() == BF_OK &&
-                           obs_state.get_blocks_transferred() < obs_state.get_blocks_transfer_queue())
-                        obs_state.check_transfer_events();
-            } else {
-                obs_state.set_transfers_complete(true);  // :398
-            }
-            source.close();  // :401
-        }
+        if (opt.verbose) log << "##########################################" << std::endl << obs_state << std::endl;
+        if (obs_state.check_ready_for_transfer())  // :378
+            if ((rc = run.transfer_block(obs_state, source, block_bytes)) != BF_OK) return rc;
         obs_state.check_transfer_events();  // :446
         if (obs_state.check_ready_for_analysis()) {  // :452
-            const long long block_index = (long long)obs_state.get_blocks_analysis_queue();
-            if (block_launch) {
-                // unit u's powers go to its sink slot, or to beam_out[queue of its launch] (later units on that queue
-                // overwrite earlier ones, in order: beam_out[q] ends up holding gemm-unit last_gemm[q])
-                const int n_units = cfg.n_gemms_per_block;
-                unit_dst.assign((size_t)n_units, nullptr);
-                for (int first = 0; first < n_units; first += upl) {
-                    // whole blocks alternate between TWO queues (block i + 1's kernel under block i's copies, as in the DEBUG flow):
-                    // more queues only put more concurrent host copies beside the H2D stream (9.6 -> 9.2 us per beam-block, and
-                    // 11.6 -> 9.x with other streams alive in the process: tools/stream_queues.py); sub-block launches rotate over all
-                    const int q = (int)(launch_seq++ % (uint64_t)n_queues_used);
-                    for (int u = first; u < first + upl; u++) {
-                        unit_dst[u] = &beam_out[(size_t)q * beam_out_stride];
-                        if (opt.sink) {
-                            unit_dst[u] = opt.sink->acquire((uint64_t)block_index * n_units + u);
-                            if (!unit_dst[u]) {
-                                log << "ERROR: detected sink has no free slot" << std::endl;
-                                return BF_ERR_STATE;
-                            }
-                        }
-                        last_gemm[q] = block_index * n_units + u;
-                    }
-                    // The DM stage owns the place its rows belong in -- directly behind its carried-over delay window: the beamformer
-                    // (one GPU) or the gather (a holder of a sharded run) writes them THERE, and the push below only launches.  The
-                    // reference's collapse reads what detect wrote, no copy in between (src/beamformer.cu:481,492-511).
-                    float* d_rows = nullptr;     // where this launch's beam-blocks are on the device, [row][freq (over the band)][beam]
-                    void* dm_qs = nullptr;
-                    if (dm_run && (rc = bf_queue_stream(h, q, &dm_qs)) == BF_OK) rc = bf_dm_stream_reserve(g.dm, dm_rows, &d_rows, dm_qs);
-                    if (rc == BF_OK)
-                        rc = (dm_run && !opt.comm) ? bf_enqueue_block_to(h, q, (int)obs_state.get_next_gpu_analysis_block(), first, upl, d_rows,
-                                                                         &unit_dst[first])
-                                                   : bf_enqueue_block(h, q, (int)obs_state.get_next_gpu_analysis_block(), first, upl,
-                                                                      opt.comm ? nullptr : &unit_dst[first]);
-                    if (rc == BF_OK && opt.comm) {
-                        // sharded (upl == n_units): bring the shards' powers together on the root, in [unit][o][f over the
-                        // band][b], behind the launch on the same queue; only the root copies to the host
-                        float *d_blk = nullptr, *d_full = nullptr, *d_stage = nullptr;
-                        void* qs = nullptr;
-                        const size_t full_det = n_f_per_detect * (size_t)opt.world;
-                        const bool root = is_root;
-                        if (dm_run) d_full = d_rows;     // (a holder with a DM stage receives straight into the stage's buffer)
-                        if ((rc = bf_block_output_device(h, q, &d_blk)) == BF_OK && (rc = bf_queue_stream(h, q, &qs)) == BF_OK &&
-                            (!root || dm_run || (rc = bf_block_gather_device(h, q, opt.world, &d_full)) == BF_OK) &&
-                            (!root || !staged || (rc = bf_block_gather_stage_device(h, q, opt.world, &d_stage)) == BF_OK))
-                            rc = staged ? bf_gather_detected_staged(opt.comm, d_blk, (size_t)n_units * cfg.n_out_per_gemm,
-                                                                    (size_t)cfg.n_freq * cfg.n_beams, opt.gather_root, d_full, d_stage, qs)
-                                        : bf_gather_detected(opt.comm, d_blk, (size_t)n_units * cfg.n_out_per_gemm,
-                                                             (size_t)cfg.n_freq * cfg.n_beams, opt.gather_root,
-                                                             BF_GATHER_LAYOUT_FREQ_MAJOR, d_full, qs);
-                        for (int u = 0; rc == BF_OK && root && u < n_units; u++)
-                            rc = bf_enqueue_d2h(h, q, d_full + full_det * (size_t)u, unit_dst[u], full_det);
-                    }
-                    if (rc == BF_OK && dm_run) {
-                        // the DM stage, where the reference's loop collapses frequency (src/beamformer.cu:492-511): this launch's rows
-                        // are in the stream's buffer already; its kernels run on the launch's own queue, the chunk that becomes complete
-                        // travels to a pinned buffer
-                        uint64_t first_t = 0;
-                        int n_t = 0;
-                        float* chunk = dm_host[(size_t)(dm_seq++ % dm_host.size())];
-                        rc = bf_dm_stream_push(g.dm, d_rows, dm_rows, chunk, &first_t, &n_t, dm_qs);
-                        if (rc == BF_OK && n_t > 0) dm_pending.push_back({(uint64_t)block_index, first_t, n_t, chunk});
-                    }
-                    if (rc != BF_OK) {
-                        log << "GPUassert: " << bf_last_error() << std::endl;
-                        return rc;
-                    }
-                }
-            } else {  // the reference's launch pattern: one gemm-unit per launch, round-robin over the compute queues
-                for (int part = 0; part < cfg.n_gemms_per_block / n_streams; part++) {
-                    for (int st = 0; st < n_streams; st++) {
-                        float* dst = &beam_out[(size_t)st * n_f_per_detect];  // the reference's destination, :485-488
-                        if (opt.sink) {
-                            dst = opt.sink->acquire((uint64_t)block_index * cfg.n_gemms_per_block + timeSlice[st]);
-                            if (!dst) {
-                                log << "ERROR: detected sink has no free slot" << std::endl;
-                                return BF_ERR_STATE;
-                            }
-                        }
-                        rc = bf_enqueue_gemm_unit(h, st, (int)obs_state.get_next_gpu_analysis_block(), timeSlice[st], dst);  // :464-488
-                        if (rc != BF_OK) {
-                            log << "GPUassert: " << bf_last_error() << std::endl;
-                            return rc;
-                        }
-                        last_gemm[st] = block_index * cfg.n_gemms_per_block + timeSlice[st];
-                        timeSlice[st] += n_streams;  // :515-519
-                        if (timeSlice[st] >= cfg.n_gemms_per_block) timeSlice[st] -= cfg.n_gemms_per_block;
-                    }
-                }
-            }
+            if ((rc = run.analyse_block(obs_state)) != BF_OK) return rc;
             obs_state.generate_analysis_event();  // :525
         }
         obs_state.check_analysis_events();  // :532
-        if (obs_state.status() != BF_OK) {  // a failed record / query: the reference exits in gpuErrchk, never keep polling
-            log << "GPUassert: event backend failed: " << bf_last_error() << std::endl;
-            return obs_state.status();
-        }
-        // the DM chunks of analysed blocks have landed too (their copies sit on the queues the analysis event joins)
-        while (!dm_pending.empty() && dm_pending.front().block < obs_state.get_blocks_analyzed()) {
-            const dm_chunk c = dm_pending.front();
-            dm_pending.pop_front();
-            dm_times += (uint64_t)c.n_t;
-            if (opt.dm_sink) {
-                dm_chunks++;
-                if (!opt.dm_sink->deliver(c.first_t, c.n_t, dm_count, cfg.n_beams, c.host)) {
-                    log << "ERROR: DM sink failed at output time " << c.first_t << std::endl;
-                    return BF_ERR_STATE;
-                }
-            }
-        }
-        if (opt.sink) {  // every D2H copy of an analysed block has landed: hand its gemm-units over, in order
-            for (; sink_committed < obs_state.get_blocks_analyzed() * (uint64_t)cfg.n_gemms_per_block; sink_committed++)
-                if (!opt.sink->commit(sink_committed)) {
-                    log << "ERROR: detected sink failed at gemm-unit " << sink_committed << std::endl;
-                    return BF_ERR_STATE;
-                }
-        }
+        if (obs_state.status() != BF_OK) return event_backend_error(log, obs_state);
+        if ((rc = run.deliver(obs_state.get_blocks_analyzed())) != BF_OK) return rc;
     }
     float ms = 0;
     bf_timer_stop(h, &ms);
     bf_stream_sync(h, -1);  // :560-562
     if (opt.sink) opt.sink->close();
     if (opt.dm_sink) opt.dm_sink->close();
-    const uint64_t blocks = obs_state.get_blocks_analyzed();
     const uint64_t chunks = obs_state.get_current_transfer_gemm() * cfg.n_out_per_gemm;  // :552
     const double rate = (double)source.get_block_size() * obs_state.get_blocks_transfer_queue() / ms / 1e6;  // :554
-    log << "Observation ran in " << ms << "milliseconds.\n";
-    log << "Code produced outputs for " << chunks << " data chunks.\n";
-    log << "Time per data chunk: " << ms / (chunks ? chunks : 1) << " milliseconds.\n";
-    log << "Approximate datarate: " << rate << "GB/s" << std::endl;
-    log << "Launch pattern: " << (block_launch ? "bf_enqueue_block" : "the reference's loop, one bf_enqueue_gemm_unit per gemm-unit (src/beamformer.cu:454-519)")
-        << std::endl;
-    log << "Synchronized" << std::endl;
+    closing_report(log, ms, chunks, ms / (chunks ? chunks : 1), rate, run.plan.block_launch ? "bf_enqueue_block" : kUnitLaunchPattern);
     if (res) {
         res->observation_time_ms = ms;
-        res->blocks = blocks;
+        res->blocks = obs_state.get_blocks_analyzed();
         res->data_chunks = chunks;
         res->gbytes_per_s = rate;
-        res->beam_out.assign(beam_out, beam_out + beam_out_stride * n_streams);
-        res->last_gemm = last_gemm;
-        res->dm_times = dm_times;
-        res->dm_chunks = dm_chunks;
+        res->beam_out.assign(run.beam_out, run.beam_out + run.beam_out_stride * cfg.n_streams);
+        res->last_gemm = run.last_gemm;
+        res->dm_times = run.dm_times;
+        res->dm_chunks = run.dm_chunks;
     }
-    if (dm_run)
-        log << "DM stage: trials " << dm_first << " .. " << dm_first + dm_count - 1 << " of " << opt.n_dm << ", " << dm_times
-            << " output times (largest delay " << bf_dm_stream_max_delay(g.dm) << " samples carried over on the device)" << std::endl;
+    if (run.plan.dm_run)
+        log << "DM stage: trials " << run.plan.dm_first << " .. " << run.plan.dm_first + run.plan.dm_count - 1 << " of " << opt.n_dm << ", "
+            << run.dm_times << " output times (largest delay " << bf_dm_stream_max_delay(run.dev.dm) << " samples carried over on the device)"
+            << std::endl;
     return BF_OK;
 }
 
