@@ -39,6 +39,25 @@ class BfGatherMsg(C.Structure):
                 ("count", C.c_size_t)]
 
 
+class BfSpsPeak(C.Structure):
+    """Mirror of ``bf_sps_peak`` (include/dsabf.h)."""
+
+    _fields_ = [("value", C.c_float), ("t_end", C.c_int32)]
+
+
+class BfSpsStat(C.Structure):
+    """Mirror of ``bf_sps_stat`` (include/dsabf.h)."""
+
+    _fields_ = [("sum", C.c_double), ("sumsq", C.c_double)]
+
+
+class BfSpsCandidate(C.Structure):
+    """Mirror of ``bf_sps_candidate`` (include/dsabf.h)."""
+
+    _fields_ = [("t_start", C.c_uint64), ("dm", C.c_int32), ("beam", C.c_int32), ("width", C.c_int32), ("peak", C.c_float),
+                ("snr", C.c_double)]
+
+
 class DsabfError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__("libdsabf error %d: %s" % (code, msg))
@@ -94,6 +113,15 @@ SIGNATURES = {
     "bf_dm_stream_max_delay": (C.c_int, [C.c_void_p]),
     "bf_dm_stream_push": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_int), C.c_void_p]),
     "bf_dm_stream_output_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "bf_dm_stream_attach_search": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "bf_sps_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_void_p)]),
+    "bf_sps_destroy": (C.c_int, [C.c_void_p]),
+    "bf_sps_push": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p]),
+    "bf_sps_collect": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "bf_sps_pending": (C.c_int, [C.c_void_p]),
+    "bf_sps_last_records": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
+    "bf_sps_select": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int, C.c_uint64, C.c_double,
+                                C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "bf_comm_unique_id": (C.c_int, [C.c_void_p]),
     "bf_comm_create": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
     "bf_comm_destroy": (C.c_int, [C.c_void_p]),

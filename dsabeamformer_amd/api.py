@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-from ._lib import BfConfig, check, load
+from ._lib import BfConfig, BfSpsCandidate, BfSpsPeak, BfSpsStat, check, load
 
 
 def debug_config(**over) -> BfConfig:
@@ -268,9 +268,99 @@ class DmStream:
         check(self._lib.bf_dm_stream_output_device(self._s, C.byref(p)))
         return p.value or 0
 
+    def attach_search(self, sps) -> None:
+        """bf_dm_stream_attach_search: every chunk a push emits from now on also goes into ``sps`` (a SinglePulseSearch; None
+        detaches), on the push's queue."""
+        check(self._lib.bf_dm_stream_attach_search(self._s, sps._s if sps is not None else None))
+
     def close(self) -> None:
         if self._s:
             self._lib.bf_dm_stream_destroy(self._s)
+            self._s = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _candidate_dtype():
+    import numpy as np
+
+    return np.dtype([("t_start", np.uint64), ("dm", np.int32), ("beam", np.int32), ("width", np.int32), ("peak", np.float32),
+                     ("snr", np.float64)], align=True)
+
+
+def sps_select(peaks, totals, n: int, n_beams: int, first_t: int = 0, dm_first: int = 0, min_samples: int = 64, threshold: float = 8.0):
+    """bf_sps_select, the candidate selection as a pure host function (no GPU).  peaks: a pair (value [K][n_dm][n_beams] float32,
+    t_end int32) or a structured array of bf_sps_peak; totals: (sum, sumsq) [n_dm][n_beams] float64 over the baseline window of
+    ``n`` samples.  Returns the candidates as a numpy structured array."""
+    import numpy as np
+
+    if isinstance(peaks, tuple):
+        value, t_end = peaks
+        pk = np.empty(np.shape(value), np.dtype([("value", np.float32), ("t_end", np.int32)]))
+        pk["value"], pk["t_end"] = value, t_end
+    else:
+        pk = np.ascontiguousarray(peaks)
+    n_widths, n_dm = pk.shape[0], pk.shape[1]
+    assert pk.shape == (n_widths, n_dm, n_beams) and pk.dtype.itemsize == C.sizeof(BfSpsPeak)
+    tot = np.empty((n_dm, n_beams), np.dtype([("sum", np.float64), ("sumsq", np.float64)]))
+    tot["sum"], tot["sumsq"] = totals
+    out = np.zeros(n_dm * n_beams, _candidate_dtype())
+    assert out.dtype.itemsize == C.sizeof(BfSpsCandidate)
+    n_out = C.c_size_t()
+    check(load().bf_sps_select(_ptr(pk), _ptr(tot), n, n_widths, n_dm, n_beams, first_t, dm_first, min_samples, threshold, _ptr(out),
+                               out.size, C.byref(n_out)))
+    return out[:n_out.value].copy()
+
+
+class SinglePulseSearch:
+    """bf_sps: boxcar single-pulse search over the chunks [n_dm][n_t][beam] of a DmStream, on the device (include/dsabf.h,
+    docs/SINGLE_PULSE.md).  Attach it with ``DmStream.attach_search`` or push chunks yourself."""
+
+    def __init__(self, bf: Beamformer, n_dm: int, n_widths: int, max_t_per_push: int, dm_first: int = 0, max_in_flight: int = 4,
+                 baseline_pushes: int = 8, min_samples: int = 64, threshold: float = 8.0):
+        self._lib = load()
+        self._s = C.c_void_p()
+        self.n_dm, self.n_widths, self.n_beams, self._bf = n_dm, n_widths, bf.cfg.n_beams, bf
+        check(self._lib.bf_sps_create(bf._h, n_dm, dm_first, n_widths, max_t_per_push, max_in_flight, baseline_pushes, min_samples,
+                                      threshold, C.byref(self._s)))
+
+    def push(self, d_chunk, n_t: int, first_t: int, stream: int = 0) -> None:
+        check(self._lib.bf_sps_push(self._s, _ptr(d_chunk), n_t, first_t, C.c_void_p(stream)))
+
+    @property
+    def pending(self) -> int:
+        return self._lib.bf_sps_pending(self._s)
+
+    def collect(self):
+        """Waits for the oldest uncollected push and returns its candidates (numpy structured array: t_start, dm, beam, width,
+        peak, snr)."""
+        import numpy as np
+
+        out = np.zeros(self.n_dm * self.n_beams, _candidate_dtype())
+        n_out = C.c_size_t()
+        check(self._lib.bf_sps_collect(self._s, _ptr(out), out.size, C.byref(n_out)))
+        return out[:n_out.value].copy()
+
+    def last_records(self) -> dict:
+        """The raw records of the push just collected (copies): value / t_end [K][n_dm][n_beams], sum / sumsq [n_dm][n_beams],
+        first_t, n_t."""
+        import numpy as np
+
+        pk, st, first, n_t = C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_int()
+        check(self._lib.bf_sps_last_records(self._s, C.byref(pk), C.byref(st), C.byref(first), C.byref(n_t)))
+        n_db = self.n_dm * self.n_beams
+        peaks = np.ctypeslib.as_array(C.cast(pk, C.POINTER(BfSpsPeak)), (self.n_widths * n_db,)).reshape(self.n_widths, self.n_dm, self.n_beams)
+        stats = np.ctypeslib.as_array(C.cast(st, C.POINTER(BfSpsStat)), (n_db,)).reshape(self.n_dm, self.n_beams)
+        return {"value": peaks["value"].copy(), "t_end": peaks["t_end"].copy(), "sum": stats["sum"].copy(), "sumsq": stats["sumsq"].copy(),
+                "first_t": int(first.value), "n_t": int(n_t.value)}
+
+    def close(self) -> None:
+        if self._s:
+            self._lib.bf_sps_destroy(self._s)
             self._s = C.c_void_p()
 
     def __del__(self):

@@ -1,6 +1,10 @@
 """Builds libdsabf.so (HIP kernels + C-ABI runtime + C++ host mirror) in-tree with hipcc for gfx950.
 
 hipcc cross-compiles without a GPU.  The .so is git-ignored but travels to the GPU box with the snapshot.
+
+kernel_build_id() identifies the kernels that the bench line and the counter summaries under profiles/ time: the sources
+directly under csrc/.  The single-pulse search stage (csrc/sps/, docs/SINGLE_PULSE.md) is not among them -- it is compiled with
+the same FLAGS into the same library, but its device code lives in a directory of its own and does not enter the id.
 """
 from __future__ import annotations
 
@@ -63,13 +67,14 @@ MAINS = {BEAM: BEAM_SRC, JUNKDB: JUNKDB_SRC, REPLICAS: REPLICAS_SRC}
 
 def sources() -> list[str]:
     """Sources of libdsabf.so (everything under csrc/ except the CLI driver)."""
-    return sorted(p for p in glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.cpp"))
+    return sorted(p for p in glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.cpp")) + glob.glob(os.path.join(SPS, "*.hip"))
                   if os.path.abspath(p) not in [os.path.abspath(m) for m in MAINS.values()])
 
 
 STAMP = os.path.join(PKG, "build", "flags.stamp")   # the flag set the in-tree library was built with
 KID_STAMP = os.path.join(PKG, "build", "kernel_id.stamp")   # the kernel build id compiled into bf_version()
 RUNTIME_SRC = os.path.join(CSRC, "bf_runtime.cpp")
+SPS = os.path.join(CSRC, "sps")                     # device code of the single-pulse search stage: outside kernel_build_id()
 
 
 def kernel_build_id() -> str:
@@ -94,6 +99,12 @@ def _stamp() -> str:
     return (" ".join(FLAGS) + " | " + repr(sorted(SCHED_BY_SUFFIX.items()))).replace(ROOT, "<root>")
 
 
+def _headers() -> list[str]:
+    """Every header a source may include: a newer one makes the library, and every object, stale."""
+    return glob.glob(os.path.join(CSRC, "*.h*")) + glob.glob(os.path.join(CSRC, "*.inc")) + glob.glob(os.path.join(SPS, "*.h")) + \
+        glob.glob(os.path.join(ROOT, "include", "*.h*"))
+
+
 def _stale() -> bool:
     if not os.path.exists(LIB):
         return True
@@ -106,8 +117,7 @@ def _stale() -> bool:
     t = os.path.getmtime(LIB)
     if not all(os.path.exists(b) for b in MAINS):
         return True
-    deps = list(MAINS.values()) + sources() + glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.hpp")) + \
-        glob.glob(os.path.join(ROOT, "include", "*.h*")) + [os.path.abspath(__file__)]
+    deps = list(MAINS.values()) + sources() + _headers() + [os.path.abspath(__file__)]
     return any(os.path.getmtime(p) > t for p in deps)
 
 
@@ -127,8 +137,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         flags_same = os.path.exists(STAMP) and open(STAMP).read() == _stamp()
         is_runtime = os.path.abspath(src) == os.path.abspath(RUNTIME_SRC)   # carries the kernel build id: rebuilt whenever that changes
         if not force and flags_same and (kid_same or not is_runtime) and os.path.exists(obj) and os.path.getmtime(obj) > max(
-                [os.path.getmtime(src)] + [os.path.getmtime(p) for p in glob.glob(os.path.join(CSRC, "*.h*"))] +
-                [os.path.getmtime(p) for p in glob.glob(os.path.join(ROOT, "include", "*.h*"))]):
+                [os.path.getmtime(src)] + [os.path.getmtime(p) for p in _headers()]):
             continue
         # .hip: device + host; .cpp: plain host C++ (HIP host API only), also through hipcc for the include paths
         cmd = [HIPCC] + flags_for(src) + (['-DDSABF_KERNEL_BUILD_ID="%s"' % kid] if is_runtime else []) + ["-c", src, "-o", obj]

@@ -21,6 +21,11 @@
 //                                                   gather root, over the gathered band.  With -R and -X: the shards' powers go to
 //                                                   EVERY rank (the one collective becomes an all-gather) and rank r dedisperses its
 //                                                   share of the ladder, writing dm_file.<r>: the DM work scales with the GPUs.
+//   beam -j n_blocks -M dm_max ... -S snr [-B n_widths] [-C cand_file]
+//                                                   the single-pulse search behind the DM stage (docs/SINGLE_PULSE.md): every chunk
+//                                                   searched on the device with boxcar widths 1 .. 2^(n_widths-1) [6]; candidates at
+//                                                   S/N >= snr to cand_file, one text line each: t_start dm beam width snr peak.
+//                                                   With -X: cand_file.<r>, trials numbered over the whole ladder.  Needs -M.
 //
 // With the reference's `make debug` geometry (default) it generates synthetic point-source voltages on the CPU,
 // streams them through the observation loop and writes bin/data.py (dedispersed beam responses, one row per source)
@@ -59,9 +64,13 @@ int main(int argc, char* argv[])
     int n_dm_cap = 0;
     bool dm_split = false;
     std::string dm_path, dm_ring;   // -W file / -Q shared-memory ring for the DM chunks
+    double sps_snr = 0.0;           // -S: threshold of the single-pulse search (0: off)
+    int sps_widths = 6;             // -B
+    bool sps_on = false, sps_widths_given = false;
+    std::string cand_path;          // -C
 
     int arg = 0;
-    while ((arg = getopt(argc, argv, "s:g:p:d:o:D:a:c:k:K:j:w:R:r:I:M:N:T:W:Q:XuvhH")) != -1) {  // src/beamformer.cu:41-43 (+ -o -D -a -v)
+    while ((arg = getopt(argc, argv, "s:g:p:d:o:D:a:c:k:K:j:w:R:r:I:M:N:T:W:Q:S:B:C:XuvhH")) != -1) {  // src/beamformer.cu:41-43 (+ -o -D -a -v)
         switch (arg) {
             case 's': sources = optarg; break;                 // :77-89
             case 'g': opt.gpu = atoi(optarg); break;           // :92-100
@@ -82,6 +91,9 @@ int main(int argc, char* argv[])
             case 'W': dm_path = optarg; break;
             case 'X': dm_split = true; break;
             case 'Q': dm_ring = optarg; break;
+            case 'S': sps_snr = atof(optarg); sps_on = true; break;
+            case 'B': sps_widths = atoi(optarg); sps_widths_given = true; break;
+            case 'C': cand_path = optarg; break;
             case 'u': per_unit = true; break;                   // the reference's launch pattern: one launch per gemm-unit
             case 'v': opt.verbose = true; cfg.verbose = 1; break;
             case 'c': core = atoi(optarg); break;              // :59-65
@@ -103,10 +115,25 @@ int main(int argc, char* argv[])
                              " -M dm_max [-N n_dm] [-T tsamp_ms]   the DM-trial stage inside the loop (notebook ladder 0 .. dm_max)\n"
                              " -W file | -Q ring       its chunks [dm][t][beam]: file of records, or shared-memory ring\n"
                              " -X                      with -R: gather to every shard, shard r dedisperses its share of the trials\n"
+                             " -S snr [-B n_widths] [-C file]   single-pulse search of every DM chunk: boxcar widths 1 .. 2^(n_widths-1) [6],\n"
+                             "                         candidates at S/N >= snr to file (t_start dm beam width snr peak; with -X: file.<rank>);\n"
+                             "                         requires -M: without it (or -B / -C without -S) beam exits with a usage error\n"
                              " -H                      this text\n";
                 return EXIT_SUCCESS;
             default: usage(true, std::cerr); return EXIT_FAILURE;
         }
+    }
+    if (sps_on && !(dm_max > 0.0)) {
+        fprintf(stderr, "beam: -S (single-pulse search) requires the DM stage: give -M dm_max\n");
+        return EXIT_FAILURE;
+    }
+    if (!sps_on && (sps_widths_given || !cand_path.empty())) {
+        fprintf(stderr, "beam: -B / -C belong to the single-pulse search: give -S snr (and -M dm_max)\n");
+        return EXIT_FAILURE;
+    }
+    if (sps_on && (sps_widths < 1 || sps_widths > 8)) {
+        fprintf(stderr, "beam: -B %d: n_widths must be 1 .. 8\n", sps_widths);
+        return EXIT_FAILURE;
     }
     opt.positions = positions.empty() ? nullptr : positions.c_str();
     opt.directions = directions.empty() ? nullptr : directions.c_str();
@@ -246,6 +273,7 @@ int main(int argc, char* argv[])
         std::vector<int32_t> delays;
         std::unique_ptr<dm_file_sink> dm_sink;
         std::unique_ptr<dm_ring_sink> dm_rsink;
+        std::unique_ptr<sps_file_sink> cand_sink;
         int n_dm = 0, my_trials = 0;
         if (dm_max > 0.0) {
             std::vector<double> dms = dm_trials(0.0, dm_max);
@@ -273,6 +301,7 @@ int main(int argc, char* argv[])
                 dmax = 0;
                 for (size_t i = (size_t)my_first * full_cfg.n_freq; i < (size_t)(my_first + my_count) * full_cfg.n_freq; i++) dmax = delays[i] > dmax ? delays[i] : dmax;
                 if (!dm_path.empty()) dm_path += "." + std::to_string(rank);
+                if (!cand_path.empty()) cand_path += "." + std::to_string(rank);
                 std::cout << "Shard " << rank << " dedisperses trials " << my_first << " .. " << my_first + my_count - 1 << std::endl;
             }
             my_trials = my_count;
@@ -295,10 +324,23 @@ int main(int argc, char* argv[])
                 oopt.dm_sink = dm_rsink.get();
             }
         }
+        if (sps_on && my_trials > 0 && (!comm || rank == 0 || oopt.dm_split_trials)) {   // -S: the search runs where the DM stage runs
+            oopt.sps_widths = sps_widths;
+            oopt.sps_threshold = sps_snr;
+            if (!cand_path.empty()) {
+                cand_sink.reset(new sps_file_sink(cand_path.c_str()));
+                if (!cand_sink->is_open()) {
+                    fprintf(stderr, "beam: could not open %s\n", cand_path.c_str());
+                    return EXIT_FAILURE;
+                }
+                oopt.sps_sink = cand_sink.get();
+            }
+        }
         observation_result ores;
         int orc = run_observation(pcfg, oopt, *src, pos.data(), dir.data(), &ores, std::cout);
         if (sink) std::cout << "Wrote " << sink->get_delivered() << " gemm-units of detected powers to " << sink_name << std::endl;
         if (dm_sink) std::cout << "Wrote " << dm_sink->get_times_written() << " dedispersed samples x " << my_trials << " trials to " << dm_path << std::endl;
+        if (cand_sink) std::cout << "Wrote " << cand_sink->get_candidates_written() << " candidates to " << cand_path << std::endl;
         bf_comm_destroy(comm);
         if (orc != BF_OK) {
             fprintf(stderr, "GPUassert: %s (%d)\n", bf_last_error(), orc);

@@ -48,11 +48,13 @@ struct bf_dm_stream {
     bool done_recorded[3] = {false, false, false}, rows_recorded[3] = {false, false, false};
     float* reserved = nullptr;    // bf_dm_stream_reserve: where the NEXT push's rows are being written by their producer ...
     int reserved_rows = 0;        // ... and how many (0: no reservation outstanding)
+    bf_sps* search = nullptr;     // bf_dm_stream_attach_search: every chunk is also pushed into this stage, before `done` is recorded
 };
 
 // device side of a DM stage (its handle's device must be current); the object itself stays, detached from the handle
 void dsabf::rt::dm_stream_release(bf_dm_stream* s)
 {
+    dm_stream_drop_search(s);
     for (int k = 0; k < 3; k++) {
         if (s->done[k]) {
             if (s->done_recorded[k]) (void)hipEventSynchronize(s->done[k]);
@@ -83,6 +85,12 @@ void dsabf::rt::dm_stream_release(bf_dm_stream* s)
 }
 
 bool dsabf::rt::dm_stream_is_ring(const bf_dm_stream* s) { return s->ring; }
+
+void dsabf::rt::dm_stream_drop_search(bf_dm_stream* s)
+{
+    if (s->search) sps_set_feeder(s->search, nullptr);
+    s->search = nullptr;
+}
 
 // Address space for the rings: taken from arenas that are reserved once per process and NEVER given back or handed out twice.
 // On this stack (ROCm 7.2, gfx950) a virtual range that is unmapped and mapped again to other physical memory keeps stale
@@ -259,6 +267,7 @@ int bf_dm_stream_create(bf_handle* h, const int32_t* delays, int n_dm, int n_fre
 int bf_dm_stream_destroy(bf_dm_stream* s)
 {
     if (!s) return BF_OK;
+    dm_stream_drop_search(s);
     if (s->h) {   // (NULL: the handle went first and took the device memory with it)
         bf_handle* h = s->h;
         DeviceScope dev_scope_(h->device);
@@ -270,6 +279,19 @@ int bf_dm_stream_destroy(bf_dm_stream* s)
 }
 
 int bf_dm_stream_max_delay(const bf_dm_stream* s) { return s ? s->max_delay : BF_ERR_INVALID; }
+
+int bf_dm_stream_attach_search(bf_dm_stream* dm, bf_sps* sps)
+{
+    if (!dm) return fail(BF_ERR_INVALID, "NULL argument");
+    if (!dm->h) return fail(BF_ERR_STATE, "the handle of this DM stage has been destroyed");
+    if (sps == dm->search) return BF_OK;
+    if (sps)
+        if (int rc = sps_check_attach(sps, dm->h, dm->n_dm, dm->max_rows)) return rc;
+    dm_stream_drop_search(dm);
+    dm->search = sps;
+    if (sps) sps_set_feeder(sps, dm);
+    return BF_OK;
+}
 
 int bf_dm_stream_output_device(bf_dm_stream* s, float** d_out)
 {
@@ -340,6 +362,10 @@ int bf_dm_stream_push(bf_dm_stream* s, const float* d_rows, int n_rows, float* h
     if (in_place && (d_rows != s->reserved || n_rows != s->reserved_rows))
         return fail(BF_ERR_STATE, "bf_dm_stream_push: %d rows are reserved at %p (bf_dm_stream_reserve); push exactly those", s->reserved_rows,
                     (void*)s->reserved);
+    // a push that will emit a chunk hands it to the attached search stage: refused HERE, before anything is queued, if that has no room
+    if (s->search && s->pushed + (uint64_t)n_rows > (uint64_t)s->max_delay && bf_sps_pending(s->search) >= sps_max_in_flight(s->search))
+        return fail(BF_ERR_STATE, "bf_dm_stream_push: the attached search stage has %d uncollected pushes (max_in_flight): bf_sps_collect first",
+                    bf_sps_pending(s->search));
     bf_handle* h = s->h;
     ON_DEVICE(h);
     hipStream_t q = as_stream(hip_stream);
@@ -384,6 +410,9 @@ int bf_dm_stream_push(bf_dm_stream* s, const float* d_rows, int n_rows, float* h
                                             s->d_flags[set], q));
         if (host_out)
             HIP_TRY(hipMemcpyAsync(host_out, s->d_out[set], (size_t)s->n_dm * n_out * h->cfg.n_beams * sizeof(float), hipMemcpyDeviceToHost, q));
+        // the search reads the chunk where it lies, on this queue and BEFORE `done` below: only that event keeps push j + 3 out of set j % 3
+        if (s->search)
+            if (int rc = bf_sps_push(s->search, s->d_out[set], n_out, emitted, q)) return rc;
     }
     // the end of push j implies the end of every push before it (chunks leave in order; a producer that waits for push j - 3 knows
     // that nothing older reads the rows it overwrites)

@@ -61,6 +61,7 @@ struct bf_handle {
     std::vector<queue_bufs> qbuf;
     int full_world = 0;
     std::vector<struct bf_dm_stream*> dm_streams;   // DM stages created on this handle: bf_destroy releases their device memory
+    std::vector<struct bf_sps*> sps_stages;         // single-pulse search stages (bf_sps.cpp): the same
     hipStream_t h2d = nullptr;
     std::vector<hipStream_t> streams;
     std::vector<hipEvent_t> join;  // one per compute queue: queue_waits_for
@@ -79,6 +80,12 @@ inline int check_weights(const bf_handle* h) { return h->weights_set ? BF_OK : f
 int flush_units(bf_handle* h);                          // bf_queues.cpp
 void dm_stream_release(struct bf_dm_stream* s);         // bf_dm_stream.cpp
 bool dm_stream_is_ring(const struct bf_dm_stream* s);
+void dm_stream_drop_search(struct bf_dm_stream* s);     // the search stage attached to `s` is going away
+// bf_sps.cpp: the single-pulse search stage
+void sps_release(struct bf_sps* s);                     // device side of a stage; the object stays, detached from its handle
+int sps_check_attach(const struct bf_sps* s, const bf_handle* h, int n_dm, int max_rows);   // bf_dm_stream_attach_search's conditions
+int sps_max_in_flight(const struct bf_sps* s);
+void sps_set_feeder(struct bf_sps* s, struct bf_dm_stream* dm);   // the DM stage that pushes into `s` (NULL: none): told when `s` is destroyed
 
 // Makes `device` current for the duration of one entry point and puts the caller's device back afterwards: a library
 // call must not change the current device of a multi-device host process (torch's included).

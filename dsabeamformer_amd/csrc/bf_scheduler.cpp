@@ -197,15 +197,17 @@ int gpu_error(std::ostream& log, int rc)
     return rc;
 }
 
-// What a run holds on the device and in pinned memory.  Released in this order: sync, the DM stream (before its handle), the pinned
+// What a run holds on the device and in pinned memory.  Released in this order: sync, the search stage and the DM stream (before their handle), the pinned
 // buffers in the order they were allocated, the handle.
 struct run_resources {
     bf_handle* h = nullptr;
     bf_dm_stream* dm = nullptr;
+    bf_sps* sps = nullptr;
     std::vector<void*> pinned;
     ~run_resources()
     {
         if (h) bf_stream_sync(h, -1);
+        bf_sps_destroy(sps);
         bf_dm_stream_destroy(dm);
         for (void* p : pinned) bf_free_pinned(p);
         bf_destroy(h);
@@ -469,6 +471,9 @@ int check_options(const bf_config& cfg, const observation_options& opt)
     if (opt.comm && opt.sink && !is_root) return set_error(BF_ERR_INVALID, "run_observation: only the gather root may have a sink");
     if (opt.dm_delays && opt.n_dm <= 0) return set_error(BF_ERR_INVALID, "run_observation: dm_delays without n_dm");
     if (opt.dm_sink && !opt.dm_delays) return set_error(BF_ERR_INVALID, "run_observation: a dm_sink needs dm_delays");
+    if (opt.sps_widths < 0 || opt.sps_widths > 8) return set_error(BF_ERR_INVALID, "run_observation: sps_widths must be 0 (off) .. 8");
+    if ((opt.sps_widths || opt.sps_sink) && !opt.dm_delays) return set_error(BF_ERR_INVALID, "run_observation: the single-pulse search needs the DM stage (dm_delays)");
+    if (opt.sps_sink && !opt.sps_widths) return set_error(BF_ERR_INVALID, "run_observation: a sps_sink needs sps_widths > 0");
     if (opt.comm && opt.dm_sink && !is_root) return set_error(BF_ERR_INVALID, "run_observation: only the gather root may have a dm_sink");
     if (opt.dm_split_trials && (!opt.comm || opt.gather_root != BF_GATHER_ROOT_ALL))
         return set_error(BF_ERR_INVALID, "run_observation: dm_split_trials needs a sharded run gathered to every rank (BF_GATHER_ROOT_ALL)");
@@ -542,6 +547,8 @@ struct production_run {
     std::deque<dm_chunk> dm_pending;      // pushed, not yet delivered (their block's analysis event has not fired)
     std::vector<float*> dm_host;          // pinned chunk buffers, used round robin
     uint64_t dm_seq = 0, dm_times = 0, dm_chunks = 0;
+    std::vector<bf_sps_candidate> cands;  // what bf_sps_collect returns for one chunk
+    uint64_t sps_candidates = 0;
 
     int create_handle_and_weights(const antenna* pos, const beam_direction* dir)
     {
@@ -566,6 +573,13 @@ struct production_run {
                 float* chunk = nullptr;
                 if ((rc = dev.alloc_pinned((size_t)plan.dm_count * plan.dm_rows * cfg.n_beams, &chunk)) != BF_OK) return rc;
                 dm_host.push_back(chunk);
+            }
+            if (opt.sps_widths > 0) {   // the search stage: as many result sets as chunk buffers (a chunk in flight = a search push in flight)
+                rc = bf_sps_create(dev.h, plan.dm_count, plan.dm_first, opt.sps_widths, plan.dm_rows, (int)n_buf, /*baseline_pushes=*/8,
+                                   /*min_samples=*/64, opt.sps_threshold, &dev.sps);
+                if (rc == BF_OK) rc = bf_dm_stream_attach_search(dev.dm, dev.sps);
+                if (rc != BF_OK) return gpu_error(log, rc);
+                cands.resize((size_t)plan.dm_count * cfg.n_beams);
             }
         }
         if (plan.block_launch)   // the per-queue block buffers are allocated on first use: do that here, not inside the timed loop
@@ -692,6 +706,16 @@ struct production_run {
             const dm_chunk c = dm_pending.front();
             dm_pending.pop_front();
             dm_times += (uint64_t)c.n_t;
+            if (dev.sps) {   // one search push per chunk, in the same order: its kernels ran on the chunk's queue; the collect waits for its records
+                size_t n = 0;
+                const int rc = bf_sps_collect(dev.sps, cands.data(), cands.size(), &n);
+                if (rc != BF_OK) return gpu_error(log, rc);
+                sps_candidates += n;
+                if (opt.sps_sink && !opt.sps_sink->deliver(cands.data(), n)) {
+                    log << "ERROR: candidate sink failed at output time " << c.first_t << std::endl;
+                    return BF_ERR_STATE;
+                }
+            }
             if (!opt.dm_sink) continue;
             dm_chunks++;
             if (!opt.dm_sink->deliver(c.first_t, c.n_t, plan.dm_count, cfg.n_beams, c.host)) {
@@ -763,6 +787,7 @@ int run_observation(const bf_config& cfg, const observation_options& opt, block_
     bf_stream_sync(h, -1);  // :560-562
     if (opt.sink) opt.sink->close();
     if (opt.dm_sink) opt.dm_sink->close();
+    if (opt.sps_sink) opt.sps_sink->close();
     const uint64_t chunks = obs_state.get_current_transfer_gemm() * cfg.n_out_per_gemm;  // :552
     const double rate = (double)source.get_block_size() * obs_state.get_blocks_transfer_queue() / ms / 1e6;  // :554
     closing_report(log, ms, chunks, ms / (chunks ? chunks : 1), rate, run.plan.block_launch ? "bf_enqueue_block" : kUnitLaunchPattern);
@@ -775,11 +800,15 @@ int run_observation(const bf_config& cfg, const observation_options& opt, block_
         res->last_gemm = run.last_gemm;
         res->dm_times = run.dm_times;
         res->dm_chunks = run.dm_chunks;
+        res->sps_candidates = run.sps_candidates;
     }
     if (run.plan.dm_run)
         log << "DM stage: trials " << run.plan.dm_first << " .. " << run.plan.dm_first + run.plan.dm_count - 1 << " of " << opt.n_dm << ", "
             << run.dm_times << " output times (largest delay " << bf_dm_stream_max_delay(run.dev.dm) << " samples carried over on the device)"
             << std::endl;
+    if (run.dev.sps)
+        log << "Single-pulse search: boxcar widths 1 .. " << (1 << (opt.sps_widths - 1)) << ", " << run.sps_candidates << " candidates at S/N >= "
+            << opt.sps_threshold << std::endl;
     return BF_OK;
 }
 

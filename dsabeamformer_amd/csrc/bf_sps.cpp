@@ -1,0 +1,268 @@
+// bf_sps.cpp -- single-pulse search behind the DM stage (include/dsabf.h: bf_sps_*; contract and measurements: docs/SINGLE_PULSE.md).
+// The device code is csrc/sps/bf_sps.hip; this file owns the stage's memory, orders its pushes and selects the candidates.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <deque>
+#include <new>
+
+#include "bf_runtime_internal.h"
+#include "sps/bf_sps_kernels.h"
+
+struct bf_sps {
+    bf_handle* h = nullptr;
+    int n_dm = 0, dm_first = 0, n_widths = 0, halo = 0, max_t = 0, max_in_flight = 0, baseline = 0, n_beams = 0;
+    uint64_t min_samples = 0;
+    double threshold = 0;
+    // The last `halo` = 2^(K-1) - 1 samples of every (trial, beam), [n_dm][halo][n_beams], zeros where the stream had none yet.
+    // Two of them: push j reads d_tail[j % 2] (all its tiles do) while its finishing pass writes d_tail[(j + 1) % 2].
+    float* d_tail[2] = {nullptr, nullptr};
+    bf_sps_peak* d_part_peaks = nullptr;   // per-tile records of the push that is running (pushes run one after the other)
+    bf_sps_stat* d_part_stats = nullptr;
+    // Push j leaves its records in set j % max_in_flight: on the device, then -- on the stage's own copy queue, so that the queue
+    // the chunk came from goes on as soon as the kernels have read it -- in pinned host memory.
+    struct result_set {
+        bf_sps_peak *d_peaks = nullptr, *h_peaks = nullptr;
+        bf_sps_stat *d_stats = nullptr, *h_stats = nullptr;
+        hipEvent_t kernels_done = nullptr, copied = nullptr;
+        uint64_t first_t = 0;
+        int n_t = 0;
+    };
+    std::vector<result_set> sets;
+    hipStream_t copy_q = nullptr;
+    uint64_t n_push = 0, n_collected = 0;
+    uint64_t seen = 0;                     // samples of the series in front of the next push
+    // the push last collected (bf_sps_last_records) and the statistics of the last `baseline` collected pushes, oldest first
+    std::vector<bf_sps_peak> last_peaks;
+    std::vector<bf_sps_stat> last_stats, totals;
+    uint64_t last_first_t = 0;
+    int last_n_t = 0;
+    std::deque<std::pair<int, std::vector<bf_sps_stat>>> window;
+    bf_dm_stream* feeder = nullptr;        // the DM stage this one is attached to
+};
+
+void dsabf::rt::sps_release(bf_sps* s)
+{
+    for (auto& r : s->sets) {
+        if (r.copied) {
+            (void)hipEventSynchronize(r.copied);   // (never recorded: returns at once)
+            (void)hipEventDestroy(r.copied);
+        }
+        if (r.kernels_done) (void)hipEventDestroy(r.kernels_done);
+        (void)hipFree(r.d_peaks);
+        (void)hipFree(r.d_stats);
+        (void)hipHostFree(r.h_peaks);
+        (void)hipHostFree(r.h_stats);
+        r = bf_sps::result_set();
+    }
+    if (s->copy_q) (void)hipStreamDestroy(s->copy_q);
+    for (void* p : {(void*)s->d_tail[0], (void*)s->d_tail[1], (void*)s->d_part_peaks, (void*)s->d_part_stats}) (void)hipFree(p);
+    s->copy_q = nullptr;
+    s->d_tail[0] = s->d_tail[1] = nullptr;
+    s->d_part_peaks = nullptr;
+    s->d_part_stats = nullptr;
+    s->h = nullptr;
+}
+
+int dsabf::rt::sps_check_attach(const bf_sps* s, const bf_handle* h, int n_dm, int max_rows)
+{
+    if (!s->h) return fail(BF_ERR_STATE, "the handle of this search stage has been destroyed");
+    if (s->h != h) return fail(BF_ERR_INVALID, "bf_dm_stream_attach_search: the two stages belong to different handles");
+    if (s->n_dm != n_dm) return fail(BF_ERR_INVALID, "bf_dm_stream_attach_search: the search stage has %d trials, the DM stage %d", s->n_dm, n_dm);
+    if (s->max_t < max_rows)
+        return fail(BF_ERR_INVALID, "bf_dm_stream_attach_search: max_t_per_push %d < max_rows_per_push %d", s->max_t, max_rows);
+    if (s->feeder) return fail(BF_ERR_STATE, "bf_dm_stream_attach_search: the search stage is attached to another DM stage");
+    return BF_OK;
+}
+
+int dsabf::rt::sps_max_in_flight(const bf_sps* s) { return s->max_in_flight; }
+void dsabf::rt::sps_set_feeder(bf_sps* s, bf_dm_stream* dm) { s->feeder = dm; }
+
+extern "C" {
+
+int bf_sps_create(bf_handle* h, int n_dm, int dm_first, int n_widths, int max_t_per_push, int max_in_flight, int baseline_pushes,
+                  int min_samples, double threshold, bf_sps** out)
+{
+    if (!out) return fail(BF_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (n_widths < 1 || n_widths > dsabf::kSpsMaxWidths)
+        return fail(BF_ERR_INVALID, "bf_sps_create: n_widths must be 1 .. %d (boxcar widths 1 .. 2^(n_widths-1)), not %d", dsabf::kSpsMaxWidths, n_widths);
+    if (!h) return fail(BF_ERR_INVALID, "bf_sps_create: the handle is NULL");
+    if (n_dm <= 0 || n_dm > 65535 || dm_first < 0 || max_t_per_push <= 0 || max_in_flight <= 0 || baseline_pushes <= 0 || min_samples < 0)
+        return fail(BF_ERR_INVALID, "bf_sps_create: need 0 < n_dm <= 65535, dm_first >= 0, max_t_per_push, max_in_flight, baseline_pushes > 0, min_samples >= 0");
+    if (!(threshold == threshold)) return fail(BF_ERR_INVALID, "bf_sps_create: threshold is NaN");
+    ON_DEVICE(h);
+    bf_sps* s = new (std::nothrow) bf_sps();
+    if (!s) return fail(BF_ERR_DEVICE, "out of host memory");
+    s->h = h;
+    s->n_dm = n_dm;
+    s->dm_first = dm_first;
+    s->n_widths = n_widths;
+    s->halo = dsabf::sps_halo(n_widths);
+    s->max_t = max_t_per_push;
+    s->max_in_flight = max_in_flight;
+    s->baseline = baseline_pushes;
+    s->min_samples = (uint64_t)min_samples;
+    s->threshold = threshold;
+    s->n_beams = h->cfg.n_beams;
+    const size_t n_db = (size_t)n_dm * s->n_beams, n_rec = (size_t)n_widths * n_db, tiles = (size_t)dsabf::sps_tiles(max_t_per_push);
+    const size_t tail_bytes = n_db * s->halo * sizeof(float);
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < 2 && e == hipSuccess && tail_bytes; k++) {
+        e = hipMalloc((void**)&s->d_tail[k], tail_bytes);
+        if (e == hipSuccess) e = hipMemset(s->d_tail[k], 0, tail_bytes);
+    }
+    if (e == hipSuccess) e = hipMalloc((void**)&s->d_part_peaks, tiles * n_rec * sizeof(bf_sps_peak));
+    if (e == hipSuccess) e = hipMalloc((void**)&s->d_part_stats, tiles * n_db * sizeof(bf_sps_stat));
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&s->copy_q, hipStreamNonBlocking);
+    s->sets.resize((size_t)max_in_flight);
+    for (auto& r : s->sets) {
+        if (e == hipSuccess) e = hipMalloc((void**)&r.d_peaks, n_rec * sizeof(bf_sps_peak));
+        if (e == hipSuccess) e = hipMalloc((void**)&r.d_stats, n_db * sizeof(bf_sps_stat));
+        if (e == hipSuccess) e = hipHostMalloc((void**)&r.h_peaks, n_rec * sizeof(bf_sps_peak), hipHostMallocDefault);
+        if (e == hipSuccess) e = hipHostMalloc((void**)&r.h_stats, n_db * sizeof(bf_sps_stat), hipHostMallocDefault);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&r.kernels_done, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&r.copied, hipEventDisableTiming);
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();   // (the memsets above ran on the null stream: pushes come on non-blocking ones)
+    h->sps_stages.push_back(s);
+    if (e != hipSuccess) {
+        bf_sps_destroy(s);
+        return fail(BF_ERR_DEVICE, "bf_sps_create: %s", hipGetErrorString(e));
+    }
+    *out = s;
+    return BF_OK;
+}
+
+int bf_sps_destroy(bf_sps* s)
+{
+    if (!s) return BF_OK;
+    if (s->feeder) dm_stream_drop_search(s->feeder);
+    if (s->h) {   // (NULL: the handle went first and took the device memory with it)
+        bf_handle* h = s->h;
+        DeviceScope dev_scope_(h->device);
+        h->sps_stages.erase(std::remove(h->sps_stages.begin(), h->sps_stages.end(), s), h->sps_stages.end());
+        sps_release(s);
+    }
+    delete s;
+    return BF_OK;
+}
+
+int bf_sps_pending(const bf_sps* s) { return s ? (int)(s->n_push - s->n_collected) : BF_ERR_INVALID; }
+
+int bf_sps_push(bf_sps* s, const float* d_chunk, int n_t, uint64_t first_t, void* hip_stream)
+{
+    if (!s || !d_chunk) return fail(BF_ERR_INVALID, "NULL argument");
+    if (n_t <= 0 || n_t > s->max_t) return fail(BF_ERR_INVALID, "n_t must be 1 .. %d (max_t_per_push)", s->max_t);
+    if (!s->h) return fail(BF_ERR_STATE, "the handle of this search stage has been destroyed");
+    if (s->n_push - s->n_collected >= (uint64_t)s->max_in_flight)
+        return fail(BF_ERR_STATE, "bf_sps_push: %d pushes are uncollected (max_in_flight): bf_sps_collect first", s->max_in_flight);
+    bf_handle* h = s->h;
+    ON_DEVICE(h);
+    hipStream_t q = as_stream(hip_stream);
+    bf_sps::result_set& r = s->sets[s->n_push % s->max_in_flight];
+    // behind the kernels of the push before this one, whatever queue they ran on: they wrote the tail this one reads, and the
+    // per-tile records are shared
+    if (s->n_push) HIP_TRY(hipStreamWaitEvent(q, s->sets[(s->n_push - 1) % s->max_in_flight].kernels_done, 0));
+    dsabf::SpsBuffers buf{s->d_tail[s->n_push % 2], s->d_tail[(s->n_push + 1) % 2], s->d_part_peaks, s->d_part_stats, r.d_peaks, r.d_stats};
+    HIP_TRY(dsabf::launch_sps_push(d_chunk, s->n_dm, n_t, s->n_beams, s->n_widths, s->seen, buf, q));
+    HIP_TRY(hipEventRecord(r.kernels_done, q));
+    HIP_TRY(hipStreamWaitEvent(s->copy_q, r.kernels_done, 0));
+    const size_t n_db = (size_t)s->n_dm * s->n_beams;
+    HIP_TRY(hipMemcpyAsync(r.h_peaks, r.d_peaks, s->n_widths * n_db * sizeof(bf_sps_peak), hipMemcpyDeviceToHost, s->copy_q));
+    HIP_TRY(hipMemcpyAsync(r.h_stats, r.d_stats, n_db * sizeof(bf_sps_stat), hipMemcpyDeviceToHost, s->copy_q));
+    HIP_TRY(hipEventRecord(r.copied, s->copy_q));
+    r.first_t = first_t;
+    r.n_t = n_t;
+    s->seen += (uint64_t)n_t;
+    s->n_push++;
+    return BF_OK;
+}
+
+int bf_sps_collect(bf_sps* s, bf_sps_candidate* out, size_t max_out, size_t* n_out)
+{
+    if (!s || !out || !n_out) return fail(BF_ERR_INVALID, "NULL argument");
+    *n_out = 0;
+    const size_t n_db = (size_t)s->n_dm * s->n_beams;
+    if (max_out < n_db) return fail(BF_ERR_INVALID, "bf_sps_collect: room for %zu candidates, a push can give n_dm * n_beams = %zu", max_out, n_db);
+    if (!s->h) return fail(BF_ERR_STATE, "the handle of this search stage has been destroyed");
+    if (s->n_collected == s->n_push) return fail(BF_ERR_STATE, "bf_sps_collect: no push is pending");
+    bf_handle* h = s->h;
+    ON_DEVICE(h);
+    bf_sps::result_set& r = s->sets[s->n_collected % s->max_in_flight];
+    HIP_TRY(hipEventSynchronize(r.copied));
+    s->last_peaks.assign(r.h_peaks, r.h_peaks + s->n_widths * n_db);
+    s->last_stats.assign(r.h_stats, r.h_stats + n_db);
+    s->last_first_t = r.first_t;
+    s->last_n_t = r.n_t;
+    s->n_collected++;   // (the set is free from here on)
+    s->window.emplace_back(r.n_t, s->last_stats);
+    while (s->window.size() > (size_t)s->baseline) s->window.pop_front();
+    uint64_t n = 0;
+    s->totals.assign(n_db, bf_sps_stat{0.0, 0.0});
+    for (const auto& w : s->window) {   // oldest first
+        n += (uint64_t)w.first;
+        for (size_t i = 0; i < n_db; i++) {
+            s->totals[i].sum += w.second[i].sum;
+            s->totals[i].sumsq += w.second[i].sumsq;
+        }
+    }
+    return bf_sps_select(s->last_peaks.data(), s->totals.data(), n, s->n_widths, s->n_dm, s->n_beams, s->last_first_t, s->dm_first,
+                         s->min_samples, s->threshold, out, max_out, n_out);
+}
+
+int bf_sps_last_records(const bf_sps* s, const bf_sps_peak** peaks, const bf_sps_stat** stats, uint64_t* first_t, int* n_t)
+{
+    if (!s) return fail(BF_ERR_INVALID, "NULL argument");
+    if (s->last_peaks.empty()) return fail(BF_ERR_STATE, "bf_sps_last_records: nothing has been collected yet");
+    if (peaks) *peaks = s->last_peaks.data();
+    if (stats) *stats = s->last_stats.data();
+    if (first_t) *first_t = s->last_first_t;
+    if (n_t) *n_t = s->last_n_t;
+    return BF_OK;
+}
+
+int bf_sps_select(const bf_sps_peak* peaks, const bf_sps_stat* totals, uint64_t n, int n_widths, int n_dm, int n_beams, uint64_t first_t,
+                  int dm_first, uint64_t min_samples, double threshold, bf_sps_candidate* out, size_t max_out, size_t* n_out)
+{
+    if (!peaks || !totals || !n_out || (!out && max_out)) return fail(BF_ERR_INVALID, "NULL argument");
+    *n_out = 0;
+    if (n_widths < 1 || n_widths > dsabf::kSpsMaxWidths || n_dm <= 0 || n_beams <= 0)
+        return fail(BF_ERR_INVALID, "bf_sps_select: need 1 <= n_widths <= %d, n_dm, n_beams > 0", dsabf::kSpsMaxWidths);
+    if (n == 0 || n < min_samples) return BF_OK;
+    const size_t n_db = (size_t)n_dm * n_beams;
+    size_t m = 0;
+    for (size_t i = 0; i < n_db; i++) {
+        const double mu = totals[i].sum / (double)n;
+        const double var = totals[i].sumsq / (double)n - mu * mu;
+        const double sigma = std::sqrt(var > 0.0 ? var : 0.0);
+        if (sigma == 0.0) continue;
+        int best_k = -1;
+        double best = 0.0;
+        for (int k = 0; k < n_widths; k++) {
+            const bf_sps_peak& p = peaks[(size_t)k * n_db + i];
+            if (p.t_end < 0) continue;
+            const double w = (double)(1 << k);
+            const double snr = ((double)p.value - w * mu) / (sigma * std::sqrt(w));
+            if (best_k < 0 || snr > best) {   // (strictly: the lowest k keeps a tie)
+                best_k = k;
+                best = snr;
+            }
+        }
+        if (best_k < 0 || !(best >= threshold)) continue;
+        if (m >= max_out) return fail(BF_ERR_INVALID, "bf_sps_select: more than max_out = %zu candidates", max_out);
+        const bf_sps_peak& p = peaks[(size_t)best_k * n_db + i];
+        bf_sps_candidate c;
+        c.t_start = first_t + (uint64_t)p.t_end - (uint64_t)((1 << best_k) - 1);
+        c.dm = dm_first + (int)(i / (size_t)n_beams);
+        c.beam = (int)(i % (size_t)n_beams);
+        c.width = 1 << best_k;
+        c.peak = p.value;
+        c.snr = best;
+        out[m++] = c;
+    }
+    *n_out = m;
+    return BF_OK;
+}
+
+}  // extern "C"

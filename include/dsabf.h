@@ -282,6 +282,60 @@ int bf_dm_stream_push(bf_dm_stream *s, const float *d_rows, int n_rows, float *h
                       void *hip_stream);
 int bf_dm_stream_output_device(bf_dm_stream *s, float **d_out);
 
+/* ---- Single-pulse search behind the DM stage (docs/SINGLE_PULSE.md) ----------------------------------------------------
+ * The reference exists to "search for FRBs in real time" (README.md:11) and stops at a DM-0 collapse copied to the host
+ * (src/beamformer.cu:498-510).  A bf_sps consumes the chunks [n_dm][n_t][beam] of a bf_dm_stream on the device and turns them
+ * into "pulse at this time, trial, beam, width, S/N":
+ *   boxcar sums of widths w_k = 2^k, k < n_widths <= 8, as the balanced pairwise tree S_0[t] = x[t],
+ *   S_k[t] = S_{k-1}[t] + S_{k-1}[t - 2^(k-1)] (fp32, one rounding per add, no running sum), defined for t >= 2^k - 1 counted
+ *   from the first sample the stage was given; the stage carries the last 2^(n_widths-1) - 1 samples of every (trial, beam) on
+ *   the device, so the bits of S_k[t] do not depend on how the series was cut into pushes;
+ *   per push and (k, trial, beam) one bf_sps_peak: the maximum of S_k over the push's times and the FIRST time attaining it,
+ *   relative to the push's first time (value -inf, t_end -1: no time of the push qualifies) -- layout [n_widths][n_dm][n_beams];
+ *   per push and (trial, beam) one bf_sps_stat: fp64 sum and sum of squares of x -- layout [n_dm][n_beams].
+ * bf_sps_push is asynchronous on hip_stream; pushes of one stage are ordered by the stage itself, whichever queues they are
+ * issued on (they share the carried samples).  Push j leaves its records in pinned set j % max_in_flight; a push whose set is
+ * still uncollected returns BF_ERR_STATE.  bf_sps_collect waits for the oldest uncollected push, selects its candidates
+ * (bf_sps_select over the statistics of the last baseline_pushes pushes, that one included) and returns them; max_out must be
+ * at least n_dm * n_beams (BF_ERR_INVALID, nothing consumed); nothing pending: BF_ERR_STATE.  bf_sps_last_records: host pointers
+ * to the raw records of the push just collected, valid until the next collect.  Lifetime as for a bf_dm_stream: a handle that
+ * goes first releases the device memory, the stage then answers BF_ERR_STATE and can still be destroyed.
+ * bf_sps_select is the selection as a pure host function (fp64, no GPU): totals[d][b] = the window's sums over n samples,
+ *   mu = sum / n, sigma = sqrt(max(sumsq / n - mu^2, 0)); (d, b) is skipped if n < min_samples or sigma == 0;
+ *   snr_k = (value_k - w_k mu) / (sigma sqrt(w_k)) for records with t_end >= 0; at most one candidate per (d, b): the k of the
+ *   largest snr_k (lowest k on ties), if snr_k >= threshold; t_start = first_t + t_end - (w_k - 1), dm = dm_first + d;
+ *   candidates leave in (d, b) order.  Returns BF_ERR_INVALID if they do not fit max_out.
+ * bf_dm_stream_attach_search(dm, sps) (sps == NULL detaches): from then on every bf_dm_stream_push that emits n_t_out > 0 also
+ * issues the search push for its chunk, on the same queue and before the chunk's buffer can be handed to a later push.  n_dm
+ * must match and the stage's max_t_per_push must cover the DM stage's max_rows_per_push. */
+typedef struct bf_sps bf_sps;
+typedef struct bf_sps_peak {
+    float value;
+    int32_t t_end;
+} bf_sps_peak;
+typedef struct bf_sps_stat {
+    double sum, sumsq;
+} bf_sps_stat;
+typedef struct bf_sps_candidate {
+    uint64_t t_start; /* first sample of the boxcar, counted like first_t */
+    int32_t dm;       /* global trial index */
+    int32_t beam;
+    int32_t width;    /* w_k */
+    float peak;       /* S_k at the peak */
+    double snr;
+} bf_sps_candidate;
+int bf_sps_create(bf_handle *h, int n_dm, int dm_first, int n_widths, int max_t_per_push, int max_in_flight, int baseline_pushes,
+                  int min_samples, double threshold, bf_sps **out);
+int bf_sps_destroy(bf_sps *s);
+int bf_sps_push(bf_sps *s, const float *d_chunk, int n_t, uint64_t first_t, void *hip_stream);
+int bf_sps_collect(bf_sps *s, bf_sps_candidate *out, size_t max_out, size_t *n_out);
+int bf_sps_pending(const bf_sps *s);
+int bf_sps_last_records(const bf_sps *s, const bf_sps_peak **peaks, const bf_sps_stat **stats, uint64_t *first_t, int *n_t);
+int bf_sps_select(const bf_sps_peak *peaks, const bf_sps_stat *totals, uint64_t n, int n_widths, int n_dm, int n_beams,
+                  uint64_t first_t, int dm_first, uint64_t min_samples, double threshold, bf_sps_candidate *out, size_t max_out,
+                  size_t *n_out);
+int bf_dm_stream_attach_search(bf_dm_stream *dm, bf_sps *sps);
+
 /* ---- Multi-GPU: frequency shards and the gather of their detected powers -------------------------------
  * The reference runs 8 independent processes, one sub-band per GPU (`-g`, src/beamformer.cu:92-100,233; README.md:168)
  * and never brings their outputs together.  Here a handle may own any contiguous range of frequencies (bf_config.n_freq

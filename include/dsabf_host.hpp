@@ -12,6 +12,7 @@
 
 #include <condition_variable>
 #include <cstdint>
+#include <cstdio>
 #include <iosfwd>
 #include <mutex>
 #include <string>
@@ -531,6 +532,47 @@ public:
     }
 };
 
+// ---- Single-pulse search behind the DM stage (include/dsabf.h: bf_sps_*; docs/SINGLE_PULSE.md) ------------------------------
+// With observation_options::sps_widths > 0 run_observation creates a bf_sps next to the DM stage, attaches it (every chunk is
+// searched on the device, on the queue that produced it) and hands each chunk's candidates to a sps_candidate_sink, in time
+// order, once the block's analysis event has fired.
+struct sps_candidate_sink {
+    virtual ~sps_candidate_sink() {}
+    virtual bool deliver(const bf_sps_candidate* cands, size_t n) = 0;
+    virtual void close() {}
+};
+
+// Text file: a `#` header line, then one line per candidate: t_start dm beam width snr peak (dm: the global trial index).
+class sps_file_sink : public sps_candidate_sink {
+    FILE* fp = nullptr;
+    uint64_t written = 0;
+
+public:
+    explicit sps_file_sink(const char* path) : fp(fopen(path, "w"))
+    {
+        if (fp) fprintf(fp, "# t_start dm beam width snr peak\n");
+    }
+    ~sps_file_sink() override { close(); }
+    sps_file_sink(const sps_file_sink&) = delete;
+    sps_file_sink& operator=(const sps_file_sink&) = delete;
+    bool is_open() const { return fp != nullptr; }
+    bool deliver(const bf_sps_candidate* c, size_t n) override
+    {
+        if (!fp) return false;
+        for (size_t i = 0; i < n; i++)
+            if (fprintf(fp, "%llu %d %d %d %.17g %.9g\n", (unsigned long long)c[i].t_start, c[i].dm, c[i].beam, c[i].width, c[i].snr, (double)c[i].peak) < 0)
+                return false;
+        written += n;
+        return true;
+    }
+    void close() override
+    {
+        if (fp) fclose(fp);
+        fp = nullptr;
+    }
+    uint64_t get_candidates_written() const { return written; }
+};
+
 struct observation_options {
     int gpu = 0;          // -g
     int device = 0;
@@ -576,6 +618,12 @@ struct observation_options {
     // one more -- so the DM work scales with the GPUs.  Every rank may then have a dm_sink of its own; a chunk carries the rank's
     // trials only (dm_file_sink records the first one as DM_FIRST_TRIAL).
     bool dm_split_trials = false;
+    // Single-pulse search of every DM chunk (needs dm_delays): boxcar widths 1 .. 2^(sps_widths-1), 0 = off; candidates at or above
+    // sps_threshold (S/N against the mean and deviation of the last 8 chunks) go to sps_sink (may be NULL: the stage still runs),
+    // with global trial indices.  With dm_split_trials every rank searches its own trials and may have a sink of its own.
+    int sps_widths = 0;
+    double sps_threshold = 8.0;
+    sps_candidate_sink* sps_sink = nullptr;
 };
 struct observation_result {
     float observation_time_ms = 0;
@@ -586,6 +634,7 @@ struct observation_result {
     std::vector<long long> last_gemm;  // global gemm-unit index (block * N_GEMMS_PER_BLOCK + time_slice) behind each stream
     uint64_t dm_times = 0;          // output times the DM stage produced (dm_delays set): rows analysed - the largest delay
     uint64_t dm_chunks = 0;         // chunks handed to dm_sink
+    uint64_t sps_candidates = 0;    // candidates the search stage found (sps_widths > 0)
 };
 // The reference's production main() loop on top of the C-ABI.  pos/dir: antenna positions and beam directions.
 int run_observation(const bf_config& cfg, const observation_options& opt, block_source& source, const antenna* pos,
