@@ -1,5 +1,6 @@
 """GPU tests (-m gpu) of the round-5 surface; every call goes through the C-ABI of libdsabf.so."""
 import os
+import sys
 
 import numpy as np
 import pytest
@@ -347,13 +348,18 @@ def test_beam_cli_dm_stage_single_gpu_and_two_loopback_ranks(orc, tmp_path):
     """`beam -j 27 -M 40 -N 6 -T 0.02 -W dm.bin` (25 burn-in reads + 2 analysed blocks of the production geometry) on one GPU,
     and the same sub-band as `-R 2` shard processes (loopback stand-in for RCCL p2p): the gather root dedisperses the GATHERED
     band.  Each file is bit-equal to orc.dedisperse_dm over the whole detected series the run produced, ascending f over all
-    256 channels -- one GPU or two.  With -X the band goes to every rank and the TRIALS are split across the shards."""
+    256 channels -- one GPU or two.  With -X the band goes to every rank and the TRIALS are split across the shards; that run has
+    the single-pulse search on (-S -B -C): every shard's candidates are the oracle's over its own file."""
     from test_gpu_multirank import FAKE, SUPPORT  # noqa: F401  (built by that module's fixture; build here if it has not run)
     import subprocess
 
     from dsabeamformer_amd import build, host
 
     import dsabeamformer_amd as bfm
+
+    if SUPPORT not in sys.path:
+        sys.path.insert(0, SUPPORT)
+    import sps_oracle
 
     src = os.path.join(SUPPORT, "fake_rccl.cpp")
     if not os.path.exists(FAKE) or os.path.getmtime(FAKE) < os.path.getmtime(src):
@@ -407,8 +413,13 @@ def test_beam_cli_dm_stage_single_gpu_and_two_loopback_ranks(orc, tmp_path):
             # ---- -X: the same two shards, the powers gathered to EVERY rank (one all-gather), the ladder split: rank r dedisperses
             # trials [3 r, 3 r + 3) of the six and writes dm_x.bin.<r>; each file is the oracle's over ITS trials (a rank's window is
             # its own trials' largest delay, so the low-DM rank completes more output times)
-            outx = tmp_path / "dm_x.bin"
-            cmdx = lambda rk: [build.BEAM] + common + ["-R", "2", "-r", str(rk), "-I", str(tmp_path / "idx"), "-X", "-W", str(outx)]  # noqa: E731
+            # ... and with -S -B 4 -C every rank searches ITS trials (docs/SINGLE_PULSE.md §4): cands.<r>, trials numbered over the
+            # whole ladder.  Threshold 4: on this run's series (computable without a GPU: orc.beamform on the junk bytes, as above)
+            # the oracle finds 33 candidates among rank 0's 1536 (trial, beam, chunk) records and 22 among rank 1's, one chunk per
+            # analysed block; no S/N closer to 4 than a relative 7e-4.
+            outx, candx, thr = tmp_path / "dm_x.bin", tmp_path / "cands_x.txt", 4.0
+            cmdx = lambda rk: [build.BEAM] + common + ["-R", "2", "-r", str(rk), "-I", str(tmp_path / "idx"), "-X", "-W", str(outx),  # noqa: E731
+                                                       "-S", str(thr), "-B", "4", "-C", str(candx)]
             procs = [subprocess.Popen(cmdx(rk), env=dict(os.environ, DSABF_RCCL_LIB=FAKE), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
                      for rk in (0, 1)]
             outs = [p.communicate(timeout=900)[0] for p in procs]
@@ -420,6 +431,26 @@ def test_beam_cli_dm_stage_single_gpu_and_two_loopback_ranks(orc, tmp_path):
                 hdr, got, chunks = host.read_dm_file(str(outx) + ".%d" % rk)
                 assert int(hdr["N_DM"]) == 3 and int(hdr["DM_FIRST_TRIAL"]) == 3 * rk and int(hdr["MAX_DELAY"]) == d_r
                 assert np.array_equal(got, orc.dedisperse_dm(series, mine, T - d_r)), rk
+                # the candidates, recomputed from this rank's file: the same chunk boundaries, the driver's window of 8 chunks and
+                # 64-sample minimum (the oracle's defaults), trial numbers from the plan's dm_first
+                search = sps_oracle.Search(got, 4, dm_first=3 * rk, threshold=thr)
+                want = [c for _, n in chunks for c in search.push(n)["cands"]]
+                print("rank %d: candidates recomputed from dm_x.bin.%d: %d of %d records" % (rk, rk, len(want), 3 * 256 * len(chunks)))
+                assert 1 <= len(want) < 3 * 256 * len(chunks)
+                every = sps_oracle.Search(got, 4, dm_first=3 * rk, threshold=-np.inf)
+                snr = np.array([c[5] for _, n in chunks for c in every.push(n)["cands"]])
+                assert np.all(np.abs(snr - thr) > 1e-7 * thr)                          # no S/N on the threshold: 100 x the tolerance below
+                assert ("Single-pulse search: boxcar widths 1 .. 8, %d candidates" % len(want)) in outs[rk], outs[rk]
+                assert ("Wrote %d candidates to %s.%d" % (len(want), candx, rk)) in outs[rk]
+                lines = open(str(candx) + ".%d" % rk).read().splitlines()
+                assert lines[0].startswith("#") and len(lines) == 1 + len(want)
+                tab = np.array([l.split() for l in lines[1:]])
+                cand = np.zeros(len(want), [("t_start", np.uint64), ("dm", np.int32), ("beam", np.int32), ("width", np.int32), ("peak", np.float32), ("snr", np.float64)])
+                for i, f in enumerate(("t_start", "dm", "beam", "width", "snr", "peak")):
+                    cand[f] = tab[:, i].astype(cand.dtype[f])
+                sps_oracle.assert_candidates_equal(cand, want, rtol=1e-9)
+                assert np.all((cand["dm"] >= 3 * rk) & (cand["dm"] < 3 * rk + 3))      # numbered over the whole ladder
+            assert not os.path.exists(str(candx))                  # (one file per shard, none without a rank)
             assert int(delays[:3].max()) < D                       # (rank 0's window really is the shorter one)
 
 

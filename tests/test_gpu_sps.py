@@ -11,6 +11,7 @@ from conftest import ROOT
 
 sys.path.insert(0, os.path.join(ROOT, "tests", "support"))
 import sps_oracle  # noqa: E402
+from sps_stage import run_stage as _run_stage  # noqa: E402
 from test_sps_cpu import series_for  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -31,52 +32,6 @@ def bfmod():
     import dsabeamformer_amd as m
 
     return m
-
-
-def _run_stage(torch, bf, x, n_widths, sizes, max_t, lag=1, **kw):
-    """Pushes x [n_dm][T][n_b] through a SinglePulseSearch in pieces `sizes` (cycled) on two alternating HIP streams, collecting
-    `lag` pushes behind, and checks every collected push against the oracle: records to the bit, statistics to n_t 2^-52."""
-    from dsabeamformer_amd import api
-
-    n_dm, T, n_b = x.shape
-    orc = sps_oracle.Search(x, n_widths, **kw)
-    sps = api.SinglePulseSearch(bf, n_dm, n_widths, max_t, max_in_flight=lag + 1, **kw)
-    streams = [torch.cuda.Stream(), torch.cuda.Stream()]
-    keep, want, at, k, n_cands = [], [], 0, 0, 0
-
-    def collect():
-        nonlocal n_cands
-        w = want.pop(0)
-        cands = sps.collect()
-        rec = sps.last_records()
-        where = (w["first_t"], w["n_t"], n_widths, n_dm, n_b)
-        assert (rec["first_t"], rec["n_t"]) == (w["first_t"], w["n_t"]), where
-        assert np.array_equal(rec["t_end"], w["t_end"]), where
-        assert np.array_equal(rec["value"], w["value"]), where                      # the -inf records included
-        assert np.array_equal(rec["value"].view(np.uint32), w["value"].view(np.uint32)), where
-        rtol = w["n_t"] * 2.0 ** -52
-        assert np.allclose(rec["sum"], w["sum"], rtol=rtol, atol=0.0) and np.allclose(rec["sumsq"], w["sumsq"], rtol=rtol, atol=0.0), where
-        sps_oracle.assert_candidates_equal(cands, w["cands"], rtol=1e-9)
-        n_cands += len(cands)
-
-    while at < T:
-        n = min(sizes[k % len(sizes)], T - at)
-        chunk = torch.from_numpy(np.ascontiguousarray(x[:, at:at + n])).cuda()    # [n_dm][n][n_b], as bf_dm_stream_push emits it
-        keep.append(chunk)
-        sps.push(chunk, n, at, streams[k % 2].cuda_stream)
-        want.append(orc.push(n))
-        assert sps.pending == len(want)
-        if len(want) > lag:
-            collect()
-        at += n
-        k += 1
-    while want:
-        collect()
-    assert sps.pending == 0
-    with pytest.raises(Exception, match="no push is pending"):
-        sps.collect()
-    sps.close()
-    return n_cands
 
 
 # 130 = one whole 128-time tile and a second of 2 (129: of 1); three 1-row pushes in a row, far shorter than the carried tail

@@ -29,6 +29,23 @@ def series_for(n_dm, n_t, n_beams, seed):
     return (1e3 + rng.standard_normal((n_dm, n_t, n_beams)) * np.exp(rng.uniform(0.0, 6.0, (n_dm, n_t, n_beams)))).astype(np.float32)
 
 
+# The push-size cycle of tests/test_gpu_sps_shapes.py: 1-row pushes, one exact 128-time tile, a tile and one row, a tile less one row,
+# two exact tiles, three tiles (257), short pushes behind long ones; 1100 times = one pass of the cycle.
+SHAPE_SIZES = [1, 1, 1, 126, 128, 129, 3, 257, 127, 2, 256, 5, 64]
+SHAPE_T = sum(SHAPE_SIZES)
+
+
+def pushes_of(sizes, n_t):
+    """(first time, times) of every push when a series of n_t times is cut into pieces `sizes`, cycled."""
+    out, at, k = [], 0, 0
+    while at < n_t:
+        n = min(sizes[k % len(sizes)], n_t - at)
+        out.append((at, n))
+        at += n
+        k += 1
+    return out
+
+
 def _hand_built_records():
     """K = 4, 3 trials, 8 beams: every branch of the selection in one set of records."""
     K, n_dm, n_b, n = 4, 3, 8, 200
@@ -154,3 +171,21 @@ def test_the_oracle_pins_the_association():
     assert np.all(t[3:] == -1) and np.all(np.isneginf(v[3:])) and np.all(t[2] == 3 + np.argmax(ti[2][:, 3:5], axis=1) - 0)
     flat = sps_oracle.push_records(sps_oracle.tree_sums(np.ones((1, 40, 4), np.float32), 3), 10, 40)
     assert np.all(flat[1] == 0) and np.array_equal(flat[0][:, 0, 0], [1, 2, 4])
+
+
+@pytest.mark.parametrize("n_beams", [4, 68])
+def test_the_oracle_pins_the_association_on_the_shape_tests_series(n_beams):
+    """tests/test_gpu_sps_shapes.py compares peak values bit for bit on few beams and short pushes: also there -- its series, its
+    push boundaries in both rotations, 4 and 68 beams -- a left-to-right sum gives other peak bits than the tree for every width
+    from 4 on, so a kernel that associated differently at any level could not pass."""
+    K = 8
+    assert SHAPE_T == 1100 and max(SHAPE_SIZES) == 257
+    x = series_for(3, SHAPE_T, n_beams, 1000 * K + n_beams)
+    tree, run = sps_oracle.tree_sums(x, K), sps_oracle.running_sums(x, K)
+    for rot in (0, 3):
+        differs = np.zeros(K, bool)
+        for lo, n in pushes_of(SHAPE_SIZES[rot:] + SHAPE_SIZES[:rot], SHAPE_T):
+            pt, pr = sps_oracle.push_records(tree, lo, lo + n), sps_oracle.push_records(run, lo, lo + n)
+            assert np.array_equal(pt[1] < 0, pr[1] < 0)                   # the same records exist
+            differs |= [not np.array_equal(pt[0][k], pr[0][k]) for k in range(K)]
+        assert not differs[:2].any() and differs[2:].all(), (rot, differs)
