@@ -103,6 +103,8 @@ SIGNATURES = {
     "bf_timer_start": (C.c_int, [C.c_void_p]),
     "bf_timer_stop": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "bf_beamform_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "bf_incoherent_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "bf_set_incoherent_beam": (C.c_int, [C.c_void_p, C.c_int]),
     "bf_expand_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "bf_gemm_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bf_dedisperse_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -100,6 +100,14 @@ class Beamformer:
     def beamform(self, d_packed, n_units: int, d_out, stream: int = 0) -> None:
         check(self._lib.bf_beamform_device(self._h, _ptr(d_packed), int(n_units), _ptr(d_out), C.c_void_p(stream)))
 
+    def incoherent(self, d_packed, n_units: int, d_out, stride: int = 1, stream: int = 0) -> None:
+        """bf_incoherent_device: the incoherent beam of n_units gemm-units, one float per (unit, output, freq) ``stride`` floats apart."""
+        check(self._lib.bf_incoherent_device(self._h, _ptr(d_packed), int(n_units), _ptr(d_out), int(stride), C.c_void_p(stream)))
+
+    def set_incoherent_beam(self, beam: int) -> None:
+        """bf_set_incoherent_beam: every detect launch from now on overwrites beam column ``beam`` with the incoherent beam (-1: off)."""
+        check(self._lib.bf_set_incoherent_beam(self._h, int(beam)))
+
     def expand(self, d_in, nbytes: int, d_out, stream: int = 0) -> None:
         check(self._lib.bf_expand_device(self._h, _ptr(d_in), int(nbytes), _ptr(d_out), C.c_void_p(stream)))
 

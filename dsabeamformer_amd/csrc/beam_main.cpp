@@ -26,6 +26,9 @@
 //                                                   searched on the device with boxcar widths 1 .. 2^(n_widths-1) [6]; candidates at
 //                                                   S/N >= snr to cand_file, one text line each: t_start dm beam width snr peak.
 //                                                   With -X: cand_file.<r>, trials numbered over the whole ladder.  Needs -M.
+//   beam -j n_blocks ... -i beam                    the incoherent beam (docs/INCOHERENT_BEAM.md): beam column `beam` of the detected
+//                                                   stream carries the antenna powers summed over the antennas instead of a tied beam,
+//                                                   for -w / -K, the DM stage and the search alike.  With -R: every shard, same index.
 //
 // With the reference's `make debug` geometry (default) it generates synthetic point-source voltages on the CPU,
 // streams them through the observation loop and writes bin/data.py (dedispersed beam responses, one row per source)
@@ -68,9 +71,11 @@ int main(int argc, char* argv[])
     int sps_widths = 6;             // -B
     bool sps_on = false, sps_widths_given = false;
     std::string cand_path;          // -C
+    int ib_beam = -1;               // -i: the beam column that carries the incoherent beam (-1: none)
+    bool ib_given = false;
 
     int arg = 0;
-    while ((arg = getopt(argc, argv, "s:g:p:d:o:D:a:c:k:K:j:w:R:r:I:M:N:T:W:Q:S:B:C:XuvhH")) != -1) {  // src/beamformer.cu:41-43 (+ -o -D -a -v)
+    while ((arg = getopt(argc, argv, "s:g:p:d:o:D:a:c:k:K:j:w:R:r:I:M:N:T:W:Q:S:B:C:i:XuvhH")) != -1) {  // src/beamformer.cu:41-43 (+ -o -D -a -v)
         switch (arg) {
             case 's': sources = optarg; break;                 // :77-89
             case 'g': opt.gpu = atoi(optarg); break;           // :92-100
@@ -94,6 +99,7 @@ int main(int argc, char* argv[])
             case 'S': sps_snr = atof(optarg); sps_on = true; break;
             case 'B': sps_widths = atoi(optarg); sps_widths_given = true; break;
             case 'C': cand_path = optarg; break;
+            case 'i': ib_beam = atoi(optarg); ib_given = true; break;
             case 'u': per_unit = true; break;                   // the reference's launch pattern: one launch per gemm-unit
             case 'v': opt.verbose = true; cfg.verbose = 1; break;
             case 'c': core = atoi(optarg); break;              // :59-65
@@ -118,6 +124,8 @@ int main(int argc, char* argv[])
                              " -S snr [-B n_widths] [-C file]   single-pulse search of every DM chunk: boxcar widths 1 .. 2^(n_widths-1) [6],\n"
                              "                         candidates at S/N >= snr to file (t_start dm beam width snr peak; with -X: file.<rank>);\n"
                              "                         requires -M: without it (or -B / -C without -S) beam exits with a usage error\n"
+                             " -i beam                 observation mode: beam column `beam` of the detected stream carries the incoherent beam\n"
+                             "                         (antenna powers summed over the antennas, no weights) for every consumer; 0 <= beam < N_BEAMS\n"
                              " -H                      this text\n";
                 return EXIT_SUCCESS;
             default: usage(true, std::cerr); return EXIT_FAILURE;
@@ -133,6 +141,14 @@ int main(int argc, char* argv[])
     }
     if (sps_on && (sps_widths < 1 || sps_widths > 8)) {
         fprintf(stderr, "beam: -B %d: n_widths must be 1 .. 8\n", sps_widths);
+        return EXIT_FAILURE;
+    }
+    if (ib_given && (ib_beam < 0 || ib_beam >= cfg.n_beams)) {
+        fprintf(stderr, "beam: -i %d: the incoherent beam takes a beam index 0 .. %d\n", ib_beam, cfg.n_beams - 1);
+        return EXIT_FAILURE;
+    }
+    if (ib_given && junk_blocks < 0 && ring_key.empty()) {
+        fprintf(stderr, "beam: -i (incoherent beam) belongs to the observation mode: give -j n_blocks or -k ring\n");
         return EXIT_FAILURE;
     }
     opt.positions = positions.empty() ? nullptr : positions.c_str();
@@ -243,6 +259,7 @@ int main(int argc, char* argv[])
         oopt.world = world;
         oopt.rank = rank;
         oopt.comm = comm;
+        oopt.incoherent_beam = ib_beam;
         const bf_config& sink_cfg = comm ? full_cfg : pcfg;
         if (comm && rank != 0) {          // only the gather root has a consumer
             out_ring.clear();

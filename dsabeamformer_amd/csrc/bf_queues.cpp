@@ -1,6 +1,17 @@
 // bf_queues.cpp -- the compute queues of a handle (include/dsabf.h): the coalescing of bf_enqueue_gemm_unit, the per-queue block
 // buffers, and the copies and syncs that order a caller's work against the queues.
 #include "bf_runtime_internal.h"
+#include "ib/bf_incoherent.h"
+
+int dsabf::rt::launch_detect(bf_handle* h, const void* in, int n_units, float* out, hipStream_t s)
+{
+    h->n_fused_launches++;
+    HIP_TRY(dsabf::launch_fused(h->geom, h->d_wimage, h->d_wimage_p, in, n_units, out, h->n_cus, s));
+    if (h->ib_beam >= 0)   // the tied beam of that column has been computed like every other: overwrite it
+        HIP_TRY(dsabf::launch_incoherent(h->geom.n_ant, h->geom.n_freq, h->geom.n_ipo, h->geom.n_out, in, n_units, out + h->ib_beam,
+                                         (size_t)h->geom.n_beams, h->n_cus, s));
+    return BF_OK;
+}
 
 static int check_queue(const bf_handle* h, int q)
 {
@@ -108,9 +119,7 @@ int dsabf::rt::flush_units(bf_handle* h)
         while (j < n && follows(j)) j++;
         const uint8_t* in = h->d_data + per_gemm * ((size_t)h->cfg.n_gemms_per_block * units[i].slot + units[i].time_slice);
         if (int rc = preserve_last_units(h, q, (size_t)units[i].time_slice, (size_t)units[i].time_slice + (j - i), &reassigned)) return rc;
-        h->n_fused_launches++;
-    HIP_TRY(dsabf::launch_fused(h->geom, h->d_wimage, h->d_wimage_p, in, (int)(j - i), blk + per_det * (size_t)units[i].time_slice,
-                                    h->n_cus, s));
+        if (int rc = launch_detect(h, in, (int)(j - i), blk + per_det * (size_t)units[i].time_slice, s)) return rc;
         for (size_t a = i; a < j;) {     // DM-0 rows of the run: one launch per stretch of units that asked for one
             if (!units[a].ded) {
                 a++;
@@ -176,8 +185,7 @@ int bf_enqueue_gemm_unit(bf_handle* h, int stream_idx, int slot, int time_slice,
         // reading them there): overwrite it behind that queue's work
         if (int rc = queue_waits_for(h, stream_idx, h->last_q[stream_idx])) return rc;
     }
-    h->n_fused_launches++;
-    HIP_TRY(dsabf::launch_fused(h->geom, h->d_wimage, h->d_wimage_p, in, 1, out, h->n_cus, s));
+    if (int rc = launch_detect(h, in, 1, out, s)) return rc;
     if (host_out) HIP_TRY(hipMemcpyAsync(host_out, out, per_det * sizeof(float), hipMemcpyDeviceToHost, s));
     h->last_out[stream_idx] = out;
     h->last_q[stream_idx] = stream_idx;
@@ -210,8 +218,7 @@ static int enqueue_block_impl(bf_handle* h, int stream_idx, int slot, int first_
     }
     const uint8_t* in = h->d_data + per_gemm * ((size_t)h->cfg.n_gemms_per_block * slot + first_unit);
     hipStream_t s = h->streams[stream_idx];
-    h->n_fused_launches++;
-    HIP_TRY(dsabf::launch_fused(h->geom, h->d_wimage, h->d_wimage_p, in, n_units, out, h->n_cus, s));
+    if (int rc = launch_detect(h, in, n_units, out, s)) return rc;
     if (!host_out) return BF_OK;
     return copy_runs_to_host((size_t)n_units, per_det, [&](size_t k) { return host_out[k]; }, [&](size_t k) { return out + per_det * k; },
                              [](size_t) { return true; }, s);
@@ -334,6 +341,19 @@ int bf_enqueue_dedisperse(bf_handle* h, int stream_idx, float* host_out_row)
     if (int rc = queue_waits_for(h, lq, stream_idx)) return rc;
     if (host_out_row)
         HIP_TRY(hipMemcpyAsync(host_out_row, ded, (size_t)h->cfg.n_beams * sizeof(float), hipMemcpyDeviceToHost, s));
+    return BF_OK;
+}
+
+int bf_set_incoherent_beam(bf_handle* h, int beam)
+{
+    if (!h) return fail(BF_ERR_INVALID, "handle is NULL");
+    if (beam < -1 || beam >= h->cfg.n_beams) return fail(BF_ERR_INVALID, "incoherent beam %d: must be -1 (off) or a beam index below %d", beam, h->cfg.n_beams);
+    if (beam >= 0 && !dsabf::incoherent_supported(h->geom.n_ant, h->geom.n_ipo))
+        return fail(BF_ERR_INVALID, "incoherent beam: 128 * %d antennas * %d samples per output exceeds 2^24 (the sum would not convert to float exactly)",
+                    h->geom.n_ant, h->geom.n_ipo);
+    ON_DEVICE(h);
+    FLUSH_UNITS(h);   // gemm-units still queued were enqueued under the old setting: launch them with it
+    h->ib_beam = beam;
     return BF_OK;
 }
 

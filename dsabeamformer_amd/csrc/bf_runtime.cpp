@@ -13,6 +13,7 @@
 
 #include "bf_host_internal.h"
 #include "bf_runtime_internal.h"
+#include "ib/bf_incoherent.h"
 
 namespace dsabf::rt {
 
@@ -420,8 +421,21 @@ int bf_beamform_device(bf_handle* h, const void* d_packed, int n_units, float* d
         return fail(BF_ERR_INVALID, "misaligned device pointer: d_packed and d_out must be 16-byte aligned (the kernel loads "
                                     "16-byte pieces and stores 16-byte groups of beams)");
     ON_DEVICE(h);
-    h->n_fused_launches++;
-    HIP_TRY(dsabf::launch_fused(h->geom, h->d_wimage, h->d_wimage_p, d_packed, n_units, d_out, h->n_cus, as_stream(hip_stream)));
+    return launch_detect(h, d_packed, n_units, d_out, as_stream(hip_stream));
+}
+
+int bf_incoherent_device(bf_handle* h, const void* d_packed, int n_units, float* d_out, size_t stride, void* hip_stream)
+{
+    if (!h || !d_packed || !d_out) return fail(BF_ERR_INVALID, "NULL argument");
+    if (n_units <= 0 || !stride) return fail(BF_ERR_INVALID, "n_units and stride must be positive");
+    if (!dsabf::incoherent_supported(h->geom.n_ant, h->geom.n_ipo))
+        return fail(BF_ERR_INVALID, "incoherent beam: 128 * %d antennas * %d samples per output exceeds 2^24 (the sum would not convert to float exactly)",
+                    h->geom.n_ant, h->geom.n_ipo);
+    if (((uintptr_t)d_packed & 15) || ((uintptr_t)d_out & 3))
+        return fail(BF_ERR_INVALID, "misaligned device pointer: d_packed must be 16-byte aligned, d_out 4-byte aligned");
+    ON_DEVICE(h);
+    HIP_TRY(dsabf::launch_incoherent(h->geom.n_ant, h->geom.n_freq, h->geom.n_ipo, h->geom.n_out, d_packed, n_units, d_out, stride, h->n_cus,
+                                     as_stream(hip_stream)));
     return BF_OK;
 }
 

@@ -48,6 +48,7 @@ struct bf_handle {
     hipEvent_t flush_done = nullptr;   // end of the previous flush's host copies: the next flush's copies queue behind it
     bool flush_recorded = false;
     uint64_t n_fused_launches = 0;        // fused-kernel launches this handle has issued (bf_get_counter)
+    int ib_beam = -1;             // bf_set_incoherent_beam: the beam column every detect launch overwrites with the incoherent beam (-1: none)
     std::vector<const float*> last_out;   // per caller-visible queue: where its most recent gemm-unit's powers are on the device ...
     std::vector<int> last_q;              // ... and the queue that wrote them
     // Per compute queue, device memory allocated at first use (bf_queues.cpp, ensure_buf); sized n_streams at bf_create.
@@ -78,6 +79,9 @@ int supported_geom(const bf_config* c, dsabf::Geometry& g);   // check_cfg + mak
 inline hipStream_t as_stream(void* s) { return static_cast<hipStream_t>(s); }
 inline int check_weights(const bf_handle* h) { return h->weights_set ? BF_OK : fail(BF_ERR_STATE, "bf_set_weights has not been called"); }
 int flush_units(bf_handle* h);                          // bf_queues.cpp
+// Every detect launch of a handle: the fused kernel over n_units gemm-units at `in` -> out [unit][o][f][b] and, behind it on the same
+// queue, the incoherent beam into column h->ib_beam of the same `out` if one is set (bf_queues.cpp)
+int launch_detect(bf_handle* h, const void* in, int n_units, float* out, hipStream_t s);
 void dm_stream_release(struct bf_dm_stream* s);         // bf_dm_stream.cpp
 bool dm_stream_is_ring(const struct bf_dm_stream* s);
 void dm_stream_drop_search(struct bf_dm_stream* s);     // the search stage attached to `s` is going away

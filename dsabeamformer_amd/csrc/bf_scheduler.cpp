@@ -474,6 +474,8 @@ int check_options(const bf_config& cfg, const observation_options& opt)
     if (opt.sps_widths < 0 || opt.sps_widths > 8) return set_error(BF_ERR_INVALID, "run_observation: sps_widths must be 0 (off) .. 8");
     if ((opt.sps_widths || opt.sps_sink) && !opt.dm_delays) return set_error(BF_ERR_INVALID, "run_observation: the single-pulse search needs the DM stage (dm_delays)");
     if (opt.sps_sink && !opt.sps_widths) return set_error(BF_ERR_INVALID, "run_observation: a sps_sink needs sps_widths > 0");
+    if (opt.incoherent_beam < -1 || opt.incoherent_beam >= cfg.n_beams)
+        return set_error(BF_ERR_INVALID, "run_observation: incoherent_beam must be -1 (off) or a beam index");
     if (opt.comm && opt.dm_sink && !is_root) return set_error(BF_ERR_INVALID, "run_observation: only the gather root may have a dm_sink");
     if (opt.dm_split_trials && (!opt.comm || opt.gather_root != BF_GATHER_ROOT_ALL))
         return set_error(BF_ERR_INVALID, "run_observation: dm_split_trials needs a sharded run gathered to every rank (BF_GATHER_ROOT_ALL)");
@@ -558,7 +560,8 @@ struct production_run {
         ::memset(beam_out, 0, beam_out_stride * cfg.n_streams * sizeof(float));
         std::vector<int8_t> fourier_coefficients((size_t)cfg.n_freq * cfg.n_ant * cfg.n_beams * 2);
         generate_fourier_coefficients(cfg.n_beams, cfg.n_ant, cfg.n_freq, opt.rank * cfg.n_freq, opt.gpu, pos, dir, fourier_coefficients.data());
-        return bf_set_weights(dev.h, fourier_coefficients.data());
+        if ((rc = bf_set_weights(dev.h, fourier_coefficients.data())) != BF_OK) return rc;
+        return opt.incoherent_beam >= 0 ? bf_set_incoherent_beam(dev.h, opt.incoherent_beam) : BF_OK;
     }
 
     int create_dm_stage_and_buffers()
@@ -806,6 +809,7 @@ int run_observation(const bf_config& cfg, const observation_options& opt, block_
         log << "DM stage: trials " << run.plan.dm_first << " .. " << run.plan.dm_first + run.plan.dm_count - 1 << " of " << opt.n_dm << ", "
             << run.dm_times << " output times (largest delay " << bf_dm_stream_max_delay(run.dev.dm) << " samples carried over on the device)"
             << std::endl;
+    if (opt.incoherent_beam >= 0) log << "Incoherent beam: in beam column " << opt.incoherent_beam << " of the detected stream" << std::endl;
     if (run.dev.sps)
         log << "Single-pulse search: boxcar widths 1 .. " << (1 << (opt.sps_widths - 1)) << ", " << run.sps_candidates << " candidates at S/N >= "
             << opt.sps_threshold << std::endl;

@@ -217,6 +217,27 @@ int bf_timer_stop(bf_handle *h, float *ms);
  * device as it found it. */
 int bf_beamform_device(bf_handle *h, const void *d_packed, int n_units, float *d_out, void *hip_stream);
 
+/* The incoherent beam (docs/INCOHERENT_BEAM.md): what detect_sum, src/beamformer.cuh:139-154, computes for a tied beam -- the sum
+ * of |.|^2 over the n_pol * n_avg samples of an output window -- taken of the antenna voltages themselves, summed over the
+ * antennas, with no weights: per gemm-unit u, output o and channel f
+ *   S = sum over the n_pol * n_avg * n_ant packed bytes of the window of re^2 + im^2        out = (float)S
+ * S is an exact integer, summed in integer arithmetic, so the result is the same for every launch path and bit-equal to a
+ * restatement in any order.  Defined where 128 * n_ant * n_pol * n_avg <= 2^24 (a sample contributes at most 128: the
+ * conversion to float is then exact); beyond that both calls return BF_ERR_INVALID.  With steering weights of modulus ~127 and
+ * detect's 1/127^2 a tied beam on noise has expectation ~S: the two are in the same units.
+ * bf_incoherent_device: d_packed [n_units][freq][time][ant] as for bf_beamform_device (16-byte aligned) ->
+ *   d_out[((u * n_out_per_gemm + o) * n_freq + f) * stride], one float each: stride 1 gives the compact [unit][o][f] array,
+ *   stride n_beams with d_out advanced by b the column of beam b in a detected array.  One kernel launch; needs no weights.
+ * bf_set_incoherent_beam(h, b): from now on EVERY detect launch of the handle -- the loop's K1-K3 of src/beamformer.cu:464-488
+ *   behind bf_enqueue_gemm_unit (coalesced or not), bf_enqueue_block, bf_enqueue_block_to, and bf_beamform_device -- is followed on
+ *   the same queue by that launch into column b of the same output, in front of everything that reads it there (the host copies,
+ *   the DM-0 collapse, the DM stage): for every consumer "beam b" IS the incoherent beam, at the price of one tied beam.  -1: off
+ *   (the default).  Gemm-units that are still only queued are launched first and keep the old setting.  The weights are
+ *   untouched and the tied beam b is still computed, then overwritten: which fused kernel runs does not change, and a caller who
+ *   wants the conjugate-pair kernel keeps that column's weights symmetric like the rest.  bf_gemm_device is no detect launch. */
+int bf_incoherent_device(bf_handle *h, const void *d_packed, int n_units, float *d_out, size_t stride, void *hip_stream);
+int bf_set_incoherent_beam(bf_handle *h, int beam);
+
 /* a1 alone (expand_input, src/beamformer.cuh:66-109): nbytes packed bytes -> 2*nbytes int8 (re, im pairs in
  * order).  nbytes must be a multiple of 16, pointers 16-byte aligned. */
 int bf_expand_device(bf_handle *h, const void *d_in, size_t nbytes, void *d_out, void *hip_stream);

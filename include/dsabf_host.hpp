@@ -624,6 +624,10 @@ struct observation_options {
     int sps_widths = 0;
     double sps_threshold = 8.0;
     sps_candidate_sink* sps_sink = nullptr;
+    // The incoherent beam (docs/INCOHERENT_BEAM.md): beam column `incoherent_beam` of the detected stream carries the antenna powers
+    // summed over the antennas instead of a tied beam (bf_set_incoherent_beam, set on the handle before the loop); -1 = off.  On a
+    // sharded run every rank gives the same index: the sum is per channel, each shard fills its own slice of the column.
+    int incoherent_beam = -1;
 };
 struct observation_result {
     float observation_time_ms = 0;
