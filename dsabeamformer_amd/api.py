@@ -199,7 +199,7 @@ class Beamformer:
                                                   C.c_void_p(stream)))
 
     def set_switch(self, name: str, value: int) -> None:
-        """bf_set_switch: a measurement / test switch of this handle ("tsplit", "lds_pad", "dm_wide", "paired")."""
+        """bf_set_switch: a measurement / test switch of this handle ("tsplit", "lds_pad", "dm_wide", "paired", "fold")."""
         check(self._lib.bf_set_switch(self._h, name.encode(), int(value)))
 
     def counter(self, name: str) -> int:

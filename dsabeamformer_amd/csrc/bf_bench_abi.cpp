@@ -43,6 +43,12 @@ int bf_set_switch(bf_handle* h, const char* name, int value)
     } else if (!strcmp(name, "lds_pad")) {
         if (value < 0 || value > dsabf::kLdsPerCuBytes) return fail(BF_ERR_INVALID, "lds_pad must be 0 .. %d bytes", dsabf::kLdsPerCuBytes);
         h->geom.lds_pad = value;
+        // (the antenna-fold kernel's launcher asks for the default 48 KiB of dynamic LDS at most: a pad beyond that hands the handle
+        //  back to the kernel the weights select otherwise -- its image is resident -- until the next bf_set_weights)
+        if (h->geom.fold && dsabf::fused_launch_shape(h->geom, 1, h->n_cus).lds_bytes > 48 * 1024) {
+            FLUSH_UNITS(h);
+            h->geom.fold = false;
+        }
     } else if (!strcmp(name, "dm_wide")) {
         h->geom.dm_wide = value != 0;
     } else if (!strcmp(name, "coalesce")) {
@@ -50,10 +56,12 @@ int bf_set_switch(bf_handle* h, const char* name, int value)
         h->coalesce = value != 0;
     } else if (!strcmp(name, "paired")) {
         h->force_general = value == 0;   // takes effect at the next bf_set_weights (the kernel is chosen per weight set)
+    } else if (!strcmp(name, "fold")) {
+        h->no_fold = value == 0;         // takes effect at the next bf_set_weights, like "paired" (which, at 0, rules the fold kernel out too)
     } else if (!strcmp(name, "dm_ring")) {
         h->dm_ring = value != 0;         // takes effect at the next bf_dm_stream_create
     } else {
-        return fail(BF_ERR_INVALID, "unknown switch \"%s\" (tsplit, rtw_kout, lds_pad, dm_wide, dm_ring, paired, coalesce)", name);
+        return fail(BF_ERR_INVALID, "unknown switch \"%s\" (tsplit, rtw_kout, lds_pad, dm_wide, dm_ring, paired, fold, coalesce)", name);
     }
     return BF_OK;
 }

@@ -16,6 +16,7 @@ struct Geometry {
     bool fast_detect;                                   // BF_DETECT_FAST requested (honoured by fused16_kernel, n_ipo >= 16)
     bool contracted_detect = false;                     // BF_DETECT_CONTRACTED requested
     bool paired = false;                                // weights verified conjugate-symmetric: beam B-1-b = conj(beam b)
+    bool fold = false;                                  // weights verified antenna-mirror symmetric (W[A-1-a] = conj(W[a])) and the fold kernel selected
     // Test / measurement switches, read from the environment ONCE per handle (read_env_switches, at bf_create) -- they decide
     // the layout of the weight images as well as the kernel, so a handle must not see them change between two calls:
     bool plain_wg_waves = false;                        // DSABF_WG_WAVES=4: 4-wave workgroups everywhere
@@ -43,6 +44,10 @@ size_t weight_image_bytes(const Geometry& g);
 // geometry has no paired kernel.
 bool pairing_supported(const Geometry& g);
 size_t weight_pair_image_bytes(const Geometry& g);
+// Antenna-fold image (fused16_fold_kernel): [freq][16-beam tile][re row|im row][lane] x 16 B; 0 bytes when the geometry has no fold kernel
+// (64 antennas, n_ipo 16 / 32 / 64 have one).
+bool fold_supported(const Geometry& g);
+size_t weight_fold_image_bytes(const Geometry& g);
 
 // True if the fused kernel has an instantiation for this geometry; `why` (optional) explains a refusal.
 bool fused_supported(const Geometry& g, const char** why);
@@ -65,11 +70,14 @@ int rtw_kout(const Geometry& g, long long S, long long base, int n_cus);
 // Reference-layout weights [f][a][b]{re,im} (device) -> fragment image (device).  Sets *d_bad to non-zero if
 // any imaginary part is -128 (its negation does not fit int8).  With d_pair_image (pairing_supported geometries) also
 // builds the conjugate-pair image and sets d_bad[1] to non-zero unless W[f][a][B-1-b] == conj(W[f][a][b]) everywhere.
-hipError_t launch_weight_relayout(const Geometry& g, const int8_t* d_w, void* d_image, void* d_pair_image, int* d_bad,
-                                  hipStream_t s);
+// With d_fold_image (fold_supported geometries) also builds the antenna-fold image and sets d_bad[2] to non-zero unless
+// W[f][A-1-a][b] == conj(W[f][a][b]) everywhere.  d_bad: three ints.
+hipError_t launch_weight_relayout(const Geometry& g, const int8_t* d_w, void* d_image, void* d_pair_image, void* d_fold_image,
+                                  int* d_bad, hipStream_t s);
 
-// Fused expand -> int8 MFMA -> detect over n_units gemm-units (g.paired selects the conjugate-pair kernel + image).
-hipError_t launch_fused(const Geometry& g, const void* d_image, const void* d_pair_image, const void* d_packed,
+// Fused expand -> int8 MFMA -> detect over n_units gemm-units (g.fold selects the antenna-fold kernel + image, else g.paired the
+// conjugate-pair kernel + image).
+hipError_t launch_fused(const Geometry& g, const void* d_image, const void* d_pair_image, const void* d_fold_image, const void* d_packed,
                         int n_units, float* d_out, int n_cus, hipStream_t s);
 
 // Same pipeline but stores the scaled complex GEMM result c[f][t][b]{re,im} for ONE gemm-unit (stage parity).

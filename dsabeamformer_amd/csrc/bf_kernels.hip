@@ -305,6 +305,55 @@ __global__ void pair_check_kernel(const int8_t* __restrict__ w, size_t n_fa, int
     if (bad) *flag = 1;
 }
 
+// Antenna-mirror test: *flag stays 0 iff W[f][A-1-a][b] == conj(W[f][a][b]) for every f, b and a < A/2 (A even).
+__global__ void fold_check_kernel(const int8_t* __restrict__ w, int n_freq, int n_ant, int n_beams, int* __restrict__ flag)
+{
+    const int half = n_ant / 2;
+    const size_t total = (size_t)n_freq * half * n_beams;
+    bool bad = false;
+    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
+        const int b = (int)(idx % n_beams);
+        const size_t fa = idx / n_beams;
+        const int a = (int)(fa % half);
+        const size_t f = fa / half;
+        const int8_t* e0 = w + 2 * ((f * n_ant + a) * n_beams + b);
+        const int8_t* e1 = w + 2 * ((f * n_ant + (n_ant - 1 - a)) * n_beams + b);
+        bad |= (e0[0] != e1[0]) || (e0[1] != -e1[1]);
+    }
+    if (bad) *flag = 1;
+}
+
+// Antenna-fold weight image (64 antennas): image[f][ct16][comp][lane] (16 bytes): lane = 16*kb + c; byte i of comp 0 (the real row,
+// multiplies (Sr | Di)) = Wr (kb 0, 1) or -Wi (kb 2, 3), of comp 1 (the imaginary row, multiplies (Dr | Si)) = Wi or Wr, of antenna
+// 16*(kb & 1) + i -- the first of mirror pair (a, 63 - a) -- for beam beam_of_tile(ct16, c) (zero behind the last beam).
+__global__ void weight_relayout16f_kernel(const int8_t* __restrict__ w, v4i* __restrict__ image, int n_freq, int n_ant, int n_beams,
+                                          int interleave)
+{
+    const int n_ct = (n_beams + 15) / 16;
+    const size_t total = (size_t)n_freq * n_ct * kFoldComps * 64;
+    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
+        const int lane = (int)(idx & 63);
+        size_t r = idx >> 6;
+        const int comp = (int)(r % kFoldComps);
+        r /= kFoldComps;
+        const int ct = (int)(r % n_ct);
+        const int f = (int)(r / n_ct);
+        const int kb = lane >> 4, b = beam_of_tile(interleave, ct, lane & 15);
+        unsigned d[4] = {0, 0, 0, 0};
+        for (int i = 0; i < 16; i++) {
+            const int ant = 16 * (kb & 1) + i;
+            int v = 0;
+            if (b < n_beams) {
+                const int8_t* e = w + 2 * (((size_t)f * n_ant + ant) * n_beams + b);
+                const int wr = e[0], wi = e[1];
+                v = comp == 0 ? (kb < 2 ? wr : -wi) : (kb < 2 ? wi : wr);
+            }
+            d[i >> 2] |= ((unsigned)v & 0xFFu) << (8 * (i & 3));
+        }
+        image[idx] = v4i{(int)d[0], (int)d[1], (int)d[2], (int)d[3]};
+    }
+}
+
 // Paired weight image: image[f][pct][comp][h][lane] (16 bytes): lane = 16*kb + c; byte i = Wr (comp 0) or Wi (comp 1) of
 // antenna 64*h + 16*kb + i (zero behind the last antenna) for base beam beam_of_tile(pct, c) (< n_beams / 2).
 __global__ void weight_relayout16p_kernel(const int8_t* __restrict__ w, v4i* __restrict__ image, int n_freq, int n_ant,
@@ -404,6 +453,7 @@ int detect_mode_of(const Geometry& g) { return g.fast_detect ? kDetFast : g.cont
 FusedVariant select_variant(const Geometry& g, bool write_c)
 {
     if (use_generic(g)) return FusedVariant{};
+    if (g.fold && !write_c) return fused16_variant_k1p16_fold(g.n_ipo, detect_mode_of(g));   // (fold_supported: 64 antennas, n_ipo 16 / 32 / 64)
     if (deep_class(g)) {
         if (write_c) return FusedVariant{};
         const bool paired = g.paired;
@@ -473,6 +523,16 @@ bool pairing_supported(const Geometry& g)
 size_t weight_pair_image_bytes(const Geometry& g)
 {
     return pairing_supported(g) ? (size_t)g.n_freq * (g.n_beams / 32) * kPairComps * ksteps16(g) * 64 * 16 : 0;
+}
+
+// the antenna-fold kernel: 64 antennas in the compile-time windows of 16 / 32 / 64 samples, any beam count (general tiles)
+bool fold_supported(const Geometry& g)
+{
+    return !use_generic(g) && !deep_class(g) && !rtw_class(g) && g.n_ant == 64 && (g.n_ipo == 16 || g.n_ipo == 32 || g.n_ipo == 64);
+}
+size_t weight_fold_image_bytes(const Geometry& g)
+{
+    return fold_supported(g) ? (size_t)g.n_freq * g.n_ctiles * kFoldComps * 64 * 16 : 0;   // [f][ct16][re row, im row][lane] x 16 B
 }
 
 bool fused_supported(const Geometry& g, const char** why)
@@ -652,7 +712,7 @@ static FusedArgs make_args(const Geometry& g, const void* d_image, const void* d
     a.S = (unsigned)((long long)n_units * g.n_time);
     a.chunks_total = ls.chunks_total;
     a.n_tsplit = ls.n_tsplit;
-    a.interleave = interleaved(g, g.paired);
+    a.interleave = interleaved(g, g.paired && !g.fold);   // (the fold kernel works on general tiles)
     if (rtw_class(g)) {
         a.rt_L = g.n_ipo;
         a.rt_kout = ls.rt_kout;
@@ -662,15 +722,16 @@ static FusedArgs make_args(const Geometry& g, const void* d_image, const void* d
     return a;
 }
 
-hipError_t launch_fused(const Geometry& g, const void* d_image, const void* d_pair_image, const void* d_packed,
+hipError_t launch_fused(const Geometry& g, const void* d_image, const void* d_pair_image, const void* d_fold_image, const void* d_packed,
                         int n_units, float* d_out, int n_cus, hipStream_t s)
 {
     if (n_units <= 0) return hipSuccess;
     if (use_generic(g)) return launch_fused_generic(g, d_image, d_packed, n_units, d_out, n_cus, false, s);
     if ((long long)n_units * g.n_time > 0x7fffffffLL / 2) return hipErrorInvalidValue;
     if (g.paired && !(pairing_supported(g) && d_pair_image)) return hipErrorInvalidValue;
+    if (g.fold && !(fold_supported(g) && d_fold_image)) return hipErrorInvalidValue;
     const LaunchShape ls = fused_launch_shape(g, n_units, n_cus);
-    const FusedArgs a = make_args(g, g.paired ? d_pair_image : d_image, d_packed, n_units, d_out, ls);
+    const FusedArgs a = make_args(g, g.fold ? d_fold_image : g.paired ? d_pair_image : d_image, d_packed, n_units, d_out, ls);
     return dispatch_fused(g, false, a, ls, s);
 }
 
@@ -678,7 +739,7 @@ hipError_t launch_gemm_only(const Geometry& g, const void* d_image, const void* 
                             hipStream_t s)
 {
     Geometry gg = g;
-    gg.paired = false;  // the stage-parity path always runs the general kernel on the general image
+    gg.paired = gg.fold = false;  // the stage-parity path always runs the general kernel on the general image
     if (use_generic(gg) || deep_class(gg))   // (the deep classes share fusedg_kernel's image: same k-steps, same 2-beam interleave)
         return launch_fused_generic(gg, d_image, d_packed, 1, d_c, n_cus, true, s);
     const LaunchShape ls = fused_launch_shape(gg, 1, n_cus, true);
@@ -690,8 +751,8 @@ hipError_t launch_gemm_only(const Geometry& g, const void* d_image, const void* 
 // hipGetDeviceProperties of a caller, say): every launcher clears the slot first so that what it returns is its own.
 static inline void clear_stale_error() { (void)hipGetLastError(); }
 
-hipError_t launch_weight_relayout(const Geometry& g, const int8_t* d_w, void* d_image, void* d_pair_image, int* d_bad,
-                                  hipStream_t s)
+hipError_t launch_weight_relayout(const Geometry& g, const int8_t* d_w, void* d_image, void* d_pair_image, void* d_fold_image,
+                                  int* d_bad, hipStream_t s)
 {
     clear_stale_error();
     const bool with_corr = use_generic(g) || deep_class(g);   // the generic kernel's offset-nibble corrections behind the fragments
@@ -711,6 +772,15 @@ hipError_t launch_weight_relayout(const Geometry& g, const int8_t* d_w, void* d_
         if (rgrid > 4096) rgrid = 4096;
         hipLaunchKernelGGL(weight_relayout16p_kernel, dim3(rgrid), dim3(256), 0, s, d_w, static_cast<v4i*>(d_pair_image),
                            g.n_freq, g.n_ant, g.n_beams, ksteps16(g), interleaved(g, true));
+    }
+    if (fold_supported(g) && d_fold_image) {
+        int cgrid = (int)(((size_t)g.n_freq * (g.n_ant / 2) * g.n_beams + 255) / 256);
+        if (cgrid > 4096) cgrid = 4096;
+        hipLaunchKernelGGL(fold_check_kernel, dim3(cgrid), dim3(256), 0, s, d_w, g.n_freq, g.n_ant, g.n_beams, d_bad + 2);
+        int rgrid = (int)((weight_fold_image_bytes(g) / 16 + 255) / 256);
+        if (rgrid > 4096) rgrid = 4096;
+        hipLaunchKernelGGL(weight_relayout16f_kernel, dim3(rgrid), dim3(256), 0, s, d_w, static_cast<v4i*>(d_fold_image), g.n_freq,
+                           g.n_ant, g.n_beams, interleaved(g, false));
     }
     hipLaunchKernelGGL(weight_relayout16_kernel, dim3(grid), dim3(256), 0, s, d_w, static_cast<v4i*>(d_image), g.n_freq,
                        g.n_ant, g.n_beams, ksteps16(g), interleaved(g, false), d_bad);
@@ -864,8 +934,9 @@ const char* fused_kernel_name(const Geometry& g, char* buf, size_t n)
         return buf;
     }
     // (the geometry in words; which template instantiation that is -- antenna CLASS, run-time or compile-time -- fused_variant_key says)
-    snprintf(buf, n, "dsabf::fused16_kernel<ANT=%d,NIPO=%d%s%s%s%s> (v_mfma_i32_16x16x64_i8)", g.n_ant, g.n_ipo, rtw_class(g) ? "(run-time)" : "", (g.fast_detect && g.n_ipo >= 16) ? ",FAST" : g.contracted_detect ? ",CONTRACTED" : "",
-             g.paired ? ",PAIRED" : "",
+    // (PAIRED: the weight set is conjugate-pair symmetric; FOLD: the antenna-fold kernel runs -- on such a set too, in place of the pair kernel)
+    snprintf(buf, n, "dsabf::fused16_kernel<ANT=%d,NIPO=%d%s%s%s%s%s> (v_mfma_i32_16x16x64_i8)", g.n_ant, g.n_ipo, rtw_class(g) ? "(run-time)" : "", (g.fast_detect && g.n_ipo >= 16) ? ",FAST" : g.contracted_detect ? ",CONTRACTED" : "",
+             g.paired ? ",PAIRED" : "", g.fold ? ",FOLD" : "",
              fused_col_tiles(g, g.paired) == kColTilesWide16 ? ",SLOTS=8" : fused_wg_waves(g) == kWavesWide16 ? ",WAVES=8" : "");
     return buf;
 }
@@ -875,10 +946,12 @@ const char* fused_variant_key(const Geometry& g, bool write_c, char* buf, size_t
     if (!n) return buf;
     buf[0] = 0;
     Geometry gg = g;
-    if (write_c) gg.paired = false;   // (launch_gemm_only: the stage-parity path always runs the general kernel)
+    if (write_c) gg.paired = gg.fold = false;   // (launch_gemm_only: the stage-parity path always runs the general kernel)
     if (use_generic(gg) || (write_c && deep_class(gg))) return generic_variant_key(gg, write_c, buf, n);
     const FusedVariant v = select_variant(gg, write_c);
-    if (v.launch)
+    if (v.launch && v.fold)
+        snprintf(buf, n, "fused16_fold_kernel<%d, %d>", v.nipo, v.mode);
+    else if (v.launch)
         snprintf(buf, n, "fused16_kernel<%d, %d, %s, %d, %s, %d, %d>", v.ain, v.nipo, v.write_c ? "true" : "false", v.mode,
                  v.paired ? "true" : "false", v.waves, v.ns);
     return buf;

@@ -6,7 +6,7 @@
 int dsabf::rt::launch_detect(bf_handle* h, const void* in, int n_units, float* out, hipStream_t s)
 {
     h->n_fused_launches++;
-    HIP_TRY(dsabf::launch_fused(h->geom, h->d_wimage, h->d_wimage_p, in, n_units, out, h->n_cus, s));
+    HIP_TRY(dsabf::launch_fused(h->geom, h->d_wimage, h->d_wimage_p, h->d_wimage_f, in, n_units, out, h->n_cus, s));
     if (h->ib_beam >= 0)   // the tied beam of that column has been computed like every other: overwrite it
         HIP_TRY(dsabf::launch_incoherent(h->geom.n_ant, h->geom.n_freq, h->geom.n_ipo, h->geom.n_out, in, n_units, out + h->ib_beam,
                                          (size_t)h->geom.n_beams, h->n_cus, s));

@@ -172,7 +172,8 @@ int bf_create(const bf_config* cfg, int device, bf_handle** out)
 
     CREATE_TRY(hipMalloc(&h->d_wimage, dsabf::weight_image_bytes(g)));
     if (dsabf::weight_pair_image_bytes(g)) CREATE_TRY(hipMalloc(&h->d_wimage_p, dsabf::weight_pair_image_bytes(g)));
-    CREATE_TRY(hipMalloc((void**)&h->d_flag, 2 * sizeof(int)));
+    if (dsabf::weight_fold_image_bytes(g)) CREATE_TRY(hipMalloc(&h->d_wimage_f, dsabf::weight_fold_image_bytes(g)));
+    CREATE_TRY(hipMalloc((void**)&h->d_flag, 3 * sizeof(int)));
     CREATE_TRY(hipMalloc((void**)&h->d_data, bf_bytes_per_block(cfg) * (size_t)cfg->n_blocks_on_gpu));
     CREATE_TRY(hipMalloc((void**)&h->d_out, bf_floats_per_detect(cfg) * sizeof(float) * (size_t)cfg->n_streams));
     CREATE_TRY(hipMalloc((void**)&h->d_ded, (size_t)cfg->n_beams * sizeof(float) * (size_t)cfg->n_streams));
@@ -222,7 +223,7 @@ int bf_destroy(bf_handle* h)
     if (h->flush_done) (void)hipEventDestroy(h->flush_done);
     if (h->t0) (void)hipEventDestroy(h->t0);
     if (h->t1) (void)hipEventDestroy(h->t1);
-    for (void* p : std::initializer_list<void*>{h->d_wimage, h->d_wimage_p, h->d_flag, h->d_data, h->d_out, h->d_ded}) (void)hipFree(p);
+    for (void* p : std::initializer_list<void*>{h->d_wimage, h->d_wimage_p, h->d_wimage_f, h->d_flag, h->d_data, h->d_out, h->d_ded}) (void)hipFree(p);
     for (auto* ds : h->dm_streams) dm_stream_release(ds);   // a DM stage that outlives its handle is left empty, not dangling
     for (auto* sp : h->sps_stages) sps_release(sp);         // ... and a search stage
     for (auto& sc : h->dm_scratch) (void)hipFree(sc.second);
@@ -243,12 +244,12 @@ static int finish_weights(bf_handle* h, const int8_t* d_w, hipStream_t s)
 {
     if (int rc = flush_units(h)) return rc;   // gemm-units still queued were enqueued under the OLD weights: launch them first
     for (auto q : h->streams) HIP_TRY(hipStreamSynchronize(q));   // ... and let them finish before the images change
-    HIP_TRY(hipMemsetAsync(h->d_flag, 0, 2 * sizeof(int), s));
-    HIP_TRY(dsabf::launch_weight_relayout(h->geom, d_w, h->d_wimage, h->d_wimage_p, h->d_flag, s));
-    int bad[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(bad, h->d_flag, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemsetAsync(h->d_flag, 0, 3 * sizeof(int), s));
+    HIP_TRY(dsabf::launch_weight_relayout(h->geom, d_w, h->d_wimage, h->d_wimage_p, h->d_wimage_f, h->d_flag, s));
+    int bad[3] = {0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(bad, h->d_flag, 3 * sizeof(int), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    h->geom.paired = false;
+    h->geom.paired = h->geom.fold = false;
     if (bad[0]) {
         h->weights_set = false;
         return fail(BF_ERR_INVALID, "weights contain an imaginary part of -128 (must be >= -127)");
@@ -257,7 +258,14 @@ static int finish_weights(bf_handle* h, const int8_t* d_w, hipStream_t s)
     // the device check above decides per weight set; DSABF_PAIRED=0 in the environment, or bf_set_switch(h, "paired", 0) before
     // the weights are set, forces the general kernel.
     const char* env = getenv("DSABF_PAIRED");   // read per weight set (not per launch): the choice is part of setting weights
-    h->geom.paired = h->d_wimage_p != nullptr && bad[1] == 0 && !h->force_general && !(env && env[0] == '0');
+    const bool general_only = h->force_general || (env && env[0] == '0');
+    h->geom.paired = h->d_wimage_p != nullptr && bad[1] == 0 && !general_only;
+    // Arrays that are point-symmetric about their phase centre (any regular line or grid) have W[A-1-a] = conj(W[a]) exactly: the
+    // antenna-fold kernel then takes the place of either kernel (same bits).  bf_set_switch(h, "fold", 0), or DSABF_PAIRED=pair in
+    // the environment (the profile refresh measures the conjugate-pair kernel through it), keeps the choice above.
+    const bool pair_only = h->no_fold || (env && !strcmp(env, "pair"));
+    h->geom.fold = h->d_wimage_f != nullptr && bad[2] == 0 && !general_only && !pair_only;
+    if (h->geom.fold && dsabf::fused_launch_shape(h->geom, 1, h->n_cus).lds_bytes > 48 * 1024) h->geom.fold = false;   // (an "lds_pad" beyond the fold launcher's 48 KiB)
     h->weights_set = true;
     return BF_OK;
 }

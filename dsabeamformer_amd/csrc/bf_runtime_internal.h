@@ -24,7 +24,8 @@ struct bf_handle {
     bool weights_set = false;
     void* d_wimage = nullptr;     // MFMA fragment image of the weights
     void* d_wimage_p = nullptr;   // conjugate-pair image (geometries with a paired kernel)
-    int* d_flag = nullptr;        // relayout flags: [0] weight out of range, [1] weights are not conjugate-paired
+    void* d_wimage_f = nullptr;   // antenna-fold image (geometries with a fold kernel)
+    int* d_flag = nullptr;        // relayout flags: [0] weight out of range, [1] weights are not conjugate-paired, [2] not antenna-mirror symmetric
     uint8_t* d_data = nullptr;    // ring: n_blocks_on_gpu x bytes_per_block
     float* d_out = nullptr;       // n_streams x floats_per_detect
     float* d_ded = nullptr;       // n_streams x n_beams
@@ -32,7 +33,8 @@ struct bf_handle {
     // wide kernel takes + a 512-byte row of zeros).  The wide kernel writes the flags and the per-thread-window kernel reads
     // them later on the same stream: calls on one stream are ordered by the stream, calls on different streams must not share.
     std::vector<std::pair<hipStream_t, int*>> dm_scratch;
-    bool force_general = false;   // bf_set_switch("paired", 0): never select the conjugate-pair kernel
+    bool force_general = false;   // bf_set_switch("paired", 0): never select the conjugate-pair kernel (nor the antenna-fold kernel)
+    bool no_fold = false;         // bf_set_switch("fold", 0): never select the antenna-fold kernel
     bool dm_ring = true;          // bf_set_switch("dm_ring", 0): the next bf_dm_stream_create takes the linear buffer (test switch)
     // bf_enqueue_gemm_unit coalesces (see flush_units): the caller keeps the reference's one-unit-per-call loop
     // (src/beamformer.cu:454-519), the device sees one launch per run of consecutive gemm-units.

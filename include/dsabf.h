@@ -114,7 +114,12 @@ int bf_get_config(const bf_handle *h, bf_config *cfg); /* the geometry the handl
  * Imaginary parts must be >= -127 (the reference's round(127*sin) never produces -128).
  * If W[f][a][n_beams-1-b] == conj(W[f][a][b]) for every f, a, b -- any beam set symmetric about the boresight, e.g. the
  * reference's -- the library notices (checked on the device, exactly) and runs a kernel that forms each such beam pair
- * from shared products: half the matrix-core work, identical results.  Nothing to configure. */
+ * from shared products: half the matrix-core work, identical results.  Nothing to configure.
+ * If W[f][n_ant-1-a][b] == conj(W[f][a][b]) for every f, a, b -- an array that is point-symmetric about its phase centre: any
+ * regular line or grid with the reference's steering weights -- and the geometry is 64 antennas with an accumulation window of
+ * 16, 32 or 64 samples, the library notices that too and folds each mirror pair of antennas into one matrix-core operand (sums and
+ * differences of the two voltages): the same halved matrix-core work for ANY beam set, fewer vector instructions per sample,
+ * identical results.  A calibrated array (per-antenna gains and phases) has neither symmetry and runs the general kernel. */
 int bf_set_weights(bf_handle *h, const int8_t *w);
 /* Same (the cudaMemcpy of src/beamformer.cu:272 becomes a device-side read), from a DEVICE array: caller-owned HBM, e.g.
  * weights computed on the GPU or a sharded slice. */

@@ -45,7 +45,10 @@ int bf_rtw_plan(const bf_config *cfg, int n_units, int n_cus, int *windows_per_s
  *   "dm_ring"  0 / 1    0: the next bf_dm_stream_create keeps its rows in a linear buffer whose carried-over window slides back to the
  *                       start when the end is reached (what a device without virtual-memory management gets), instead of the ring
  *                       that is mapped twice back to back (nothing ever moves); same chunks
- *   "paired"   0 / 1    0: the next bf_set_weights selects the general kernel even for conjugate-symmetric weights
+ *   "paired"   0 / 1    0: the next bf_set_weights selects the general kernel even for conjugate-symmetric weights (and never
+ *                       the antenna-fold kernel)
+ *   "fold"     0 / 1    0: the next bf_set_weights does not select the antenna-fold kernel (mirror-symmetric 64-antenna arrays,
+ *                       include/dsabf.h); what it selects instead is what "paired" and the weights decide
  *   "coalesce" 0 / 1    0: bf_enqueue_gemm_unit launches one kernel per call (the reference's literal launch pattern) */
 int bf_set_switch(bf_handle *h, const char *name, int value);
 /* Counters of one handle: "fused_launches" = fused-kernel launches issued so far (what coalescing saves),
@@ -64,7 +67,8 @@ int bf_launch_plan(const bf_config *cfg, int paired, int n_units, int n_cus, int
  * per wave>, "fusedg_kernel<true, 0, false>" = <16-byte rows, detect mode, stage-parity store>.  write_c != 0: the kernel of
  * bf_gemm_device (the stage-parity launch).  bf_variant_key is host arithmetic (no device); bf_handle_variant_key answers for a
  * live handle -- after bf_set_weights, which decides `paired` -- so a test can assert that the launch it checked against the oracle
- * WAS the instantiation it meant to cover. */
+ * WAS the instantiation it meant to cover.  A handle on the antenna-fold kernel answers "fused16_fold_kernel<32, 0>" = <window,
+ * detect mode>; bf_variant_key knows nothing of the antenna symmetry and never names it. */
 int bf_variant_key(const bf_config *cfg, int paired, int write_c, char *buf, size_t buflen);
 int bf_handle_variant_key(const bf_handle *h, int write_c, char *buf, size_t buflen);
 

@@ -4,12 +4,14 @@
 # bench.py quotes a summary beside its timings only when the key is its own run's.
 set -x
 R=$PWD; O=$R/gpurun_out/r06p; mkdir -p $O
-python bench.py --full > $O/r06_c3_bench.json 2> $O/r06_c3_bench.err
+# (the r06_c3 records are the conjugate-pair kernel's: DSABF_PAIRED=pair keeps the antenna-fold kernel, which the default fan would
+#  otherwise select, out of them; the fold kernel's own records are the r07_c3_fold_* files at the end)
+DSABF_PAIRED=pair python bench.py --full > $O/r06_c3_bench.json 2> $O/r06_c3_bench.err
 python bench.py --full --workload c5 --units 16 --no-cpu-baseline > $O/r06_c5_bench.json 2> $O/r06_c5_bench.err
 python bench.py --full --workload c2 --no-cpu-baseline > $O/r06_c2_bench.json 2> $O/r06_c2_bench.err
 cd /tmp; export TMPDIR=/tmp
 for V in paired general; do
-  if [ $V = general ]; then export DSABF_PAIRED=0; else unset DSABF_PAIRED; fi
+  if [ $V = general ]; then export DSABF_PAIRED=0; else export DSABF_PAIRED=pair; fi
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$V -- python3 $R/bench.py --steps 50 --warmup 10 --no-cpu-baseline --no-extras > $O/prof_$V.log 2>&1
   find $O/prof_$V -name "*kernel_stats.csv" | head -1 | xargs -I{} sh -c "grep -E 'Name|fused16|relayout|pair_check' {} > $O/r06_c3_${V}_kernel_stats.csv"
   rm -rf $O/prof_$V
@@ -45,4 +47,10 @@ SEED=61 CASES=300 python tools/fuzz_dm_stream.py > $O/r06_fuzz_dm_stream.txt 2>&
 python -m pytest tests -m gpu -q --durations=25 -p no:cacheprovider > $O/r06_gputest_durations.txt 2>&1
 cp gpurun_out/census_gpu.txt $O/r06_census_gpu.txt
 DSABF_LONG_TESTS=1 python -m pytest tests -m gpu -q -p no:cacheprovider 2>&1 | tail -4 > $O/r06_gputest_long_tail.txt
+# the antenna-fold kernel (what the C3 bench line runs on the default fan): kernel trace and counters.  The counters go to a file
+# bench.py does not quote (tests/test_gpu_round5.py holds a quoted summary of the headline to the pair kernel's VALU per MFMA).
+(cd /tmp; rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_fold -- python3 $R/bench.py --steps 50 --warmup 10 --no-cpu-baseline --no-extras > $O/prof_fold.log 2>&1)
+find $O/prof_fold -name "*kernel_stats.csv" | head -1 | xargs -I{} sh -c "grep -E 'Name|fused16|relayout|_check' {} > $O/r07_c3_fold_kernel_stats.csv"
+rm -rf $O/prof_fold
+(bash tools/pmc.sh r06p/pmc_fold > /dev/null 2>&1 && cp $O/pmc_fold/summary.txt $O/r07_c3_fold_counters.txt; rm -rf $O/pmc_fold)
 rm -f $O/*.log; ls -la $O
