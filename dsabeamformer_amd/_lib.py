@@ -105,6 +105,15 @@ SIGNATURES = {
     "bf_beamform_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "bf_incoherent_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "bf_set_incoherent_beam": (C.c_int, [C.c_void_p, C.c_int]),
+    "bf_correlate_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "bf_corr_entries": (C.c_size_t, [C.POINTER(BfConfig)]),
+    "bf_corr_create": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
+    "bf_corr_destroy": (C.c_int, [C.c_void_p]),
+    "bf_corr_push": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "bf_corr_push_block": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "bf_corr_dump": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "bf_corr_collect": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "bf_corr_pending": (C.c_int, [C.c_void_p]),
     "bf_expand_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "bf_gemm_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bf_dedisperse_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -108,6 +108,16 @@ class Beamformer:
         """bf_set_incoherent_beam: every detect launch from now on overwrites beam column ``beam`` with the incoherent beam (-1: off)."""
         check(self._lib.bf_set_incoherent_beam(self._h, int(beam)))
 
+    def correlate(self, d_packed, n_units: int, d_vis, accumulate: bool = False, stream: int = 0) -> None:
+        """bf_correlate_device: the visibilities of n_units gemm-units into d_vis, int64 [freq][pol][a1 (a1 + 1) / 2 + a2]{re, im}
+        (``corr_entries`` entries), overwritten or -- ``accumulate`` -- added to.  Needs no weights."""
+        check(self._lib.bf_correlate_device(self._h, _ptr(d_packed), int(n_units), _ptr(d_vis), int(bool(accumulate)), C.c_void_p(stream)))
+
+    @property
+    def corr_entries(self) -> int:
+        """bf_corr_entries: n_freq * n_pol * n_ant (n_ant + 1) / 2 complex entries (two int64 each)."""
+        return self._lib.bf_corr_entries(C.byref(self.cfg))
+
     def expand(self, d_in, nbytes: int, d_out, stream: int = 0) -> None:
         check(self._lib.bf_expand_device(self._h, _ptr(d_in), int(nbytes), _ptr(d_out), C.c_void_p(stream)))
 
@@ -376,6 +386,69 @@ class SinglePulseSearch:
             self.close()
         except Exception:
             pass
+
+
+class Correlator:
+    """bf_corr: the correlator as a stage (include/dsabf.h, docs/CORRELATOR.md): one int64 accumulator on the device that pushes add
+    to and a dump snapshots and zeroes; the stage orders its pushes and dumps itself, whatever queues they are issued on."""
+
+    def __init__(self, bf: Beamformer, max_in_flight: int = 2):
+        self._lib = load()
+        self._c = C.c_void_p()
+        self._bf = bf
+        cfg = bf.cfg
+        self.shape = (cfg.n_freq, cfg.n_pol, cfg.n_ant * (cfg.n_ant + 1) // 2, 2)
+        check(self._lib.bf_corr_create(bf._h, int(max_in_flight), C.byref(self._c)))
+
+    def push(self, d_packed, n_units: int, stream: int = 0) -> None:
+        check(self._lib.bf_corr_push(self._c, _ptr(d_packed), int(n_units), C.c_void_p(stream)))
+
+    def push_block(self, stream_idx: int, slot: int, first_unit: int, n_units: int) -> None:
+        """The gemm-units [first_unit, first_unit + n_units) of ring slot ``slot`` (what enqueue_block reads), on compute queue stream_idx."""
+        check(self._lib.bf_corr_push_block(self._c, int(stream_idx), int(slot), int(first_unit), int(n_units)))
+
+    def dump(self, stream: int = 0) -> None:
+        """Snapshot the accumulator to pinned host memory, then zero it (BF_ERR_STATE beyond max_in_flight uncollected dumps)."""
+        check(self._lib.bf_corr_dump(self._c, C.c_void_p(stream)))
+
+    @property
+    def pending(self) -> int:
+        return self._lib.bf_corr_pending(self._c)
+
+    def collect(self):
+        """Waits for the oldest uncollected dump; returns (int64 array [freq][pol][baseline][2], columns per polarisation)."""
+        import numpy as np
+
+        out = np.empty(self.shape, np.int64)
+        n = C.c_uint64()
+        check(self._lib.bf_corr_collect(self._c, _ptr(out), C.byref(n)))
+        return out, int(n.value)
+
+    def close(self) -> None:
+        if self._c:
+            self._lib.bf_corr_destroy(self._c)
+            self._c = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def vis_to_square(tri, n_ant: int):
+    """The packed lower triangle [...][a1 (a1 + 1) / 2 + a2][2] (re, im) as the full Hermitian complex128 array [...][a1][a2]:
+    V[a2][a1] = conj(V[a1][a2])."""
+    import numpy as np
+
+    tri = np.asarray(tri)
+    assert tri.shape[-1] == 2 and tri.shape[-2] == n_ant * (n_ant + 1) // 2
+    a1, a2 = np.tril_indices(n_ant)          # row-major over the lower triangle: exactly bl = a1 (a1 + 1) / 2 + a2
+    z = tri[..., 0].astype(np.float64) + 1j * tri[..., 1].astype(np.float64)
+    sq = np.zeros(tri.shape[:-2] + (n_ant, n_ant), np.complex128)
+    sq[..., a2, a1] = np.conj(z)
+    sq[..., a1, a2] = z
+    return sq
 
 
 # events / pinned memory as free functions (they are not tied to a handle in the C-ABI)

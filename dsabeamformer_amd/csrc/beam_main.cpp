@@ -29,6 +29,12 @@
 //   beam -j n_blocks ... -i beam                    the incoherent beam (docs/INCOHERENT_BEAM.md): beam column `beam` of the detected
 //                                                   stream carries the antenna powers summed over the antennas instead of a tied beam,
 //                                                   for -w / -K, the DM stage and the search alike.  With -R: every shard, same index.
+//   beam -j n_blocks ... -V vis_file [-L corr_blocks]
+//                                                   the correlator (docs/CORRELATOR.md): the antenna visibilities of every analysed
+//                                                   block, integrated over corr_blocks blocks [1] per dump, to vis_file (int64 lower
+//                                                   triangle per channel and polarisation).  With -R: every shard correlates its own
+//                                                   channels and writes vis_file.<rank>.  (-j counts the 25 burn-in reads: -j 27
+//                                                   analyses two blocks.)
 //
 // With the reference's `make debug` geometry (default) it generates synthetic point-source voltages on the CPU,
 // streams them through the observation loop and writes bin/data.py (dedispersed beam responses, one row per source)
@@ -73,9 +79,12 @@ int main(int argc, char* argv[])
     std::string cand_path;          // -C
     int ib_beam = -1;               // -i: the beam column that carries the incoherent beam (-1: none)
     bool ib_given = false;
+    std::string vis_path;           // -V: where the correlator's dumps go
+    int corr_blocks = 1;            // -L: analysed blocks integrated per dump
+    bool corr_blocks_given = false;
 
     int arg = 0;
-    while ((arg = getopt(argc, argv, "s:g:p:d:o:D:a:c:k:K:j:w:R:r:I:M:N:T:W:Q:S:B:C:i:XuvhH")) != -1) {  // src/beamformer.cu:41-43 (+ -o -D -a -v)
+    while ((arg = getopt(argc, argv, "s:g:p:d:o:D:a:c:k:K:j:w:R:r:I:M:N:T:W:Q:S:B:C:i:V:L:XuvhH")) != -1) {  // src/beamformer.cu:41-43 (+ -o -D -a -v)
         switch (arg) {
             case 's': sources = optarg; break;                 // :77-89
             case 'g': opt.gpu = atoi(optarg); break;           // :92-100
@@ -100,6 +109,8 @@ int main(int argc, char* argv[])
             case 'B': sps_widths = atoi(optarg); sps_widths_given = true; break;
             case 'C': cand_path = optarg; break;
             case 'i': ib_beam = atoi(optarg); ib_given = true; break;
+            case 'V': vis_path = optarg; break;
+            case 'L': corr_blocks = atoi(optarg); corr_blocks_given = true; break;
             case 'u': per_unit = true; break;                   // the reference's launch pattern: one launch per gemm-unit
             case 'v': opt.verbose = true; cfg.verbose = 1; break;
             case 'c': core = atoi(optarg); break;              // :59-65
@@ -126,6 +137,9 @@ int main(int argc, char* argv[])
                              "                         requires -M: without it (or -B / -C without -S) beam exits with a usage error\n"
                              " -i beam                 observation mode: beam column `beam` of the detected stream carries the incoherent beam\n"
                              "                         (antenna powers summed over the antennas, no weights) for every consumer; 0 <= beam < N_BEAMS\n"
+                             " -V file [-L corr_blocks]   observation mode: the correlator -- antenna visibilities of the analysed blocks, integrated\n"
+                             "                         over corr_blocks blocks [1] per dump, to file (with -R: file.<rank>, each shard its own channels);\n"
+                             "                         -j counts the 25 burn-in reads: -j 27 analyses two blocks\n"
                              " -H                      this text\n";
                 return EXIT_SUCCESS;
             default: usage(true, std::cerr); return EXIT_FAILURE;
@@ -149,6 +163,18 @@ int main(int argc, char* argv[])
     }
     if (ib_given && junk_blocks < 0 && ring_key.empty()) {
         fprintf(stderr, "beam: -i (incoherent beam) belongs to the observation mode: give -j n_blocks or -k ring\n");
+        return EXIT_FAILURE;
+    }
+    if (corr_blocks_given && vis_path.empty()) {
+        fprintf(stderr, "beam: -L (blocks per dump) belongs to the correlator: give -V vis_file\n");
+        return EXIT_FAILURE;
+    }
+    if (corr_blocks_given && corr_blocks < 1) {
+        fprintf(stderr, "beam: -L %d: the correlator integrates at least one block per dump\n", corr_blocks);
+        return EXIT_FAILURE;
+    }
+    if (!vis_path.empty() && junk_blocks < 0 && ring_key.empty()) {
+        fprintf(stderr, "beam: -V (correlator) belongs to the observation mode: give -j n_blocks or -k ring\n");
         return EXIT_FAILURE;
     }
     opt.positions = positions.empty() ? nullptr : positions.c_str();
@@ -353,11 +379,23 @@ int main(int argc, char* argv[])
                 oopt.sps_sink = cand_sink.get();
             }
         }
+        std::unique_ptr<vis_file_sink> vsink;
+        if (!vis_path.empty()) {   // -V: every shard correlates its own channels
+            if (comm) vis_path += "." + std::to_string(rank);
+            vsink.reset(new vis_file_sink(pcfg, vis_path.c_str(), rank * pcfg.n_freq, opt.gpu));
+            if (!vsink->is_open()) {
+                fprintf(stderr, "beam: could not open %s\n", vis_path.c_str());
+                return EXIT_FAILURE;
+            }
+            oopt.corr_blocks = corr_blocks;
+            oopt.vis_sink = vsink.get();
+        }
         observation_result ores;
         int orc = run_observation(pcfg, oopt, *src, pos.data(), dir.data(), &ores, std::cout);
         if (sink) std::cout << "Wrote " << sink->get_delivered() << " gemm-units of detected powers to " << sink_name << std::endl;
         if (dm_sink) std::cout << "Wrote " << dm_sink->get_times_written() << " dedispersed samples x " << my_trials << " trials to " << dm_path << std::endl;
         if (cand_sink) std::cout << "Wrote " << cand_sink->get_candidates_written() << " candidates to " << cand_path << std::endl;
+        if (vsink) std::cout << "Wrote " << vsink->get_dumps_written() << " visibility dumps of " << corr_blocks << " blocks to " << vis_path << std::endl;
         bf_comm_destroy(comm);
         if (orc != BF_OK) {
             fprintf(stderr, "GPUassert: %s (%d)\n", bf_last_error(), orc);

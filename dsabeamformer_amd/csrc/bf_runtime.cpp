@@ -226,6 +226,7 @@ int bf_destroy(bf_handle* h)
     for (void* p : std::initializer_list<void*>{h->d_wimage, h->d_wimage_p, h->d_wimage_f, h->d_flag, h->d_data, h->d_out, h->d_ded}) (void)hipFree(p);
     for (auto* ds : h->dm_streams) dm_stream_release(ds);   // a DM stage that outlives its handle is left empty, not dangling
     for (auto* sp : h->sps_stages) sps_release(sp);         // ... and a search stage
+    for (auto* cs : h->corr_stages) corr_release(cs);       // ... and a correlator stage
     for (auto& sc : h->dm_scratch) (void)hipFree(sc.second);
     for (auto& b : h->qbuf)
         for (float* p : {b.out_blk, b.full_blk, b.stage_blk, b.ded_blk}) (void)hipFree(p);

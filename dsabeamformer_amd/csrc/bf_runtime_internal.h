@@ -65,6 +65,7 @@ struct bf_handle {
     int full_world = 0;
     std::vector<struct bf_dm_stream*> dm_streams;   // DM stages created on this handle: bf_destroy releases their device memory
     std::vector<struct bf_sps*> sps_stages;         // single-pulse search stages (bf_sps.cpp): the same
+    std::vector<struct bf_corr*> corr_stages;       // correlator stages (bf_corr.cpp): the same
     hipStream_t h2d = nullptr;
     std::vector<hipStream_t> streams;
     std::vector<hipEvent_t> join;  // one per compute queue: queue_waits_for
@@ -92,6 +93,7 @@ void sps_release(struct bf_sps* s);                     // device side of a stag
 int sps_check_attach(const struct bf_sps* s, const bf_handle* h, int n_dm, int max_rows);   // bf_dm_stream_attach_search's conditions
 int sps_max_in_flight(const struct bf_sps* s);
 void sps_set_feeder(struct bf_sps* s, struct bf_dm_stream* dm);   // the DM stage that pushes into `s` (NULL: none): told when `s` is destroyed
+void corr_release(struct bf_corr* c);                   // bf_corr.cpp: device side of a correlator stage; the object stays, detached from its handle
 
 // Makes `device` current for the duration of one entry point and puts the caller's device back afterwards: a library
 // call must not change the current device of a multi-device host process (torch's included).

@@ -203,10 +203,12 @@ struct run_resources {
     bf_handle* h = nullptr;
     bf_dm_stream* dm = nullptr;
     bf_sps* sps = nullptr;
+    bf_corr* corr = nullptr;
     std::vector<void*> pinned;
     ~run_resources()
     {
         if (h) bf_stream_sync(h, -1);
+        bf_corr_destroy(corr);
         bf_sps_destroy(sps);
         bf_dm_stream_destroy(dm);
         for (void* p : pinned) bf_free_pinned(p);
@@ -476,6 +478,9 @@ int check_options(const bf_config& cfg, const observation_options& opt)
     if (opt.sps_sink && !opt.sps_widths) return set_error(BF_ERR_INVALID, "run_observation: a sps_sink needs sps_widths > 0");
     if (opt.incoherent_beam < -1 || opt.incoherent_beam >= cfg.n_beams)
         return set_error(BF_ERR_INVALID, "run_observation: incoherent_beam must be -1 (off) or a beam index");
+    if (opt.corr_blocks < 0) return set_error(BF_ERR_INVALID, "run_observation: corr_blocks must be 0 (off) or the blocks per dump");
+    if (opt.vis_sink && !opt.corr_blocks) return set_error(BF_ERR_INVALID, "run_observation: a vis_sink needs corr_blocks > 0");
+    if (opt.corr_blocks && !opt.block_launch) return set_error(BF_ERR_INVALID, "run_observation: the correlator needs block-granular launches");
     if (opt.comm && opt.dm_sink && !is_root) return set_error(BF_ERR_INVALID, "run_observation: only the gather root may have a dm_sink");
     if (opt.dm_split_trials && (!opt.comm || opt.gather_root != BF_GATHER_ROOT_ALL))
         return set_error(BF_ERR_INVALID, "run_observation: dm_split_trials needs a sharded run gathered to every rank (BF_GATHER_ROOT_ALL)");
@@ -521,6 +526,7 @@ int resolve_plan(const bf_config& cfg, const observation_options& opt, launch_pl
     p.n_freq_band = cfg.n_freq * (opt.comm ? opt.world : 1);
     p.dm_rows = p.upl * cfg.n_out_per_gemm;
     if (opt.dm_delays && !p.block_launch) return set_error(BF_ERR_INVALID, "run_observation: the DM stage needs block-granular launches");
+    if (opt.corr_blocks && !p.block_launch) return set_error(BF_ERR_INVALID, "run_observation: the correlator needs block-granular launches");
     // a sharded run dedisperses the gathered band (more ranks than trials: the surplus ranks only beamform)
     p.dm_run = opt.dm_delays && p.is_root && p.dm_count > 0;
     return BF_OK;
@@ -551,6 +557,10 @@ struct production_run {
     uint64_t dm_seq = 0, dm_times = 0, dm_chunks = 0;
     std::vector<bf_sps_candidate> cands;  // what bf_sps_collect returns for one chunk
     uint64_t sps_candidates = 0;
+    // the correlator (corr_blocks > 0): dumps issued and not yet collected -- {first block of the integration, its last block}
+    std::deque<std::pair<uint64_t, uint64_t>> vis_pending;
+    std::vector<int64_t> vis;             // what bf_corr_collect returns for one dump
+    uint64_t corr_blocks_pushed = 0, vis_dumps = 0;
 
     int create_handle_and_weights(const antenna* pos, const beam_direction* dir)
     {
@@ -584,6 +594,10 @@ struct production_run {
                 if (rc != BF_OK) return gpu_error(log, rc);
                 cands.resize((size_t)plan.dm_count * cfg.n_beams);
             }
+        }
+        if (opt.corr_blocks > 0) {   // dumps in flight: one per block queued at most, + the one being delivered
+            if ((rc = bf_corr_create(dev.h, kMaxTotalSep + 2, &dev.corr)) != BF_OK) return gpu_error(log, rc);
+            vis.resize(2 * bf_corr_entries(&cfg));
         }
         if (plan.block_launch)   // the per-queue block buffers are allocated on first use: do that here, not inside the timed loop
             for (int q = 0; q < plan.n_queues_used; q++) {
@@ -636,6 +650,10 @@ struct production_run {
         unit_dst.assign((size_t)n_units, nullptr);
         for (int first = 0; first < n_units; first += plan.upl)
             if (const int rc = launch_units(block_index, gpu_block, first)) return rc;
+        if (dev.corr && ++corr_blocks_pushed % (uint64_t)opt.corr_blocks == 0) {   // the integration is complete: snapshot and zero
+            if (const int rc = bf_corr_dump(dev.corr, nullptr)) return gpu_error(log, rc);
+            vis_pending.emplace_back((uint64_t)block_index + 1 - (uint64_t)opt.corr_blocks, (uint64_t)block_index);
+        }
         return BF_OK;
     }
 
@@ -663,6 +681,8 @@ struct production_run {
                                             : bf_enqueue_block(dev.h, q, gpu_block, first, upl, opt.comm ? nullptr : &unit_dst[first]);
         if (rc == BF_OK && opt.comm) rc = gather_block(q, d_rows);
         if (rc == BF_OK && plan.dm_run) rc = push_dm_rows(block_index, d_rows, dm_qs);
+        // the correlator reads the same resident units on the same queue, behind the detect launch and what follows it
+        if (rc == BF_OK && dev.corr) rc = bf_corr_push_block(dev.corr, q, gpu_block, first, upl);
         return rc == BF_OK ? BF_OK : gpu_error(log, rc);
     }
 
@@ -723,6 +743,18 @@ struct production_run {
             dm_chunks++;
             if (!opt.dm_sink->deliver(c.first_t, c.n_t, plan.dm_count, cfg.n_beams, c.host)) {
                 log << "ERROR: DM sink failed at output time " << c.first_t << std::endl;
+                return BF_ERR_STATE;
+            }
+        }
+        while (!vis_pending.empty() && vis_pending.front().second < blocks_analyzed) {   // (the collect waits for the dump's own copy)
+            const uint64_t first_block = vis_pending.front().first;
+            vis_pending.pop_front();
+            uint64_t n_columns = 0;
+            const int rc = bf_corr_collect(dev.corr, vis.data(), &n_columns);
+            if (rc != BF_OK) return gpu_error(log, rc);
+            vis_dumps++;
+            if (opt.vis_sink && !opt.vis_sink->deliver(first_block, n_columns, vis.data(), vis.size())) {
+                log << "ERROR: visibility sink failed at block " << first_block << std::endl;
                 return BF_ERR_STATE;
             }
         }
@@ -791,6 +823,7 @@ int run_observation(const bf_config& cfg, const observation_options& opt, block_
     if (opt.sink) opt.sink->close();
     if (opt.dm_sink) opt.dm_sink->close();
     if (opt.sps_sink) opt.sps_sink->close();
+    if (opt.vis_sink) opt.vis_sink->close();
     const uint64_t chunks = obs_state.get_current_transfer_gemm() * cfg.n_out_per_gemm;  // :552
     const double rate = (double)source.get_block_size() * obs_state.get_blocks_transfer_queue() / ms / 1e6;  // :554
     closing_report(log, ms, chunks, ms / (chunks ? chunks : 1), rate, run.plan.block_launch ? "bf_enqueue_block" : kUnitLaunchPattern);
@@ -804,12 +837,16 @@ int run_observation(const bf_config& cfg, const observation_options& opt, block_
         res->dm_times = run.dm_times;
         res->dm_chunks = run.dm_chunks;
         res->sps_candidates = run.sps_candidates;
+        res->vis_dumps = run.vis_dumps;
     }
     if (run.plan.dm_run)
         log << "DM stage: trials " << run.plan.dm_first << " .. " << run.plan.dm_first + run.plan.dm_count - 1 << " of " << opt.n_dm << ", "
             << run.dm_times << " output times (largest delay " << bf_dm_stream_max_delay(run.dev.dm) << " samples carried over on the device)"
             << std::endl;
     if (opt.incoherent_beam >= 0) log << "Incoherent beam: in beam column " << opt.incoherent_beam << " of the detected stream" << std::endl;
+    if (run.dev.corr)
+        log << "Correlator: " << run.vis_dumps << " dumps of " << opt.corr_blocks << " blocks each (an incomplete integration at the end is dropped)"
+            << std::endl;
     if (run.dev.sps)
         log << "Single-pulse search: boxcar widths 1 .. " << (1 << (opt.sps_widths - 1)) << ", " << run.sps_candidates << " candidates at S/N >= "
             << opt.sps_threshold << std::endl;

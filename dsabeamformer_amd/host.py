@@ -283,6 +283,24 @@ def read_dm_file(path: str):
     return hdr, data, chunks
 
 
+def read_vis_file(path: str):
+    """Parse a dsabf::vis_file_sink file (docs/CORRELATOR.md): returns (header dict, list of (first_block, n_columns_per_pol,
+    int64 array [n_freq][n_pol][n_ant (n_ant + 1) / 2][2]) per dump)."""
+    raw = open(path, "rb").read()
+    text = raw[:DETECTED_HEADER_BYTES].split(b"\0", 1)[0].decode()
+    hdr = dict(line.split(None, 1) for line in text.splitlines() if line.strip())
+    n_ant, shape = int(hdr["NANT"]), None
+    shape = (int(hdr["NFREQ"]), int(hdr["NPOL"]), n_ant * (n_ant + 1) // 2, 2)
+    n = shape[0] * shape[1] * shape[2] * 2
+    at, rec, dumps = int(hdr["HDR_SIZE"]), int(hdr["RECORD_HEADER_BYTES"]), []
+    while at < len(raw):
+        first_block, n_columns = (int(v) for v in np.frombuffer(raw, "<u8", 2, at))
+        at += rec
+        dumps.append((first_block, n_columns, np.frombuffer(raw, "<i8", n, at).reshape(shape)))
+        at += 8 * n
+    return hdr, dumps
+
+
 def run_observation_junk_dm(cfg: BfConfig, n_blocks: int, delays, dm_path: str | None, detected_path: str | None = None,
                             ring_blocks: int = 4, seed: int = 0xD5A, gpu: int = 0, device: int = 0, burn_in: int = 0,
                             verbose: bool = False):

@@ -243,6 +243,47 @@ int bf_beamform_device(bf_handle *h, const void *d_packed, int n_units, float *d
 int bf_incoherent_device(bf_handle *h, const void *d_packed, int n_units, float *d_out, size_t stride, void *hip_stream);
 int bf_set_incoherent_beam(bf_handle *h, int beam);
 
+/* ---- The correlator (docs/CORRELATOR.md) ---------------------------------------------------------------------------------
+ * The reference uploads steering weights only (src/beamformer.cu:230-241); a real array multiplies them by per-(frequency, antenna)
+ * gains, and those are solved from VISIBILITIES: per channel the cross-products of the antenna voltages, taken on a calibrator.
+ * The voltages are the packed bytes the beamformer reads ([unit][freq][time][ant], time = n_out_per_gemm * n_pol * n_avg).
+ * POLARISATION ORDER -- the one place the library reads it: the reference never tells polarisation from time inside a window; its
+ * README documents the order Time x Polarization x Antenna, polarisation fastest, and the correlator takes that order: column c of
+ * a gemm-unit belongs to polarisation c % n_pol.  Per channel f and polarisation p
+ *   V[f][p][a1][a2] = sum over the units and over the columns c = p (mod n_pol) of v[u][f][c][a1] * conj(v[u][f][c][a2]),   a2 <= a1
+ * stored as the packed lower triangle [freq][pol][bl]{re, im}, bl = a1 * (a1 + 1) / 2 + a2: n_ant * (n_ant + 1) / 2 entries per
+ * (f, p), two int64 each; the diagonal is the autocorrelation (im == 0).  Every sum is an exact integer (int8 MFMA with time as the
+ * K axis, int32 within a launch, int64 in memory): the result is the same for every launch path and bit-equal to a restatement in
+ * any order (tests/support/corr_oracle.py).  Known answer: bytes 0xD7 (-3+7i) at antenna 1 and 0x25 (2+5i) at antenna 0 in one
+ * column give V[1][0] = (29, 29), V[1][1] = (58, 0), V[0][0] = (29, 0).
+ * Bounds: a column contributes at most 128 to either part; with N = n_units * n_out_per_gemm * n_avg columns per polarisation in
+ * one call, the call is defined for 128 * N <= 2^31 - 1, i.e. N < 2^24, and for n_ant <= 256 (any multiple of 4; the output grows
+ * as n_ant^2).  Beyond either every call below returns BF_ERR_INVALID and launches nothing.
+ * bf_correlate_device: d_packed as for bf_beamform_device (16-byte aligned) -> d_vis (device, bf_corr_entries(cfg) * 2 int64),
+ *   overwritten (accumulate == 0) or added to (accumulate != 0).  One kernel launch; needs no weights: callable before
+ *   bf_set_weights.  bf_corr_entries: n_freq * n_pol * n_ant * (n_ant + 1) / 2 complex entries (two int64 each).
+ * A bf_corr is the correlator as a STAGE: it owns one int64 accumulator on the device, a column count and max_in_flight pinned
+ *   result sets.  bf_corr_push adds n_units gemm-units at d_packed, asynchronously on hip_stream; bf_corr_push_block the units
+ *   [first_unit, first_unit + n_units) of ring slot `slot` -- the resident block bf_enqueue_block reads -- on compute queue
+ *   stream_idx, behind whatever that queue holds.  bf_corr_dump snapshots the accumulator into the next pinned set and zeroes it
+ *   (on a copy queue of the stage; hip_stream is not held).  Pushes and dumps of one stage share the accumulator, so the stage
+ *   orders them itself, whichever queues they are issued on: each waits for the kernel or copy of the one before it, and a push
+ *   holds the caller's queue for its kernel only.  A dump beyond max_in_flight uncollected ones returns BF_ERR_STATE before it
+ *   queues anything.  bf_corr_collect waits for the OLDEST uncollected dump and copies its entries to `out` (host, bf_corr_entries
+ *   * 2 int64) and the columns per polarisation it integrated to *n_columns_per_pol (may be NULL); nothing pending: BF_ERR_STATE.
+ *   bf_corr_pending: dumps not yet collected.  Lifetime as for a bf_sps: a handle that goes first releases the device memory, the
+ *   stage then answers BF_ERR_STATE and can still be destroyed. */
+int bf_correlate_device(bf_handle *h, const void *d_packed, int n_units, int64_t *d_vis, int accumulate, void *hip_stream);
+size_t bf_corr_entries(const bf_config *cfg);
+typedef struct bf_corr bf_corr;
+int bf_corr_create(bf_handle *h, int max_in_flight, bf_corr **out);
+int bf_corr_destroy(bf_corr *c);
+int bf_corr_push(bf_corr *c, const void *d_packed, int n_units, void *hip_stream);
+int bf_corr_push_block(bf_corr *c, int stream_idx, int slot, int first_unit, int n_units);
+int bf_corr_dump(bf_corr *c, void *hip_stream);
+int bf_corr_collect(bf_corr *c, int64_t *out, uint64_t *n_columns_per_pol);
+int bf_corr_pending(const bf_corr *c);
+
 /* a1 alone (expand_input, src/beamformer.cuh:66-109): nbytes packed bytes -> 2*nbytes int8 (re, im pairs in
  * order).  nbytes must be a multiple of 16, pointers 16-byte aligned. */
 int bf_expand_device(bf_handle *h, const void *d_in, size_t nbytes, void *d_out, void *hip_stream);

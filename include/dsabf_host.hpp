@@ -573,6 +573,53 @@ public:
     uint64_t get_candidates_written() const { return written; }
 };
 
+// ---- The correlator inside the loop (include/dsabf.h: bf_corr_*; docs/CORRELATOR.md) ------------------------------------------
+// With observation_options::corr_blocks > 0 run_observation creates a bf_corr, pushes the gemm-units of every launch into it on the
+// launch's queue (behind the detect launch, from the resident block), dumps after the last launch of every corr_blocks-th analysed
+// block and hands each dump to a vis_sink once that block's analysis event has fired.
+struct vis_sink {
+    virtual ~vis_sink() {}
+    // one integration: blocks first_block .. first_block + corr_blocks - 1 (counted from the first analysed block), n_columns_per_pol
+    // columns per polarisation, vis = int64 [freq][pol][a1 (a1 + 1) / 2 + a2]{re, im} (n_int64 values)
+    virtual bool deliver(uint64_t first_block, uint64_t n_columns_per_pol, const int64_t* vis, size_t n_int64) = 0;
+    virtual void close() {}
+};
+
+// File: the 4096-byte ASCII header (`KEY value` lines, NUL padded: CONTENT visibilities, DTYPE int64, NANT, NPOL, NFREQ,
+// FIRST_CHANNEL, LAYOUT freq,pol,baseline(lower triangle a1*(a1+1)/2+a2),reim), then one record per dump: uint64 first_block,
+// uint64 n_columns_per_pol, the entries (little-endian int64).
+class vis_file_sink : public vis_sink {
+    int fd = -1;
+    uint64_t dumps = 0;
+
+public:
+    static constexpr size_t kHeaderBytes = 4096;
+    static constexpr size_t kRecordBytes = 16;
+    vis_file_sink(const bf_config& cfg, const char* path, int first_channel, int gpu);
+    ~vis_file_sink() override;
+    vis_file_sink(const vis_file_sink&) = delete;
+    vis_file_sink& operator=(const vis_file_sink&) = delete;
+    bool is_open() const { return fd >= 0; }
+    bool deliver(uint64_t first_block, uint64_t n_columns_per_pol, const int64_t* vis, size_t n_int64) override;
+    void close() override;
+    uint64_t get_dumps_written() const { return dumps; }
+};
+
+// Keeps the dumps in host memory (tests, small runs).
+class vis_memory_sink : public vis_sink {
+public:
+    struct dump {
+        uint64_t first_block, n_columns_per_pol;
+        std::vector<int64_t> vis;
+    };
+    std::vector<dump> dumps;
+    bool deliver(uint64_t first_block, uint64_t n_columns_per_pol, const int64_t* vis, size_t n_int64) override
+    {
+        dumps.push_back({first_block, n_columns_per_pol, std::vector<int64_t>(vis, vis + n_int64)});
+        return true;
+    }
+};
+
 struct observation_options {
     int gpu = 0;          // -g
     int device = 0;
@@ -628,6 +675,11 @@ struct observation_options {
     // summed over the antennas instead of a tied beam (bf_set_incoherent_beam, set on the handle before the loop); -1 = off.  On a
     // sharded run every rank gives the same index: the sum is per channel, each shard fills its own slice of the column.
     int incoherent_beam = -1;
+    // The correlator (docs/CORRELATOR.md; needs block_launch): corr_blocks = analysed blocks integrated per dump, 0 = off.  Every dump
+    // goes to vis_sink (may be NULL: the stage still runs).  An integration that is incomplete when the run ends is dropped.  On a
+    // sharded run every rank correlates its own channels and has a sink of its own; the gather is untouched.
+    int corr_blocks = 0;
+    dsabf::vis_sink* vis_sink = nullptr;
 };
 struct observation_result {
     float observation_time_ms = 0;
@@ -639,6 +691,7 @@ struct observation_result {
     uint64_t dm_times = 0;          // output times the DM stage produced (dm_delays set): rows analysed - the largest delay
     uint64_t dm_chunks = 0;         // chunks handed to dm_sink
     uint64_t sps_candidates = 0;    // candidates the search stage found (sps_widths > 0)
+    uint64_t vis_dumps = 0;         // integrations the correlator dumped (corr_blocks > 0)
 };
 // The reference's production main() loop on top of the C-ABI.  pos/dir: antenna positions and beam directions.
 int run_observation(const bf_config& cfg, const observation_options& opt, block_source& source, const antenna* pos,
