@@ -12,6 +12,7 @@ BF_OK = 0
 BF_NOT_READY = 1
 BF_ERR_INVALID, BF_ERR_DEVICE, BF_ERR_NO_DEVICE, BF_ERR_STATE = -1, -2, -3, -4
 BF_DETECT_CANONICAL, BF_DETECT_FAST, BF_DETECT_CONTRACTED = 0, 1, 2
+BF_CAL_PHASE, BF_CAL_FULL = 0, 1
 
 
 class BfConfig(C.Structure):
@@ -56,6 +57,12 @@ class BfSpsCandidate(C.Structure):
 
     _fields_ = [("t_start", C.c_uint64), ("dm", C.c_int32), ("beam", C.c_int32), ("width", C.c_int32), ("peak", C.c_float),
                 ("snr", C.c_double)]
+
+
+class BfCalOptions(C.Structure):
+    """Mirror of ``bf_cal_options`` (include/dsabf.h)."""
+
+    _fields_ = [("tol", C.c_double), ("max_iter", C.c_int), ("ref_ant", C.c_int), ("joint_pol", C.c_int)]
 
 
 class DsabfError(RuntimeError):
@@ -114,6 +121,11 @@ SIGNATURES = {
     "bf_corr_dump": (C.c_int, [C.c_void_p, C.c_void_p]),
     "bf_corr_collect": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
     "bf_corr_pending": (C.c_int, [C.c_void_p]),
+    "bf_cal_default_options": (C.c_int, [C.POINTER(BfCalOptions)]),
+    "bf_cal_gain_entries": (C.c_size_t, [C.POINTER(BfConfig), C.c_int]),
+    "bf_solve_gains_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(BfCalOptions), C.c_void_p, C.c_void_p,
+                                        C.c_void_p]),
+    "bf_calibrate_weights_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "bf_expand_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "bf_gemm_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bf_dedisperse_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -256,6 +268,9 @@ SIGNATURES = {
     "bfh_run_debug_observation2": (C.c_int, [C.POINTER(BfConfig), C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p,
                                              C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_int),
                                              C.POINTER(C.c_float), C.c_int]),
+    "bfh_run_debug_observation3": (C.c_int, [C.POINTER(BfConfig), C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p,
+                                             C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_int),
+                                             C.POINTER(C.c_float), C.c_int, C.c_char_p, C.c_void_p]),
 }
 
 

@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-from ._lib import BfConfig, BfSpsCandidate, BfSpsPeak, BfSpsStat, check, load
+from ._lib import BF_CAL_FULL, BF_CAL_PHASE, BfCalOptions, BfConfig, BfSpsCandidate, BfSpsPeak, BfSpsStat, check, load
 
 
 def debug_config(**over) -> BfConfig:
@@ -117,6 +117,28 @@ class Beamformer:
     def corr_entries(self) -> int:
         """bf_corr_entries: n_freq * n_pol * n_ant (n_ant + 1) / 2 complex entries (two int64 each)."""
         return self._lib.bf_corr_entries(C.byref(self.cfg))
+
+    def solve_gains(self, d_vis, d_gains, d_info, model=None, flags=None, tol: float = 1e-10, max_iter: int = 200, ref_ant: int = -1,
+                    joint_pol: bool = False, stream: int = 0) -> None:
+        """bf_solve_gains_device (docs/CALIBRATION.md): the visibilities d_vis (as ``correlate`` leaves them) -> d_gains, float64
+        [pol_out][freq][ant]{re, im} (``gain_entries(joint_pol)`` complex entries), and d_info, int32 [pol_out][freq]{iterations,
+        status}.  ``model``: float64 [freq][ant]{re, im} on the device or None (all ones); ``flags``: uint8 [ant] on the device or None."""
+        opt = BfCalOptions(float(tol), int(max_iter), int(ref_ant), int(bool(joint_pol)))
+        check(self._lib.bf_solve_gains_device(self._h, _ptr(d_vis), _ptr(model), _ptr(flags), C.byref(opt), _ptr(d_gains), _ptr(d_info),
+                                              C.c_void_p(stream)))
+
+    def calibrate_weights(self, d_w_in, d_gains_layer, d_w_out, flags=None, mode: str = "phase", stream: int = 0) -> None:
+        """bf_calibrate_weights_device: d_w_out = d_w_in times conj(g) / |g| (``mode`` "phase"), times k_f / |g| as well ("full"),
+        rounded half to even and clipped to +-127; int8 [freq][ant][beam]{re, im}, the array ``set_weights_device`` takes."""
+        modes = {"phase": BF_CAL_PHASE, "full": BF_CAL_FULL}
+        if mode not in modes:
+            raise ValueError("mode must be 'phase' or 'full', not %r" % (mode,))
+        check(self._lib.bf_calibrate_weights_device(self._h, _ptr(d_w_in), _ptr(d_gains_layer), _ptr(flags), modes[mode], _ptr(d_w_out),
+                                                    C.c_void_p(stream)))
+
+    def gain_entries(self, joint_pol: bool = False) -> int:
+        """bf_cal_gain_entries: (joint_pol ? 1 : n_pol) * n_freq * n_ant complex entries (two float64 each)."""
+        return self._lib.bf_cal_gain_entries(C.byref(self.cfg), int(bool(joint_pol)))
 
     def expand(self, d_in, nbytes: int, d_out, stream: int = 0) -> None:
         check(self._lib.bf_expand_device(self._h, _ptr(d_in), int(nbytes), _ptr(d_out), C.c_void_p(stream)))

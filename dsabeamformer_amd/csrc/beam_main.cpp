@@ -35,6 +35,12 @@
 //                                                   triangle per channel and polarisation).  With -R: every shard correlates its own
 //                                                   channels and writes vis_file.<rank>.  (-j counts the 25 burn-in reads: -j 27
 //                                                   analyses two blocks.)
+//   beam -E vis_file -G gains_file [-P]            the gain solver (docs/CALIBRATION.md), no observation: every record of a file written
+//                                                   by -V is solved for the per-(channel, polarisation, antenna) gains of a calibrator at
+//                                                   the phase centre (-P: the polarisations jointly, one layer) and written as one record
+//                                                   of gains_file; the geometry comes from vis_file's header (a shard's vis_file.<rank> too).
+//   beam ... -A gains_file                          DEBUG run or observation mode: layer 0 of the last record of gains_file calibrates the
+//                                                   steering weights (conj(g) / |g|) before they are set.
 //
 // With the reference's `make debug` geometry (default) it generates synthetic point-source voltages on the CPU,
 // streams them through the observation loop and writes bin/data.py (dedispersed beam responses, one row per source)
@@ -82,9 +88,11 @@ int main(int argc, char* argv[])
     std::string vis_path;           // -V: where the correlator's dumps go
     int corr_blocks = 1;            // -L: analysed blocks integrated per dump
     bool corr_blocks_given = false;
+    std::string solve_vis, solve_gains_path, apply_gains;   // -E / -G: the gain solver on a -V file; -A: gains applied to the weights
+    bool solve_joint = false;                               // -P
 
     int arg = 0;
-    while ((arg = getopt(argc, argv, "s:g:p:d:o:D:a:c:k:K:j:w:R:r:I:M:N:T:W:Q:S:B:C:i:V:L:XuvhH")) != -1) {  // src/beamformer.cu:41-43 (+ -o -D -a -v)
+    while ((arg = getopt(argc, argv, "s:g:p:d:o:D:a:c:k:K:j:w:R:r:I:M:N:T:W:Q:S:B:C:i:V:L:E:G:A:PXuvhH")) != -1) {  // src/beamformer.cu:41-43 (+ -o -D -a -v)
         switch (arg) {
             case 's': sources = optarg; break;                 // :77-89
             case 'g': opt.gpu = atoi(optarg); break;           // :92-100
@@ -111,6 +119,10 @@ int main(int argc, char* argv[])
             case 'i': ib_beam = atoi(optarg); ib_given = true; break;
             case 'V': vis_path = optarg; break;
             case 'L': corr_blocks = atoi(optarg); corr_blocks_given = true; break;
+            case 'E': solve_vis = optarg; break;
+            case 'G': solve_gains_path = optarg; break;
+            case 'A': apply_gains = optarg; break;
+            case 'P': solve_joint = true; break;
             case 'u': per_unit = true; break;                   // the reference's launch pattern: one launch per gemm-unit
             case 'v': opt.verbose = true; cfg.verbose = 1; break;
             case 'c': core = atoi(optarg); break;              // :59-65
@@ -140,6 +152,11 @@ int main(int argc, char* argv[])
                              " -V file [-L corr_blocks]   observation mode: the correlator -- antenna visibilities of the analysed blocks, integrated\n"
                              "                         over corr_blocks blocks [1] per dump, to file (with -R: file.<rank>, each shard its own channels);\n"
                              "                         -j counts the 25 burn-in reads: -j 27 analyses two blocks\n"
+                             " -E vis_file -G gains_file [-P]   the gain solver, no observation: every record of a -V file solved for the antenna gains\n"
+                             "                         of a calibrator at the phase centre (StEFCal on the device; -P: both polarisations jointly,\n"
+                             "                         one layer) and written as one record of gains_file; works on a shard's vis_file.<rank> too\n"
+                             " -A gains_file           DEBUG run and observation mode: layer 0 of the last record of gains_file calibrates the\n"
+                             "                         steering weights (conj(g) / |g|); its NANT / NFREQ / FIRST_CHANNEL must be the run's\n"
                              " -H                      this text\n";
                 return EXIT_SUCCESS;
             default: usage(true, std::cerr); return EXIT_FAILURE;
@@ -177,6 +194,49 @@ int main(int argc, char* argv[])
         fprintf(stderr, "beam: -V (correlator) belongs to the observation mode: give -j n_blocks or -k ring\n");
         return EXIT_FAILURE;
     }
+    if (!solve_gains_path.empty() && solve_vis.empty()) {
+        fprintf(stderr, "beam: -G (where the gains go) belongs to the gain solver: give -E vis_file\n");
+        return EXIT_FAILURE;
+    }
+    if (solve_joint && solve_vis.empty()) {
+        fprintf(stderr, "beam: -P (joint polarisations) belongs to the gain solver: give -E vis_file -G gains_file\n");
+        return EXIT_FAILURE;
+    }
+    if (!solve_vis.empty()) {   // solve mode: no observation of either kind
+        if (junk_blocks >= 0 || !ring_key.empty()) {
+            fprintf(stderr, "beam: -E (gain solver) runs no observation: leave out -j / -k\n");
+            return EXIT_FAILURE;
+        }
+        if (solve_gains_path.empty()) {
+            fprintf(stderr, "beam: -E needs -G gains_file (where the gains go)\n");
+            return EXIT_FAILURE;
+        }
+        if (!apply_gains.empty()) {
+            fprintf(stderr, "beam: -A (apply gains) belongs to a run; -E only solves\n");
+            return EXIT_FAILURE;
+        }
+        record_file_header vh;
+        std::string why;
+        if (!read_record_file_header(solve_vis.c_str(), &vh, &why) || vh.content != "visibilities") {
+            fprintf(stderr, "beam: -E %s\n", why.empty() ? (solve_vis + " is not a file of visibilities").c_str() : why.c_str());
+            return EXIT_FAILURE;
+        }
+    }
+    // -A: read before any device is touched; a DEBUG run has the DEBUG geometry, observation mode a rank's share of the production one
+    std::vector<double> gains_layer;
+    if (!apply_gains.empty()) {
+        const bool observe = junk_blocks >= 0 || !ring_key.empty();
+        bf_config gcfg;
+        bf_config_default(&gcfg, observe ? 0 : 1);
+        const int n_freq = observe && world >= 1 && gcfg.n_freq % world == 0 ? gcfg.n_freq / world : gcfg.n_freq;
+        const int first = observe && rank >= 0 ? rank * n_freq : 0;
+        std::string why;
+        if (!read_gains_layer(apply_gains.c_str(), gcfg.n_ant, n_freq, first, &gains_layer, &why)) {
+            fprintf(stderr, "beam: -A %s\n", why.c_str());
+            return EXIT_FAILURE;
+        }
+        opt.gains = gains_layer.data();
+    }
     opt.positions = positions.empty() ? nullptr : positions.c_str();
     opt.directions = directions.empty() ? nullptr : directions.c_str();
     opt.sources = sources.empty() ? nullptr : sources.c_str();
@@ -190,6 +250,17 @@ int main(int argc, char* argv[])
     }
     char name[256];
     if (bf_device_name(opt.device, name, sizeof name) == BF_OK) std::cout << "Selected: " << name << std::endl;
+
+    if (!solve_vis.empty()) {   // -E / -G: the gain solver on a file of visibilities
+        uint64_t n_records = 0;
+        int src = solve_vis_file(solve_vis.c_str(), solve_gains_path.c_str(), solve_joint, opt.device, &n_records, std::cout);
+        if (src != BF_OK) {
+            fprintf(stderr, "GPUassert: %s (%d)\n", bf_last_error(), src);
+            return EXIT_FAILURE;
+        }
+        std::cout << "Wrote " << n_records << " gain records to " << solve_gains_path << std::endl;
+        return 0;
+    }
 
     if (junk_blocks >= 0 || !ring_key.empty()) {  // observation (production) mode: N_AVERAGING 16
         bf_config pcfg;
@@ -286,6 +357,7 @@ int main(int argc, char* argv[])
         oopt.rank = rank;
         oopt.comm = comm;
         oopt.incoherent_beam = ib_beam;
+        oopt.gains = gains_layer.empty() ? nullptr : gains_layer.data();
         const bf_config& sink_cfg = comm ? full_cfg : pcfg;
         if (comm && rank != 0) {          // only the gather root has a consumer
             out_ring.clear();

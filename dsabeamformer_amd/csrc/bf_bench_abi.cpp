@@ -60,8 +60,10 @@ int bf_set_switch(bf_handle* h, const char* name, int value)
         h->no_fold = value == 0;         // takes effect at the next bf_set_weights, like "paired" (which, at 0, rules the fold kernel out too)
     } else if (!strcmp(name, "dm_ring")) {
         h->dm_ring = value != 0;         // takes effect at the next bf_dm_stream_create
+    } else if (!strcmp(name, "cal_resident")) {
+        h->cal_resident = value != 0;    // 0: bf_solve_gains_device streams the visibilities at every antenna count (same bits)
     } else {
-        return fail(BF_ERR_INVALID, "unknown switch \"%s\" (tsplit, rtw_kout, lds_pad, dm_wide, dm_ring, paired, fold, coalesce)", name);
+        return fail(BF_ERR_INVALID, "unknown switch \"%s\" (tsplit, rtw_kout, lds_pad, dm_wide, dm_ring, paired, fold, coalesce, cal_resident)", name);
     }
     return BF_OK;
 }

@@ -350,8 +350,22 @@ int bfh_run_debug_observation2(const bf_config* cfg, int gpu, const char* positi
                                const char* sources, const char* output, int device, int verbose, float* ded_out,
                                size_t ded_capacity, int* n_pt_sources, float* observation_ms, int per_unit_launches)
 {
+    return bfh_run_debug_observation3(cfg, gpu, positions, directions, sources, output, device, verbose, ded_out, ded_capacity, n_pt_sources,
+                                      observation_ms, per_unit_launches, nullptr, nullptr);
+}
+int bfh_run_debug_observation3(const bf_config* cfg, int gpu, const char* positions, const char* directions, const char* sources,
+                               const char* output, int device, int verbose, float* ded_out, size_t ded_capacity, int* n_pt_sources,
+                               float* observation_ms, int per_unit_launches, const char* gains_file, int8_t* weights_out)
+{
     if (!cfg) return BF_ERR_INVALID;
     debug_run_options opt;
+    std::vector<double> gains_layer;
+    if (gains_file) {
+        std::string why;
+        if (!read_gains_layer(gains_file, cfg->n_ant, cfg->n_freq, 0, &gains_layer, &why)) return set_error(BF_ERR_INVALID, why.c_str());
+        opt.gains = gains_layer.data();
+    }
+    opt.weights_out = weights_out;
     opt.block_launch = per_unit_launches == 0;
     opt.gpu = gpu;
     opt.positions = positions;

@@ -331,7 +331,14 @@ int run_debug_observation(const bf_config& cfg, const debug_run_options& opt, de
         std::vector<int8_t> fourier_coefficients((size_t)cfg.n_freq * cfg.n_ant * cfg.n_beams * 2);
         generate_fourier_coefficients(cfg.n_beams, cfg.n_ant, cfg.n_freq, 0, opt.gpu, pos.data(), dir.data(),
                                       fourier_coefficients.data());
-        if ((rc = bf_set_weights(h, fourier_coefficients.data())) != BF_OK) return gpu_error(log, rc);
+        if (opt.gains) {
+            rc = set_weights_calibrated(h, opt.device, fourier_coefficients.data(), opt.gains, opt.weights_out);
+            if (rc == BF_OK) log << "Calibrated the weights with one layer of gains" << std::endl;
+        } else {
+            rc = bf_set_weights(h, fourier_coefficients.data());
+            if (rc == BF_OK && opt.weights_out) ::memcpy(opt.weights_out, fourier_coefficients.data(), fourier_coefficients.size());
+        }
+        if (rc != BF_OK) return gpu_error(log, rc);
     }
 
     std::vector<int> timeSlice((size_t)n_streams);
@@ -570,7 +577,12 @@ struct production_run {
         ::memset(beam_out, 0, beam_out_stride * cfg.n_streams * sizeof(float));
         std::vector<int8_t> fourier_coefficients((size_t)cfg.n_freq * cfg.n_ant * cfg.n_beams * 2);
         generate_fourier_coefficients(cfg.n_beams, cfg.n_ant, cfg.n_freq, opt.rank * cfg.n_freq, opt.gpu, pos, dir, fourier_coefficients.data());
-        if ((rc = bf_set_weights(dev.h, fourier_coefficients.data())) != BF_OK) return rc;
+        if (opt.gains) {
+            if ((rc = set_weights_calibrated(dev.h, opt.device, fourier_coefficients.data(), opt.gains)) != BF_OK) return rc;
+            log << "Calibrated the weights with one layer of gains" << std::endl;
+        } else if ((rc = bf_set_weights(dev.h, fourier_coefficients.data())) != BF_OK) {
+            return rc;
+        }
         return opt.incoherent_beam >= 0 ? bf_set_incoherent_beam(dev.h, opt.incoherent_beam) : BF_OK;
     }
 

@@ -204,16 +204,22 @@ class ObservationLoopState:
 
 def run_debug_observation(cfg: BfConfig, gpu: int = 0, positions: str | None = None, directions: str | None = None,
                           sources: str | None = None, output: str | None = None, device: int = 0,
-                          verbose: bool = False, max_sources: int = 4096, per_unit_launches: bool = False):
+                          verbose: bool = False, max_sources: int = 4096, per_unit_launches: bool = False,
+                          gains: str | None = None, return_weights: bool = False):
     """The reference's `make debug` main() end to end; returns (dedispersed [n_src][n_beams], observation_ms).
-    per_unit_launches: the reference's own launch pattern instead of one launch / copy / DM-0 launch per block."""
+    per_unit_launches: the reference's own launch pattern instead of one launch / copy / DM-0 launch per block.
+    gains: a file of gains (read_gains_file) whose last record's layer 0 calibrates the steering weights, as `beam -A` does.
+    return_weights: return dict(dedispersed, ms, weights) instead, weights = the int8 [freq][ant][beam][2] array the run set."""
     ded = np.zeros((max_sources, cfg.n_beams), np.float32)
     n = C.c_int()
     ms = C.c_float()
     enc = lambda s: s.encode() if s else None  # noqa: E731
-    check(load().bfh_run_debug_observation2(C.byref(cfg), gpu, enc(positions), enc(directions), enc(sources), enc(output),
+    w = np.zeros((cfg.n_freq, cfg.n_ant, cfg.n_beams, 2), np.int8) if return_weights else None
+    check(load().bfh_run_debug_observation3(C.byref(cfg), gpu, enc(positions), enc(directions), enc(sources), enc(output),
                                             device, 1 if verbose else 0, _p(ded), ded.size, C.byref(n), C.byref(ms),
-                                            1 if per_unit_launches else 0))
+                                            1 if per_unit_launches else 0, enc(gains), _p(w) if return_weights else None))
+    if return_weights:
+        return {"dedispersed": ded[:n.value].copy(), "ms": ms.value, "weights": w}
     return ded[:n.value].copy(), ms.value
 
 
@@ -299,6 +305,43 @@ def read_vis_file(path: str):
         dumps.append((first_block, n_columns, np.frombuffer(raw, "<i8", n, at).reshape(shape)))
         at += 8 * n
     return hdr, dumps
+
+
+GAINS_LAYOUT = "pol,freq,ant,reim"
+
+
+def read_gains_file(path: str):
+    """Parse a dsabf::gains_file_sink file (docs/CALIBRATION.md): returns (header dict, list of (first_block, n_columns_per_pol,
+    float64 gains [pol_out][n_freq][n_ant][2], int32 info [pol_out][n_freq][2] = iterations, status) per record)."""
+    raw = open(path, "rb").read()
+    text = raw[:DETECTED_HEADER_BYTES].split(b"\0", 1)[0].decode()
+    hdr = dict(line.split(None, 1) for line in text.splitlines() if line.strip())
+    assert hdr["CONTENT"] == "gains" and hdr["DTYPE"] == "float64" and hdr["LAYOUT"] == GAINS_LAYOUT, hdr
+    shape = (int(hdr["NPOL"]), int(hdr["NFREQ"]), int(hdr["NANT"]), 2)
+    n, n_info = shape[0] * shape[1] * shape[2] * 2, shape[0] * shape[1] * 2
+    at, rec, records = int(hdr["HDR_SIZE"]), int(hdr["RECORD_HEADER_BYTES"]), []
+    while at < len(raw):
+        first_block, n_columns = (int(v) for v in np.frombuffer(raw, "<u8", 2, at))
+        at += rec
+        gains = np.frombuffer(raw, "<f8", n, at).reshape(shape)
+        at += 8 * n
+        records.append((first_block, n_columns, gains, np.frombuffer(raw, "<i4", n_info, at).reshape(shape[0], shape[1], 2)))
+        at += 4 * n_info
+    return hdr, records
+
+
+def write_gains_file(path: str, n_ant: int, n_pol: int, n_freq: int, first_channel: int, records) -> None:
+    """Write a file of gains in dsabf::gains_file_sink's format, e.g. gains solved elsewhere for `beam -A`: records is a list of
+    (first_block, n_columns_per_pol, gains [n_pol][n_freq][n_ant][2], info [n_pol][n_freq][2]); n_pol is the file's NPOL (pol_out)."""
+    text = ("HDR_VERSION 1.0\nHDR_SIZE %d\nINSTRUMENT DSA\nCONTENT gains\nDTYPE float64\nENDIAN little\nLAYOUT %s\n"
+            "RECORD_HEADER_BYTES 16\nNANT %d\nNPOL %d\nNFREQ %d\nFIRST_CHANNEL %d\nINFO int32 pol,freq,(iterations,status)\n"
+            % (DETECTED_HEADER_BYTES, GAINS_LAYOUT, n_ant, n_pol, n_freq, first_channel)).encode()
+    with open(path, "wb") as fp:
+        fp.write(text.ljust(DETECTED_HEADER_BYTES, b"\0"))
+        for first_block, n_columns, gains, info in records:
+            g, i = np.ascontiguousarray(gains, "<f8"), np.ascontiguousarray(info, "<i4")
+            assert g.shape == (n_pol, n_freq, n_ant, 2) and i.shape == (n_pol, n_freq, 2)
+            fp.write(np.array([first_block, n_columns], "<u8").tobytes() + g.tobytes() + i.tobytes())
 
 
 def run_observation_junk_dm(cfg: BfConfig, n_blocks: int, delays, dm_path: str | None, detected_path: str | None = None,

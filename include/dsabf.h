@@ -284,6 +284,47 @@ int bf_corr_dump(bf_corr *c, void *hip_stream);
 int bf_corr_collect(bf_corr *c, int64_t *out, uint64_t *n_columns_per_pol);
 int bf_corr_pending(const bf_corr *c);
 
+/* ---- The gain solver and calibrated weights (docs/CALIBRATION.md) ------------------------------------------------------------
+ * Extends the weight upload, src/beamformer.cu:230-241 (the steering weights), :251, :272 (their allocation and copy): between
+ * the visibilities of a calibrator (bf_correlate_device) and the weights a calibrated array uploads (bf_set_weights_device) sit the
+ * per-(channel, polarisation, antenna) complex gains g with V[a1][a2] ~ g[a1] conj(g[a2]) M[a1][a2], M[p][q] = s_p conj(s_q) the
+ * model of one point source.  bf_solve_gains_device solves them with StEFCal (Salvini & Wijnholds 2014) on the device, one
+ * workgroup per (channel, polarisation layer); bf_calibrate_weights_device multiplies a weight array by conj(g) / |g|.
+ * The arithmetic is fp64, one rounding per operation (no fused multiply-add), every sum in ONE fixed order (OSUM, docs/CALIBRATION.md
+ * section 2), so the result is bit-equal to a numpy restatement (tests/support/cal_oracle.py) whatever path the kernel takes.
+ * bf_solve_gains_device: d_vis as bf_correlate_device leaves it ([freq][pol][bl]{re, im} int64), d_model NULL (all ones: the source
+ *   at the phase centre) or fp64 [freq][ant]{re, im} (the calibrator's steering phasors s), d_flags NULL or uint8 [ant] (non-zero:
+ *   the antenna is left out and its gain is exactly (0, 0)).  opt: tol (stop when |g - g_prev| <= tol |g|, tested on even
+ *   iterations), max_iter >= 1, ref_ant (the antenna whose gain gets zero phase; -1: the first unflagged one), joint_pol (non-zero:
+ *   the polarisations' integers are added first and ONE layer is solved -- the beamformer has one weight per (f, a, b) for both).
+ *   d_gains: fp64 [pol_out][freq][ant]{re, im}, pol_out = joint_pol ? 1 : n_pol (bf_cal_gain_entries complex entries; one layer is
+ *   contiguous); d_info: int32 [pol_out][freq]{iterations, status}, status 1 = converged, 0 = max_iter ran out.  A dead antenna
+ *   (a zero row) stays at (0, 0); no NaN is produced.  d_vis, d_model, d_gains 16-byte aligned.
+ * bf_calibrate_weights_device: d_w_in / d_w_out int8 [freq][ant][beam]{re, im} as for bf_set_weights_device (4-byte aligned; they
+ *   may be the same array), d_gains_layer ONE layer [freq][ant]{re, im}.  Per (f, a) with m = |g|: BF_CAL_PHASE c = conj(g) / m;
+ *   BF_CAL_FULL c = conj(g) / m * (k_f / m), k_f the smallest non-zero m among the channel's unflagged antennas (|c| <= 1); a flagged
+ *   or zero-gain antenna gets c = 0.  Each part of w * c is rounded half to even and clipped to [-127, 127].
+ * Both calls are asynchronous on hip_stream, need no weights set, leave the caller's current device as found and keep NO state or
+ *   scratch in the handle (the solver reads d_vis in place), so calls issued on different queues without synchronisation are
+ *   independent.  One exception to "asynchronous": with ref_ant >= 0 AND d_flags given, the solver reads that one flag byte back
+ *   behind hip_stream (it waits for the queue) to refuse a flagged reference.  Defined for n_ant a multiple of 4 up to 256; beyond
+ *   that, and for max_iter < 1, tol < 0, ref_ant out of range or flagged, a mode that is neither, or a NULL pointer, they return
+ *   BF_ERR_INVALID and launch nothing.  bf_cal_default_options: tol 1e-10, max_iter 200, ref_ant -1, joint_pol 0. */
+typedef struct {
+    double tol;
+    int max_iter;
+    int ref_ant;
+    int joint_pol;
+} bf_cal_options;
+#define BF_CAL_PHASE 0
+#define BF_CAL_FULL 1
+int bf_cal_default_options(bf_cal_options *o);
+size_t bf_cal_gain_entries(const bf_config *cfg, int joint_pol);
+int bf_solve_gains_device(bf_handle *h, const int64_t *d_vis, const double *d_model, const uint8_t *d_flags, const bf_cal_options *opt,
+                          double *d_gains, int32_t *d_info, void *hip_stream);
+int bf_calibrate_weights_device(bf_handle *h, const int8_t *d_w_in, const double *d_gains_layer, const uint8_t *d_flags, int mode,
+                                int8_t *d_w_out, void *hip_stream);
+
 /* a1 alone (expand_input, src/beamformer.cuh:66-109): nbytes packed bytes -> 2*nbytes int8 (re, im pairs in
  * order).  nbytes must be a multiple of 16, pointers 16-byte aligned. */
 int bf_expand_device(bf_handle *h, const void *d_in, size_t nbytes, void *d_out, void *hip_stream);

@@ -89,6 +89,13 @@ int bfh_run_debug_observation(const bf_config *cfg, int gpu, const char *positio
 int bfh_run_debug_observation2(const bf_config *cfg, int gpu, const char *positions, const char *directions,
                                const char *sources, const char *output, int device, int verbose, float *ded_out,
                                size_t ded_capacity, int *n_pt_sources, float *observation_ms, int per_unit_launches);
+/* The same with calibrated weights (docs/CALIBRATION.md; `beam -A`): gains_file (may be NULL) is a file of gains whose geometry is the
+ * run's (NANT, NFREQ, FIRST_CHANNEL 0; anything else: BF_ERR_INVALID before any device work); layer 0 of its last record multiplies the
+ * steering weights by conj(g) / |g| on the device before they are set.  weights_out (may be NULL) receives the int8 weights the run
+ * set, [freq][ant][beam]{re, im}. */
+int bfh_run_debug_observation3(const bf_config *cfg, int gpu, const char *positions, const char *directions, const char *sources,
+                               const char *output, int device, int verbose, float *ded_out, size_t ded_capacity, int *n_pt_sources,
+                               float *observation_ms, int per_unit_launches, const char *gains_file, int8_t *weights_out);
 
 /* Production observation loop (src/beamformer.cu:364-534 without -DDEBUG) fed by the in-memory dada_junkdb stand-in:
  * n_blocks pseudo-random PSRDADA-sized blocks from a pinned ring of ring_blocks distinct blocks, default linear

@@ -202,6 +202,10 @@ struct debug_run_options {
     // N_GEMMS_PER_BLOCK sources, alternating between two compute queues; false = the reference's own pattern, per
     // gemm-unit launches + copies round-robin over the N_STREAMS queues (src/beamformer.cu:454-519).  Same data.py.
     bool block_launch = true;
+    // -A: one layer of gains, host [freq][ant]{re, im} (read_gains_layer): the steering weights are multiplied by conj(g) / |g| before
+    // they are set (set_weights_calibrated).  weights_out (optional, host, the size of the weight array) receives what was set.
+    const double* gains = nullptr;
+    int8_t* weights_out = nullptr;
 };
 struct debug_run_result {
     float observation_time_ms = 0;
@@ -620,6 +624,59 @@ public:
     }
 };
 
+// ---- The gain solver (include/dsabf.h: bf_solve_gains_device, bf_calibrate_weights_device; docs/CALIBRATION.md) ----------------
+// Thin wrappers: device pointers in, asynchronous on `stream`, the C-ABI's return codes.
+inline int solve_gains(bf_handle* h, const int64_t* d_vis, const double* d_model, const uint8_t* d_flags, const bf_cal_options& opt, double* d_gains,
+                       int32_t* d_info, void* stream = nullptr)
+{
+    return bf_solve_gains_device(h, d_vis, d_model, d_flags, &opt, d_gains, d_info, stream);
+}
+inline int calibrate_weights(bf_handle* h, const int8_t* d_w_in, const double* d_gains_layer, const uint8_t* d_flags, int mode, int8_t* d_w_out,
+                             void* stream = nullptr)
+{
+    return bf_calibrate_weights_device(h, d_w_in, d_gains_layer, d_flags, mode, d_w_out, stream);
+}
+
+// File of gains: the 4096-byte ASCII header (`KEY value` lines, NUL padded: CONTENT gains, DTYPE float64, NANT, NPOL (= pol_out), NFREQ,
+// FIRST_CHANNEL, LAYOUT pol,freq,ant,reim), then one record per solve: uint64 first_block, uint64 n_columns_per_pol (those of the
+// visibility record it was solved from), the gains (little-endian float64 [pol_out][freq][ant]{re, im}), the info (int32
+// [pol_out][freq]{iterations, status}).
+class gains_file_sink {
+    int fd = -1;
+    uint64_t records = 0;
+    size_t n_gain_doubles = 0, n_info = 0;
+
+public:
+    static constexpr size_t kHeaderBytes = 4096;
+    static constexpr size_t kRecordBytes = 16;
+    gains_file_sink(int n_ant, int pol_out, int n_freq, int first_channel, const char* path);
+    ~gains_file_sink();
+    gains_file_sink(const gains_file_sink&) = delete;
+    gains_file_sink& operator=(const gains_file_sink&) = delete;
+    bool is_open() const { return fd >= 0; }
+    bool deliver(uint64_t first_block, uint64_t n_columns_per_pol, const double* gains, const int32_t* info);
+    void close();
+    uint64_t get_records_written() const { return records; }
+};
+
+// The header both record files share (vis_file_sink, gains_file_sink).  read_record_file_header: false + *why if the file cannot be read
+// or is neither.  No device is touched.
+struct record_file_header {
+    std::string content, dtype;
+    int n_ant = 0, n_pol = 0, n_freq = 0, first_channel = 0;
+    size_t header_bytes = 0, record_header_bytes = 0, file_bytes = 0;
+};
+bool read_record_file_header(const char* path, record_file_header* out, std::string* why);
+// Layer 0 of the LAST record of a gains file, [freq][ant]{re, im}: what `beam -A` applies.  The geometry must be n_ant x n_freq
+// starting at first_channel; false + *why otherwise.  No device is touched.
+bool read_gains_layer(const char* path, int n_ant, int n_freq, int first_channel, std::vector<double>* layer, std::string* why);
+// `beam -E vis_file -G gains_file [-P]`: every record of a vis_file_sink file uploaded, solved with the all-ones model and the default
+// options (joint_pol as given) and written as one gains record; the geometry comes from the file's header.
+int solve_vis_file(const char* vis_path, const char* gains_path, bool joint_pol, int device, uint64_t* n_records, std::ostream& log);
+// Weights `w` (host, the layout of bf_set_weights) times conj(g) / |g| of one layer of gains (host, [freq][ant]{re, im}), on the device
+// (bf_calibrate_weights_device, BF_CAL_PHASE), then set on the handle (bf_set_weights_device); w_set (optional, host) receives them.
+int set_weights_calibrated(bf_handle* h, int device, const int8_t* w, const double* gains_layer, int8_t* w_set = nullptr);
+
 struct observation_options {
     int gpu = 0;          // -g
     int device = 0;
@@ -680,6 +737,8 @@ struct observation_options {
     // sharded run every rank correlates its own channels and has a sink of its own; the gather is untouched.
     int corr_blocks = 0;
     dsabf::vis_sink* vis_sink = nullptr;
+    // -A: one layer of gains for THIS rank's channels, host [freq][ant]{re, im}: as debug_run_options::gains.
+    const double* gains = nullptr;
 };
 struct observation_result {
     float observation_time_ms = 0;
