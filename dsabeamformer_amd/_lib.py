@@ -52,6 +52,11 @@ class BfSpsStat(C.Structure):
     _fields_ = [("sum", C.c_double), ("sumsq", C.c_double)]
 
 
+class BfCondOptions(C.Structure):
+    """Mirror of ``bf_cond_options`` (include/dsabf.h)."""
+    _fields_ = [("baseline_pushes", C.c_int), ("zero_dm", C.c_int), ("auto_threshold", C.c_double)]
+
+
 class BfSpsCandidate(C.Structure):
     """Mirror of ``bf_sps_candidate`` (include/dsabf.h)."""
 
@@ -145,6 +150,13 @@ SIGNATURES = {
     "bf_sps_last_records": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]),
     "bf_sps_select": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_int, C.c_uint64, C.c_double,
                                 C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "bf_cond_default_options": (None, [C.POINTER(BfCondOptions)]),
+    "bf_cond_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(BfCondOptions), C.POINTER(C.c_void_p)]),
+    "bf_cond_destroy": (C.c_int, [C.c_void_p]),
+    "bf_cond_set_mask": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "bf_cond_push": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "bf_cond_mask_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "bf_dm_stream_attach_conditioner": (C.c_int, [C.c_void_p, C.c_void_p]),
     "bf_comm_unique_id": (C.c_int, [C.c_void_p]),
     "bf_comm_create": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
     "bf_comm_destroy": (C.c_int, [C.c_void_p]),

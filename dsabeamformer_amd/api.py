@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-from ._lib import BF_CAL_FULL, BF_CAL_PHASE, BfCalOptions, BfConfig, BfSpsCandidate, BfSpsPeak, BfSpsStat, check, load
+from ._lib import BF_CAL_FULL, BF_CAL_PHASE, BfCalOptions, BfCondOptions, BfConfig, DsabfError, BfSpsCandidate, BfSpsPeak, BfSpsStat, check, load
 
 
 def debug_config(**over) -> BfConfig:
@@ -313,6 +313,11 @@ class DmStream:
         detaches), on the push's queue."""
         check(self._lib.bf_dm_stream_attach_search(self._s, sps._s if sps is not None else None))
 
+    def attach_conditioner(self, cond) -> None:
+        """bf_dm_stream_attach_conditioner: every push from now on conditions its new rows in the stage's buffer (``cond``: a
+        Conditioner; None detaches) before they are dedispersed."""
+        check(self._lib.bf_dm_stream_attach_conditioner(self._s, cond._c if cond is not None else None))
+
     def close(self) -> None:
         if self._s:
             self._lib.bf_dm_stream_destroy(self._s)
@@ -402,6 +407,58 @@ class SinglePulseSearch:
         if self._s:
             self._lib.bf_sps_destroy(self._s)
             self._s = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Conditioner:
+    """bf_cond: the detected rows [t][f][b] rewritten in place on the device -- normalised per (channel, beam) against the last
+    ``baseline_pushes`` pushes, bad channels masked, the per-(time, beam) mean over the channels removed (include/dsabf.h,
+    docs/CONDITIONING.md).  Attach it with ``DmStream.attach_conditioner`` or push rows yourself."""
+
+    def __init__(self, bf: Beamformer, n_freq_total: int, max_rows: int, baseline_pushes: int = 8, zero_dm: bool = True,
+                 auto_threshold: float = 0.0, mask=None):
+        self._lib = load()
+        self._c = C.c_void_p()
+        self.n_freq_total, self.n_beams, self._bf = n_freq_total, bf.cfg.n_beams, bf
+        opt = BfCondOptions(baseline_pushes, int(bool(zero_dm)), auto_threshold)
+        check(self._lib.bf_cond_create(bf._h, n_freq_total, max_rows, C.byref(opt), C.byref(self._c)))
+        if mask is not None:
+            self.set_mask(mask)
+
+    def push(self, d_rows, n_rows: int, stream: int = 0) -> None:
+        check(self._lib.bf_cond_push(self._c, _ptr(d_rows), n_rows, C.c_void_p(stream)))
+
+    def set_mask(self, mask) -> None:
+        """The static mask (nonzero = masked), one entry per channel: holds from the next push on."""
+        import numpy as np
+
+        m = np.ascontiguousarray(np.asarray(mask) != 0, np.uint8)
+        assert m.shape == (self.n_freq_total,)
+        check(self._lib.bf_cond_set_mask(self._c, _ptr(m)))
+
+    def mask(self):
+        """mask[f] of the most recent push (uint8 host copy, after a device synchronisation)."""
+        import numpy as np
+
+        from ._lib import _preload_hip_runtime
+
+        p = C.c_void_p()
+        check(self._lib.bf_cond_mask_device(self._c, C.byref(p)))
+        out = np.zeros(self.n_freq_total, np.uint8)
+        hip = _preload_hip_runtime()
+        if hip.hipDeviceSynchronize() != 0 or hip.hipMemcpy(_ptr(out), p, C.c_size_t(out.size), 2) != 0:
+            raise DsabfError(-3, "Conditioner.mask: the copy from the device failed")
+        return out
+
+    def close(self) -> None:
+        if self._c:
+            self._lib.bf_cond_destroy(self._c)
+            self._c = C.c_void_p()
 
     def __del__(self):
         try:

@@ -26,6 +26,13 @@
 //                                                   searched on the device with boxcar widths 1 .. 2^(n_widths-1) [6]; candidates at
 //                                                   S/N >= snr to cand_file, one text line each: t_start dm beam width snr peak.
 //                                                   With -X: cand_file.<r>, trials numbered over the whole ladder.  Needs -M.
+//   beam -j n_blocks -M dm_max ... -n baseline_pushes [-z] [-U auto_threshold] [-F mask_file]
+//                                                   the conditioner in front of the DM stage (docs/CONDITIONING.md): every analysed block
+//                                                   normalised per (channel, beam) against the last baseline_pushes blocks and masked, in
+//                                                   the DM stage's buffer (-w / -K keep the raw stream).  -z: also subtract the mean over
+//                                                   the unmasked channels per (time, beam) (off here unless given); -U: mask channels whose
+//                                                   cv / cm^2 lies more than auto_threshold scaled median deviations above the median;
+//                                                   -F: a text file of channel indices to mask, one per line, # comments.  Needs -M.
 //   beam -j n_blocks ... -i beam                    the incoherent beam (docs/INCOHERENT_BEAM.md): beam column `beam` of the detected
 //                                                   stream carries the antenna powers summed over the antennas instead of a tied beam,
 //                                                   for -w / -K, the DM stage and the search alike.  With -R: every shard, same index.
@@ -83,6 +90,10 @@ int main(int argc, char* argv[])
     int sps_widths = 6;             // -B
     bool sps_on = false, sps_widths_given = false;
     std::string cand_path;          // -C
+    int cond_n = 0;                 // -n: the conditioner's window in pushes (0: no conditioner)
+    bool cond_given = false, cond_zdm = false, cond_auto_given = false;   // -z: zero-DM (off in the driver unless given)
+    double cond_auto = 0.0;         // -U
+    std::string cond_mask_path;     // -F
     int ib_beam = -1;               // -i: the beam column that carries the incoherent beam (-1: none)
     bool ib_given = false;
     std::string vis_path;           // -V: where the correlator's dumps go
@@ -92,7 +103,7 @@ int main(int argc, char* argv[])
     bool solve_joint = false;                               // -P
 
     int arg = 0;
-    while ((arg = getopt(argc, argv, "s:g:p:d:o:D:a:c:k:K:j:w:R:r:I:M:N:T:W:Q:S:B:C:i:V:L:E:G:A:PXuvhH")) != -1) {  // src/beamformer.cu:41-43 (+ -o -D -a -v)
+    while ((arg = getopt(argc, argv, "s:g:p:d:o:D:a:c:k:K:j:w:R:r:I:M:N:T:W:Q:S:B:C:i:V:L:E:G:A:n:U:F:zPXuvhH")) != -1) {  // src/beamformer.cu:41-43 (+ -o -D -a -v)
         switch (arg) {
             case 's': sources = optarg; break;                 // :77-89
             case 'g': opt.gpu = atoi(optarg); break;           // :92-100
@@ -116,6 +127,10 @@ int main(int argc, char* argv[])
             case 'S': sps_snr = atof(optarg); sps_on = true; break;
             case 'B': sps_widths = atoi(optarg); sps_widths_given = true; break;
             case 'C': cand_path = optarg; break;
+            case 'n': cond_n = atoi(optarg); cond_given = true; break;
+            case 'z': cond_zdm = true; break;
+            case 'U': cond_auto = atof(optarg); cond_auto_given = true; break;
+            case 'F': cond_mask_path = optarg; break;
             case 'i': ib_beam = atoi(optarg); ib_given = true; break;
             case 'V': vis_path = optarg; break;
             case 'L': corr_blocks = atoi(optarg); corr_blocks_given = true; break;
@@ -147,6 +162,14 @@ int main(int argc, char* argv[])
                              " -S snr [-B n_widths] [-C file]   single-pulse search of every DM chunk: boxcar widths 1 .. 2^(n_widths-1) [6],\n"
                              "                         candidates at S/N >= snr to file (t_start dm beam width snr peak; with -X: file.<rank>);\n"
                              "                         requires -M: without it (or -B / -C without -S) beam exits with a usage error\n"
+                             " -n baseline_pushes [-z] [-U auto_threshold] [-F mask_file]   the conditioner in front of the DM stage: every block\n"
+                             "                         normalised per (channel, beam) against the last baseline_pushes blocks (1 .. 64) and masked, in\n"
+                             "                         the DM stage's buffer (-w / -K keep the raw stream); -z: zero-DM, the mean over the unmasked\n"
+                             "                         channels subtracted per (time, beam); -U: automatic mask at auto_threshold scaled median\n"
+                             "                         deviations; -F: channel indices to mask, one per line, # comments; requires -M, and -z / -U / -F\n"
+                             "                         require -n: otherwise beam exits with a usage error\n"
+                             "                         (with -z the ladder's DM-0 trial sums to the subtraction's rounding residue: its candidates,\n"
+                             "                         S/N 7 .. 8 at bursts, mean nothing -- discard trial 0 of a -z run)\n"
                              " -i beam                 observation mode: beam column `beam` of the detected stream carries the incoherent beam\n"
                              "                         (antenna powers summed over the antennas, no weights) for every consumer; 0 <= beam < N_BEAMS\n"
                              " -V file [-L corr_blocks]   observation mode: the correlator -- antenna visibilities of the analysed blocks, integrated\n"
@@ -173,6 +196,47 @@ int main(int argc, char* argv[])
     if (sps_on && (sps_widths < 1 || sps_widths > 8)) {
         fprintf(stderr, "beam: -B %d: n_widths must be 1 .. 8\n", sps_widths);
         return EXIT_FAILURE;
+    }
+    if ((cond_given || cond_zdm || cond_auto_given || !cond_mask_path.empty()) && !(dm_max > 0.0)) {
+        fprintf(stderr, "beam: -n / -z / -U / -F (conditioner) require the DM stage: give -M dm_max\n");
+        return EXIT_FAILURE;
+    }
+    if (!cond_given && (cond_zdm || cond_auto_given || !cond_mask_path.empty())) {
+        fprintf(stderr, "beam: -z / -U / -F belong to the conditioner: give -n baseline_pushes\n");
+        return EXIT_FAILURE;
+    }
+    if (cond_given && (cond_n < 1 || cond_n > 64)) {
+        fprintf(stderr, "beam: -n %d: baseline_pushes must be 1 .. 64\n", cond_n);
+        return EXIT_FAILURE;
+    }
+    if (cond_auto_given && !(cond_auto >= 0.0)) {
+        fprintf(stderr, "beam: -U %s: the automatic mask's threshold must be >= 0\n", std::to_string(cond_auto).c_str());
+        return EXIT_FAILURE;
+    }
+    std::vector<uint8_t> cond_mask;   // -F: read before any device is touched; the band is the production geometry's, whatever -R
+    if (!cond_mask_path.empty()) {
+        bf_config band;
+        bf_config_default(&band, /*debug=*/0);
+        std::ifstream in(cond_mask_path);
+        if (!in) {
+            fprintf(stderr, "beam: -F %s: could not be read\n", cond_mask_path.c_str());
+            return EXIT_FAILURE;
+        }
+        cond_mask.assign((size_t)band.n_freq, 0);
+        std::string line;
+        while (std::getline(in, line)) {
+            line = line.substr(0, line.find('#'));
+            const size_t a = line.find_first_not_of(" \t\r");
+            if (a == std::string::npos) continue;
+            char* end = nullptr;
+            const long ch = strtol(line.c_str() + a, &end, 10);
+            while (*end == ' ' || *end == '\t' || *end == '\r') end++;
+            if (end == line.c_str() + a || *end || ch < 0 || ch >= band.n_freq) {
+                fprintf(stderr, "beam: -F %s: '%s' is not a channel index 0 .. %d\n", cond_mask_path.c_str(), line.c_str() + a, band.n_freq - 1);
+                return EXIT_FAILURE;
+            }
+            cond_mask[(size_t)ch] = 1;
+        }
     }
     if (ib_given && (ib_beam < 0 || ib_beam >= cfg.n_beams)) {
         fprintf(stderr, "beam: -i %d: the incoherent beam takes a beam index 0 .. %d\n", ib_beam, cfg.n_beams - 1);
@@ -450,6 +514,16 @@ int main(int argc, char* argv[])
                 }
                 oopt.sps_sink = cand_sink.get();
             }
+        }
+        if (cond_given && my_trials > 0 && (!comm || rank == 0 || oopt.dm_split_trials)) {   // -n: the conditioner runs where the DM stage runs
+            oopt.cond_baseline = cond_n;
+            oopt.cond_zero_dm = cond_zdm;
+            oopt.cond_auto_threshold = cond_auto;
+            if (!cond_mask.empty() && (int)cond_mask.size() != full_cfg.n_freq) {   // (-F was checked against the production band)
+                fprintf(stderr, "beam: -F: the mask has %zu channels, the band of this run %d\n", cond_mask.size(), full_cfg.n_freq);
+                return EXIT_FAILURE;
+            }
+            oopt.cond_mask = cond_mask.empty() ? nullptr : cond_mask.data();
         }
         std::unique_ptr<vis_file_sink> vsink;
         if (!vis_path.empty()) {   // -V: every shard correlates its own channels

@@ -1,0 +1,204 @@
+// bf_cond.cpp -- conditioning of the detected stream in front of the DM stage (include/dsabf.h: bf_cond_*; contract, ordering and
+// measurements: docs/CONDITIONING.md).  The device code is csrc/cond/bf_cond.hip; this file owns the stage's memory, keeps the
+// window's row counts and orders the pushes.
+#include <algorithm>
+#include <deque>
+#include <mutex>
+#include <new>
+
+#include "cond/bf_cond_host.h"
+#include "cond/bf_cond_kernels.h"
+
+struct bf_cond {
+    bf_handle* h = nullptr;
+    int n_freq = 0, n_beams = 0, max_rows = 0, window = 0;
+    bool zero_dm = true;
+    double k_auto = 0.0;                  // auto_threshold * 1.4826, formed once, here, in fp64
+    dsabf::CondBuffers buf{};
+    uint8_t* d_static = nullptr;          // the caller's mask (buf.static_mask)
+    // Push j runs behind done[(j - 1) % 2], whatever queue that ran on, and records done[j % 2]: the pushes share the ring of
+    // totals, the per-cell and per-channel scratch and the mask.
+    hipEvent_t done[2] = {nullptr, nullptr};
+    uint64_t n_push = 0;
+    std::deque<int> rows_in_window;       // row counts of the pushes in the window, oldest first
+    bf_dm_stream* feeder = nullptr;       // the DM stage this one is attached to
+};
+
+namespace {
+// The stages of every handle: bf_destroy finds its own here (the handle itself keeps no list of them).
+std::mutex g_mu;
+std::vector<bf_cond*> g_stages;
+
+void cond_release(bf_cond* c)
+{
+    for (hipEvent_t& e : c->done) {
+        if (e) {
+            (void)hipEventSynchronize(e);   // (never recorded: returns at once)
+            (void)hipEventDestroy(e);
+        }
+        e = nullptr;
+    }
+    for (void* p : {(void*)c->buf.seg, (void*)c->buf.ring, (void*)c->buf.cell_mu, (void*)c->buf.cell_var, (void*)c->buf.mr32, (void*)c->buf.cm,
+                    (void*)c->buf.cv, (void*)c->buf.q, (void*)c->buf.dev, (void*)c->d_static, (void*)c->buf.mask, (void*)c->buf.params})
+        (void)hipFree(p);
+    c->buf = dsabf::CondBuffers{};
+    c->d_static = nullptr;
+    c->h = nullptr;
+}
+
+void forget(bf_cond* c)
+{
+    std::lock_guard<std::mutex> lock(g_mu);
+    g_stages.erase(std::remove(g_stages.begin(), g_stages.end(), c), g_stages.end());
+}
+}  // namespace
+
+void dsabf::rt::cond_release_handle(bf_handle* h)
+{
+    std::vector<bf_cond*> mine;
+    {
+        std::lock_guard<std::mutex> lock(g_mu);
+        for (bf_cond* c : g_stages)
+            if (c->h == h) mine.push_back(c);
+    }
+    for (bf_cond* c : mine) {
+        forget(c);
+        cond_release(c);
+    }
+}
+
+int dsabf::rt::cond_check_attach(const bf_cond* c, const bf_handle* h, int n_freq_total, int max_rows)
+{
+    if (!c->h) return fail(BF_ERR_STATE, "the handle of this conditioner has been destroyed");
+    if (c->h != h) return fail(BF_ERR_INVALID, "bf_dm_stream_attach_conditioner: the two stages belong to different handles");
+    if (c->n_freq != n_freq_total)
+        return fail(BF_ERR_INVALID, "bf_dm_stream_attach_conditioner: the conditioner has %d channels, the DM stage %d", c->n_freq, n_freq_total);
+    if (c->max_rows < max_rows)
+        return fail(BF_ERR_INVALID, "bf_dm_stream_attach_conditioner: max_rows_per_push %d < the DM stage's %d", c->max_rows, max_rows);
+    if (c->feeder) return fail(BF_ERR_STATE, "bf_dm_stream_attach_conditioner: the conditioner is attached to another DM stage");
+    return BF_OK;
+}
+
+void dsabf::rt::cond_set_feeder(bf_cond* c, bf_dm_stream* dm)
+{
+    c->feeder = dm;
+    if (dm) c->rows_in_window.clear();   // attached, in mid-stream or not: the window starts empty there
+}
+
+extern "C" {
+
+void bf_cond_default_options(bf_cond_options* o)
+{
+    if (!o) return;
+    o->baseline_pushes = 8;
+    o->zero_dm = 1;
+    o->auto_threshold = 0.0;
+}
+
+int bf_cond_create(bf_handle* h, int n_freq_total, int max_rows_per_push, const bf_cond_options* o, bf_cond** out)
+{
+    if (!out) return fail(BF_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    if (!h || !o) return fail(BF_ERR_INVALID, "bf_cond_create: NULL argument");
+    if (n_freq_total < 1 || max_rows_per_push < 1) return fail(BF_ERR_INVALID, "bf_cond_create: need n_freq_total, max_rows_per_push >= 1");
+    if (o->baseline_pushes < 1 || o->baseline_pushes > dsabf::kCondMaxWindow)
+        return fail(BF_ERR_INVALID, "bf_cond_create: baseline_pushes must be 1 .. %d, not %d", dsabf::kCondMaxWindow, o->baseline_pushes);
+    if (!(o->auto_threshold >= 0.0)) return fail(BF_ERR_INVALID, "bf_cond_create: auto_threshold must be >= 0 (0: no automatic mask), not negative or NaN");
+    ON_DEVICE(h);
+    bf_cond* c = new (std::nothrow) bf_cond();
+    if (!c) return fail(BF_ERR_DEVICE, "out of host memory");
+    c->h = h;
+    c->n_freq = n_freq_total;
+    c->n_beams = h->cfg.n_beams;
+    c->max_rows = max_rows_per_push;
+    c->window = o->baseline_pushes;
+    c->zero_dm = o->zero_dm != 0;
+    c->k_auto = o->auto_threshold * 1.4826;
+    const size_t F = (size_t)n_freq_total, cells = F * c->n_beams;
+    hipError_t e = hipMalloc((void**)&c->buf.ring, (size_t)c->window * cells * sizeof(dsabf::CondStat));
+    if (e == hipSuccess) e = hipMalloc((void**)&c->buf.cell_mu, cells * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&c->buf.cell_var, cells * sizeof(double));
+    const size_t n_seg = ((size_t)max_rows_per_push + dsabf::kCondSegment - 1) / dsabf::kCondSegment;
+    if (e == hipSuccess) e = hipMalloc((void**)&c->buf.seg, n_seg * cells * sizeof(dsabf::CondStat));
+    if (e == hipSuccess) e = hipMalloc((void**)&c->buf.mr32, cells * sizeof(float2));
+    if (e == hipSuccess) e = hipMalloc((void**)&c->buf.cm, F * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&c->buf.cv, F * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&c->buf.q, F * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&c->buf.dev, F * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&c->d_static, F);
+    if (e == hipSuccess) e = hipMalloc((void**)&c->buf.mask, (F + 3) / 4 * 4);   // (whole dwords: a host mirror may copy it as such)
+    if (e == hipSuccess) e = hipMalloc((void**)&c->buf.params, sizeof(dsabf::CondParams));
+    if (e == hipSuccess) e = hipMemset(c->d_static, 0, F);
+    if (e == hipSuccess) e = hipMemset(c->buf.mask, 0, (F + 3) / 4 * 4);
+    for (int k = 0; k < 2 && e == hipSuccess; k++) e = hipEventCreateWithFlags(&c->done[k], hipEventDisableTiming);
+    if (e == hipSuccess) e = hipDeviceSynchronize();   // (the memsets above ran on the null stream: pushes come on non-blocking ones)
+    c->buf.static_mask = c->d_static;
+    {
+        std::lock_guard<std::mutex> lock(g_mu);
+        g_stages.push_back(c);
+    }
+    if (e != hipSuccess) {
+        bf_cond_destroy(c);
+        return fail(BF_ERR_DEVICE, "bf_cond_create: %s", hipGetErrorString(e));
+    }
+    *out = c;
+    return BF_OK;
+}
+
+int bf_cond_destroy(bf_cond* c)
+{
+    if (!c) return BF_OK;
+    if (c->feeder) dm_stream_drop_conditioner(c->feeder);
+    if (c->h) {   // (NULL: the handle went first and took the device memory with it)
+        DeviceScope dev_scope_(c->h->device);
+        forget(c);
+        cond_release(c);
+    }
+    delete c;
+    return BF_OK;
+}
+
+int bf_cond_set_mask(bf_cond* c, const uint8_t* host_mask)
+{
+    if (!c || !host_mask) return fail(BF_ERR_INVALID, "NULL argument");
+    if (!c->h) return fail(BF_ERR_STATE, "the handle of this conditioner has been destroyed");
+    bf_handle* h = c->h;
+    ON_DEVICE(h);
+    // the push in flight still reads the old mask: wait for it, then copy (a blocking call: masks change rarely)
+    if (c->n_push) HIP_TRY(hipEventSynchronize(c->done[(c->n_push - 1) % 2]));
+    HIP_TRY(hipMemcpy(c->d_static, host_mask, (size_t)c->n_freq, hipMemcpyHostToDevice));
+    return BF_OK;
+}
+
+int bf_cond_push(bf_cond* c, float* d_rows, int n_rows, void* hip_stream)
+{
+    if (!c || !d_rows) return fail(BF_ERR_INVALID, "NULL argument");
+    if (n_rows < 1 || n_rows > c->max_rows) return fail(BF_ERR_INVALID, "n_rows must be 1 .. %d (max_rows_per_push)", c->max_rows);
+    if (!c->h) return fail(BF_ERR_STATE, "the handle of this conditioner has been destroyed");
+    bf_handle* h = c->h;
+    ON_DEVICE(h);
+    hipStream_t q = as_stream(hip_stream);
+    // behind the push before this one, whatever queue it ran on: the window, the scratch and the mask are shared
+    if (c->n_push) HIP_TRY(hipStreamWaitEvent(q, c->done[(c->n_push - 1) % 2], 0));
+    const int n_sets = (int)std::min<size_t>(c->rows_in_window.size() + 1, (size_t)c->window);
+    uint64_t n_window = (uint64_t)n_rows;
+    for (size_t i = c->rows_in_window.size() + 1 - (size_t)n_sets; i < c->rows_in_window.size(); i++) n_window += (uint64_t)c->rows_in_window[i];
+    HIP_TRY(dsabf::launch_cond_push(d_rows, n_rows, c->n_freq, c->n_beams, c->buf, c->window, (int)(c->n_push % (uint64_t)c->window), n_sets, n_window,
+                                    c->zero_dm, c->k_auto, q));
+    HIP_TRY(hipEventRecord(c->done[c->n_push % 2], q));
+    c->rows_in_window.push_back(n_rows);
+    while (c->rows_in_window.size() > (size_t)c->window) c->rows_in_window.pop_front();
+    c->n_push++;
+    return BF_OK;
+}
+
+int bf_cond_mask_device(bf_cond* c, const uint8_t** d_mask)
+{
+    if (!c || !d_mask) return fail(BF_ERR_INVALID, "NULL argument");
+    *d_mask = nullptr;
+    if (!c->h) return fail(BF_ERR_STATE, "the handle of this conditioner has been destroyed");
+    *d_mask = c->buf.mask;
+    return BF_OK;
+}
+
+}  // extern "C"

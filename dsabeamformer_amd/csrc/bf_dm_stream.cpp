@@ -6,6 +6,7 @@
 #include <numeric>
 
 #include "bf_runtime_internal.h"
+#include "cond/bf_cond_host.h"
 
 // ---- DM-trial dedispersion as a stage of the observation loop (include/dsabf.h) ---------------------------
 // The detected stream arrives block by block; out[dm][t][b] needs rows t .. t + max_delay.  The stream keeps the last
@@ -49,12 +50,14 @@ struct bf_dm_stream {
     float* reserved = nullptr;    // bf_dm_stream_reserve: where the NEXT push's rows are being written by their producer ...
     int reserved_rows = 0;        // ... and how many (0: no reservation outstanding)
     bf_sps* search = nullptr;     // bf_dm_stream_attach_search: every chunk is also pushed into this stage, before `done` is recorded
+    bf_cond* cond = nullptr;      // bf_dm_stream_attach_conditioner: every push's new rows are conditioned in place, before `rows_ready` is recorded
 };
 
 // device side of a DM stage (its handle's device must be current); the object itself stays, detached from the handle
 void dsabf::rt::dm_stream_release(bf_dm_stream* s)
 {
     dm_stream_drop_search(s);
+    dm_stream_drop_conditioner(s);
     for (int k = 0; k < 3; k++) {
         if (s->done[k]) {
             if (s->done_recorded[k]) (void)hipEventSynchronize(s->done[k]);
@@ -90,6 +93,12 @@ void dsabf::rt::dm_stream_drop_search(bf_dm_stream* s)
 {
     if (s->search) sps_set_feeder(s->search, nullptr);
     s->search = nullptr;
+}
+
+void dsabf::rt::dm_stream_drop_conditioner(bf_dm_stream* s)
+{
+    if (s->cond) cond_set_feeder(s->cond, nullptr);
+    s->cond = nullptr;
 }
 
 // Address space for the rings: taken from arenas that are reserved once per process and NEVER given back or handed out twice.
@@ -268,6 +277,7 @@ int bf_dm_stream_destroy(bf_dm_stream* s)
 {
     if (!s) return BF_OK;
     dm_stream_drop_search(s);
+    dm_stream_drop_conditioner(s);
     if (s->h) {   // (NULL: the handle went first and took the device memory with it)
         bf_handle* h = s->h;
         DeviceScope dev_scope_(h->device);
@@ -290,6 +300,19 @@ int bf_dm_stream_attach_search(bf_dm_stream* dm, bf_sps* sps)
     dm_stream_drop_search(dm);
     dm->search = sps;
     if (sps) sps_set_feeder(sps, dm);
+    return BF_OK;
+}
+
+int bf_dm_stream_attach_conditioner(bf_dm_stream* dm, bf_cond* c)
+{
+    if (!dm) return fail(BF_ERR_INVALID, "NULL argument");
+    if (!dm->h) return fail(BF_ERR_STATE, "the handle of this DM stage has been destroyed");
+    if (c == dm->cond) return BF_OK;
+    if (c)
+        if (int rc = cond_check_attach(c, dm->h, dm->n_freq, dm->max_rows)) return rc;
+    dm_stream_drop_conditioner(dm);
+    dm->cond = c;
+    if (c) cond_set_feeder(c, dm);
     return BF_OK;
 }
 
@@ -381,18 +404,29 @@ int bf_dm_stream_push(bf_dm_stream* s, const float* d_rows, int n_rows, float* h
         HIP_TRY(hipMemsetAsync(s->d_flags[set], 0, dsabf::kDmScratchBytes, q));
         s->flags_zeroed[set] = true;
     }
-    // (the stream's bookkeeping -- wpos / fill, pushed -- is committed at the end: a call that fails on the way leaves it as it found it)
+    // (the stream's bookkeeping -- wpos / fill, pushed -- is committed at the end: a call that fails on the way leaves it as it found it.
+    //  One exception: an attached conditioner.  Once bf_cond_push below has been issued the rows are rewritten and the push is in its
+    //  window; if a LATER step of this call fails, do not push the same rows again -- detach, or destroy the stages.)
     const size_t D = (size_t)s->max_delay;
     const size_t carry = s->pushed < D ? (size_t)s->pushed : D;          // the rows in front of the new ones = series rows [pushed - carry, pushed)
+    float* new_rows = s->reserved;                                        // where this push's rows lie in the stage's buffer
     if (!in_place) {                                                      // rows that live elsewhere: brought behind the carry first
-        float* dst = nullptr;
-        if (int rc = dm_place_rows(s, n_rows, q, &dst)) return rc;
-        HIP_TRY(hipMemcpyAsync(dst, d_rows, (size_t)n_rows * s->row_floats * sizeof(float), hipMemcpyDeviceToDevice, q));
+        if (int rc = dm_place_rows(s, n_rows, q, &new_rows)) return rc;
+        HIP_TRY(hipMemcpyAsync(new_rows, d_rows, (size_t)n_rows * s->row_floats * sizeof(float), hipMemcpyDeviceToDevice, q));
     }
+    // the kernels read [carry | new rows]: the carry was written by the producers of the pushes before this one, possibly on
+    // other queues -- wait until THEIR rows are in place (not for their dedispersion), then say that ours are
+    if (s->ring && s->n_push && s->rows_recorded[prev]) HIP_TRY(hipStreamWaitEvent(q, s->rows_ready[prev], 0));
+    // The conditioner's hook (docs/CONDITIONING.md section 3): the new rows are rewritten where they lie -- behind the copy-in (the
+    // caller's source rows stay raw; host copies that bf_enqueue_block_to queued are in front of this push on q and carry raw rows
+    // too), behind rows_ready of the push before this one, and BEFORE rows_ready of this push is recorded.  That one placement is
+    // the whole ordering argument for the three pushes in flight: push j + 1's kernels read push j's rows as carry only behind that
+    // event, so they see them conditioned; and conditioner j + 1 runs behind conditioner j (the stage's own event chain, and this
+    // wait).  In the ring the rows may run past cap_rows into the second mapping: one contiguous range, taken as such.  The linear
+    // buffer has no rows_ready: there the whole push already runs behind the previous one.
+    if (s->cond)
+        if (int rc = bf_cond_push(s->cond, new_rows, n_rows, q)) return rc;
     if (s->ring) {
-        // the kernels read [carry | new rows]: the carry was written by the producers of the pushes before this one, possibly on
-        // other queues -- wait until THEIR rows are in place (not for their dedispersion), then say that ours are
-        if (s->n_push && s->rows_recorded[prev]) HIP_TRY(hipStreamWaitEvent(q, s->rows_ready[prev], 0));
         HIP_TRY(hipEventRecord(s->rows_ready[mine], q));
         s->rows_recorded[mine] = true;
     }

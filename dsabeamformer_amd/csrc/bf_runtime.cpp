@@ -13,6 +13,7 @@
 
 #include "bf_host_internal.h"
 #include "bf_runtime_internal.h"
+#include "cond/bf_cond_host.h"
 #include "ib/bf_incoherent.h"
 
 namespace dsabf::rt {
@@ -227,6 +228,7 @@ int bf_destroy(bf_handle* h)
     for (auto* ds : h->dm_streams) dm_stream_release(ds);   // a DM stage that outlives its handle is left empty, not dangling
     for (auto* sp : h->sps_stages) sps_release(sp);         // ... and a search stage
     for (auto* cs : h->corr_stages) corr_release(cs);       // ... and a correlator stage
+    cond_release_handle(h);                                 // ... and its conditioners (bf_cond.cpp keeps their list)
     for (auto& sc : h->dm_scratch) (void)hipFree(sc.second);
     for (auto& b : h->qbuf)
         for (float* p : {b.out_blk, b.full_blk, b.stage_blk, b.ded_blk}) (void)hipFree(p);

@@ -203,6 +203,7 @@ struct run_resources {
     bf_handle* h = nullptr;
     bf_dm_stream* dm = nullptr;
     bf_sps* sps = nullptr;
+    bf_cond* cond = nullptr;
     bf_corr* corr = nullptr;
     std::vector<void*> pinned;
     ~run_resources()
@@ -210,6 +211,7 @@ struct run_resources {
         if (h) bf_stream_sync(h, -1);
         bf_corr_destroy(corr);
         bf_sps_destroy(sps);
+        bf_cond_destroy(cond);
         bf_dm_stream_destroy(dm);
         for (void* p : pinned) bf_free_pinned(p);
         bf_destroy(h);
@@ -483,6 +485,10 @@ int check_options(const bf_config& cfg, const observation_options& opt)
     if (opt.sps_widths < 0 || opt.sps_widths > 8) return set_error(BF_ERR_INVALID, "run_observation: sps_widths must be 0 (off) .. 8");
     if ((opt.sps_widths || opt.sps_sink) && !opt.dm_delays) return set_error(BF_ERR_INVALID, "run_observation: the single-pulse search needs the DM stage (dm_delays)");
     if (opt.sps_sink && !opt.sps_widths) return set_error(BF_ERR_INVALID, "run_observation: a sps_sink needs sps_widths > 0");
+    if (opt.cond_baseline < 0 || opt.cond_baseline > 64) return set_error(BF_ERR_INVALID, "run_observation: cond_baseline must be 0 (off) .. 64");
+    if (opt.cond_baseline && !opt.dm_delays) return set_error(BF_ERR_INVALID, "run_observation: the conditioner needs the DM stage (dm_delays)");
+    if (!opt.cond_baseline && (opt.cond_mask || opt.cond_auto_threshold != 0.0))
+        return set_error(BF_ERR_INVALID, "run_observation: cond_mask / cond_auto_threshold need cond_baseline > 0");
     if (opt.incoherent_beam < -1 || opt.incoherent_beam >= cfg.n_beams)
         return set_error(BF_ERR_INVALID, "run_observation: incoherent_beam must be -1 (off) or a beam index");
     if (opt.corr_blocks < 0) return set_error(BF_ERR_INVALID, "run_observation: corr_blocks must be 0 (off) or the blocks per dump");
@@ -564,6 +570,19 @@ struct production_run {
     uint64_t dm_seq = 0, dm_times = 0, dm_chunks = 0;
     std::vector<bf_sps_candidate> cands;  // what bf_sps_collect returns for one chunk
     uint64_t sps_candidates = 0;
+    float* cond_mask_host = nullptr;      // pinned, whole dwords: where the conditioner's mask of the last push is read back at the end
+
+    // channels the conditioner masked in the last push (-1: no conditioner, or no push)
+    int cond_masked_channels()
+    {
+        const uint8_t* d_mask = nullptr;
+        if (!dev.cond || !dm_seq || bf_cond_mask_device(dev.cond, &d_mask) != BF_OK) return -1;
+        if (bf_enqueue_d2h(dev.h, 0, reinterpret_cast<const float*>(d_mask), cond_mask_host, ((size_t)plan.n_freq_band + 3) / 4) != BF_OK) return -1;
+        if (bf_stream_sync(dev.h, 0) != BF_OK) return -1;
+        int n = 0;
+        for (int f = 0; f < plan.n_freq_band; f++) n += reinterpret_cast<const uint8_t*>(cond_mask_host)[f] != 0;
+        return n;
+    }
     // the correlator (corr_blocks > 0): dumps issued and not yet collected -- {first block of the integration, its last block}
     std::deque<std::pair<uint64_t, uint64_t>> vis_pending;
     std::vector<int64_t> vis;             // what bf_corr_collect returns for one dump
@@ -598,6 +617,18 @@ struct production_run {
                 float* chunk = nullptr;
                 if ((rc = dev.alloc_pinned((size_t)plan.dm_count * plan.dm_rows * cfg.n_beams, &chunk)) != BF_OK) return rc;
                 dm_host.push_back(chunk);
+            }
+            if (opt.cond_baseline > 0) {   // the conditioner: in front of the DM stage, on the rows in its buffer (docs/CONDITIONING.md)
+                bf_cond_options co;
+                bf_cond_default_options(&co);
+                co.baseline_pushes = opt.cond_baseline;
+                co.zero_dm = opt.cond_zero_dm ? 1 : 0;
+                co.auto_threshold = opt.cond_auto_threshold;
+                rc = bf_cond_create(dev.h, plan.n_freq_band, plan.dm_rows, &co, &dev.cond);
+                if (rc == BF_OK && opt.cond_mask) rc = bf_cond_set_mask(dev.cond, opt.cond_mask);
+                if (rc == BF_OK) rc = bf_dm_stream_attach_conditioner(dev.dm, dev.cond);
+                if (rc != BF_OK) return gpu_error(log, rc);
+                if ((rc = dev.alloc_pinned(((size_t)plan.n_freq_band + 3) / 4, &cond_mask_host)) != BF_OK) return rc;
             }
             if (opt.sps_widths > 0) {   // the search stage: as many result sets as chunk buffers (a chunk in flight = a search push in flight)
                 rc = bf_sps_create(dev.h, plan.dm_count, plan.dm_first, opt.sps_widths, plan.dm_rows, (int)n_buf, /*baseline_pushes=*/8,
@@ -850,11 +881,21 @@ int run_observation(const bf_config& cfg, const observation_options& opt, block_
         res->dm_chunks = run.dm_chunks;
         res->sps_candidates = run.sps_candidates;
         res->vis_dumps = run.vis_dumps;
+        res->cond_masked = run.cond_masked_channels();
     }
     if (run.plan.dm_run)
         log << "DM stage: trials " << run.plan.dm_first << " .. " << run.plan.dm_first + run.plan.dm_count - 1 << " of " << opt.n_dm << ", "
             << run.dm_times << " output times (largest delay " << bf_dm_stream_max_delay(run.dev.dm) << " samples carried over on the device)"
             << std::endl;
+    if (run.dev.cond) {
+        log << "Conditioner: window of " << opt.cond_baseline << " pushes, zero-DM " << (opt.cond_zero_dm ? "on" : "off") << ", automatic mask ";
+        if (opt.cond_auto_threshold > 0.0)
+            log << "at " << opt.cond_auto_threshold << " deviations";
+        else
+            log << "off";
+        log << std::endl;
+        if (opt.verbose) log << "Conditioner: " << run.cond_masked_channels() << " of " << run.plan.n_freq_band << " channels masked in the last push" << std::endl;
+    }
     if (opt.incoherent_beam >= 0) log << "Incoherent beam: in beam column " << opt.incoherent_beam << " of the detected stream" << std::endl;
     if (run.dev.corr)
         log << "Correlator: " << run.vis_dumps << " dumps of " << opt.corr_blocks << " blocks each (an incomplete integration at the end is dropped)"

@@ -444,6 +444,45 @@ int bf_sps_select(const bf_sps_peak *peaks, const bf_sps_stat *totals, uint64_t 
                   size_t *n_out);
 int bf_dm_stream_attach_search(bf_dm_stream *dm, bf_sps *sps);
 
+/* ---- Conditioning the detected stream in front of the DM stage (docs/CONDITIONING.md) -----------------------------------
+ * The reference collapses the detected powers as they come (src/beamformer.cu:498-510): no bandpass, no mask, no veto of
+ * what arrives in every beam at DM 0.  A bf_cond rewrites pushed rows x[t][f][b] (fp32, the layout bf_dm_stream_push takes,
+ * n_beams = the handle's) IN PLACE on the device; docs/CONDITIONING.md section 1 is the contract, to the bit:
+ *   per push and (f, b): fp64 sum and sum of squares of the raw rows, in segments of 32 rows, ascending;
+ *   over the last baseline_pushes pushes (1 .. 64, this one included, oldest first): mu, var = Q / n - mu mu, sigma;
+ *     a cell is dead unless var > mu mu 2^-40;
+ *   per channel: the means of mu and of max(var, 0) over the beams; mask[f] = the static mask, or a mean that is not > 0, or
+ *     -- auto_threshold > 0 -- cv / cm^2 more than auto_threshold * 1.4826 median absolute deviations above the median of the
+ *     channels still unmasked (high side only);
+ *   y = (x - (float)mu) * (float)(1 / sigma), +0 in masked channels and dead cells;
+ *   zero_dm: per (t, b) the mean of y over the unmasked channels (ascending fp32 sum * (float)(1 / n_good)) is subtracted
+ *     from them.
+ * The output depends on how the stream is cut into pushes (the statistics are per push), not on queues or launch shapes.
+ * bf_cond_push is asynchronous on hip_stream; pushes of one stage are ordered by the stage itself, whichever queues they are
+ * issued on (they share the window).  bf_cond_set_mask copies a host uint8 [n_freq_total] (nonzero = masked) that holds from
+ * the next push on; bf_cond_mask_device: the device's uint8 mask[f] of the most recent push (valid behind that push).
+ * BF_ERR_INVALID, with nothing launched: n_freq_total < 1, max_rows_per_push < 1, baseline_pushes outside 1 .. 64, a negative
+ * or NaN auto_threshold, n_rows outside 1 .. max_rows_per_push, NULL pointers.  Lifetime as for a bf_sps: a handle that goes
+ * first releases the device memory, the stage then answers BF_ERR_STATE and can still be destroyed.
+ * bf_dm_stream_attach_conditioner(dm, c) (c == NULL detaches): from then on every bf_dm_stream_push conditions its new rows
+ * where they lie in the DM stage's buffer -- behind the copy-in of rows that live elsewhere (the caller's source rows stay
+ * raw), behind the rows of the push before it, and before its own rows are announced to the push behind it.  Same handle,
+ * same n_freq_total, max_rows_per_push >= the DM stage's; attaching in mid-stream starts with an empty window.  Host copies
+ * that bf_enqueue_block_to queued are in front of the push on the same queue: they carry the raw rows. */
+typedef struct bf_cond bf_cond;
+typedef struct bf_cond_options {
+    int baseline_pushes;   /* 1 .. 64 */
+    int zero_dm;           /* nonzero: subtract the per-(t, b) mean over the unmasked channels */
+    double auto_threshold; /* 0: no automatic mask */
+} bf_cond_options;
+void bf_cond_default_options(bf_cond_options *o); /* 8, 1, 0.0 (src/beamformer.cu:498-510 has no such stage) */
+int bf_cond_create(bf_handle *h, int n_freq_total, int max_rows_per_push, const bf_cond_options *o, bf_cond **out);
+int bf_cond_destroy(bf_cond *c);
+int bf_cond_set_mask(bf_cond *c, const uint8_t *host_mask);
+int bf_cond_push(bf_cond *c, float *d_rows, int n_rows, void *hip_stream);
+int bf_cond_mask_device(bf_cond *c, const uint8_t **d_mask);
+int bf_dm_stream_attach_conditioner(bf_dm_stream *dm, bf_cond *c);
+
 /* ---- Multi-GPU: frequency shards and the gather of their detected powers -------------------------------
  * The reference runs 8 independent processes, one sub-band per GPU (`-g`, src/beamformer.cu:92-100,233; README.md:168)
  * and never brings their outputs together.  Here a handle may own any contiguous range of frequencies (bf_config.n_freq

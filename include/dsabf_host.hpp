@@ -728,6 +728,16 @@ struct observation_options {
     int sps_widths = 0;
     double sps_threshold = 8.0;
     sps_candidate_sink* sps_sink = nullptr;
+    // Conditioning in front of the DM stage (docs/CONDITIONING.md; needs dm_delays): cond_baseline = pushes of the statistics' window
+    // (1 .. 64), 0 = off.  A bf_cond is created next to the DM stage and attached to it: every pushed block is normalised per
+    // (channel, beam), masked (cond_mask: host uint8 [cfg.n_freq * world], nonzero = masked, or NULL; cond_auto_threshold > 0 adds the
+    // automatic mask) and, with cond_zero_dm, freed of its per-(time, beam) mean over the channels -- in the stage's buffer, so the
+    // detected sinks keep the raw stream.  On a sharded run every rank that dedisperses conditions its gathered rows itself:
+    // redundant and identical, nothing is exchanged.
+    int cond_baseline = 0;
+    bool cond_zero_dm = true;
+    double cond_auto_threshold = 0.0;
+    const uint8_t* cond_mask = nullptr;
     // The incoherent beam (docs/INCOHERENT_BEAM.md): beam column `incoherent_beam` of the detected stream carries the antenna powers
     // summed over the antennas instead of a tied beam (bf_set_incoherent_beam, set on the handle before the loop); -1 = off.  On a
     // sharded run every rank gives the same index: the sum is per channel, each shard fills its own slice of the column.
@@ -751,6 +761,7 @@ struct observation_result {
     uint64_t dm_chunks = 0;         // chunks handed to dm_sink
     uint64_t sps_candidates = 0;    // candidates the search stage found (sps_widths > 0)
     uint64_t vis_dumps = 0;         // integrations the correlator dumped (corr_blocks > 0)
+    int cond_masked = -1;           // channels the conditioner masked in the last push (cond_baseline > 0 and a block analysed), else -1
 };
 // The reference's production main() loop on top of the C-ABI.  pos/dir: antenna positions and beam directions.
 int run_observation(const bf_config& cfg, const observation_options& opt, block_source& source, const antenna* pos,
