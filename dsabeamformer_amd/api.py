@@ -58,8 +58,32 @@ def _ptr(x) -> C.c_void_p:
     return x
 
 
-class Beamformer:
+class _Owner:
+    """Owns one pointer of the C-ABI: the attribute named ``_ptr_attr`` (``_h``, ``_s`` or ``_c``), destroyed once by the library
+    function named ``_destroy``."""
+    _ptr_attr = _destroy = ""
+
+    def close(self) -> None:
+        if getattr(self, self._ptr_attr, None):
+            getattr(self._lib, self._destroy)(getattr(self, self._ptr_attr))
+            setattr(self, self._ptr_attr, C.c_void_p())
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+class Beamformer(_Owner):
     """One handle = one GPU = one frequency shard (the reference runs one process per GPU, README.md:168)."""
+    _ptr_attr, _destroy = "_h", "bf_destroy"
 
     def __init__(self, cfg: BfConfig, device: int = 0):
         self._lib = load()
@@ -254,27 +278,11 @@ class Beamformer:
         check(self._lib.bf_handle_variant_key(self._h, int(write_c), buf, 120))
         return buf.value.decode()
 
-    def close(self) -> None:
-        if self._h:
-            self._lib.bf_destroy(self._h)
-            self._h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-
-class DmStream:
+class DmStream(_Owner):
     """bf_dm_stream: DM-trial dedispersion of the detected stream, block by block, with the delay window carried over on the
     device (include/dsabf.h).  delays: int32 host array [n_dm][n_freq_total]."""
+    _ptr_attr, _destroy = "_s", "bf_dm_stream_destroy"
 
     def __init__(self, bf: Beamformer, delays, n_freq_total: int, max_rows_per_push: int):
         import numpy as np
@@ -318,17 +326,6 @@ class DmStream:
         Conditioner; None detaches) before they are dedispersed."""
         check(self._lib.bf_dm_stream_attach_conditioner(self._s, cond._c if cond is not None else None))
 
-    def close(self) -> None:
-        if self._s:
-            self._lib.bf_dm_stream_destroy(self._s)
-            self._s = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def _candidate_dtype():
     import numpy as np
@@ -361,9 +358,10 @@ def sps_select(peaks, totals, n: int, n_beams: int, first_t: int = 0, dm_first: 
     return out[:n_out.value].copy()
 
 
-class SinglePulseSearch:
+class SinglePulseSearch(_Owner):
     """bf_sps: boxcar single-pulse search over the chunks [n_dm][n_t][beam] of a DmStream, on the device (include/dsabf.h,
     docs/SINGLE_PULSE.md).  Attach it with ``DmStream.attach_search`` or push chunks yourself."""
+    _ptr_attr, _destroy = "_s", "bf_sps_destroy"
 
     def __init__(self, bf: Beamformer, n_dm: int, n_widths: int, max_t_per_push: int, dm_first: int = 0, max_in_flight: int = 4,
                  baseline_pushes: int = 8, min_samples: int = 64, threshold: float = 8.0):
@@ -403,22 +401,12 @@ class SinglePulseSearch:
         return {"value": peaks["value"].copy(), "t_end": peaks["t_end"].copy(), "sum": stats["sum"].copy(), "sumsq": stats["sumsq"].copy(),
                 "first_t": int(first.value), "n_t": int(n_t.value)}
 
-    def close(self) -> None:
-        if self._s:
-            self._lib.bf_sps_destroy(self._s)
-            self._s = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Conditioner:
+class Conditioner(_Owner):
     """bf_cond: the detected rows [t][f][b] rewritten in place on the device -- normalised per (channel, beam) against the last
     ``baseline_pushes`` pushes, bad channels masked, the per-(time, beam) mean over the channels removed (include/dsabf.h,
     docs/CONDITIONING.md).  Attach it with ``DmStream.attach_conditioner`` or push rows yourself."""
+    _ptr_attr, _destroy = "_c", "bf_cond_destroy"
 
     def __init__(self, bf: Beamformer, n_freq_total: int, max_rows: int, baseline_pushes: int = 8, zero_dm: bool = True,
                  auto_threshold: float = 0.0, mask=None):
@@ -455,21 +443,11 @@ class Conditioner:
             raise DsabfError(-3, "Conditioner.mask: the copy from the device failed")
         return out
 
-    def close(self) -> None:
-        if self._c:
-            self._lib.bf_cond_destroy(self._c)
-            self._c = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Correlator:
+class Correlator(_Owner):
     """bf_corr: the correlator as a stage (include/dsabf.h, docs/CORRELATOR.md): one int64 accumulator on the device that pushes add
     to and a dump snapshots and zeroes; the stage orders its pushes and dumps itself, whatever queues they are issued on."""
+    _ptr_attr, _destroy = "_c", "bf_corr_destroy"
 
     def __init__(self, bf: Beamformer, max_in_flight: int = 2):
         self._lib = load()
@@ -502,17 +480,6 @@ class Correlator:
         n = C.c_uint64()
         check(self._lib.bf_corr_collect(self._c, _ptr(out), C.byref(n)))
         return out, int(n.value)
-
-    def close(self) -> None:
-        if self._c:
-            self._lib.bf_corr_destroy(self._c)
-            self._c = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def vis_to_square(tri, n_ant: int):
@@ -549,8 +516,9 @@ def comm_library_info() -> dict:
     return {"version": v.value, "lib": path.value.decode(errors="replace")}
 
 
-class Comm:
+class Comm(_Owner):
     """bf_comm: this rank's place in the frequency partition + the RCCL communicator behind bf_gather_detected."""
+    _ptr_attr, _destroy = "_c", "bf_comm_destroy"
 
     def __init__(self, rank: int, world: int, unique_id: bytes | None = None, device: int = 0):
         self._lib = load()
@@ -576,17 +544,6 @@ class Comm:
         """bf_gather_detected_staged: freq-major result, rank-major on the wire + one device re-layout pass."""
         check(self._lib.bf_gather_detected_staged(self._c, _ptr(d_local), n_rows, row_floats, root, _ptr(d_full), _ptr(d_stage),
                                                   C.c_void_p(stream)))
-
-    def close(self) -> None:
-        if self._c:
-            self._lib.bf_comm_destroy(self._c)
-            self._c = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def event_create(bf=None) -> C.c_void_p:

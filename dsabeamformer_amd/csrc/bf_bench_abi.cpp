@@ -77,7 +77,7 @@ int bf_get_counter(const bf_handle* h, const char* name, uint64_t* value)
         *value = h->pending.size();
     else if (!strcmp(name, "dm_ring_stages")) {   // live DM stages of this handle whose buffer is the twice-mapped ring (the rest: linear)
         uint64_t n = 0;
-        for (const bf_dm_stream* s : h->dm_streams) n += dm_stream_is_ring(s) ? 1 : 0;
+        for (const bf_stage* s : h->stages) n += s->ring ? 1 : 0;
         *value = n;
     } else
         return fail(BF_ERR_INVALID, "unknown counter \"%s\" (fused_launches, queued_units, dm_ring_stages)", name);

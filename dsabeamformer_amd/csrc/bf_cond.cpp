@@ -3,14 +3,13 @@
 // window's row counts and orders the pushes.
 #include <algorithm>
 #include <deque>
-#include <mutex>
 #include <new>
 
-#include "cond/bf_cond_host.h"
+#include "bf_runtime_internal.h"
 #include "cond/bf_cond_kernels.h"
 
-struct bf_cond {
-    bf_handle* h = nullptr;
+struct bf_cond : bf_stage {
+    bf_cond() : bf_stage("conditioner") {}
     int n_freq = 0, n_beams = 0, max_rows = 0, window = 0;
     bool zero_dm = true;
     double k_auto = 0.0;                  // auto_threshold * 1.4826, formed once, here, in fp64
@@ -21,55 +20,14 @@ struct bf_cond {
     hipEvent_t done[2] = {nullptr, nullptr};
     uint64_t n_push = 0;
     std::deque<int> rows_in_window;       // row counts of the pushes in the window, oldest first
-    bf_dm_stream* feeder = nullptr;       // the DM stage this one is attached to
+    void attached() override { rows_in_window.clear(); }   // attached, in mid-stream or not: the window starts empty there
 };
 
-namespace {
-// The stages of every handle: bf_destroy finds its own here (the handle itself keeps no list of them).
-std::mutex g_mu;
-std::vector<bf_cond*> g_stages;
-
-void cond_release(bf_cond* c)
-{
-    for (hipEvent_t& e : c->done) {
-        if (e) {
-            (void)hipEventSynchronize(e);   // (never recorded: returns at once)
-            (void)hipEventDestroy(e);
-        }
-        e = nullptr;
-    }
-    for (void* p : {(void*)c->buf.seg, (void*)c->buf.ring, (void*)c->buf.cell_mu, (void*)c->buf.cell_var, (void*)c->buf.mr32, (void*)c->buf.cm,
-                    (void*)c->buf.cv, (void*)c->buf.q, (void*)c->buf.dev, (void*)c->d_static, (void*)c->buf.mask, (void*)c->buf.params})
-        (void)hipFree(p);
-    c->buf = dsabf::CondBuffers{};
-    c->d_static = nullptr;
-    c->h = nullptr;
-}
-
-void forget(bf_cond* c)
-{
-    std::lock_guard<std::mutex> lock(g_mu);
-    g_stages.erase(std::remove(g_stages.begin(), g_stages.end(), c), g_stages.end());
-}
-}  // namespace
-
-void dsabf::rt::cond_release_handle(bf_handle* h)
-{
-    std::vector<bf_cond*> mine;
-    {
-        std::lock_guard<std::mutex> lock(g_mu);
-        for (bf_cond* c : g_stages)
-            if (c->h == h) mine.push_back(c);
-    }
-    for (bf_cond* c : mine) {
-        forget(c);
-        cond_release(c);
-    }
-}
+bf_stage* dsabf::rt::as_stage(bf_cond* c) { return c; }
 
 int dsabf::rt::cond_check_attach(const bf_cond* c, const bf_handle* h, int n_freq_total, int max_rows)
 {
-    if (!c->h) return fail(BF_ERR_STATE, "the handle of this conditioner has been destroyed");
+    if (int rc = orphaned(c)) return rc;
     if (c->h != h) return fail(BF_ERR_INVALID, "bf_dm_stream_attach_conditioner: the two stages belong to different handles");
     if (c->n_freq != n_freq_total)
         return fail(BF_ERR_INVALID, "bf_dm_stream_attach_conditioner: the conditioner has %d channels, the DM stage %d", c->n_freq, n_freq_total);
@@ -77,12 +35,6 @@ int dsabf::rt::cond_check_attach(const bf_cond* c, const bf_handle* h, int n_fre
         return fail(BF_ERR_INVALID, "bf_dm_stream_attach_conditioner: max_rows_per_push %d < the DM stage's %d", c->max_rows, max_rows);
     if (c->feeder) return fail(BF_ERR_STATE, "bf_dm_stream_attach_conditioner: the conditioner is attached to another DM stage");
     return BF_OK;
-}
-
-void dsabf::rt::cond_set_feeder(bf_cond* c, bf_dm_stream* dm)
-{
-    c->feeder = dm;
-    if (dm) c->rows_in_window.clear();   // attached, in mid-stream or not: the window starts empty there
 }
 
 extern "C" {
@@ -115,53 +67,31 @@ int bf_cond_create(bf_handle* h, int n_freq_total, int max_rows_per_push, const 
     c->zero_dm = o->zero_dm != 0;
     c->k_auto = o->auto_threshold * 1.4826;
     const size_t F = (size_t)n_freq_total, cells = F * c->n_beams;
-    hipError_t e = hipMalloc((void**)&c->buf.ring, (size_t)c->window * cells * sizeof(dsabf::CondStat));
-    if (e == hipSuccess) e = hipMalloc((void**)&c->buf.cell_mu, cells * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&c->buf.cell_var, cells * sizeof(double));
     const size_t n_seg = ((size_t)max_rows_per_push + dsabf::kCondSegment - 1) / dsabf::kCondSegment;
-    if (e == hipSuccess) e = hipMalloc((void**)&c->buf.seg, n_seg * cells * sizeof(dsabf::CondStat));
-    if (e == hipSuccess) e = hipMalloc((void**)&c->buf.mr32, cells * sizeof(float2));
-    if (e == hipSuccess) e = hipMalloc((void**)&c->buf.cm, F * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&c->buf.cv, F * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&c->buf.q, F * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&c->buf.dev, F * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&c->d_static, F);
-    if (e == hipSuccess) e = hipMalloc((void**)&c->buf.mask, (F + 3) / 4 * 4);   // (whole dwords: a host mirror may copy it as such)
-    if (e == hipSuccess) e = hipMalloc((void**)&c->buf.params, sizeof(dsabf::CondParams));
-    if (e == hipSuccess) e = hipMemset(c->d_static, 0, F);
-    if (e == hipSuccess) e = hipMemset(c->buf.mask, 0, (F + 3) / 4 * 4);
-    for (int k = 0; k < 2 && e == hipSuccess; k++) e = hipEventCreateWithFlags(&c->done[k], hipEventDisableTiming);
-    if (e == hipSuccess) e = hipDeviceSynchronize();   // (the memsets above ran on the null stream: pushes come on non-blocking ones)
+    bf_resources& res = c->res;
+    res.dev(&c->buf.ring, (size_t)c->window * cells * sizeof(dsabf::CondStat));
+    res.dev(&c->buf.cell_mu, cells * sizeof(double));
+    res.dev(&c->buf.cell_var, cells * sizeof(double));
+    res.dev(&c->buf.seg, n_seg * cells * sizeof(dsabf::CondStat));
+    res.dev(&c->buf.mr32, cells * sizeof(float2));
+    for (double** p : {&c->buf.cm, &c->buf.cv, &c->buf.q, &c->buf.dev}) res.dev(p, F * sizeof(double));
+    res.dev(&c->d_static, F, true);
+    res.dev(&c->buf.mask, (F + 3) / 4 * 4, true);   // (whole dwords: a host mirror may copy it as such)
+    res.dev(&c->buf.params, sizeof(dsabf::CondParams));
+    for (hipEvent_t& ev : c->done) res.event(&ev);
+    res.device_sync();
     c->buf.static_mask = c->d_static;
-    {
-        std::lock_guard<std::mutex> lock(g_mu);
-        g_stages.push_back(c);
-    }
-    if (e != hipSuccess) {
-        bf_cond_destroy(c);
-        return fail(BF_ERR_DEVICE, "bf_cond_create: %s", hipGetErrorString(e));
-    }
+    if (int rc = stage_adopt(c, "bf_cond_create")) return rc;
     *out = c;
     return BF_OK;
 }
 
-int bf_cond_destroy(bf_cond* c)
-{
-    if (!c) return BF_OK;
-    if (c->feeder) dm_stream_drop_conditioner(c->feeder);
-    if (c->h) {   // (NULL: the handle went first and took the device memory with it)
-        DeviceScope dev_scope_(c->h->device);
-        forget(c);
-        cond_release(c);
-    }
-    delete c;
-    return BF_OK;
-}
+int bf_cond_destroy(bf_cond* c) { return stage_destroy(c); }
 
 int bf_cond_set_mask(bf_cond* c, const uint8_t* host_mask)
 {
     if (!c || !host_mask) return fail(BF_ERR_INVALID, "NULL argument");
-    if (!c->h) return fail(BF_ERR_STATE, "the handle of this conditioner has been destroyed");
+    if (int rc = orphaned(c)) return rc;
     bf_handle* h = c->h;
     ON_DEVICE(h);
     // the push in flight still reads the old mask: wait for it, then copy (a blocking call: masks change rarely)
@@ -174,7 +104,7 @@ int bf_cond_push(bf_cond* c, float* d_rows, int n_rows, void* hip_stream)
 {
     if (!c || !d_rows) return fail(BF_ERR_INVALID, "NULL argument");
     if (n_rows < 1 || n_rows > c->max_rows) return fail(BF_ERR_INVALID, "n_rows must be 1 .. %d (max_rows_per_push)", c->max_rows);
-    if (!c->h) return fail(BF_ERR_STATE, "the handle of this conditioner has been destroyed");
+    if (int rc = orphaned(c)) return rc;
     bf_handle* h = c->h;
     ON_DEVICE(h);
     hipStream_t q = as_stream(hip_stream);
@@ -196,7 +126,7 @@ int bf_cond_mask_device(bf_cond* c, const uint8_t** d_mask)
 {
     if (!c || !d_mask) return fail(BF_ERR_INVALID, "NULL argument");
     *d_mask = nullptr;
-    if (!c->h) return fail(BF_ERR_STATE, "the handle of this conditioner has been destroyed");
+    if (int rc = orphaned(c)) return rc;
     *d_mask = c->buf.mask;
     return BF_OK;
 }

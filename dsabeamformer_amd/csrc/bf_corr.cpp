@@ -1,14 +1,13 @@
 // bf_corr.cpp -- the correlator (include/dsabf.h: bf_correlate_device, bf_corr_*; contract and measurements: docs/CORRELATOR.md).
 // The device code is csrc/corr/bf_corr.hip; this file checks the bounds, owns a stage's accumulator and orders its pushes and dumps.
-#include <algorithm>
 #include <cstring>
 #include <new>
 
 #include "bf_runtime_internal.h"
 #include "corr/bf_corr_kernels.h"
 
-struct bf_corr {
-    bf_handle* h = nullptr;
+struct bf_corr : bf_stage {
+    bf_corr() : bf_stage("correlator stage") {}
     int max_in_flight = 0;
     size_t n_int64 = 0;                // 2 * bf_corr_entries
     long long* d_acc = nullptr;        // the integration in progress: every push adds to it, a dump copies it out and zeroes it
@@ -27,34 +26,6 @@ struct bf_corr {
     hipStream_t copy_q = nullptr;
     uint64_t n_dump = 0, n_collected = 0;
 };
-
-void dsabf::rt::corr_release(bf_corr* c)
-{
-    for (auto& r : c->sets) {
-        if (r.copied) {
-            (void)hipEventSynchronize(r.copied);   // (never recorded: returns at once)
-            (void)hipEventDestroy(r.copied);
-        }
-        (void)hipHostFree(r.h_vis);
-        r = bf_corr::result_set();
-    }
-    if (c->copy_q) {
-        (void)hipStreamSynchronize(c->copy_q);
-        (void)hipStreamDestroy(c->copy_q);
-    }
-    for (auto& e : c->push_done) {
-        if (e) {
-            (void)hipEventSynchronize(e);
-            (void)hipEventDestroy(e);
-        }
-        e = nullptr;
-    }
-    (void)hipFree(c->d_acc);
-    c->copy_q = nullptr;
-    c->d_acc = nullptr;
-    c->last = nullptr;
-    c->h = nullptr;
-}
 
 // The bounds of one launch (include/dsabf.h): n_ant <= 256, fewer than 2^24 columns per polarisation.
 static int check_launch(const bf_handle* h, int n_units, const char* who)
@@ -123,45 +94,29 @@ int bf_corr_create(bf_handle* h, int max_in_flight, bf_corr** out)
     c->max_in_flight = max_in_flight;
     c->n_int64 = 2 * bf_corr_entries(&h->cfg);
     const size_t bytes = c->n_int64 * sizeof(long long);
-    hipError_t e = hipMalloc((void**)&c->d_acc, bytes);
-    if (e == hipSuccess) e = hipMemset(c->d_acc, 0, bytes);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->copy_q, hipStreamNonBlocking);
-    for (auto& ev : c->push_done)
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+    bf_resources& res = c->res;
+    res.dev(&c->d_acc, bytes, true);
+    res.queue(&c->copy_q);
+    for (auto& ev : c->push_done) res.event(&ev);
     c->sets.resize((size_t)max_in_flight);
     for (auto& r : c->sets) {
-        if (e == hipSuccess) e = hipHostMalloc((void**)&r.h_vis, bytes, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&r.copied, hipEventDisableTiming);
+        res.host(&r.h_vis, bytes);
+        res.event(&r.copied);
     }
-    if (e == hipSuccess) e = hipDeviceSynchronize();   // (the memset above ran on the null stream: pushes come on non-blocking ones)
-    h->corr_stages.push_back(c);
-    if (e != hipSuccess) {
-        bf_corr_destroy(c);
-        return fail(BF_ERR_DEVICE, "bf_corr_create: %s", hipGetErrorString(e));
-    }
+    res.device_sync();
+    if (int rc = stage_adopt(c, "bf_corr_create")) return rc;
     *out = c;
     return BF_OK;
 }
 
-int bf_corr_destroy(bf_corr* c)
-{
-    if (!c) return BF_OK;
-    if (c->h) {   // (NULL: the handle went first and took the device memory with it)
-        bf_handle* h = c->h;
-        DeviceScope dev_scope_(h->device);
-        h->corr_stages.erase(std::remove(h->corr_stages.begin(), h->corr_stages.end(), c), h->corr_stages.end());
-        corr_release(c);
-    }
-    delete c;
-    return BF_OK;
-}
+int bf_corr_destroy(bf_corr* c) { return stage_destroy(c); }
 
 int bf_corr_pending(const bf_corr* c) { return c ? (int)(c->n_dump - c->n_collected) : fail(BF_ERR_INVALID, "the stage is NULL"); }
 
 int bf_corr_push(bf_corr* c, const void* d_packed, int n_units, void* hip_stream)
 {
     if (!c || !d_packed) return fail(BF_ERR_INVALID, "NULL argument");
-    if (!c->h) return fail(BF_ERR_STATE, "the handle of this correlator stage has been destroyed");
+    if (int rc = orphaned(c)) return rc;
     if (int rc = check_launch(c->h, n_units, "bf_corr_push")) return rc;
     if ((uintptr_t)d_packed & 15) return fail(BF_ERR_INVALID, "misaligned device pointer: d_packed must be 16-byte aligned");
     ON_DEVICE(c->h);
@@ -171,7 +126,7 @@ int bf_corr_push(bf_corr* c, const void* d_packed, int n_units, void* hip_stream
 int bf_corr_push_block(bf_corr* c, int stream_idx, int slot, int first_unit, int n_units)
 {
     if (!c) return fail(BF_ERR_INVALID, "the stage is NULL");
-    if (!c->h) return fail(BF_ERR_STATE, "the handle of this correlator stage has been destroyed");
+    if (int rc = orphaned(c)) return rc;
     bf_handle* h = c->h;
     if (stream_idx < 0 || stream_idx >= h->cfg.n_streams) return fail(BF_ERR_INVALID, "stream %d out of range", stream_idx);
     if (slot < 0 || slot >= h->cfg.n_blocks_on_gpu) return fail(BF_ERR_INVALID, "slot %d out of range", slot);
@@ -188,7 +143,7 @@ int bf_corr_dump(bf_corr* c, void* hip_stream)
 {
     (void)hip_stream;   // the dump never holds the caller's queue: it is ordered by the stage's own chain
     if (!c) return fail(BF_ERR_INVALID, "the stage is NULL");
-    if (!c->h) return fail(BF_ERR_STATE, "the handle of this correlator stage has been destroyed");
+    if (int rc = orphaned(c)) return rc;
     if (c->n_dump - c->n_collected >= (uint64_t)c->max_in_flight)
         return fail(BF_ERR_STATE, "bf_corr_dump: %d dumps are uncollected (max_in_flight): bf_corr_collect first", c->max_in_flight);
     ON_DEVICE(c->h);
@@ -208,7 +163,7 @@ int bf_corr_dump(bf_corr* c, void* hip_stream)
 int bf_corr_collect(bf_corr* c, int64_t* out, uint64_t* n_columns_per_pol)
 {
     if (!c || !out) return fail(BF_ERR_INVALID, "NULL argument");
-    if (!c->h) return fail(BF_ERR_STATE, "the handle of this correlator stage has been destroyed");
+    if (int rc = orphaned(c)) return rc;
     if (c->n_collected == c->n_dump) return fail(BF_ERR_STATE, "bf_corr_collect: no dump is pending");
     ON_DEVICE(c->h);
     bf_corr::result_set& r = c->sets[c->n_collected % c->max_in_flight];

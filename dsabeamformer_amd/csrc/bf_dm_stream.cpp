@@ -1,12 +1,10 @@
 // bf_dm_stream.cpp -- DM-trial dedispersion (include/dsabf.h): the caller-stream calls and the stage of the observation loop
 // (bf_dm_stream_*) with its twice-mapped ring.
-#include <algorithm>
 #include <mutex>
 #include <new>
 #include <numeric>
 
 #include "bf_runtime_internal.h"
-#include "cond/bf_cond_host.h"
 
 // ---- DM-trial dedispersion as a stage of the observation loop (include/dsabf.h) ---------------------------
 // The detected stream arrives block by block; out[dm][t][b] needs rows t .. t + max_delay.  The stream keeps the last
@@ -14,16 +12,16 @@
 // end is reached), so every push runs the SAME kernels over [carry | new rows] that bf_dedisperse_dm_device runs over a
 // whole series -- and emits exactly the output times that became complete.  Every (trial, time, beam) sum still runs over
 // ascending f in one register from +0: the concatenated chunks are bit-identical to one call over the whole series.
-struct bf_dm_stream {
-    bf_handle* h = nullptr;
+struct bf_dm_stream : bf_stage {
+    bf_dm_stream() : bf_stage("DM stage") {}
+    void release_device() override;
     int n_dm = 0, n_freq = 0, max_delay = 0, max_rows = 0;
     size_t row_floats = 0;
     // The rows live in a RING of cap_rows rows whose physical memory is mapped TWICE, back to back, into one virtual range (HIP's
     // virtual-memory API): row i is also row i + cap_rows, so every window of <= cap_rows consecutive rows -- the carried-over
     // delay window in front of a push's rows -- is contiguous for the kernels wherever it starts, and nothing ever moves.  (Rounds
     // 5's linear buffer slid the carry back to its start every few pushes: at the production block, 31 MiB read and written again
-    // every 2.5 blocks.)  ring == false: that linear buffer -- for a device without VMM support, and bf_set_switch("dm_ring", 0).
-    bool ring = false;
+    // every 2.5 blocks.)  ring (bf_stage) == false: that linear buffer -- for a device without VMM support, and bf_set_switch("dm_ring", 0).
     size_t cap_rows = 0;          // ring: rows of physical memory (>= max_delay + 3 max_rows); linear: 2 (max_delay + max_rows)
     size_t wpos = 0;              // ring: physical row the next pushed row goes to (< cap_rows)
     size_t fill = 0;              // linear: rows of d_buf in use, [fill - carry, fill) are the newest rows of the series
@@ -53,52 +51,35 @@ struct bf_dm_stream {
     bf_cond* cond = nullptr;      // bf_dm_stream_attach_conditioner: every push's new rows are conditioned in place, before `rows_ready` is recorded
 };
 
-// device side of a DM stage (its handle's device must be current); the object itself stays, detached from the handle
-void dsabf::rt::dm_stream_release(bf_dm_stream* s)
+// One link to an attached stage: the member of the DM stage (search, cond) and that stage's feeder, set and cleared together.
+template <class T>
+static void set_link(bf_dm_stream* dm, T*& member, T* to)
 {
-    dm_stream_drop_search(s);
-    dm_stream_drop_conditioner(s);
-    for (int k = 0; k < 3; k++) {
-        if (s->done[k]) {
-            if (s->done_recorded[k]) (void)hipEventSynchronize(s->done[k]);
-            (void)hipEventDestroy(s->done[k]);
-        }
-        if (s->rows_ready[k]) (void)hipEventDestroy(s->rows_ready[k]);
-        s->done[k] = s->rows_ready[k] = nullptr;
-        s->done_recorded[k] = s->rows_recorded[k] = false;
-    }
-    if (s->ring || s->phys_created) {
-        if (s->mapped0) (void)hipMemUnmap(s->d_buf, s->phys_bytes);
-        if (s->mapped1) (void)hipMemUnmap(reinterpret_cast<char*>(s->d_buf) + s->phys_bytes, s->phys_bytes);
-        if (s->phys_created) (void)hipMemRelease(s->phys);   // (the addresses go back to nobody: ring_address_space)
-        s->mapped0 = s->mapped1 = s->phys_created = false;
-    } else {
-        (void)hipFree(s->d_buf);
-    }
-    for (int k = 0; k < 3; k++) {
-        (void)hipFree(s->d_out[k]);
-        (void)hipFree(s->d_flags[k]);
-        s->d_out[k] = nullptr;
-        s->d_flags[k] = nullptr;
-    }
-    (void)hipFree(s->d_delays);
-    s->d_buf = nullptr;
-    s->d_delays = nullptr;
-    s->h = nullptr;
+    if (member) as_stage(member)->feeder = nullptr;
+    member = to;
+    if (!to) return;
+    as_stage(to)->feeder = dm;
+    as_stage(to)->attached();
 }
 
-bool dsabf::rt::dm_stream_is_ring(const bf_dm_stream* s) { return s->ring; }
-
-void dsabf::rt::dm_stream_drop_search(bf_dm_stream* s)
+void dsabf::rt::dm_stream_drop(bf_dm_stream* dm, bf_stage* attached)
 {
-    if (s->search) sps_set_feeder(s->search, nullptr);
-    s->search = nullptr;
+    if (dm->search && as_stage(dm->search) == attached) set_link<bf_sps>(dm, dm->search, nullptr);
+    if (dm->cond && as_stage(dm->cond) == attached) set_link<bf_cond>(dm, dm->cond, nullptr);
 }
 
-void dsabf::rt::dm_stream_drop_conditioner(bf_dm_stream* s)
+// The ring is no hipMalloc: it is unmapped and released here, behind the wait for everything in flight, and the stage's resource
+// list (events, chunks, scratch, delays, the linear buffer) goes after it.
+void bf_dm_stream::release_device()
 {
-    if (s->cond) cond_set_feeder(s->cond, nullptr);
-    s->cond = nullptr;
+    set_link<bf_sps>(this, search, nullptr);
+    set_link<bf_cond>(this, cond, nullptr);
+    res.wait();
+    if (mapped0) (void)hipMemUnmap(d_buf, phys_bytes);
+    if (mapped1) (void)hipMemUnmap(reinterpret_cast<char*>(d_buf) + phys_bytes, phys_bytes);
+    if (phys_created) (void)hipMemRelease(phys);   // (the addresses go back to nobody: ring_address_space)
+    mapped0 = mapped1 = phys_created = false;
+    res.release();
 }
 
 // Address space for the rings: taken from arenas that are reserved once per process and NEVER given back or handed out twice.
@@ -246,80 +227,60 @@ int bf_dm_stream_create(bf_handle* h, const int32_t* delays, int n_dm, int n_fre
     s->max_delay = dmax;
     s->max_rows = max_rows_per_push;
     s->row_floats = (size_t)n_freq_total * h->cfg.n_beams;
-    hipError_t e = hipSuccess;
+    bf_resources& res = s->res;
     // the ring: the window of a push (<= max_delay + max_rows rows) + two more pushes' rows that may be written while it is read
     if (!h->dm_ring || !dm_ring_create(s, h->device, (size_t)dmax + 3 * (size_t)max_rows_per_push)) {
         // linear: room for the carry and a push twice over -- when the end is reached the carry moves to the start without overlapping itself
         s->cap_rows = 2 * ((size_t)dmax + (size_t)max_rows_per_push);
-        e = hipMalloc((void**)&s->d_buf, s->cap_rows * s->row_floats * sizeof(float));
+        res.dev(&s->d_buf, s->cap_rows * s->row_floats * sizeof(float));
     }
     const int n_sets = s->ring ? 3 : 1;   // (the linear buffer keeps one push at a time: one chunk, one scratch)
-    for (int k = 0; k < n_sets && e == hipSuccess; k++) {
-        e = hipMalloc((void**)&s->d_out[k], (size_t)n_dm * max_rows_per_push * h->cfg.n_beams * sizeof(float));
-        if (e == hipSuccess) e = hipMalloc((void**)&s->d_flags[k], dsabf::kDmScratchBytes);
+    for (int k = 0; k < n_sets; k++) {
+        res.dev(&s->d_out[k], (size_t)n_dm * max_rows_per_push * h->cfg.n_beams * sizeof(float));
+        res.dev(&s->d_flags[k], dsabf::kDmScratchBytes);
     }
-    if (e == hipSuccess) e = hipMalloc((void**)&s->d_delays, (size_t)n_dm * n_freq_total * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMemcpy(s->d_delays, delays, (size_t)n_dm * n_freq_total * sizeof(int32_t), hipMemcpyHostToDevice);
-    for (int k = 0; k < 3 && e == hipSuccess; k++) {
-        e = hipEventCreateWithFlags(&s->done[k], hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&s->rows_ready[k], hipEventDisableTiming);
+    res.dev(&s->d_delays, (size_t)n_dm * n_freq_total * sizeof(int32_t));
+    if (res.err == hipSuccess) res.err = hipMemcpy(s->d_delays, delays, (size_t)n_dm * n_freq_total * sizeof(int32_t), hipMemcpyHostToDevice);
+    for (int k = 0; k < 3; k++) {
+        res.event(&s->done[k]);
+        res.event(&s->rows_ready[k]);
     }
-    h->dm_streams.push_back(s);
-    if (e != hipSuccess) {
-        bf_dm_stream_destroy(s);
-        return fail(BF_ERR_DEVICE, "bf_dm_stream_create: %s", hipGetErrorString(e));
-    }
+    if (int rc = stage_adopt(s, "bf_dm_stream_create")) return rc;
     *out = s;
     return BF_OK;
 }
 
-int bf_dm_stream_destroy(bf_dm_stream* s)
-{
-    if (!s) return BF_OK;
-    dm_stream_drop_search(s);
-    dm_stream_drop_conditioner(s);
-    if (s->h) {   // (NULL: the handle went first and took the device memory with it)
-        bf_handle* h = s->h;
-        DeviceScope dev_scope_(h->device);
-        h->dm_streams.erase(std::remove(h->dm_streams.begin(), h->dm_streams.end(), s), h->dm_streams.end());
-        dm_stream_release(s);
-    }
-    delete s;
-    return BF_OK;
-}
+// (a stage whose handle went first lost its links then; one that still has its handle loses them in release_device)
+int bf_dm_stream_destroy(bf_dm_stream* s) { return stage_destroy(s); }
 
 int bf_dm_stream_max_delay(const bf_dm_stream* s) { return s ? s->max_delay : BF_ERR_INVALID; }
 
 int bf_dm_stream_attach_search(bf_dm_stream* dm, bf_sps* sps)
 {
     if (!dm) return fail(BF_ERR_INVALID, "NULL argument");
-    if (!dm->h) return fail(BF_ERR_STATE, "the handle of this DM stage has been destroyed");
+    if (int rc = orphaned(dm)) return rc;
     if (sps == dm->search) return BF_OK;
     if (sps)
         if (int rc = sps_check_attach(sps, dm->h, dm->n_dm, dm->max_rows)) return rc;
-    dm_stream_drop_search(dm);
-    dm->search = sps;
-    if (sps) sps_set_feeder(sps, dm);
+    set_link(dm, dm->search, sps);
     return BF_OK;
 }
 
 int bf_dm_stream_attach_conditioner(bf_dm_stream* dm, bf_cond* c)
 {
     if (!dm) return fail(BF_ERR_INVALID, "NULL argument");
-    if (!dm->h) return fail(BF_ERR_STATE, "the handle of this DM stage has been destroyed");
+    if (int rc = orphaned(dm)) return rc;
     if (c == dm->cond) return BF_OK;
     if (c)
         if (int rc = cond_check_attach(c, dm->h, dm->n_freq, dm->max_rows)) return rc;
-    dm_stream_drop_conditioner(dm);
-    dm->cond = c;
-    if (c) cond_set_feeder(c, dm);
+    set_link(dm, dm->cond, c);
     return BF_OK;
 }
 
 int bf_dm_stream_output_device(bf_dm_stream* s, float** d_out)
 {
     if (!s || !d_out) return fail(BF_ERR_INVALID, "NULL argument");
-    if (!s->h) return fail(BF_ERR_STATE, "the handle of this DM stage has been destroyed");
+    if (int rc = orphaned(s)) return rc;
     *d_out = s->d_out[s->ring && s->n_push ? (s->n_push - 1) % 3 : 0];   // the most recent push's chunk
     return BF_OK;
 }
@@ -363,7 +324,7 @@ int bf_dm_stream_reserve(bf_dm_stream* s, int n_rows, float** d_dst, void* hip_s
     if (!s || !d_dst) return fail(BF_ERR_INVALID, "NULL argument");
     *d_dst = nullptr;
     if (n_rows <= 0 || n_rows > s->max_rows) return fail(BF_ERR_INVALID, "n_rows must be 1 .. %d (max_rows_per_push)", s->max_rows);
-    if (!s->h) return fail(BF_ERR_STATE, "the handle of this DM stage has been destroyed");
+    if (int rc = orphaned(s)) return rc;
     if (s->reserved_rows) return fail(BF_ERR_STATE, "bf_dm_stream_reserve: the previous reservation has not been pushed");
     bf_handle* h = s->h;
     ON_DEVICE(h);
@@ -380,7 +341,7 @@ int bf_dm_stream_push(bf_dm_stream* s, const float* d_rows, int n_rows, float* h
 {
     if (!s || !d_rows) return fail(BF_ERR_INVALID, "NULL argument");
     if (n_rows <= 0 || n_rows > s->max_rows) return fail(BF_ERR_INVALID, "n_rows must be 1 .. %d (max_rows_per_push)", s->max_rows);
-    if (!s->h) return fail(BF_ERR_STATE, "the handle of this DM stage has been destroyed");
+    if (int rc = orphaned(s)) return rc;
     const bool in_place = s->reserved_rows != 0;
     if (in_place && (d_rows != s->reserved || n_rows != s->reserved_rows))
         return fail(BF_ERR_STATE, "bf_dm_stream_push: %d rows are reserved at %p (bf_dm_stream_reserve); push exactly those", s->reserved_rows,

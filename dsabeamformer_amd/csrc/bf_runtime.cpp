@@ -5,6 +5,7 @@
 // detected-power buffer per compute queue.  There is no CPU fallback: without a gfx950 device every compute
 // entry point fails with BF_ERR_NO_DEVICE / BF_ERR_DEVICE.  The compute queues are bf_queues.cpp, the DM-trial stage
 // bf_dm_stream.cpp, the measurement ABI (include/dsabf_bench.h) bf_bench_abi.cpp.
+#include <algorithm>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -13,8 +14,51 @@
 
 #include "bf_host_internal.h"
 #include "bf_runtime_internal.h"
-#include "cond/bf_cond_host.h"
 #include "ib/bf_incoherent.h"
+
+// ---- what every stage shares (bf_runtime_internal.h): its device resources here, its lifetime (orphaned, stage_*) below
+void* bf_resources::alloc(size_t bytes, bool zeroed, bool on_host)
+{
+    void* p = nullptr;
+    if (err == hipSuccess) err = on_host ? hipHostMalloc(&p, bytes, hipHostMallocDefault) : hipMalloc(&p, bytes);
+    if (err != hipSuccess) return nullptr;
+    (on_host ? pinned : device).push_back(p);
+    if (zeroed) err = hipMemset(p, 0, bytes);
+    return p;
+}
+
+void bf_resources::event(hipEvent_t* e)
+{
+    if (err == hipSuccess) err = hipEventCreateWithFlags(e, hipEventDisableTiming);
+    if (err == hipSuccess) events.push_back(*e);
+}
+
+void bf_resources::queue(hipStream_t* q)
+{
+    if (err == hipSuccess) err = hipStreamCreateWithFlags(q, hipStreamNonBlocking);
+    if (err == hipSuccess) queues.push_back(*q);
+}
+
+void bf_resources::device_sync()
+{
+    if (err == hipSuccess) err = hipDeviceSynchronize();
+}
+
+void bf_resources::wait()
+{
+    for (hipEvent_t e : events) (void)hipEventSynchronize(e);
+    for (hipStream_t q : queues) (void)hipStreamSynchronize(q);
+}
+
+void bf_resources::release()
+{
+    wait();
+    for (hipEvent_t e : events) (void)hipEventDestroy(e);
+    for (hipStream_t q : queues) (void)hipStreamDestroy(q);
+    for (void* p : device) (void)hipFree(p);
+    for (void* p : pinned) (void)hipHostFree(p);
+    *this = bf_resources();
+}
 
 namespace dsabf::rt {
 
@@ -29,6 +73,37 @@ int fail(int code, const char* fmt, ...)
     va_end(ap);
     g_err = buf;
     return code;
+}
+
+int orphaned(const bf_stage* s) { return s->h ? BF_OK : fail(BF_ERR_STATE, "the handle of this %s has been destroyed", s->noun); }
+
+int stage_adopt(bf_stage* s, const char* who)
+{
+    s->h->stages.push_back(s);
+    const hipError_t e = s->res.err;
+    if (e == hipSuccess) return BF_OK;
+    stage_destroy(s);
+    return fail(BF_ERR_DEVICE, "%s: %s", who, hipGetErrorString(e));
+}
+
+void stage_release(bf_stage* s)
+{
+    s->release_device();
+    s->h = nullptr;
+}
+
+int stage_destroy(bf_stage* s)
+{
+    if (!s) return BF_OK;
+    if (s->feeder) dm_stream_drop(s->feeder, s);
+    if (s->h) {   // (NULL: the handle went first and took the device side with it)
+        DeviceScope dev_scope_(s->h->device);
+        std::vector<bf_stage*>& all = s->h->stages;
+        all.erase(std::remove(all.begin(), all.end(), s), all.end());
+        stage_release(s);
+    }
+    delete s;
+    return BF_OK;
 }
 
 static int check_cfg(const bf_config* c)
@@ -225,10 +300,7 @@ int bf_destroy(bf_handle* h)
     if (h->t0) (void)hipEventDestroy(h->t0);
     if (h->t1) (void)hipEventDestroy(h->t1);
     for (void* p : std::initializer_list<void*>{h->d_wimage, h->d_wimage_p, h->d_wimage_f, h->d_flag, h->d_data, h->d_out, h->d_ded}) (void)hipFree(p);
-    for (auto* ds : h->dm_streams) dm_stream_release(ds);   // a DM stage that outlives its handle is left empty, not dangling
-    for (auto* sp : h->sps_stages) sps_release(sp);         // ... and a search stage
-    for (auto* cs : h->corr_stages) corr_release(cs);       // ... and a correlator stage
-    cond_release_handle(h);                                 // ... and its conditioners (bf_cond.cpp keeps their list)
+    for (bf_stage* st : h->stages) stage_release(st);   // a stage that outlives its handle is left empty, not dangling
     for (auto& sc : h->dm_scratch) (void)hipFree(sc.second);
     for (auto& b : h->qbuf)
         for (float* p : {b.out_blk, b.full_blk, b.stage_blk, b.ded_blk}) (void)hipFree(p);

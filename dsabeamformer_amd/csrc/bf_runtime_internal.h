@@ -1,5 +1,6 @@
 // bf_runtime_internal.h -- what the C-ABI runtime's translation units share (bf_runtime.cpp, bf_queues.cpp, bf_dm_stream.cpp,
-// bf_bench_abi.cpp): the handle, the error string, the device scope.  Host-only and not installed: no .hip / .hpp file includes it.
+// bf_sps.cpp, bf_cond.cpp, bf_corr.cpp, bf_bench_abi.cpp): the handle, the base of its stages, the error string, the device scope.
+// Host-only and not installed: no .hip / .hpp file includes it.
 #pragma once
 #include "../../include/dsabf.h"
 
@@ -64,13 +65,43 @@ struct bf_handle {
     };
     std::vector<queue_bufs> qbuf;
     int full_world = 0;
-    std::vector<struct bf_dm_stream*> dm_streams;   // DM stages created on this handle: bf_destroy releases their device memory
-    std::vector<struct bf_sps*> sps_stages;         // single-pulse search stages (bf_sps.cpp): the same
-    std::vector<struct bf_corr*> corr_stages;       // correlator stages (bf_corr.cpp): the same
+    std::vector<struct bf_stage*> stages;   // every stage created on this handle, of whatever kind: bf_destroy releases their device side
     hipStream_t h2d = nullptr;
     std::vector<hipStream_t> streams;
     std::vector<hipEvent_t> join;  // one per compute queue: queue_waits_for
     hipEvent_t t0 = nullptr, t1 = nullptr;
+};
+
+// What a stage owns on the device, held by value and shared with nobody.  Every call records what it made and keeps the FIRST
+// error; after an error the calls that follow do nothing, so a create is straight-line code that looks at `err` once, at its end.
+struct bf_resources {
+    hipError_t err = hipSuccess;
+    std::vector<void*> device, pinned;
+    std::vector<hipEvent_t> events;
+    std::vector<hipStream_t> queues;
+    void* alloc(size_t bytes, bool zeroed, bool on_host);
+    template <class T> void dev(T** p, size_t bytes, bool zeroed = false) { *p = static_cast<T*>(alloc(bytes, zeroed, false)); }   // (zeroed: on the null stream)
+    template <class T> void host(T** p, size_t bytes) { *p = static_cast<T*>(alloc(bytes, false, true)); }                         // pinned
+    void event(hipEvent_t* e);      // timing disabled
+    void queue(hipStream_t* q);     // non-blocking
+    void device_sync();             // end of a create that zeroed memory: the memsets ran on the null stream, pushes come on non-blocking ones
+    // The one rule for in-flight work: every event is waited for, then every queue (wait); then events and queues are destroyed,
+    // then the memory is freed.  (An event that was never recorded returns at once.)
+    void wait();
+    void release();
+};
+
+// The base of the four stage objects (bf_dm_stream, bf_sps, bf_cond, bf_corr: opaque to callers, each defined in its own file).
+struct bf_stage {
+    bf_handle* h = nullptr;                 // NULL: the handle went first and took the device side with it
+    const char* const noun;                 // "DM stage", "search stage", ...: the orphan check's message
+    struct bf_dm_stream* feeder = nullptr;  // search stage, conditioner: the DM stage it is attached to
+    bool ring = false;                      // DM stage: its buffer is the twice-mapped ring (bf_get_counter "dm_ring_stages")
+    bf_resources res;
+    explicit bf_stage(const char* noun_) : noun(noun_) {}
+    virtual ~bf_stage() = default;
+    virtual void release_device() { res.release(); }   // the handle's device is current; the object stays
+    virtual void attached() {}                          // a DM stage has just become the feeder
 };
 
 // (hidden: shared by the runtime's translation units, not exported from libdsabf.so)
@@ -86,15 +117,19 @@ int flush_units(bf_handle* h);                          // bf_queues.cpp
 // Every detect launch of a handle: the fused kernel over n_units gemm-units at `in` -> out [unit][o][f][b] and, behind it on the same
 // queue, the incoherent beam into column h->ib_beam of the same `out` if one is set (bf_queues.cpp)
 int launch_detect(bf_handle* h, const void* in, int n_units, float* out, hipStream_t s);
-void dm_stream_release(struct bf_dm_stream* s);         // bf_dm_stream.cpp
-bool dm_stream_is_ring(const struct bf_dm_stream* s);
-void dm_stream_drop_search(struct bf_dm_stream* s);     // the search stage attached to `s` is going away
-// bf_sps.cpp: the single-pulse search stage
-void sps_release(struct bf_sps* s);                     // device side of a stage; the object stays, detached from its handle
-int sps_check_attach(const struct bf_sps* s, const bf_handle* h, int n_dm, int max_rows);   // bf_dm_stream_attach_search's conditions
+
+int orphaned(const bf_stage* s);                        // BF_ERR_STATE "the handle of this <noun> has been destroyed", or BF_OK
+// End of every create: `s` (s->h set) joins its handle's list; a HIP error in s->res destroys it and fails as "<who>: <error>".
+int stage_adopt(bf_stage* s, const char* who);
+void stage_release(bf_stage* s);                        // device side of a stage; the object stays, detached from its handle
+int stage_destroy(bf_stage* s);                         // every bf_*_destroy: unlinked from its feeder and its handle, released, deleted
+// The link "attached to a DM stage" has two ends: a member of the DM stage (search, cond) and the feeder of the stage it points at.
+bf_stage* as_stage(struct bf_sps* s);                   // bf_sps.cpp
+bf_stage* as_stage(struct bf_cond* c);                  // bf_cond.cpp
+void dm_stream_drop(struct bf_dm_stream* dm, bf_stage* attached);   // bf_dm_stream.cpp: `attached` is going away
+int sps_check_attach(const struct bf_sps* s, const bf_handle* h, int n_dm, int max_rows);            // bf_dm_stream_attach_search's conditions
 int sps_max_in_flight(const struct bf_sps* s);
-void sps_set_feeder(struct bf_sps* s, struct bf_dm_stream* dm);   // the DM stage that pushes into `s` (NULL: none): told when `s` is destroyed
-void corr_release(struct bf_corr* c);                   // bf_corr.cpp: device side of a correlator stage; the object stays, detached from its handle
+int cond_check_attach(const struct bf_cond* c, const bf_handle* h, int n_freq_total, int max_rows);  // bf_dm_stream_attach_conditioner's conditions
 
 // Makes `device` current for the duration of one entry point and puts the caller's device back afterwards: a library
 // call must not change the current device of a multi-device host process (torch's included).

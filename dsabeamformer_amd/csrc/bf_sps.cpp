@@ -1,6 +1,5 @@
 // bf_sps.cpp -- single-pulse search behind the DM stage (include/dsabf.h: bf_sps_*; contract and measurements: docs/SINGLE_PULSE.md).
 // The device code is csrc/sps/bf_sps.hip; this file owns the stage's memory, orders its pushes and selects the candidates.
-#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <deque>
@@ -9,8 +8,8 @@
 #include "bf_runtime_internal.h"
 #include "sps/bf_sps_kernels.h"
 
-struct bf_sps {
-    bf_handle* h = nullptr;
+struct bf_sps : bf_stage {
+    bf_sps() : bf_stage("search stage") {}
     int n_dm = 0, dm_first = 0, n_widths = 0, halo = 0, max_t = 0, max_in_flight = 0, baseline = 0, n_beams = 0;
     uint64_t min_samples = 0;
     double threshold = 0;
@@ -38,35 +37,13 @@ struct bf_sps {
     uint64_t last_first_t = 0;
     int last_n_t = 0;
     std::deque<std::pair<int, std::vector<bf_sps_stat>>> window;
-    bf_dm_stream* feeder = nullptr;        // the DM stage this one is attached to
 };
 
-void dsabf::rt::sps_release(bf_sps* s)
-{
-    for (auto& r : s->sets) {
-        if (r.copied) {
-            (void)hipEventSynchronize(r.copied);   // (never recorded: returns at once)
-            (void)hipEventDestroy(r.copied);
-        }
-        if (r.kernels_done) (void)hipEventDestroy(r.kernels_done);
-        (void)hipFree(r.d_peaks);
-        (void)hipFree(r.d_stats);
-        (void)hipHostFree(r.h_peaks);
-        (void)hipHostFree(r.h_stats);
-        r = bf_sps::result_set();
-    }
-    if (s->copy_q) (void)hipStreamDestroy(s->copy_q);
-    for (void* p : {(void*)s->d_tail[0], (void*)s->d_tail[1], (void*)s->d_part_peaks, (void*)s->d_part_stats}) (void)hipFree(p);
-    s->copy_q = nullptr;
-    s->d_tail[0] = s->d_tail[1] = nullptr;
-    s->d_part_peaks = nullptr;
-    s->d_part_stats = nullptr;
-    s->h = nullptr;
-}
+bf_stage* dsabf::rt::as_stage(bf_sps* s) { return s; }
 
 int dsabf::rt::sps_check_attach(const bf_sps* s, const bf_handle* h, int n_dm, int max_rows)
 {
-    if (!s->h) return fail(BF_ERR_STATE, "the handle of this search stage has been destroyed");
+    if (int rc = orphaned(s)) return rc;
     if (s->h != h) return fail(BF_ERR_INVALID, "bf_dm_stream_attach_search: the two stages belong to different handles");
     if (s->n_dm != n_dm) return fail(BF_ERR_INVALID, "bf_dm_stream_attach_search: the search stage has %d trials, the DM stage %d", s->n_dm, n_dm);
     if (s->max_t < max_rows)
@@ -76,7 +53,6 @@ int dsabf::rt::sps_check_attach(const bf_sps* s, const bf_handle* h, int n_dm, i
 }
 
 int dsabf::rt::sps_max_in_flight(const bf_sps* s) { return s->max_in_flight; }
-void dsabf::rt::sps_set_feeder(bf_sps* s, bf_dm_stream* dm) { s->feeder = dm; }
 
 extern "C" {
 
@@ -107,46 +83,27 @@ int bf_sps_create(bf_handle* h, int n_dm, int dm_first, int n_widths, int max_t_
     s->n_beams = h->cfg.n_beams;
     const size_t n_db = (size_t)n_dm * s->n_beams, n_rec = (size_t)n_widths * n_db, tiles = (size_t)dsabf::sps_tiles(max_t_per_push);
     const size_t tail_bytes = n_db * s->halo * sizeof(float);
-    hipError_t e = hipSuccess;
-    for (int k = 0; k < 2 && e == hipSuccess && tail_bytes; k++) {
-        e = hipMalloc((void**)&s->d_tail[k], tail_bytes);
-        if (e == hipSuccess) e = hipMemset(s->d_tail[k], 0, tail_bytes);
-    }
-    if (e == hipSuccess) e = hipMalloc((void**)&s->d_part_peaks, tiles * n_rec * sizeof(bf_sps_peak));
-    if (e == hipSuccess) e = hipMalloc((void**)&s->d_part_stats, tiles * n_db * sizeof(bf_sps_stat));
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&s->copy_q, hipStreamNonBlocking);
+    bf_resources& res = s->res;
+    for (int k = 0; k < 2 && tail_bytes; k++) res.dev(&s->d_tail[k], tail_bytes, true);
+    res.dev(&s->d_part_peaks, tiles * n_rec * sizeof(bf_sps_peak));
+    res.dev(&s->d_part_stats, tiles * n_db * sizeof(bf_sps_stat));
+    res.queue(&s->copy_q);
     s->sets.resize((size_t)max_in_flight);
     for (auto& r : s->sets) {
-        if (e == hipSuccess) e = hipMalloc((void**)&r.d_peaks, n_rec * sizeof(bf_sps_peak));
-        if (e == hipSuccess) e = hipMalloc((void**)&r.d_stats, n_db * sizeof(bf_sps_stat));
-        if (e == hipSuccess) e = hipHostMalloc((void**)&r.h_peaks, n_rec * sizeof(bf_sps_peak), hipHostMallocDefault);
-        if (e == hipSuccess) e = hipHostMalloc((void**)&r.h_stats, n_db * sizeof(bf_sps_stat), hipHostMallocDefault);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&r.kernels_done, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&r.copied, hipEventDisableTiming);
+        res.dev(&r.d_peaks, n_rec * sizeof(bf_sps_peak));
+        res.dev(&r.d_stats, n_db * sizeof(bf_sps_stat));
+        res.host(&r.h_peaks, n_rec * sizeof(bf_sps_peak));
+        res.host(&r.h_stats, n_db * sizeof(bf_sps_stat));
+        res.event(&r.kernels_done);
+        res.event(&r.copied);
     }
-    if (e == hipSuccess) e = hipDeviceSynchronize();   // (the memsets above ran on the null stream: pushes come on non-blocking ones)
-    h->sps_stages.push_back(s);
-    if (e != hipSuccess) {
-        bf_sps_destroy(s);
-        return fail(BF_ERR_DEVICE, "bf_sps_create: %s", hipGetErrorString(e));
-    }
+    res.device_sync();
+    if (int rc = stage_adopt(s, "bf_sps_create")) return rc;
     *out = s;
     return BF_OK;
 }
 
-int bf_sps_destroy(bf_sps* s)
-{
-    if (!s) return BF_OK;
-    if (s->feeder) dm_stream_drop_search(s->feeder);
-    if (s->h) {   // (NULL: the handle went first and took the device memory with it)
-        bf_handle* h = s->h;
-        DeviceScope dev_scope_(h->device);
-        h->sps_stages.erase(std::remove(h->sps_stages.begin(), h->sps_stages.end(), s), h->sps_stages.end());
-        sps_release(s);
-    }
-    delete s;
-    return BF_OK;
-}
+int bf_sps_destroy(bf_sps* s) { return stage_destroy(s); }
 
 int bf_sps_pending(const bf_sps* s) { return s ? (int)(s->n_push - s->n_collected) : BF_ERR_INVALID; }
 
@@ -154,7 +111,7 @@ int bf_sps_push(bf_sps* s, const float* d_chunk, int n_t, uint64_t first_t, void
 {
     if (!s || !d_chunk) return fail(BF_ERR_INVALID, "NULL argument");
     if (n_t <= 0 || n_t > s->max_t) return fail(BF_ERR_INVALID, "n_t must be 1 .. %d (max_t_per_push)", s->max_t);
-    if (!s->h) return fail(BF_ERR_STATE, "the handle of this search stage has been destroyed");
+    if (int rc = orphaned(s)) return rc;
     if (s->n_push - s->n_collected >= (uint64_t)s->max_in_flight)
         return fail(BF_ERR_STATE, "bf_sps_push: %d pushes are uncollected (max_in_flight): bf_sps_collect first", s->max_in_flight);
     bf_handle* h = s->h;
@@ -185,7 +142,7 @@ int bf_sps_collect(bf_sps* s, bf_sps_candidate* out, size_t max_out, size_t* n_o
     *n_out = 0;
     const size_t n_db = (size_t)s->n_dm * s->n_beams;
     if (max_out < n_db) return fail(BF_ERR_INVALID, "bf_sps_collect: room for %zu candidates, a push can give n_dm * n_beams = %zu", max_out, n_db);
-    if (!s->h) return fail(BF_ERR_STATE, "the handle of this search stage has been destroyed");
+    if (int rc = orphaned(s)) return rc;
     if (s->n_collected == s->n_push) return fail(BF_ERR_STATE, "bf_sps_collect: no push is pending");
     bf_handle* h = s->h;
     ON_DEVICE(h);
