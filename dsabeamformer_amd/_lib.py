@@ -13,6 +13,7 @@ BF_NOT_READY = 1
 BF_ERR_INVALID, BF_ERR_DEVICE, BF_ERR_NO_DEVICE, BF_ERR_STATE = -1, -2, -3, -4
 BF_DETECT_CANONICAL, BF_DETECT_FAST, BF_DETECT_CONTRACTED = 0, 1, 2
 BF_CAL_PHASE, BF_CAL_FULL = 0, 1
+BF_SK_DEAD, BF_SK_LOW, BF_SK_HIGH = 1, 2, 4   # cell codes of bf_sk_select (include/dsabf.h)
 
 
 class BfConfig(C.Structure):
@@ -68,6 +69,12 @@ class BfCalOptions(C.Structure):
     """Mirror of ``bf_cal_options`` (include/dsabf.h)."""
 
     _fields_ = [("tol", C.c_double), ("max_iter", C.c_int), ("ref_ant", C.c_int), ("joint_pol", C.c_int)]
+
+
+class BfSkOptions(C.Structure):
+    """Mirror of ``bf_sk_options`` (include/dsabf.h)."""
+
+    _fields_ = [("centre", C.c_double), ("n_sigma", C.c_double), ("max_bad_fraction_ant", C.c_double), ("max_bad_fraction_chan", C.c_double)]
 
 
 class DsabfError(RuntimeError):
@@ -131,6 +138,18 @@ SIGNATURES = {
     "bf_solve_gains_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(BfCalOptions), C.c_void_p, C.c_void_p,
                                         C.c_void_p]),
     "bf_calibrate_weights_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "bf_sk_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "bf_sk_entries": (C.c_size_t, [C.POINTER(BfConfig)]),
+    "bf_sk_default_options": (C.c_int, [C.POINTER(BfSkOptions)]),
+    "bf_sk_select": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.POINTER(BfSkOptions), C.c_void_p, C.c_void_p, C.c_void_p,
+                               C.c_void_p]),
+    "bf_sk_create": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
+    "bf_sk_destroy": (C.c_int, [C.c_void_p]),
+    "bf_sk_push": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "bf_sk_push_block": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "bf_sk_dump": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "bf_sk_collect": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "bf_sk_pending": (C.c_int, [C.c_void_p]),
     "bf_expand_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "bf_gemm_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bf_dedisperse_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-from ._lib import BF_CAL_FULL, BF_CAL_PHASE, BfCalOptions, BfCondOptions, BfConfig, DsabfError, BfSpsCandidate, BfSpsPeak, BfSpsStat, check, load
+from ._lib import BF_CAL_FULL, BF_CAL_PHASE, BfCalOptions, BfCondOptions, BfConfig, BfSkOptions, DsabfError, BfSpsCandidate, BfSpsPeak, BfSpsStat, check, load
 
 
 def debug_config(**over) -> BfConfig:
@@ -141,6 +141,16 @@ class Beamformer(_Owner):
     def corr_entries(self) -> int:
         """bf_corr_entries: n_freq * n_pol * n_ant (n_ant + 1) / 2 complex entries (two int64 each)."""
         return self._lib.bf_corr_entries(C.byref(self.cfg))
+
+    def voltage_moments(self, d_packed, n_units: int, d_moments, accumulate: bool = False, stream: int = 0) -> None:
+        """bf_sk_device (docs/SPECTRAL_KURTOSIS.md): the power moments of n_units gemm-units into d_moments, int64 [freq][pol][ant]{m1, m2}
+        (``sk_entries`` cells), overwritten or -- ``accumulate`` -- added to.  Needs no weights."""
+        check(self._lib.bf_sk_device(self._h, _ptr(d_packed), int(n_units), _ptr(d_moments), int(bool(accumulate)), C.c_void_p(stream)))
+
+    @property
+    def sk_entries(self) -> int:
+        """bf_sk_entries: n_freq * n_pol * n_ant cells (two int64 each)."""
+        return self._lib.bf_sk_entries(C.byref(self.cfg))
 
     def solve_gains(self, d_vis, d_gains, d_info, model=None, flags=None, tol: float = 1e-10, max_iter: int = 200, ref_ant: int = -1,
                     joint_pol: bool = False, stream: int = 0) -> None:
@@ -480,6 +490,68 @@ class Correlator(_Owner):
         n = C.c_uint64()
         check(self._lib.bf_corr_collect(self._c, _ptr(out), C.byref(n)))
         return out, int(n.value)
+
+
+class SpectralKurtosis(_Owner):
+    """bf_sk: the voltage moments as a stage (include/dsabf.h, docs/SPECTRAL_KURTOSIS.md), a twin of ``Correlator``: one int64
+    accumulator on the device that pushes add to and a dump snapshots and zeroes; the stage orders its pushes and dumps itself."""
+    _ptr_attr, _destroy = "_c", "bf_sk_destroy"
+
+    def __init__(self, bf: Beamformer, max_in_flight: int = 2):
+        self._lib = load()
+        self._c = C.c_void_p()
+        self._bf = bf
+        cfg = bf.cfg
+        self.shape = (cfg.n_freq, cfg.n_pol, cfg.n_ant, 2)
+        check(self._lib.bf_sk_create(bf._h, int(max_in_flight), C.byref(self._c)))
+
+    def push(self, d_packed, n_units: int, stream: int = 0) -> None:
+        check(self._lib.bf_sk_push(self._c, _ptr(d_packed), int(n_units), C.c_void_p(stream)))
+
+    def push_block(self, stream_idx: int, slot: int, first_unit: int, n_units: int) -> None:
+        """The gemm-units [first_unit, first_unit + n_units) of ring slot ``slot`` (what enqueue_block reads), on compute queue stream_idx."""
+        check(self._lib.bf_sk_push_block(self._c, int(stream_idx), int(slot), int(first_unit), int(n_units)))
+
+    def dump(self, stream: int = 0) -> None:
+        """Snapshot the accumulator to pinned host memory, then zero it (BF_ERR_STATE beyond max_in_flight uncollected dumps)."""
+        check(self._lib.bf_sk_dump(self._c, C.c_void_p(stream)))
+
+    @property
+    def pending(self) -> int:
+        return self._lib.bf_sk_pending(self._c)
+
+    def collect(self):
+        """Waits for the oldest uncollected dump; returns (int64 array [freq][pol][ant][2] = {m1, m2}, columns per polarisation)."""
+        import numpy as np
+
+        out = np.empty(self.shape, np.int64)
+        n = C.c_uint64()
+        check(self._lib.bf_sk_collect(self._c, _ptr(out), C.byref(n)))
+        return out, int(n.value)
+
+
+def sk_select(moments, M: int, centre: float | None = None, n_sigma: float | None = None, max_bad_fraction_ant: float | None = None,
+              max_bad_fraction_chan: float | None = None):
+    """bf_sk_select (host only): moments int64 [freq][pol][ant][2] over ``M`` columns per polarisation -> (sk float64 [freq][pol][ant],
+    cell uint8 [freq][pol][ant], ant_flags uint8 [ant], chan_flags uint8 [freq]).  Options left None keep bf_sk_default_options."""
+    import numpy as np
+
+    lib = load()
+    mom = np.ascontiguousarray(moments, np.int64)
+    if mom.ndim != 4 or mom.shape[3] != 2:
+        raise ValueError("moments must be [freq][pol][ant][2], not %r" % (mom.shape,))
+    n_freq, n_pol, n_ant = mom.shape[:3]
+    opt = BfSkOptions()
+    check(lib.bf_sk_default_options(C.byref(opt)))
+    for name, v in (("centre", centre), ("n_sigma", n_sigma), ("max_bad_fraction_ant", max_bad_fraction_ant),
+                    ("max_bad_fraction_chan", max_bad_fraction_chan)):
+        if v is not None:
+            setattr(opt, name, float(v))
+    sk = np.empty((n_freq, n_pol, n_ant), np.float64)
+    cell = np.empty((n_freq, n_pol, n_ant), np.uint8)
+    ant_flags, chan_flags = np.empty(n_ant, np.uint8), np.empty(n_freq, np.uint8)
+    check(lib.bf_sk_select(_ptr(mom), int(M), n_freq, n_pol, n_ant, C.byref(opt), _ptr(sk), _ptr(cell), _ptr(ant_flags), _ptr(chan_flags)))
+    return sk, cell, ant_flags, chan_flags
 
 
 def vis_to_square(tri, n_ant: int):

@@ -48,6 +48,16 @@
 //                                                   of gains_file; the geometry comes from vis_file's header (a shard's vis_file.<rank> too).
 //   beam ... -A gains_file                          DEBUG run or observation mode: layer 0 of the last record of gains_file calibrates the
 //                                                   steering weights (conj(g) / |g|) before they are set.
+//   beam -j n_blocks ... -Y moments_file [-J sk_blocks]
+//                                                   the voltage moments (docs/SPECTRAL_KURTOSIS.md): sum |v|^2 and sum |v|^4 per (channel,
+//                                                   polarisation, antenna) of every analysed block, integrated over sk_blocks blocks [1] per
+//                                                   dump, to moments_file.  With -R: every shard its own channels, moments_file.<rank>.
+//   beam -e moments_file -O ant_file [-q chan_file] [-t n_sigma] [-m centre]
+//                                                   select mode, no device: the records of a -Y file summed, the spectral-kurtosis rule
+//                                                   (bf_sk_select, defaults centre 1, 5 sigma) applied, the flagged antennas to ant_file and
+//                                                   the flagged channels to chan_file, both in the -F format (chan_file can be given to -F).
+//   beam -E vis_file -G gains_file -f ant_file     the solver leaves the listed antennas out (their gains are exactly zero);
+//   beam ... -A gains_file -f ant_file              the listed antennas get zero weights.
 //
 // With the reference's `make debug` geometry (default) it generates synthetic point-source voltages on the CPU,
 // streams them through the observation loop and writes bin/data.py (dedispersed beam responses, one row per source)
@@ -101,9 +111,17 @@ int main(int argc, char* argv[])
     bool corr_blocks_given = false;
     std::string solve_vis, solve_gains_path, apply_gains;   // -E / -G: the gain solver on a -V file; -A: gains applied to the weights
     bool solve_joint = false;                               // -P
+    std::string sk_path;            // -Y: where the voltage moments go
+    int sk_blocks = 1;              // -J: analysed blocks integrated per dump
+    bool sk_blocks_given = false;
+    std::string select_path, select_ant_path, select_chan_path;   // -e / -O / -q: flags from a -Y file
+    bf_sk_options sk_opt;           // -t n_sigma, -m centre
+    bf_sk_default_options(&sk_opt);
+    bool sk_sigma_given = false, sk_centre_given = false;
+    std::string ant_flags_path;     // -f: antenna flags for -E or -A
 
     int arg = 0;
-    while ((arg = getopt(argc, argv, "s:g:p:d:o:D:a:c:k:K:j:w:R:r:I:M:N:T:W:Q:S:B:C:i:V:L:E:G:A:n:U:F:zPXuvhH")) != -1) {  // src/beamformer.cu:41-43 (+ -o -D -a -v)
+    while ((arg = getopt(argc, argv, "s:g:p:d:o:D:a:c:k:K:j:w:R:r:I:M:N:T:W:Q:S:B:C:i:V:L:E:G:A:n:U:F:Y:J:e:O:q:t:m:f:zPXuvhH")) != -1) {  // src/beamformer.cu:41-43 (+ -o -D -a -v)
         switch (arg) {
             case 's': sources = optarg; break;                 // :77-89
             case 'g': opt.gpu = atoi(optarg); break;           // :92-100
@@ -138,6 +156,14 @@ int main(int argc, char* argv[])
             case 'G': solve_gains_path = optarg; break;
             case 'A': apply_gains = optarg; break;
             case 'P': solve_joint = true; break;
+            case 'Y': sk_path = optarg; break;
+            case 'J': sk_blocks = atoi(optarg); sk_blocks_given = true; break;
+            case 'e': select_path = optarg; break;
+            case 'O': select_ant_path = optarg; break;
+            case 'q': select_chan_path = optarg; break;
+            case 't': sk_opt.n_sigma = atof(optarg); sk_sigma_given = true; break;
+            case 'm': sk_opt.centre = atof(optarg); sk_centre_given = true; break;
+            case 'f': ant_flags_path = optarg; break;
             case 'u': per_unit = true; break;                   // the reference's launch pattern: one launch per gemm-unit
             case 'v': opt.verbose = true; cfg.verbose = 1; break;
             case 'c': core = atoi(optarg); break;              // :59-65
@@ -180,6 +206,13 @@ int main(int argc, char* argv[])
                              "                         one layer) and written as one record of gains_file; works on a shard's vis_file.<rank> too\n"
                              " -A gains_file           DEBUG run and observation mode: layer 0 of the last record of gains_file calibrates the\n"
                              "                         steering weights (conj(g) / |g|); its NANT / NFREQ / FIRST_CHANNEL must be the run's\n"
+                             " -Y file [-J sk_blocks]  observation mode: the voltage moments -- sum |v|^2 and sum |v|^4 per (channel, polarisation,\n"
+                             "                         antenna) of the analysed blocks, integrated over sk_blocks blocks [1] per dump, to file (with -R:\n"
+                             "                         file.<rank>, each shard its own channels)\n"
+                             " -e moments_file -O ant_file [-q chan_file] [-t n_sigma] [-m centre]   select mode, no device: the records of a -Y file\n"
+                             "                         summed, the spectral-kurtosis rule applied (centre [1] +- n_sigma [5] * 2 / sqrt(columns)); flagged\n"
+                             "                         antennas to ant_file, flagged channels to chan_file, one index per line (chan_file can be given to -F)\n"
+                             " -f ant_file             with -E: the solver leaves the listed antennas out (gains exactly 0); with -A: they get zero weights\n"
                              " -H                      this text\n";
                 return EXIT_SUCCESS;
             default: usage(true, std::cerr); return EXIT_FAILURE;
@@ -258,6 +291,43 @@ int main(int argc, char* argv[])
         fprintf(stderr, "beam: -V (correlator) belongs to the observation mode: give -j n_blocks or -k ring\n");
         return EXIT_FAILURE;
     }
+    const bool observe_mode = junk_blocks >= 0 || !ring_key.empty();
+    if (sk_blocks_given && sk_path.empty()) {
+        fprintf(stderr, "beam: -J (blocks per dump) belongs to the voltage moments: give -Y moments_file\n");
+        return EXIT_FAILURE;
+    }
+    if (sk_blocks_given && sk_blocks < 1) {
+        fprintf(stderr, "beam: -J %d: the moments integrate at least one block per dump\n", sk_blocks);
+        return EXIT_FAILURE;
+    }
+    if (!sk_path.empty() && !observe_mode) {
+        fprintf(stderr, "beam: -Y (voltage moments) belongs to the observation mode: give -j n_blocks or -k ring\n");
+        return EXIT_FAILURE;
+    }
+    if (select_path.empty() && (!select_ant_path.empty() || !select_chan_path.empty() || sk_sigma_given || sk_centre_given)) {
+        fprintf(stderr, "beam: -O / -q / -t / -m belong to the select mode: give -e moments_file\n");
+        return EXIT_FAILURE;
+    }
+    if (!ant_flags_path.empty() && solve_vis.empty() && apply_gains.empty()) {
+        fprintf(stderr, "beam: -f (antenna flags) belongs to the gain solver or to calibrated weights: give -E vis_file or -A gains_file\n");
+        return EXIT_FAILURE;
+    }
+    if (!select_path.empty()) {   // select mode: host only
+        if (observe_mode || !solve_vis.empty() || !apply_gains.empty()) {
+            fprintf(stderr, "beam: -e (select flags) runs nothing else: leave out -j / -k / -E / -A\n");
+            return EXIT_FAILURE;
+        }
+        if (select_ant_path.empty()) {
+            fprintf(stderr, "beam: -e needs -O ant_file (where the antenna flags go)\n");
+            return EXIT_FAILURE;
+        }
+        if (select_moments_file(select_path.c_str(), sk_opt, select_ant_path.c_str(), select_chan_path.empty() ? nullptr : select_chan_path.c_str(),
+                                std::cout) != BF_OK) {
+            fprintf(stderr, "beam: -e %s\n", bf_last_error());
+            return EXIT_FAILURE;
+        }
+        return 0;
+    }
     if (!solve_gains_path.empty() && solve_vis.empty()) {
         fprintf(stderr, "beam: -G (where the gains go) belongs to the gain solver: give -E vis_file\n");
         return EXIT_FAILURE;
@@ -266,6 +336,7 @@ int main(int argc, char* argv[])
         fprintf(stderr, "beam: -P (joint polarisations) belongs to the gain solver: give -E vis_file -G gains_file\n");
         return EXIT_FAILURE;
     }
+    std::vector<uint8_t> ant_flags;   // -f: read before any device is touched, against NANT of the vis file (-E) or of the run (-A)
     if (!solve_vis.empty()) {   // solve mode: no observation of either kind
         if (junk_blocks >= 0 || !ring_key.empty()) {
             fprintf(stderr, "beam: -E (gain solver) runs no observation: leave out -j / -k\n");
@@ -285,6 +356,10 @@ int main(int argc, char* argv[])
             fprintf(stderr, "beam: -E %s\n", why.empty() ? (solve_vis + " is not a file of visibilities").c_str() : why.c_str());
             return EXIT_FAILURE;
         }
+        if (!ant_flags_path.empty() && !read_index_file(ant_flags_path.c_str(), vh.n_ant, &ant_flags, &why)) {
+            fprintf(stderr, "beam: -f %s\n", why.c_str());
+            return EXIT_FAILURE;
+        }
     }
     // -A: read before any device is touched; a DEBUG run has the DEBUG geometry, observation mode a rank's share of the production one
     std::vector<double> gains_layer;
@@ -300,6 +375,13 @@ int main(int argc, char* argv[])
             return EXIT_FAILURE;
         }
         opt.gains = gains_layer.data();
+        if (!ant_flags_path.empty()) {
+            if (!read_index_file(ant_flags_path.c_str(), gcfg.n_ant, &ant_flags, &why)) {
+                fprintf(stderr, "beam: -f %s\n", why.c_str());
+                return EXIT_FAILURE;
+            }
+            opt.ant_flags = ant_flags.data();
+        }
     }
     opt.positions = positions.empty() ? nullptr : positions.c_str();
     opt.directions = directions.empty() ? nullptr : directions.c_str();
@@ -317,7 +399,8 @@ int main(int argc, char* argv[])
 
     if (!solve_vis.empty()) {   // -E / -G: the gain solver on a file of visibilities
         uint64_t n_records = 0;
-        int src = solve_vis_file(solve_vis.c_str(), solve_gains_path.c_str(), solve_joint, opt.device, &n_records, std::cout);
+        int src = solve_vis_file(solve_vis.c_str(), solve_gains_path.c_str(), solve_joint, opt.device, &n_records, std::cout,
+                                 ant_flags.empty() ? nullptr : ant_flags.data());
         if (src != BF_OK) {
             fprintf(stderr, "GPUassert: %s (%d)\n", bf_last_error(), src);
             return EXIT_FAILURE;
@@ -422,6 +505,7 @@ int main(int argc, char* argv[])
         oopt.comm = comm;
         oopt.incoherent_beam = ib_beam;
         oopt.gains = gains_layer.empty() ? nullptr : gains_layer.data();
+        oopt.ant_flags = gains_layer.empty() || ant_flags.empty() ? nullptr : ant_flags.data();
         const bf_config& sink_cfg = comm ? full_cfg : pcfg;
         if (comm && rank != 0) {          // only the gather root has a consumer
             out_ring.clear();
@@ -536,12 +620,24 @@ int main(int argc, char* argv[])
             oopt.corr_blocks = corr_blocks;
             oopt.vis_sink = vsink.get();
         }
+        std::unique_ptr<sk_file_sink> ksink;
+        if (!sk_path.empty()) {   // -Y: every shard measures its own channels
+            if (comm) sk_path += "." + std::to_string(rank);
+            ksink.reset(new sk_file_sink(pcfg, sk_path.c_str(), rank * pcfg.n_freq, opt.gpu));
+            if (!ksink->is_open()) {
+                fprintf(stderr, "beam: could not open %s\n", sk_path.c_str());
+                return EXIT_FAILURE;
+            }
+            oopt.sk_blocks = sk_blocks;
+            oopt.sk_sink = ksink.get();
+        }
         observation_result ores;
         int orc = run_observation(pcfg, oopt, *src, pos.data(), dir.data(), &ores, std::cout);
         if (sink) std::cout << "Wrote " << sink->get_delivered() << " gemm-units of detected powers to " << sink_name << std::endl;
         if (dm_sink) std::cout << "Wrote " << dm_sink->get_times_written() << " dedispersed samples x " << my_trials << " trials to " << dm_path << std::endl;
         if (cand_sink) std::cout << "Wrote " << cand_sink->get_candidates_written() << " candidates to " << cand_path << std::endl;
         if (vsink) std::cout << "Wrote " << vsink->get_dumps_written() << " visibility dumps of " << corr_blocks << " blocks to " << vis_path << std::endl;
+        if (ksink) std::cout << "Wrote " << ksink->get_dumps_written() << " moment dumps of " << sk_blocks << " blocks to " << sk_path << std::endl;
         bf_comm_destroy(comm);
         if (orc != BF_OK) {
             fprintf(stderr, "GPUassert: %s (%d)\n", bf_last_error(), orc);

@@ -1,5 +1,5 @@
 // bf_cal_host.cpp -- host mirror of the gain solver (include/dsabf_host.hpp: gains_file_sink, read_gains_layer, solve_vis_file,
-// set_weights_calibrated; docs/CALIBRATION.md).  The C-ABI's solver and weight calls take device pointers and the C-ABI has no device
+// set_weights_calibrated, and the flag files that feed them: read_index_file, read_moments_sum, select_moments_file; docs/CALIBRATION.md).  The C-ABI's solver and weight calls take device pointers and the C-ABI has no device
 // allocator, so this is the one host-mirror file that allocates device memory itself.
 #include <fcntl.h>
 #include <hip/hip_runtime.h>
@@ -7,6 +7,7 @@
 #include <unistd.h>
 
 #include <cstring>
+#include <fstream>
 #include <iostream>
 #include <map>
 #include <sstream>
@@ -175,7 +176,8 @@ bool read_gains_layer(const char* path, int n_ant, int n_freq, int first_channel
     return true;
 }
 
-int solve_vis_file(const char* vis_path, const char* gains_path, bool joint_pol, int device, uint64_t* n_records, std::ostream& log)
+int solve_vis_file(const char* vis_path, const char* gains_path, bool joint_pol, int device, uint64_t* n_records, std::ostream& log,
+                   const uint8_t* ant_flags)
 {
     record_file_header vh;
     std::string why;
@@ -206,6 +208,9 @@ int solve_vis_file(const char* vis_path, const char* gains_path, bool joint_pol,
     int64_t* d_vis = nullptr;
     double* d_gains = nullptr;
     int32_t* d_info = nullptr;
+    uint8_t* d_flags = nullptr;
+    if (e == hipSuccess && ant_flags) e = mem.alloc(&d_flags, (size_t)cfg.n_ant);
+    if (e == hipSuccess && ant_flags) e = hipMemcpy(d_flags, ant_flags, (size_t)cfg.n_ant, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = mem.alloc(&d_vis, n_vis * sizeof(int64_t));
     if (e == hipSuccess) e = mem.alloc(&d_gains, n_gains * sizeof(double));
     if (e == hipSuccess) e = mem.alloc(&d_info, n_info * sizeof(int32_t));
@@ -222,7 +227,7 @@ int solve_vis_file(const char* vis_path, const char* gains_path, bool joint_pol,
         if (!pread_all(in.fd, rec, sizeof rec, (off_t)at) || !pread_all(in.fd, vis.data(), n_vis * sizeof(int64_t), (off_t)(at + sizeof rec)))
             return set_error(BF_ERR_INVALID, (std::string(vis_path) + ": a record cannot be read").c_str());
         if ((e = hipMemcpy(d_vis, vis.data(), n_vis * sizeof(int64_t), hipMemcpyHostToDevice)) != hipSuccess) return hip_fail("solve_vis_file", e);
-        if ((rc = solve_gains(h, d_vis, nullptr, nullptr, opt, d_gains, d_info)) != BF_OK) return rc;
+        if ((rc = solve_gains(h, d_vis, nullptr, d_flags, opt, d_gains, d_info)) != BF_OK) return rc;
         if ((e = hipMemcpy(gains.data(), d_gains, n_gains * sizeof(double), hipMemcpyDeviceToHost)) != hipSuccess) return hip_fail("solve_vis_file", e);
         if ((e = hipMemcpy(info.data(), d_info, n_info * sizeof(int32_t), hipMemcpyDeviceToHost)) != hipSuccess) return hip_fail("solve_vis_file", e);
         if (!sink.deliver(rec[0], rec[1], gains.data(), info.data())) return set_error(BF_ERR_INVALID, (std::string(gains_path) + ": write failed").c_str());
@@ -234,7 +239,88 @@ int solve_vis_file(const char* vis_path, const char* gains_path, bool joint_pol,
     return BF_OK;
 }
 
-int set_weights_calibrated(bf_handle* h, int device, const int8_t* w, const double* gains_layer, int8_t* w_set)
+bool read_index_file(const char* path, int n, std::vector<uint8_t>* flags, std::string* why)
+{
+    auto no = [&](const std::string& msg) {
+        if (why) *why = std::string(path) + ": " + msg;
+        return false;
+    };
+    std::ifstream in(path);
+    if (!in) return no("could not be read");
+    flags->assign((size_t)n, 0);
+    std::string line;
+    while (std::getline(in, line)) {
+        line = line.substr(0, line.find('#'));
+        const size_t a = line.find_first_not_of(" \t\r");
+        if (a == std::string::npos) continue;
+        char* end = nullptr;
+        const long i = strtol(line.c_str() + a, &end, 10);
+        while (*end == ' ' || *end == '\t' || *end == '\r') end++;
+        if (end == line.c_str() + a || *end || i < 0 || i >= n) return no("'" + line.substr(a) + "' is not an index 0 .. " + std::to_string(n - 1));
+        (*flags)[(size_t)i] = 1;
+    }
+    return true;
+}
+
+bool read_moments_sum(const char* path, record_file_header* header, std::vector<int64_t>* moments, uint64_t* n_columns_per_pol, std::string* why)
+{
+    record_file_header h;
+    if (!read_record_file_header(path, &h, why)) return false;
+    auto no = [&](const std::string& msg) {
+        if (why) *why = std::string(path) + ": " + msg;
+        return false;
+    };
+    if (h.content != "voltage_moments" || h.dtype != "int64") return no("CONTENT " + h.content + " is not a file of voltage moments");
+    const size_t n = (size_t)h.n_freq * h.n_pol * h.n_ant * 2;
+    const size_t rec_bytes = h.record_header_bytes + n * sizeof(int64_t), body = h.file_bytes - h.header_bytes;
+    if (body == 0 || body % rec_bytes) return no("holds no whole record");
+    fd_guard f{::open(path, O_RDONLY)};
+    if (f.fd < 0) return no("cannot be opened");
+    moments->assign(n, 0);
+    std::vector<int64_t> one(n);
+    uint64_t columns = 0;
+    for (size_t at = h.header_bytes; at < h.file_bytes; at += rec_bytes) {
+        uint64_t rec[2];
+        if (!pread_all(f.fd, rec, sizeof rec, (off_t)at) || !pread_all(f.fd, one.data(), n * sizeof(int64_t), (off_t)(at + sizeof rec)))
+            return no("a record cannot be read");
+        for (size_t i = 0; i < n; i++) (*moments)[i] += one[i];
+        columns += rec[1];
+    }
+    *header = h;
+    *n_columns_per_pol = columns;
+    return true;
+}
+
+int select_moments_file(const char* moments_path, const bf_sk_options& opt, const char* ant_path, const char* chan_path, std::ostream& log)
+{
+    record_file_header h;
+    std::vector<int64_t> moments;
+    uint64_t columns = 0;
+    std::string why;
+    if (!read_moments_sum(moments_path, &h, &moments, &columns, &why)) return set_error(BF_ERR_INVALID, why.c_str());
+    std::vector<uint8_t> ant((size_t)h.n_ant), chan((size_t)h.n_freq);
+    const int rc = bf_sk_select(moments.data(), columns, h.n_freq, h.n_pol, h.n_ant, &opt, nullptr, nullptr, ant.data(), chan.data());
+    if (rc != BF_OK) return rc;
+    auto write = [&](const char* path, const char* what, const std::vector<uint8_t>& flags, int offset) {
+        std::ofstream out(path);
+        out << "# " << what << " flagged by spectral kurtosis (beam -e " << moments_path << "): " << columns << " columns per polarisation, centre "
+            << opt.centre << ", " << opt.n_sigma << " sigma\n";
+        for (size_t i = 0; i < flags.size(); i++)
+            if (flags[i]) out << (long)i + offset << "\n";
+        out.close();
+        return !out.fail();
+    };
+    if (!write(ant_path, "antennas", ant, 0)) return set_error(BF_ERR_INVALID, (std::string(ant_path) + " cannot be written").c_str());
+    if (chan_path && !write(chan_path, "channels", chan, h.first_channel)) return set_error(BF_ERR_INVALID, (std::string(chan_path) + " cannot be written").c_str());
+    size_t n_ant = 0, n_chan = 0;
+    for (uint8_t f : ant) n_ant += f != 0;
+    for (uint8_t f : chan) n_chan += f != 0;
+    log << "Spectral kurtosis: " << columns << " columns per polarisation, " << n_ant << " of " << h.n_ant << " antennas and " << n_chan << " of "
+        << h.n_freq << " channels flagged" << std::endl;
+    return BF_OK;
+}
+
+int set_weights_calibrated(bf_handle* h, int device, const int8_t* w, const double* gains_layer, int8_t* w_set, const uint8_t* ant_flags)
 {
     if (!h || !w || !gains_layer) return set_error(BF_ERR_INVALID, "set_weights_calibrated: NULL argument");
     bf_config cfg;
@@ -245,12 +331,15 @@ int set_weights_calibrated(bf_handle* h, int device, const int8_t* w, const doub
     hipError_t e = mem.begin(device);
     int8_t* d_w = nullptr;
     double* d_g = nullptr;
+    uint8_t* d_flags = nullptr;
+    if (e == hipSuccess && ant_flags) e = mem.alloc(&d_flags, (size_t)cfg.n_ant);
+    if (e == hipSuccess && ant_flags) e = hipMemcpy(d_flags, ant_flags, (size_t)cfg.n_ant, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = mem.alloc(&d_w, w_bytes);
     if (e == hipSuccess) e = mem.alloc(&d_g, g_bytes);
     if (e == hipSuccess) e = hipMemcpy(d_w, w, w_bytes, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(d_g, gains_layer, g_bytes, hipMemcpyHostToDevice);
     if (e != hipSuccess) return hip_fail("set_weights_calibrated", e);
-    if ((rc = calibrate_weights(h, d_w, d_g, nullptr, BF_CAL_PHASE, d_w)) != BF_OK) return rc;   // (in place; the null stream)
+    if ((rc = calibrate_weights(h, d_w, d_g, d_flags, BF_CAL_PHASE, d_w)) != BF_OK) return rc;   // (in place; the null stream)
     if ((rc = bf_set_weights_device(h, d_w, nullptr)) != BF_OK) return rc;
     if ((e = hipDeviceSynchronize()) != hipSuccess) return hip_fail("set_weights_calibrated", e);    // d_w is freed on return
     if (w_set && (e = hipMemcpy(w_set, d_w, w_bytes, hipMemcpyDeviceToHost)) != hipSuccess) return hip_fail("set_weights_calibrated", e);

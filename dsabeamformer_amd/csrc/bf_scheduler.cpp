@@ -205,11 +205,13 @@ struct run_resources {
     bf_sps* sps = nullptr;
     bf_cond* cond = nullptr;
     bf_corr* corr = nullptr;
+    bf_sk* sk = nullptr;
     std::vector<void*> pinned;
     ~run_resources()
     {
         if (h) bf_stream_sync(h, -1);
         bf_corr_destroy(corr);
+        bf_sk_destroy(sk);
         bf_sps_destroy(sps);
         bf_cond_destroy(cond);
         bf_dm_stream_destroy(dm);
@@ -334,7 +336,7 @@ int run_debug_observation(const bf_config& cfg, const debug_run_options& opt, de
         generate_fourier_coefficients(cfg.n_beams, cfg.n_ant, cfg.n_freq, 0, opt.gpu, pos.data(), dir.data(),
                                       fourier_coefficients.data());
         if (opt.gains) {
-            rc = set_weights_calibrated(h, opt.device, fourier_coefficients.data(), opt.gains, opt.weights_out);
+            rc = set_weights_calibrated(h, opt.device, fourier_coefficients.data(), opt.gains, opt.weights_out, opt.ant_flags);
             if (rc == BF_OK) log << "Calibrated the weights with one layer of gains" << std::endl;
         } else {
             rc = bf_set_weights(h, fourier_coefficients.data());
@@ -494,6 +496,9 @@ int check_options(const bf_config& cfg, const observation_options& opt)
     if (opt.corr_blocks < 0) return set_error(BF_ERR_INVALID, "run_observation: corr_blocks must be 0 (off) or the blocks per dump");
     if (opt.vis_sink && !opt.corr_blocks) return set_error(BF_ERR_INVALID, "run_observation: a vis_sink needs corr_blocks > 0");
     if (opt.corr_blocks && !opt.block_launch) return set_error(BF_ERR_INVALID, "run_observation: the correlator needs block-granular launches");
+    if (opt.sk_blocks < 0) return set_error(BF_ERR_INVALID, "run_observation: sk_blocks must be 0 (off) or the blocks per dump");
+    if (opt.sk_sink && !opt.sk_blocks) return set_error(BF_ERR_INVALID, "run_observation: a sk_sink needs sk_blocks > 0");
+    if (opt.sk_blocks && !opt.block_launch) return set_error(BF_ERR_INVALID, "run_observation: the voltage moments need block-granular launches");
     if (opt.comm && opt.dm_sink && !is_root) return set_error(BF_ERR_INVALID, "run_observation: only the gather root may have a dm_sink");
     if (opt.dm_split_trials && (!opt.comm || opt.gather_root != BF_GATHER_ROOT_ALL))
         return set_error(BF_ERR_INVALID, "run_observation: dm_split_trials needs a sharded run gathered to every rank (BF_GATHER_ROOT_ALL)");
@@ -540,6 +545,7 @@ int resolve_plan(const bf_config& cfg, const observation_options& opt, launch_pl
     p.dm_rows = p.upl * cfg.n_out_per_gemm;
     if (opt.dm_delays && !p.block_launch) return set_error(BF_ERR_INVALID, "run_observation: the DM stage needs block-granular launches");
     if (opt.corr_blocks && !p.block_launch) return set_error(BF_ERR_INVALID, "run_observation: the correlator needs block-granular launches");
+    if (opt.sk_blocks && !p.block_launch) return set_error(BF_ERR_INVALID, "run_observation: the voltage moments need block-granular launches");
     // a sharded run dedisperses the gathered band (more ranks than trials: the surplus ranks only beamform)
     p.dm_run = opt.dm_delays && p.is_root && p.dm_count > 0;
     return BF_OK;
@@ -587,6 +593,10 @@ struct production_run {
     std::deque<std::pair<uint64_t, uint64_t>> vis_pending;
     std::vector<int64_t> vis;             // what bf_corr_collect returns for one dump
     uint64_t corr_blocks_pushed = 0, vis_dumps = 0;
+    // the voltage moments (sk_blocks > 0): the same bookkeeping
+    std::deque<std::pair<uint64_t, uint64_t>> sk_pending;
+    std::vector<int64_t> moments;         // what bf_sk_collect returns for one dump
+    uint64_t sk_blocks_pushed = 0, sk_dumps = 0;
 
     int create_handle_and_weights(const antenna* pos, const beam_direction* dir)
     {
@@ -597,7 +607,7 @@ struct production_run {
         std::vector<int8_t> fourier_coefficients((size_t)cfg.n_freq * cfg.n_ant * cfg.n_beams * 2);
         generate_fourier_coefficients(cfg.n_beams, cfg.n_ant, cfg.n_freq, opt.rank * cfg.n_freq, opt.gpu, pos, dir, fourier_coefficients.data());
         if (opt.gains) {
-            if ((rc = set_weights_calibrated(dev.h, opt.device, fourier_coefficients.data(), opt.gains)) != BF_OK) return rc;
+            if ((rc = set_weights_calibrated(dev.h, opt.device, fourier_coefficients.data(), opt.gains, nullptr, opt.ant_flags)) != BF_OK) return rc;
             log << "Calibrated the weights with one layer of gains" << std::endl;
         } else if ((rc = bf_set_weights(dev.h, fourier_coefficients.data())) != BF_OK) {
             return rc;
@@ -641,6 +651,10 @@ struct production_run {
         if (opt.corr_blocks > 0) {   // dumps in flight: one per block queued at most, + the one being delivered
             if ((rc = bf_corr_create(dev.h, kMaxTotalSep + 2, &dev.corr)) != BF_OK) return gpu_error(log, rc);
             vis.resize(2 * bf_corr_entries(&cfg));
+        }
+        if (opt.sk_blocks > 0) {
+            if ((rc = bf_sk_create(dev.h, kMaxTotalSep + 2, &dev.sk)) != BF_OK) return gpu_error(log, rc);
+            moments.resize(2 * bf_sk_entries(&cfg));
         }
         if (plan.block_launch)   // the per-queue block buffers are allocated on first use: do that here, not inside the timed loop
             for (int q = 0; q < plan.n_queues_used; q++) {
@@ -697,6 +711,10 @@ struct production_run {
             if (const int rc = bf_corr_dump(dev.corr, nullptr)) return gpu_error(log, rc);
             vis_pending.emplace_back((uint64_t)block_index + 1 - (uint64_t)opt.corr_blocks, (uint64_t)block_index);
         }
+        if (dev.sk && ++sk_blocks_pushed % (uint64_t)opt.sk_blocks == 0) {
+            if (const int rc = bf_sk_dump(dev.sk, nullptr)) return gpu_error(log, rc);
+            sk_pending.emplace_back((uint64_t)block_index + 1 - (uint64_t)opt.sk_blocks, (uint64_t)block_index);
+        }
         return BF_OK;
     }
 
@@ -726,6 +744,7 @@ struct production_run {
         if (rc == BF_OK && plan.dm_run) rc = push_dm_rows(block_index, d_rows, dm_qs);
         // the correlator reads the same resident units on the same queue, behind the detect launch and what follows it
         if (rc == BF_OK && dev.corr) rc = bf_corr_push_block(dev.corr, q, gpu_block, first, upl);
+        if (rc == BF_OK && dev.sk) rc = bf_sk_push_block(dev.sk, q, gpu_block, first, upl);   // and so do the voltage moments
         return rc == BF_OK ? BF_OK : gpu_error(log, rc);
     }
 
@@ -801,6 +820,18 @@ struct production_run {
                 return BF_ERR_STATE;
             }
         }
+        while (!sk_pending.empty() && sk_pending.front().second < blocks_analyzed) {
+            const uint64_t first_block = sk_pending.front().first;
+            sk_pending.pop_front();
+            uint64_t n_columns = 0;
+            const int rc = bf_sk_collect(dev.sk, moments.data(), &n_columns);
+            if (rc != BF_OK) return gpu_error(log, rc);
+            sk_dumps++;
+            if (opt.sk_sink && !opt.sk_sink->deliver(first_block, n_columns, moments.data(), moments.size())) {
+                log << "ERROR: moments sink failed at block " << first_block << std::endl;
+                return BF_ERR_STATE;
+            }
+        }
         for (; opt.sink && sink_committed < blocks_analyzed * (uint64_t)cfg.n_gemms_per_block; sink_committed++)
             if (!opt.sink->commit(sink_committed)) {
                 log << "ERROR: detected sink failed at gemm-unit " << sink_committed << std::endl;
@@ -867,6 +898,7 @@ int run_observation(const bf_config& cfg, const observation_options& opt, block_
     if (opt.dm_sink) opt.dm_sink->close();
     if (opt.sps_sink) opt.sps_sink->close();
     if (opt.vis_sink) opt.vis_sink->close();
+    if (opt.sk_sink) opt.sk_sink->close();
     const uint64_t chunks = obs_state.get_current_transfer_gemm() * cfg.n_out_per_gemm;  // :552
     const double rate = (double)source.get_block_size() * obs_state.get_blocks_transfer_queue() / ms / 1e6;  // :554
     closing_report(log, ms, chunks, ms / (chunks ? chunks : 1), rate, run.plan.block_launch ? "bf_enqueue_block" : kUnitLaunchPattern);
@@ -881,6 +913,7 @@ int run_observation(const bf_config& cfg, const observation_options& opt, block_
         res->dm_chunks = run.dm_chunks;
         res->sps_candidates = run.sps_candidates;
         res->vis_dumps = run.vis_dumps;
+        res->sk_dumps = run.sk_dumps;
         res->cond_masked = run.cond_masked_channels();
     }
     if (run.plan.dm_run)
@@ -899,6 +932,9 @@ int run_observation(const bf_config& cfg, const observation_options& opt, block_
     if (opt.incoherent_beam >= 0) log << "Incoherent beam: in beam column " << opt.incoherent_beam << " of the detected stream" << std::endl;
     if (run.dev.corr)
         log << "Correlator: " << run.vis_dumps << " dumps of " << opt.corr_blocks << " blocks each (an incomplete integration at the end is dropped)"
+            << std::endl;
+    if (run.dev.sk)
+        log << "Voltage moments: " << run.sk_dumps << " dumps of " << opt.sk_blocks << " blocks each (an incomplete integration at the end is dropped)"
             << std::endl;
     if (run.dev.sps)
         log << "Single-pulse search: boxcar widths 1 .. " << (1 << (opt.sps_widths - 1)) << ", " << run.sps_candidates << " candidates at S/N >= "

@@ -319,6 +319,43 @@ void vis_file_sink::close()
     fd = -1;
 }
 
+sk_file_sink::sk_file_sink(const bf_config& cfg, const char* path, int first_channel, int gpu)
+{
+    fd = ::open(path, O_CREAT | O_TRUNC | O_WRONLY, 0644);
+    if (fd < 0) return;
+    char header[kHeaderBytes];
+    ::memset(header, 0, sizeof(header));
+    ::snprintf(header, sizeof(header),
+               "HDR_VERSION 1.0\nHDR_SIZE %zu\nINSTRUMENT DSA\nCONTENT voltage_moments\nDTYPE int64\nENDIAN little\n"
+               "LAYOUT freq,pol,ant,m1m2\nRECORD_HEADER_BYTES %zu\nNANT %d\nNPOL %d\nNFREQ %d\n"
+               "FIRST_CHANNEL %d\nN_OUTPUTS_PER_GEMM %d\nN_GEMMS_PER_BLOCK %d\nN_AVERAGING %d\nGPU %d\n",
+               kHeaderBytes, kRecordBytes, cfg.n_ant, cfg.n_pol, cfg.n_freq, first_channel, cfg.n_out_per_gemm, cfg.n_gemms_per_block, cfg.n_avg, gpu);
+    if (!pwrite_all(fd, header, sizeof(header), 0) || ::lseek(fd, (off_t)kHeaderBytes, SEEK_SET) < 0) {
+        ::close(fd);
+        fd = -1;
+    }
+}
+
+sk_file_sink::~sk_file_sink() { close(); }
+
+bool sk_file_sink::deliver(uint64_t first_block, uint64_t n_columns_per_pol, const int64_t* moments, size_t n_int64)
+{
+    if (fd < 0) return false;
+    const uint64_t rec[2] = {first_block, n_columns_per_pol};
+    static_assert(sizeof rec == kRecordBytes, "the record header is two uint64");
+    if (!write_all(fd, reinterpret_cast<const char*>(rec), sizeof rec) ||
+        !write_all(fd, reinterpret_cast<const char*>(moments), n_int64 * sizeof(int64_t)))
+        return false;
+    dumps++;
+    return true;
+}
+
+void sk_file_sink::close()
+{
+    if (fd >= 0) ::close(fd);
+    fd = -1;
+}
+
 dm_ring_sink::dm_ring_sink(const bf_config& cfg, int n_freq_total, int n_dm, int max_delay, int max_rows, const char* ring_name,
                            uint64_t ring_blocks, int gpu, int first_trial)
     : name(ring_name ? ring_name : "")

@@ -307,6 +307,27 @@ def read_vis_file(path: str):
     return hdr, dumps
 
 
+MOMENTS_LAYOUT = "freq,pol,ant,m1m2"
+
+
+def read_moments_file(path: str):
+    """Parse a dsabf::sk_file_sink file (docs/SPECTRAL_KURTOSIS.md): returns (header dict, list of (first_block, n_columns_per_pol,
+    int64 array [n_freq][n_pol][n_ant][2] = {m1, m2}) per dump)."""
+    raw = open(path, "rb").read()
+    text = raw[:DETECTED_HEADER_BYTES].split(b"\0", 1)[0].decode()
+    hdr = dict(line.split(None, 1) for line in text.splitlines() if line.strip())
+    assert hdr["CONTENT"] == "voltage_moments" and hdr["DTYPE"] == "int64" and hdr["LAYOUT"] == MOMENTS_LAYOUT, hdr
+    shape = (int(hdr["NFREQ"]), int(hdr["NPOL"]), int(hdr["NANT"]), 2)
+    n = shape[0] * shape[1] * shape[2] * 2
+    at, rec, dumps = int(hdr["HDR_SIZE"]), int(hdr["RECORD_HEADER_BYTES"]), []
+    while at < len(raw):
+        first_block, n_columns = (int(v) for v in np.frombuffer(raw, "<u8", 2, at))
+        at += rec
+        dumps.append((first_block, n_columns, np.frombuffer(raw, "<i8", n, at).reshape(shape)))
+        at += 8 * n
+    return hdr, dumps
+
+
 GAINS_LAYOUT = "pol,freq,ant,reim"
 
 

@@ -325,6 +325,71 @@ int bf_solve_gains_device(bf_handle *h, const int64_t *d_vis, const double *d_mo
 int bf_calibrate_weights_device(bf_handle *h, const int8_t *d_w_in, const double *d_gains_layer, const uint8_t *d_flags, int mode,
                                 int8_t *d_w_out, void *hip_stream);
 
+/* ---- Voltage moments and spectral kurtosis (docs/SPECTRAL_KURTOSIS.md) --------------------------------------------------------
+ * Reads what the loop's kernels read, src/beamformer.cu:454-488 (the packed voltages of the resident gemm-units), and produces what
+ * the calibration path above takes and nothing else here makes: antenna flags.  Per (antenna, channel, polarisation) cell two power
+ * moments of the voltages, S1 = sum |v|^2 and S2 = sum |v|^4, give the spectral-kurtosis estimator: ~1 for Gaussian noise, ~0 for a
+ * constant-envelope carrier, > 1 for intermittent interference; S1 == 0 is a dead input.
+ * Input: packed [unit][freq][time][ant], one byte per complex sample, re in the high nibble and im in the low nibble, both two's
+ * complement, time = n_out_per_gemm * n_pol * n_avg; polarisation order as for the correlator: column c of a unit belongs to
+ * polarisation c % n_pol.  With p = re^2 + im^2 (0 ... 128)
+ *   M1[f][pol][a] = sum over the units and the columns c = pol (mod n_pol) of p          M2[f][pol][a] = the same sum of p^2
+ * stored as [freq][pol][ant]{m1, m2}, two int64 per cell; bf_sk_entries(cfg) = n_freq * n_pol * n_ant cells.  The sums are exact
+ * integers, so their order is free and the result is bit-equal to a numpy restatement (tests/support/sk_oracle.py) for every
+ * geometry and launch path.  Known answer: the bytes 0xD7 0x25 0xA8 0x70 as four columns of one antenna with n_pol = 1 give
+ * M1 = 58 + 29 + 100 + 49 = 236 and M2 = 58^2 + 29^2 + 100^2 + 49^2 = 16606.
+ * Bounds: a call is defined for N < 2^24 columns per polarisation, N = n_units * n_out_per_gemm * n_avg (the correlator's bound:
+ * M1 <= 128 * N fits int32; p^2 <= 2^14, so the kernel widens its int32 partials of M2 before 2^17 columns), for any n_ant % 4 == 0
+ * up to 2048 (the output is linear in n_ant: the correlator's 256 do not apply) and n_pol <= 64.  Beyond them every entry point
+ * below returns BF_ERR_INVALID with a message and launches nothing.
+ * bf_sk_device: d_packed as for bf_beamform_device (16-byte aligned) -> d_moments (device, bf_sk_entries(cfg) * 2 int64, 8-byte
+ *   aligned), overwritten (accumulate == 0) or added to (accumulate != 0).  Asynchronous on hip_stream; needs no weights; leaves
+ *   the caller's current device as found.
+ * bf_sk_select: a pure host function in fp64, one rounding per operation in exactly this order (it touches no device).  For M =
+ *   n_columns_per_pol >= 2 and per cell with moments m1, m2:
+ *     m1 == 0 -> sk = 0.0, cell code BF_SK_DEAD
+ *     else       r = ((double)M * (double)m2) / ((double)m1 * (double)m1)        sk = ((double)(M + 1) / (double)(M - 1)) * (r - 1.0)
+ *                half_width = n_sigma * 2.0 / sqrt((double)M)
+ *                code |= BF_SK_LOW if sk < centre - half_width                   code |= BF_SK_HIGH if sk > centre + half_width
+ *   Antenna a is flagged when (double)bad_a > max_bad_fraction_ant * (double)(n_freq * n_pol), bad_a its cells with a non-zero code;
+ *   channel f when the bad cells of the UNFLAGGED antennas at f satisfy (double)bad_f > max_bad_fraction_chan * (double)(n_good_ant *
+ *   n_pol), and always when no antenna is unflagged.  Outputs, each may be NULL: sk double [freq][pol][ant], cell uint8
+ *   [freq][pol][ant], ant_flags uint8 [ant] (what bf_solve_gains_device and bf_calibrate_weights_device take as d_flags),
+ *   chan_flags uint8 [freq] (what bf_cond_set_mask takes).  opt NULL: the defaults.  M < 2 or moments NULL: BF_ERR_INVALID.
+ *   bf_sk_default_options: centre 1.0, n_sigma 5.0, both fractions 0.5 -- conventions, not measurements: 4-bit quantisation moves
+ *   the centre (docs/SPECTRAL_KURTOSIS.md), an operator takes it from a clean moments file of their own levels.
+ * A bf_sk is the measurement as a STAGE, a twin of bf_corr: one int64 accumulator on the device, a column count and max_in_flight
+ *   pinned result sets.  bf_sk_push adds n_units gemm-units at d_packed, asynchronously on hip_stream; bf_sk_push_block the units
+ *   [first_unit, first_unit + n_units) of ring slot `slot` on compute queue stream_idx, behind whatever that queue holds.
+ *   bf_sk_dump snapshots the accumulator into the next pinned set and zeroes it, on a copy queue of the stage (hip_stream is not
+ *   held).  The stage orders its pushes and dumps itself, whichever queues they are issued on.  A dump beyond max_in_flight
+ *   uncollected ones returns BF_ERR_STATE before it queues anything.  bf_sk_collect waits for the OLDEST uncollected dump and copies
+ *   its moments to `out` (host, bf_sk_entries * 2 int64) and the columns per polarisation it integrated to *n_columns_per_pol (may
+ *   be NULL); nothing pending: BF_ERR_STATE.  bf_sk_pending: dumps not yet collected.  A handle that goes first releases the device
+ *   memory; the stage then answers BF_ERR_STATE and can still be destroyed. */
+typedef struct {
+    double centre;
+    double n_sigma;
+    double max_bad_fraction_ant;
+    double max_bad_fraction_chan;
+} bf_sk_options;
+#define BF_SK_DEAD 1
+#define BF_SK_LOW 2
+#define BF_SK_HIGH 4
+int bf_sk_device(bf_handle *h, const void *d_packed, int n_units, int64_t *d_moments, int accumulate, void *hip_stream);
+size_t bf_sk_entries(const bf_config *cfg);
+int bf_sk_default_options(bf_sk_options *o);
+int bf_sk_select(const int64_t *moments, uint64_t n_columns_per_pol, int n_freq, int n_pol, int n_ant, const bf_sk_options *opt, double *sk,
+                 uint8_t *cell, uint8_t *ant_flags, uint8_t *chan_flags);
+typedef struct bf_sk bf_sk;
+int bf_sk_create(bf_handle *h, int max_in_flight, bf_sk **out);
+int bf_sk_destroy(bf_sk *c);
+int bf_sk_push(bf_sk *c, const void *d_packed, int n_units, void *hip_stream);
+int bf_sk_push_block(bf_sk *c, int stream_idx, int slot, int first_unit, int n_units);
+int bf_sk_dump(bf_sk *c, void *hip_stream);
+int bf_sk_collect(bf_sk *c, int64_t *out, uint64_t *n_columns_per_pol);
+int bf_sk_pending(const bf_sk *c);
+
 /* a1 alone (expand_input, src/beamformer.cuh:66-109): nbytes packed bytes -> 2*nbytes int8 (re, im pairs in
  * order).  nbytes must be a multiple of 16, pointers 16-byte aligned. */
 int bf_expand_device(bf_handle *h, const void *d_in, size_t nbytes, void *d_out, void *hip_stream);

@@ -205,6 +205,7 @@ struct debug_run_options {
     // -A: one layer of gains, host [freq][ant]{re, im} (read_gains_layer): the steering weights are multiplied by conj(g) / |g| before
     // they are set (set_weights_calibrated).  weights_out (optional, host, the size of the weight array) receives what was set.
     const double* gains = nullptr;
+    const uint8_t* ant_flags = nullptr;   // -f with -A: uint8 [n_ant], flagged antennas get zero weights (needs gains)
     int8_t* weights_out = nullptr;
 };
 struct debug_run_result {
@@ -624,6 +625,38 @@ public:
     }
 };
 
+// ---- The voltage moments inside the loop (include/dsabf.h: bf_sk_*; docs/SPECTRAL_KURTOSIS.md) ---------------------------------
+// With observation_options::sk_blocks > 0 run_observation creates a bf_sk and treats it exactly as the correlator above: a push per
+// launch on the launch's queue, a dump after every sk_blocks-th analysed block, each dump handed to a sk_sink once that block's
+// analysis event has fired.
+struct sk_sink {
+    virtual ~sk_sink() {}
+    // one integration: blocks first_block .. first_block + sk_blocks - 1, n_columns_per_pol columns per polarisation,
+    // moments = int64 [freq][pol][ant]{m1, m2} (n_int64 values)
+    virtual bool deliver(uint64_t first_block, uint64_t n_columns_per_pol, const int64_t* moments, size_t n_int64) = 0;
+    virtual void close() {}
+};
+
+// File: the 4096-byte ASCII header (`KEY value` lines, NUL padded: CONTENT voltage_moments, DTYPE int64, NANT, NPOL, NFREQ,
+// FIRST_CHANNEL, LAYOUT freq,pol,ant,m1m2), then one record per dump: uint64 first_block, uint64 n_columns_per_pol, the entries
+// (little-endian int64).
+class sk_file_sink : public sk_sink {
+    int fd = -1;
+    uint64_t dumps = 0;
+
+public:
+    static constexpr size_t kHeaderBytes = 4096;
+    static constexpr size_t kRecordBytes = 16;
+    sk_file_sink(const bf_config& cfg, const char* path, int first_channel, int gpu);
+    ~sk_file_sink() override;
+    sk_file_sink(const sk_file_sink&) = delete;
+    sk_file_sink& operator=(const sk_file_sink&) = delete;
+    bool is_open() const { return fd >= 0; }
+    bool deliver(uint64_t first_block, uint64_t n_columns_per_pol, const int64_t* moments, size_t n_int64) override;
+    void close() override;
+    uint64_t get_dumps_written() const { return dumps; }
+};
+
 // ---- The gain solver (include/dsabf.h: bf_solve_gains_device, bf_calibrate_weights_device; docs/CALIBRATION.md) ----------------
 // Thin wrappers: device pointers in, asynchronous on `stream`, the C-ABI's return codes.
 inline int solve_gains(bf_handle* h, const int64_t* d_vis, const double* d_model, const uint8_t* d_flags, const bf_cal_options& opt, double* d_gains,
@@ -672,10 +705,24 @@ bool read_record_file_header(const char* path, record_file_header* out, std::str
 bool read_gains_layer(const char* path, int n_ant, int n_freq, int first_channel, std::vector<double>* layer, std::string* why);
 // `beam -E vis_file -G gains_file [-P]`: every record of a vis_file_sink file uploaded, solved with the all-ones model and the default
 // options (joint_pol as given) and written as one gains record; the geometry comes from the file's header.
-int solve_vis_file(const char* vis_path, const char* gains_path, bool joint_pol, int device, uint64_t* n_records, std::ostream& log);
+// ant_flags (optional, host, uint8 [NANT of the file]; `beam -f`): non-zero antennas are left out, their gains are exactly (0, 0);
+// ref_ant stays -1, the first unflagged antenna.
+int solve_vis_file(const char* vis_path, const char* gains_path, bool joint_pol, int device, uint64_t* n_records, std::ostream& log,
+                   const uint8_t* ant_flags = nullptr);
 // Weights `w` (host, the layout of bf_set_weights) times conj(g) / |g| of one layer of gains (host, [freq][ant]{re, im}), on the device
 // (bf_calibrate_weights_device, BF_CAL_PHASE), then set on the handle (bf_set_weights_device); w_set (optional, host) receives them.
-int set_weights_calibrated(bf_handle* h, int device, const int8_t* w, const double* gains_layer, int8_t* w_set = nullptr);
+// ant_flags (optional, host, uint8 [n_ant]): flagged antennas get zero weights.
+int set_weights_calibrated(bf_handle* h, int device, const int8_t* w, const double* gains_layer, int8_t* w_set = nullptr,
+                           const uint8_t* ant_flags = nullptr);
+// An index file in the format of `beam -F` (one index per line, # comments) -> flags[n] (1 at every index listed).  false + *why if the
+// file cannot be read or holds anything but indices 0 .. n - 1.  No device is touched.
+bool read_index_file(const char* path, int n, std::vector<uint8_t>* flags, std::string* why);
+// The moments file of a sk_file_sink (`beam -Y`): its records SUMMED -- the moments add, and so do the columns per polarisation.
+// false + *why if it is not such a file or holds no whole record.  No device is touched.
+bool read_moments_sum(const char* path, record_file_header* header, std::vector<int64_t>* moments, uint64_t* n_columns_per_pol, std::string* why);
+// `beam -e moments_file -O ant_file [-q chan_file]`: bf_sk_select on the summed records; the flagged antenna indices to ant_path and (if
+// given) the flagged channel indices, offset by the file's FIRST_CHANNEL, to chan_path, both in the `-F` format.  No device is touched.
+int select_moments_file(const char* moments_path, const bf_sk_options& opt, const char* ant_path, const char* chan_path, std::ostream& log);
 
 struct observation_options {
     int gpu = 0;          // -g
@@ -747,8 +794,14 @@ struct observation_options {
     // sharded run every rank correlates its own channels and has a sink of its own; the gather is untouched.
     int corr_blocks = 0;
     dsabf::vis_sink* vis_sink = nullptr;
+    // The voltage moments (docs/SPECTRAL_KURTOSIS.md; needs block_launch): sk_blocks = analysed blocks integrated per dump, 0 = off.
+    // Every dump goes to sk_sink (may be NULL: the stage still runs); an incomplete integration at the end of the run is dropped.  On a
+    // sharded run every rank measures its own channels and has a sink of its own.
+    int sk_blocks = 0;
+    dsabf::sk_sink* sk_sink = nullptr;
     // -A: one layer of gains for THIS rank's channels, host [freq][ant]{re, im}: as debug_run_options::gains.
     const double* gains = nullptr;
+    const uint8_t* ant_flags = nullptr;   // -f with -A: uint8 [n_ant], flagged antennas get zero weights (needs gains)
 };
 struct observation_result {
     float observation_time_ms = 0;
@@ -761,6 +814,7 @@ struct observation_result {
     uint64_t dm_chunks = 0;         // chunks handed to dm_sink
     uint64_t sps_candidates = 0;    // candidates the search stage found (sps_widths > 0)
     uint64_t vis_dumps = 0;         // integrations the correlator dumped (corr_blocks > 0)
+    uint64_t sk_dumps = 0;          // integrations the moments stage dumped (sk_blocks > 0)
     int cond_masked = -1;           // channels the conditioner masked in the last push (cond_baseline > 0 and a block analysed), else -1
 };
 // The reference's production main() loop on top of the C-ABI.  pos/dir: antenna positions and beam directions.
