@@ -14,6 +14,7 @@ BF_ERR_INVALID, BF_ERR_DEVICE, BF_ERR_NO_DEVICE, BF_ERR_STATE = -1, -2, -3, -4
 BF_DETECT_CANONICAL, BF_DETECT_FAST, BF_DETECT_CONTRACTED = 0, 1, 2
 BF_CAL_PHASE, BF_CAL_FULL = 0, 1
 BF_SK_DEAD, BF_SK_LOW, BF_SK_HIGH = 1, 2, 4   # cell codes of bf_sk_select (include/dsabf.h)
+BF_STOKES_MAX_BEAMS = 16
 
 
 class BfConfig(C.Structure):
@@ -150,6 +151,16 @@ SIGNATURES = {
     "bf_sk_dump": (C.c_int, [C.c_void_p, C.c_void_p]),
     "bf_sk_collect": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
     "bf_sk_pending": (C.c_int, [C.c_void_p]),
+    "bf_stokes_entries": (C.c_size_t, [C.POINTER(BfConfig), C.c_int, C.c_int]),
+    "bf_stokes_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "bf_stokes_destroy": (C.c_int, [C.c_void_p]),
+    "bf_stokes_set_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_int]),
+    "bf_stokes_set_weights_device": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_void_p]),
+    "bf_stokes_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "bf_stokes_push": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "bf_stokes_push_block": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "bf_stokes_collect": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
+    "bf_stokes_pending": (C.c_int, [C.c_void_p]),
     "bf_expand_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "bf_gemm_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bf_dedisperse_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

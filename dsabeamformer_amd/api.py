@@ -530,6 +530,71 @@ class SpectralKurtosis(_Owner):
         return out, int(n.value)
 
 
+class StokesBeams(_Owner):
+    """bf_stokes: full-Stokes follow-up beams as a stage (include/dsabf.h, docs/STOKES.md).  For up to 16 beams picked from a weight
+    array in the layout of ``set_weights`` it forms I, Q, U, V as exact int64 over windows of ``n_int`` samples (None: n_avg, the
+    detected stream's resolution; 1: the voltages' own) from the packed voltages the beamformer reads."""
+    _ptr_attr, _destroy = "_c", "bf_stokes_destroy"
+
+    def __init__(self, bf: Beamformer, n_int: int | None = None, max_in_flight: int = 2):
+        self._lib = load()
+        self._c = C.c_void_p()
+        self._bf = bf
+        self.cfg = bf.cfg
+        self.n_int = int(bf.cfg.n_avg if n_int is None else n_int)
+        self.n_sel = 0
+        self._pushed = []   # beams selected at each uncollected push, oldest first
+        check(self._lib.bf_stokes_create(bf._h, self.n_int, int(max_in_flight), C.byref(self._c)))
+
+    def set_weights(self, w, beams, stream: int = 0) -> None:
+        """w: int8 [freq][ant][beam][2] as a host numpy array (bf_stokes_set_weights, returns when the copy has run) or a device tensor
+        (bf_stokes_set_weights_device, asynchronous on ``stream``); beams: the indices to follow, in the order of the output."""
+        sel = [int(b) for b in beams]
+        arr = (C.c_int * max(len(sel), 1))(*sel)
+        if hasattr(w, "data_ptr") and getattr(w, "is_cuda", False):
+            check(self._lib.bf_stokes_set_weights_device(self._c, _ptr(w), arr, len(sel), C.c_void_p(stream)))
+        else:
+            check(self._lib.bf_stokes_set_weights(self._c, _ptr(w), arr, len(sel)))
+        self.n_sel = len(sel)
+
+    @property
+    def entries(self) -> int:
+        """bf_stokes_entries at the beams now selected: T * n_freq * K cells (four int64 each) per gemm-unit; 0 before set_weights."""
+        return self._lib.bf_stokes_entries(C.byref(self.cfg), self.n_sel, self.n_int)
+
+    def compute(self, d_packed, n_units: int, d_out, stream: int = 0) -> None:
+        """bf_stokes_device: the kernel alone into d_out (device int64, n_units * entries * 4), asynchronously on ``stream``."""
+        check(self._lib.bf_stokes_device(self._c, _ptr(d_packed), int(n_units), _ptr(d_out), C.c_void_p(stream)))
+
+    def push(self, d_packed, n_units: int, stream: int = 0) -> None:
+        check(self._lib.bf_stokes_push(self._c, _ptr(d_packed), int(n_units), C.c_void_p(stream)))
+        self._pushed.append(self.n_sel)
+
+    def push_block(self, stream_idx: int, slot: int, first_unit: int, n_units: int) -> None:
+        """The gemm-units [first_unit, first_unit + n_units) of ring slot ``slot`` (what enqueue_block reads), on compute queue stream_idx."""
+        check(self._lib.bf_stokes_push_block(self._c, int(stream_idx), int(slot), int(first_unit), int(n_units)))
+        self._pushed.append(self.n_sel)
+
+    @property
+    def pending(self) -> int:
+        return self._lib.bf_stokes_pending(self._c)
+
+    def collect(self):
+        """Waits for the oldest uncollected push; returns its int64 array [unit][t][freq][k][4] = {I, Q, U, V}."""
+        import numpy as np
+
+        if not self._pushed:
+            check(self._lib.bf_stokes_collect(self._c, _ptr(np.empty(4, np.int64)), None))   # (raises BF_ERR_STATE: nothing pending)
+        k = self._pushed[0]
+        cfg = self.cfg
+        T = cfg.n_out_per_gemm * cfg.n_avg // self.n_int
+        out = np.empty((cfg.n_gemms_per_block, T, cfg.n_freq, k, 4), np.int64)
+        n = C.c_int()
+        check(self._lib.bf_stokes_collect(self._c, _ptr(out), C.byref(n)))
+        self._pushed.pop(0)
+        return out[:n.value].copy()
+
+
 def sk_select(moments, M: int, centre: float | None = None, n_sigma: float | None = None, max_bad_fraction_ant: float | None = None,
               max_bad_fraction_chan: float | None = None):
     """bf_sk_select (host only): moments int64 [freq][pol][ant][2] over ``M`` columns per polarisation -> (sk float64 [freq][pol][ant],

@@ -6,8 +6,8 @@ kernel_build_id() identifies the kernels that the bench line and the counter sum
 directly under csrc/.  The single-pulse search stage (csrc/sps/, docs/SINGLE_PULSE.md) is not among them -- it is compiled with
 the same FLAGS into the same library, but its device code lives in a directory of its own and does not enter the id.  The same
 holds for the incoherent beam (csrc/ib/, docs/INCOHERENT_BEAM.md), the correlator (csrc/corr/, docs/CORRELATOR.md), the gain
-solver (csrc/cal/, docs/CALIBRATION.md), the conditioning stage (csrc/cond/, docs/CONDITIONING.md) and the voltage moments
-(csrc/sk/, docs/SPECTRAL_KURTOSIS.md).
+solver (csrc/cal/, docs/CALIBRATION.md), the conditioning stage (csrc/cond/, docs/CONDITIONING.md), the voltage moments
+(csrc/sk/, docs/SPECTRAL_KURTOSIS.md) and the full-Stokes follow-up beams (csrc/stokes/, docs/STOKES.md).
 """
 from __future__ import annotations
 
@@ -72,7 +72,8 @@ def sources() -> list[str]:
     """Sources of libdsabf.so (everything under csrc/ except the CLI driver)."""
     return sorted(p for p in glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.cpp")) + glob.glob(os.path.join(SPS, "*.hip")) +
                   glob.glob(os.path.join(IB, "*.hip")) + glob.glob(os.path.join(CORR, "*.hip")) + glob.glob(os.path.join(CAL, "*.hip")) +
-                  glob.glob(os.path.join(COND, "*.hip")) + glob.glob(os.path.join(SK, "*.hip"))
+                  glob.glob(os.path.join(COND, "*.hip")) + glob.glob(os.path.join(SK, "*.hip")) +
+                  glob.glob(os.path.join(STOKES, "*.hip"))
                   if os.path.abspath(p) not in [os.path.abspath(m) for m in MAINS.values()])
 
 
@@ -85,6 +86,7 @@ CORR = os.path.join(CSRC, "corr")                   # device code of the correla
 CAL = os.path.join(CSRC, "cal")                     # device code of the gain solver: the same
 COND = os.path.join(CSRC, "cond")                   # device code of the conditioning stage: the same
 SK = os.path.join(CSRC, "sk")                       # device code of the voltage moments: the same
+STOKES = os.path.join(CSRC, "stokes")               # device code of the full-Stokes follow-up beams: the same
 
 
 def kernel_build_id() -> str:
@@ -113,6 +115,7 @@ def _headers() -> list[str]:
     """Every header a source may include: a newer one makes the library, and every object, stale."""
     return glob.glob(os.path.join(CSRC, "*.h*")) + glob.glob(os.path.join(CSRC, "*.inc")) + glob.glob(os.path.join(SPS, "*.h")) + glob.glob(os.path.join(IB, "*.h")) + \
         glob.glob(os.path.join(CORR, "*.h")) + glob.glob(os.path.join(CAL, "*.h")) + glob.glob(os.path.join(COND, "*.h")) + glob.glob(os.path.join(SK, "*.h")) + \
+        glob.glob(os.path.join(STOKES, "*.h")) + \
         glob.glob(os.path.join(ROOT, "include", "*.h*"))
 
 

@@ -56,6 +56,10 @@
 //                                                   select mode, no device: the records of a -Y file summed, the spectral-kurtosis rule
 //                                                   (bf_sk_select, defaults centre 1, 5 sigma) applied, the flagged antennas to ant_file and
 //                                                   the flagged channels to chan_file, both in the -F format (chan_file can be given to -F).
+//   beam -j n_blocks ... -x stokes_file -b b0,b1,... [-l n_int]
+//                                                   full-Stokes follow-up beams (docs/STOKES.md): I, Q, U, V as exact int64 of up to 16
+//                                                   of the beams, summed over windows of n_int samples [N_AVERAGING; 1 = every voltage
+//                                                   sample], one record per launch, to stokes_file.  With -R: stokes_file.<rank>.
 //   beam -E vis_file -G gains_file -f ant_file     the solver leaves the listed antennas out (their gains are exactly zero);
 //   beam ... -A gains_file -f ant_file              the listed antennas get zero weights.
 //
@@ -119,9 +123,12 @@ int main(int argc, char* argv[])
     bf_sk_default_options(&sk_opt);
     bool sk_sigma_given = false, sk_centre_given = false;
     std::string ant_flags_path;     // -f: antenna flags for -E or -A
+    std::string stokes_path, stokes_list;   // -x: where the Stokes beams go; -b: the beams to follow
+    int stokes_int = 0;                     // -l: samples per integration window (0: N_AVERAGING)
+    bool stokes_int_given = false;
 
     int arg = 0;
-    while ((arg = getopt(argc, argv, "s:g:p:d:o:D:a:c:k:K:j:w:R:r:I:M:N:T:W:Q:S:B:C:i:V:L:E:G:A:n:U:F:Y:J:e:O:q:t:m:f:zPXuvhH")) != -1) {  // src/beamformer.cu:41-43 (+ -o -D -a -v)
+    while ((arg = getopt(argc, argv, "s:g:p:d:o:D:a:c:k:K:j:w:R:r:I:M:N:T:W:Q:S:B:C:i:V:L:E:G:A:n:U:F:Y:J:e:O:q:t:m:f:x:b:l:zPXuvhH")) != -1) {  // src/beamformer.cu:41-43 (+ -o -D -a -v)
         switch (arg) {
             case 's': sources = optarg; break;                 // :77-89
             case 'g': opt.gpu = atoi(optarg); break;           // :92-100
@@ -164,6 +171,9 @@ int main(int argc, char* argv[])
             case 't': sk_opt.n_sigma = atof(optarg); sk_sigma_given = true; break;
             case 'm': sk_opt.centre = atof(optarg); sk_centre_given = true; break;
             case 'f': ant_flags_path = optarg; break;
+            case 'x': stokes_path = optarg; break;
+            case 'b': stokes_list = optarg; break;
+            case 'l': stokes_int = atoi(optarg); stokes_int_given = true; break;
             case 'u': per_unit = true; break;                   // the reference's launch pattern: one launch per gemm-unit
             case 'v': opt.verbose = true; cfg.verbose = 1; break;
             case 'c': core = atoi(optarg); break;              // :59-65
@@ -213,6 +223,9 @@ int main(int argc, char* argv[])
                              "                         summed, the spectral-kurtosis rule applied (centre [1] +- n_sigma [5] * 2 / sqrt(columns)); flagged\n"
                              "                         antennas to ant_file, flagged channels to chan_file, one index per line (chan_file can be given to -F)\n"
                              " -f ant_file             with -E: the solver leaves the listed antennas out (gains exactly 0); with -A: they get zero weights\n"
+                             " -x file -b b0,b1,... [-l n_int]   observation mode: full-Stokes follow-up beams -- I, Q, U, V (exact int64) of up to 16\n"
+                             "                         of the beams per window of n_int voltage samples [N_AVERAGING; 1 = full time resolution; must\n"
+                             "                         divide N_OUTPUTS_PER_GEMM * N_AVERAGING], one record per launch, to file (with -R: file.<rank>)\n"
                              " -H                      this text\n";
                 return EXIT_SUCCESS;
             default: usage(true, std::cerr); return EXIT_FAILURE;
@@ -303,6 +316,33 @@ int main(int argc, char* argv[])
     if (!sk_path.empty() && !observe_mode) {
         fprintf(stderr, "beam: -Y (voltage moments) belongs to the observation mode: give -j n_blocks or -k ring\n");
         return EXIT_FAILURE;
+    }
+    std::vector<int> stokes_beams;   // -b: parsed before any device is touched
+    if (stokes_path.empty() && (!stokes_list.empty() || stokes_int_given)) {
+        fprintf(stderr, "beam: -b / -l belong to the Stokes beams: give -x stokes_file\n");
+        return EXIT_FAILURE;
+    }
+    if (!stokes_path.empty()) {
+        if (!observe_mode) {
+            fprintf(stderr, "beam: -x (Stokes beams) belongs to the observation mode: give -j n_blocks or -k ring\n");
+            return EXIT_FAILURE;
+        }
+        if (stokes_list.empty()) {
+            fprintf(stderr, "beam: -x needs -b b0,b1,... (the beams to follow)\n");
+            return EXIT_FAILURE;
+        }
+        bf_config band;   // the observation mode's geometry
+        bf_config_default(&band, /*debug=*/0);
+        std::string why;
+        if (!parse_beam_list(stokes_list.c_str(), band.n_beams, &stokes_beams, &why)) {
+            fprintf(stderr, "beam: -b %s\n", why.c_str());
+            return EXIT_FAILURE;
+        }
+        const int samples = band.n_out_per_gemm * band.n_avg;
+        if (stokes_int_given && (stokes_int < 1 || samples % stokes_int)) {
+            fprintf(stderr, "beam: -l %d: the window must be at least 1 and divide the %d samples of a gemm-unit\n", stokes_int, samples);
+            return EXIT_FAILURE;
+        }
     }
     if (select_path.empty() && (!select_ant_path.empty() || !select_chan_path.empty() || sk_sigma_given || sk_centre_given)) {
         fprintf(stderr, "beam: -O / -q / -t / -m belong to the select mode: give -e moments_file\n");
@@ -631,12 +671,26 @@ int main(int argc, char* argv[])
             oopt.sk_blocks = sk_blocks;
             oopt.sk_sink = ksink.get();
         }
+        std::unique_ptr<stokes_file_sink> xsink;
+        if (!stokes_path.empty()) {   // -x: every shard follows the beams in its own channels
+            if (comm) stokes_path += "." + std::to_string(rank);
+            const int n_int = stokes_int_given ? stokes_int : pcfg.n_avg;
+            xsink.reset(new stokes_file_sink(pcfg, stokes_path.c_str(), rank * pcfg.n_freq, opt.gpu, stokes_beams, n_int));
+            if (!xsink->is_open()) {
+                fprintf(stderr, "beam: could not open %s\n", stokes_path.c_str());
+                return EXIT_FAILURE;
+            }
+            oopt.stokes_beams = stokes_beams;
+            oopt.stokes_int = n_int;
+            oopt.stokes_sink = xsink.get();
+        }
         observation_result ores;
         int orc = run_observation(pcfg, oopt, *src, pos.data(), dir.data(), &ores, std::cout);
         if (sink) std::cout << "Wrote " << sink->get_delivered() << " gemm-units of detected powers to " << sink_name << std::endl;
         if (dm_sink) std::cout << "Wrote " << dm_sink->get_times_written() << " dedispersed samples x " << my_trials << " trials to " << dm_path << std::endl;
         if (cand_sink) std::cout << "Wrote " << cand_sink->get_candidates_written() << " candidates to " << cand_path << std::endl;
         if (vsink) std::cout << "Wrote " << vsink->get_dumps_written() << " visibility dumps of " << corr_blocks << " blocks to " << vis_path << std::endl;
+        if (xsink) std::cout << "Wrote " << xsink->get_sets_written() << " sets of Stokes beams to " << stokes_path << std::endl;
         if (ksink) std::cout << "Wrote " << ksink->get_dumps_written() << " moment dumps of " << sk_blocks << " blocks to " << sk_path << std::endl;
         bf_comm_destroy(comm);
         if (orc != BF_OK) {

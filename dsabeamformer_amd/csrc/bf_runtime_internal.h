@@ -1,5 +1,5 @@
 // bf_runtime_internal.h -- what the C-ABI runtime's translation units share (bf_runtime.cpp, bf_queues.cpp, bf_dm_stream.cpp,
-// bf_sps.cpp, bf_cond.cpp, bf_corr.cpp, bf_sk.cpp, bf_bench_abi.cpp): the handle, the base of its stages, the error string, the device scope.
+// bf_sps.cpp, bf_cond.cpp, bf_corr.cpp, bf_sk.cpp, bf_stokes.cpp, bf_bench_abi.cpp): the handle, the base of its stages, the error string, the device scope.
 // Host-only and not installed: no .hip / .hpp file includes it.
 #pragma once
 #include "../../include/dsabf.h"
@@ -91,7 +91,7 @@ struct bf_resources {
     void release();
 };
 
-// The base of the five stage objects (bf_dm_stream, bf_sps, bf_cond, bf_corr, bf_sk: opaque to callers, each defined in its own file).
+// The base of the six stage objects (bf_dm_stream, bf_sps, bf_cond, bf_corr, bf_sk, bf_stokes: opaque to callers, each defined in its own file).
 struct bf_stage {
     bf_handle* h = nullptr;                 // NULL: the handle went first and took the device side with it
     const char* const noun;                 // "DM stage", "search stage", ...: the orphan check's message

@@ -206,12 +206,14 @@ struct run_resources {
     bf_cond* cond = nullptr;
     bf_corr* corr = nullptr;
     bf_sk* sk = nullptr;
+    bf_stokes* stokes = nullptr;
     std::vector<void*> pinned;
     ~run_resources()
     {
         if (h) bf_stream_sync(h, -1);
         bf_corr_destroy(corr);
         bf_sk_destroy(sk);
+        bf_stokes_destroy(stokes);
         bf_sps_destroy(sps);
         bf_cond_destroy(cond);
         bf_dm_stream_destroy(dm);
@@ -499,6 +501,18 @@ int check_options(const bf_config& cfg, const observation_options& opt)
     if (opt.sk_blocks < 0) return set_error(BF_ERR_INVALID, "run_observation: sk_blocks must be 0 (off) or the blocks per dump");
     if (opt.sk_sink && !opt.sk_blocks) return set_error(BF_ERR_INVALID, "run_observation: a sk_sink needs sk_blocks > 0");
     if (opt.sk_blocks && !opt.block_launch) return set_error(BF_ERR_INVALID, "run_observation: the voltage moments need block-granular launches");
+    if (opt.stokes_beams.empty() && (opt.stokes_sink || opt.stokes_int))
+        return set_error(BF_ERR_INVALID, "run_observation: a stokes_sink / stokes_int needs stokes_beams");
+    if (!opt.stokes_beams.empty()) {
+        if (!opt.block_launch) return set_error(BF_ERR_INVALID, "run_observation: the Stokes beams need block-granular launches");
+        if (opt.stokes_beams.size() > (size_t)BF_STOKES_MAX_BEAMS)
+            return set_error(BF_ERR_INVALID, "run_observation: stokes_beams holds more than BF_STOKES_MAX_BEAMS beams");
+        for (int b : opt.stokes_beams)
+            if (b < 0 || b >= cfg.n_beams) return set_error(BF_ERR_INVALID, "run_observation: a stokes_beams index is not a beam");
+        const int n_int = opt.stokes_int ? opt.stokes_int : cfg.n_avg;
+        if (n_int < 1 || (cfg.n_out_per_gemm * cfg.n_avg) % n_int)
+            return set_error(BF_ERR_INVALID, "run_observation: stokes_int must divide n_out_per_gemm * n_avg");
+    }
     if (opt.comm && opt.dm_sink && !is_root) return set_error(BF_ERR_INVALID, "run_observation: only the gather root may have a dm_sink");
     if (opt.dm_split_trials && (!opt.comm || opt.gather_root != BF_GATHER_ROOT_ALL))
         return set_error(BF_ERR_INVALID, "run_observation: dm_split_trials needs a sharded run gathered to every rank (BF_GATHER_ROOT_ALL)");
@@ -546,10 +560,13 @@ int resolve_plan(const bf_config& cfg, const observation_options& opt, launch_pl
     if (opt.dm_delays && !p.block_launch) return set_error(BF_ERR_INVALID, "run_observation: the DM stage needs block-granular launches");
     if (opt.corr_blocks && !p.block_launch) return set_error(BF_ERR_INVALID, "run_observation: the correlator needs block-granular launches");
     if (opt.sk_blocks && !p.block_launch) return set_error(BF_ERR_INVALID, "run_observation: the voltage moments need block-granular launches");
+    if (!opt.stokes_beams.empty() && !p.block_launch) return set_error(BF_ERR_INVALID, "run_observation: the Stokes beams need block-granular launches");
     // a sharded run dedisperses the gathered band (more ranks than trials: the surplus ranks only beamform)
     p.dm_run = opt.dm_delays && p.is_root && p.dm_count > 0;
     return BF_OK;
 }
+
+constexpr size_t kStokesSetBytesMax = (size_t)8 << 30;   // all result sets of a run's Stokes stage, per side (device, pinned)
 
 struct dm_chunk {
     uint64_t block, first_t;
@@ -597,6 +614,11 @@ struct production_run {
     std::deque<std::pair<uint64_t, uint64_t>> sk_pending;
     std::vector<int64_t> moments;         // what bf_sk_collect returns for one dump
     uint64_t sk_blocks_pushed = 0, sk_dumps = 0;
+    // the Stokes stage (stokes_beams non-empty): pushes issued and not yet collected -- {block of the launch, its first gemm-unit}
+    std::deque<std::pair<uint64_t, uint64_t>> stokes_pending;
+    std::vector<int8_t> stokes_weights;   // the host weights the handle got: what the stage's beams are picked from
+    std::vector<int64_t> stokes;          // what bf_stokes_collect returns for one push
+    uint64_t stokes_units = 0;
 
     int create_handle_and_weights(const antenna* pos, const beam_direction* dir)
     {
@@ -606,12 +628,16 @@ struct production_run {
         ::memset(beam_out, 0, beam_out_stride * cfg.n_streams * sizeof(float));
         std::vector<int8_t> fourier_coefficients((size_t)cfg.n_freq * cfg.n_ant * cfg.n_beams * 2);
         generate_fourier_coefficients(cfg.n_beams, cfg.n_ant, cfg.n_freq, opt.rank * cfg.n_freq, opt.gpu, pos, dir, fourier_coefficients.data());
+        const bool follow = !opt.stokes_beams.empty();   // (the Stokes stage takes the weights as they were set: calibrated, in place)
         if (opt.gains) {
-            if ((rc = set_weights_calibrated(dev.h, opt.device, fourier_coefficients.data(), opt.gains, nullptr, opt.ant_flags)) != BF_OK) return rc;
+            if ((rc = set_weights_calibrated(dev.h, opt.device, fourier_coefficients.data(), opt.gains, follow ? fourier_coefficients.data() : nullptr,
+                                             opt.ant_flags)) != BF_OK)
+                return rc;
             log << "Calibrated the weights with one layer of gains" << std::endl;
         } else if ((rc = bf_set_weights(dev.h, fourier_coefficients.data())) != BF_OK) {
             return rc;
         }
+        if (follow) stokes_weights.swap(fourier_coefficients);
         return opt.incoherent_beam >= 0 ? bf_set_incoherent_beam(dev.h, opt.incoherent_beam) : BF_OK;
     }
 
@@ -655,6 +681,23 @@ struct production_run {
         if (opt.sk_blocks > 0) {
             if ((rc = bf_sk_create(dev.h, kMaxTotalSep + 2, &dev.sk)) != BF_OK) return gpu_error(log, rc);
             moments.resize(2 * bf_sk_entries(&cfg));
+        }
+        if (!opt.stokes_beams.empty()) {   // sets in flight: as the DM chunks -- the launches of the blocks queued + the one being delivered
+            const int n_int = opt.stokes_int ? opt.stokes_int : cfg.n_avg, n_sel = (int)opt.stokes_beams.size();
+            const int n_sets = (kMaxTotalSep + 2) * (cfg.n_gemms_per_block / plan.upl);
+            // The C-ABI sizes every set for a whole block, on the device and again pinned: small launches multiply that.  Reported, and
+            // refused beyond kStokesSetBytesMax per side before anything is allocated.
+            const size_t set_bytes = (size_t)cfg.n_gemms_per_block * bf_stokes_entries(&cfg, n_sel, n_int) * 4 * sizeof(int64_t);
+            log << "Stokes beams: " << n_sets << " result sets of " << (set_bytes >> 20) << " MiB, on the device and pinned" << std::endl;
+            if ((size_t)n_sets * set_bytes > kStokesSetBytesMax) {
+                log << "ERROR: the Stokes result sets exceed " << (kStokesSetBytesMax >> 30) << " GiB per side" << std::endl;
+                return set_error(BF_ERR_INVALID, "run_observation: the Stokes result sets (sets in flight x a block of entries) exceed 8 GiB on the device "
+                                                 "and pinned: fewer stokes_beams, a longer stokes_int or more units_per_launch");
+            }
+            if ((rc = bf_stokes_create(dev.h, n_int, n_sets, &dev.stokes)) != BF_OK) return gpu_error(log, rc);
+            if ((rc = bf_stokes_set_weights(dev.stokes, stokes_weights.data(), opt.stokes_beams.data(), n_sel)) != BF_OK) return gpu_error(log, rc);
+            stokes.resize(4 * (size_t)plan.upl * bf_stokes_entries(&cfg, n_sel, n_int));
+            std::vector<int8_t>().swap(stokes_weights);
         }
         if (plan.block_launch)   // the per-queue block buffers are allocated on first use: do that here, not inside the timed loop
             for (int q = 0; q < plan.n_queues_used; q++) {
@@ -745,6 +788,10 @@ struct production_run {
         // the correlator reads the same resident units on the same queue, behind the detect launch and what follows it
         if (rc == BF_OK && dev.corr) rc = bf_corr_push_block(dev.corr, q, gpu_block, first, upl);
         if (rc == BF_OK && dev.sk) rc = bf_sk_push_block(dev.sk, q, gpu_block, first, upl);   // and so do the voltage moments
+        if (rc == BF_OK && dev.stokes) {                                                      // and the Stokes beams, one set per launch
+            rc = bf_stokes_push_block(dev.stokes, q, gpu_block, first, upl);
+            if (rc == BF_OK) stokes_pending.emplace_back((uint64_t)block_index, (uint64_t)block_index * (uint64_t)n_units + (uint64_t)first);
+        }
         return rc == BF_OK ? BF_OK : gpu_error(log, rc);
     }
 
@@ -832,6 +879,18 @@ struct production_run {
                 return BF_ERR_STATE;
             }
         }
+        while (!stokes_pending.empty() && stokes_pending.front().first < blocks_analyzed) {   // (the collect waits for the set's own copy)
+            const uint64_t first_unit = stokes_pending.front().second;
+            stokes_pending.pop_front();
+            int n = 0;
+            const int rc = bf_stokes_collect(dev.stokes, stokes.data(), &n);
+            if (rc != BF_OK) return gpu_error(log, rc);
+            stokes_units += (uint64_t)n;
+            if (opt.stokes_sink && !opt.stokes_sink->deliver(first_unit, (uint64_t)n, stokes.data(), stokes.size())) {
+                log << "ERROR: Stokes sink failed at gemm-unit " << first_unit << std::endl;
+                return BF_ERR_STATE;
+            }
+        }
         for (; opt.sink && sink_committed < blocks_analyzed * (uint64_t)cfg.n_gemms_per_block; sink_committed++)
             if (!opt.sink->commit(sink_committed)) {
                 log << "ERROR: detected sink failed at gemm-unit " << sink_committed << std::endl;
@@ -899,6 +958,7 @@ int run_observation(const bf_config& cfg, const observation_options& opt, block_
     if (opt.sps_sink) opt.sps_sink->close();
     if (opt.vis_sink) opt.vis_sink->close();
     if (opt.sk_sink) opt.sk_sink->close();
+    if (opt.stokes_sink) opt.stokes_sink->close();
     const uint64_t chunks = obs_state.get_current_transfer_gemm() * cfg.n_out_per_gemm;  // :552
     const double rate = (double)source.get_block_size() * obs_state.get_blocks_transfer_queue() / ms / 1e6;  // :554
     closing_report(log, ms, chunks, ms / (chunks ? chunks : 1), rate, run.plan.block_launch ? "bf_enqueue_block" : kUnitLaunchPattern);
@@ -914,6 +974,7 @@ int run_observation(const bf_config& cfg, const observation_options& opt, block_
         res->sps_candidates = run.sps_candidates;
         res->vis_dumps = run.vis_dumps;
         res->sk_dumps = run.sk_dumps;
+        res->stokes_units = run.stokes_units;
         res->cond_masked = run.cond_masked_channels();
     }
     if (run.plan.dm_run)
@@ -936,6 +997,9 @@ int run_observation(const bf_config& cfg, const observation_options& opt, block_
     if (run.dev.sk)
         log << "Voltage moments: " << run.sk_dumps << " dumps of " << opt.sk_blocks << " blocks each (an incomplete integration at the end is dropped)"
             << std::endl;
+    if (run.dev.stokes)
+        log << "Stokes beams: " << opt.stokes_beams.size() << " beams, windows of " << (opt.stokes_int ? opt.stokes_int : cfg.n_avg) << " samples, "
+            << run.stokes_units << " gemm-units" << std::endl;
     if (run.dev.sps)
         log << "Single-pulse search: boxcar widths 1 .. " << (1 << (opt.sps_widths - 1)) << ", " << run.sps_candidates << " candidates at S/N >= "
             << opt.sps_threshold << std::endl;

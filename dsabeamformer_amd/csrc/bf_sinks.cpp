@@ -356,6 +356,68 @@ void sk_file_sink::close()
     fd = -1;
 }
 
+stokes_file_sink::stokes_file_sink(const bf_config& cfg, const char* path, int first_channel, int gpu, const std::vector<int>& beams, int n_int)
+{
+    fd = ::open(path, O_CREAT | O_TRUNC | O_WRONLY, 0644);
+    if (fd < 0) return;
+    std::string list;
+    for (size_t i = 0; i < beams.size(); i++) list += (i ? "," : "") + std::to_string(beams[i]);
+    char header[kHeaderBytes];
+    ::memset(header, 0, sizeof(header));
+    ::snprintf(header, sizeof(header),
+               "HDR_VERSION 1.0\nHDR_SIZE %zu\nINSTRUMENT DSA\nCONTENT stokes\nDTYPE int64\nENDIAN little\n"
+               "LAYOUT unit,time,freq,beam,iquv\nRECORD_HEADER_BYTES %zu\nNANT %d\nNPOL %d\nNFREQ %d\n"
+               "FIRST_CHANNEL %d\nN_OUTPUTS_PER_GEMM %d\nN_GEMMS_PER_BLOCK %d\nN_AVERAGING %d\nNINT %d\nNSEL %zu\nBEAMS %s\nGPU %d\n",
+               kHeaderBytes, kRecordBytes, cfg.n_ant, cfg.n_pol, cfg.n_freq, first_channel, cfg.n_out_per_gemm, cfg.n_gemms_per_block, cfg.n_avg, n_int,
+               beams.size(), list.c_str(), gpu);
+    if (!pwrite_all(fd, header, sizeof(header), 0) || ::lseek(fd, (off_t)kHeaderBytes, SEEK_SET) < 0) {
+        ::close(fd);
+        fd = -1;
+    }
+}
+
+stokes_file_sink::~stokes_file_sink() { close(); }
+
+bool stokes_file_sink::deliver(uint64_t first_unit, uint64_t n_units, const int64_t* stokes, size_t n_int64)
+{
+    if (fd < 0) return false;
+    const uint64_t rec[2] = {first_unit, n_units};
+    static_assert(sizeof rec == kRecordBytes, "the record header is two uint64");
+    if (!write_all(fd, reinterpret_cast<const char*>(rec), sizeof rec) ||
+        !write_all(fd, reinterpret_cast<const char*>(stokes), n_int64 * sizeof(int64_t)))
+        return false;
+    sets++;
+    return true;
+}
+
+void stokes_file_sink::close()
+{
+    if (fd >= 0) ::close(fd);
+    fd = -1;
+}
+
+bool parse_beam_list(const char* text, int n_beams, std::vector<int>* beams, std::string* why)
+{
+    auto no = [&](const std::string& msg) {
+        if (why) *why = msg;
+        return false;
+    };
+    beams->clear();
+    const char* p = text ? text : "";
+    for (;;) {
+        char* end = nullptr;
+        const long b = strtol(p, &end, 10);
+        if (end == p || (*end && *end != ',')) return no("'" + std::string(text ? text : "") + "' is not a comma-separated list of beam indices");
+        if (b < 0 || b >= n_beams) return no("beam " + std::to_string(b) + " is not one of the " + std::to_string(n_beams) + " beams");
+        for (int seen : *beams)
+            if (seen == (int)b) return no("beam " + std::to_string(b) + " is listed twice");
+        if (beams->size() == (size_t)BF_STOKES_MAX_BEAMS) return no("more than " + std::to_string(BF_STOKES_MAX_BEAMS) + " beams");
+        beams->push_back((int)b);
+        if (!*end) return true;
+        p = end + 1;
+    }
+}
+
 dm_ring_sink::dm_ring_sink(const bf_config& cfg, int n_freq_total, int n_dm, int max_delay, int max_rows, const char* ring_name,
                            uint64_t ring_blocks, int gpu, int first_trial)
     : name(ring_name ? ring_name : "")

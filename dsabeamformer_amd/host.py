@@ -328,6 +328,31 @@ def read_moments_file(path: str):
     return hdr, dumps
 
 
+STOKES_LAYOUT = "unit,time,freq,beam,iquv"
+
+
+def read_stokes_file(path: str):
+    """Parse a dsabf::stokes_file_sink file (docs/STOKES.md): returns (header dict, with BEAMS as a list of ints, and a list of
+    (first_unit, n_units, int64 array [n_units][T][n_freq][n_sel][4] = {I, Q, U, V}) per record)."""
+    raw = open(path, "rb").read()
+    text = raw[:DETECTED_HEADER_BYTES].split(b"\0", 1)[0].decode()
+    hdr = dict(line.split(None, 1) for line in text.splitlines() if line.strip())
+    assert hdr["CONTENT"] == "stokes" and hdr["DTYPE"] == "int64" and hdr["LAYOUT"] == STOKES_LAYOUT, hdr
+    hdr["BEAMS"] = [int(b) for b in hdr["BEAMS"].split(",")]
+    n_int, n_sel = int(hdr["NINT"]), int(hdr["NSEL"])
+    assert n_sel == len(hdr["BEAMS"]), hdr
+    T = int(hdr["N_OUTPUTS_PER_GEMM"]) * int(hdr["N_AVERAGING"]) // n_int
+    cell = (T, int(hdr["NFREQ"]), n_sel, 4)
+    per_unit = T * cell[1] * n_sel * 4
+    at, rec, records = int(hdr["HDR_SIZE"]), int(hdr["RECORD_HEADER_BYTES"]), []
+    while at < len(raw):
+        first_unit, n_units = (int(v) for v in np.frombuffer(raw, "<u8", 2, at))
+        at += rec
+        records.append((first_unit, n_units, np.frombuffer(raw, "<i8", n_units * per_unit, at).reshape((n_units,) + cell)))
+        at += 8 * n_units * per_unit
+    return hdr, records
+
+
 GAINS_LAYOUT = "pol,freq,ant,reim"
 
 

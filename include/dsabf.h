@@ -390,6 +390,54 @@ int bf_sk_dump(bf_sk *c, void *hip_stream);
 int bf_sk_collect(bf_sk *c, int64_t *out, uint64_t *n_columns_per_pol);
 int bf_sk_pending(const bf_sk *c);
 
+/* ---- Full-Stokes follow-up beams (docs/STOKES.md) --------------------------------------------------------------------------------
+ * The detect of the loop adds |X|^2 + |Y|^2 of the two polarisation columns into one float (src/beamformer.hh:116, BF_DETECT_* above)
+ * and integrates N_AVERAGING samples (src/beamformer.hh:52); the phase between the feeds -- Stokes Q, U, V -- and every time scale
+ * below the window are gone.  A bf_stokes reads the same resident packed voltages the loop's GEMM reads (src/beamformer.cu:179) and
+ * forms, for a FEW selected beams, all four Stokes parameters at a window of its own.
+ * Input: packed [unit][freq][time][ant], one byte per complex sample, re in the high nibble and im in the low nibble, both two's
+ * complement; time = n_out_per_gemm * n_pol * n_avg; column c belongs to polarisation c % n_pol (README.md:53, the correlator's order).
+ * n_pol must be 2: sample j of a unit is the column pair (2j, 2j + 1) = (X, Y); a unit has S = n_out_per_gemm * n_avg samples.
+ * Weights: K beams of the stage's own, 1 <= K <= BF_STOKES_MAX_BEAMS, picked by the index list `beams` (any order, any of [0, n_beams))
+ * from an array in the layout of bf_set_weights, [freq][ant][beam]{re, im} int8, every value legal (-128 included), on the host
+ * (bf_stokes_set_weights) or the device (bf_stokes_set_weights_device: what bf_calibrate_weights_device writes).  The handle's own
+ * operand copy is not read: the stage gathers a compact copy.
+ * Beam sample (exact integers, no conjugation):  n[u][f][c][k] = sum over a of v[u][f][c][a] * w[f][a][beam_k].
+ * Stokes, with X = n[...][2j], Y = n[...][2j + 1] and a window n_int >= 1 that divides S (T = S / n_int outputs per unit), summed over
+ * j in [t n_int, (t + 1) n_int), all exact int64:
+ *   I = sum Xr^2 + Xi^2 + Yr^2 + Yi^2        Q = sum Xr^2 + Xi^2 - Yr^2 - Yi^2
+ *   U = sum 2 (Xr Yr + Xi Yi) = 2 Re(X conj Y)      V = sum 2 (Xi Yr - Xr Yi) = 2 Im(X conj Y)
+ * Layout [unit][t][freq][k]{I, Q, U, V}, four int64 per cell; bf_stokes_entries(cfg, K, n_int) = T * n_freq * K cells per unit (0 if
+ * undefined).  n_int = n_avg is the detected stream's time resolution, n_int = 1 the voltages' own.
+ * Bounds: n_pol == 2, n_ant % 4 == 0, n_ant <= 256 (|Xr|, |Xi| <= 2048 n_ant <= 2^19 fits the int32 accumulator, a term is <= 2^40),
+ * K in 1 ... 16, every beam index in [0, n_beams), n_int dividing S; otherwise BF_ERR_INVALID with a message, and nothing is launched.
+ * bf_stokes_create: n_int as above, max_in_flight result sets, each for the n_gemms_per_block units of a block.
+ * bf_stokes_set_weights / _device: may be called again at any time, on any queue, and hold for the kernels issued after them; every
+ *   write of the weights waits (on the device) for the write issued before it and for the pushes and bf_stokes_device kernels in flight.  The _device form is asynchronous on hip_stream; the host form returns when the copy has run.
+ *   A selection of more beams than any before needs the stage drained (BF_ERR_STATE otherwise): the result sets grow with it.
+ * bf_stokes_device: the kernel alone, n_units units at d_packed (16-byte aligned) -> d_out (device, n_units * entries * 4 int64, 16-byte
+ *   aligned), asynchronously on hip_stream, behind the last gather.
+ * bf_stokes_push: the kernel on hip_stream into the next result set, then -- on a queue of the stage's own, so hip_stream is held for
+ *   the kernel only -- the copy to that set's pinned memory.  bf_stokes_push_block: the units [first_unit, first_unit + n_units) of ring
+ *   slot `slot` (what bf_enqueue_block reads; any unit of it, 4-byte aligned at least) on compute queue stream_idx, behind what that queue holds.  A push before any weights, or
+ *   with max_in_flight sets uncollected: BF_ERR_STATE; n_units > n_gemms_per_block: BF_ERR_INVALID; nothing is queued.
+ * bf_stokes_collect waits for the OLDEST uncollected set and copies it to `out` (host; the size of ITS push: n_units * entries at the
+ *   beams selected when it was pushed) and its units to *n_units (may be NULL); nothing pending: BF_ERR_STATE.  bf_stokes_pending: sets
+ *   not yet collected.  A handle that goes first releases the device side; the stage then answers BF_ERR_STATE and can still be
+ *   destroyed.  Every entry point leaves the caller's current device as it found it. */
+#define BF_STOKES_MAX_BEAMS 16
+typedef struct bf_stokes bf_stokes;
+size_t bf_stokes_entries(const bf_config *cfg, int n_sel, int n_int);
+int bf_stokes_create(bf_handle *h, int n_int, int max_in_flight, bf_stokes **out);
+int bf_stokes_destroy(bf_stokes *s);
+int bf_stokes_set_weights(bf_stokes *s, const int8_t *w_host, const int *beams, int n_sel);
+int bf_stokes_set_weights_device(bf_stokes *s, const int8_t *d_w, const int *beams, int n_sel, void *hip_stream);
+int bf_stokes_device(bf_stokes *s, const void *d_packed, int n_units, int64_t *d_out, void *hip_stream);
+int bf_stokes_push(bf_stokes *s, const void *d_packed, int n_units, void *hip_stream);
+int bf_stokes_push_block(bf_stokes *s, int stream_idx, int slot, int first_unit, int n_units);
+int bf_stokes_collect(bf_stokes *s, int64_t *out, int *n_units);
+int bf_stokes_pending(const bf_stokes *s);
+
 /* a1 alone (expand_input, src/beamformer.cuh:66-109): nbytes packed bytes -> 2*nbytes int8 (re, im pairs in
  * order).  nbytes must be a multiple of 16, pointers 16-byte aligned. */
 int bf_expand_device(bf_handle *h, const void *d_in, size_t nbytes, void *d_out, void *hip_stream);

@@ -657,6 +657,42 @@ public:
     uint64_t get_dumps_written() const { return dumps; }
 };
 
+// ---- Full-Stokes follow-up beams inside the loop (include/dsabf.h: bf_stokes_*; docs/STOKES.md) --------------------------------
+// With observation_options::stokes_beams non-empty run_observation creates a bf_stokes, sets its weights from the host weights the
+// handle got (the calibrated ones with gains), pushes every launch's units on that launch's queue behind the detect launch and hands
+// every collected set to a stokes_sink once the launch's block has been analysed.
+struct stokes_sink {
+    virtual ~stokes_sink() {}
+    // one push: the gemm-units first_unit .. first_unit + n_units - 1, counted from the first analysed block;
+    // stokes = int64 [unit][t][freq][beam]{I, Q, U, V} (n_int64 values)
+    virtual bool deliver(uint64_t first_unit, uint64_t n_units, const int64_t* stokes, size_t n_int64) = 0;
+    virtual void close() {}
+};
+
+// File: the 4096-byte ASCII header (`KEY value` lines, NUL padded: CONTENT stokes, DTYPE int64, NANT, NFREQ, FIRST_CHANNEL, NINT, NSEL,
+// BEAMS b0,b1,..., LAYOUT unit,time,freq,beam,iquv), then one record per collected set: uint64 first_unit, uint64 n_units, the entries
+// (little-endian int64).
+class stokes_file_sink : public stokes_sink {
+    int fd = -1;
+    uint64_t sets = 0;
+
+public:
+    static constexpr size_t kHeaderBytes = 4096;
+    static constexpr size_t kRecordBytes = 16;
+    stokes_file_sink(const bf_config& cfg, const char* path, int first_channel, int gpu, const std::vector<int>& beams, int n_int);
+    ~stokes_file_sink() override;
+    stokes_file_sink(const stokes_file_sink&) = delete;
+    stokes_file_sink& operator=(const stokes_file_sink&) = delete;
+    bool is_open() const { return fd >= 0; }
+    bool deliver(uint64_t first_unit, uint64_t n_units, const int64_t* stokes, size_t n_int64) override;
+    void close() override;
+    uint64_t get_sets_written() const { return sets; }
+};
+
+// `beam -b`: a comma-separated list of beam indices -> beams.  false + *why if it is empty, holds anything but indices 0 .. n_beams - 1,
+// more than BF_STOKES_MAX_BEAMS of them, or one twice.  No device is touched.
+bool parse_beam_list(const char* text, int n_beams, std::vector<int>* beams, std::string* why);
+
 // ---- The gain solver (include/dsabf.h: bf_solve_gains_device, bf_calibrate_weights_device; docs/CALIBRATION.md) ----------------
 // Thin wrappers: device pointers in, asynchronous on `stream`, the C-ABI's return codes.
 inline int solve_gains(bf_handle* h, const int64_t* d_vis, const double* d_model, const uint8_t* d_flags, const bf_cal_options& opt, double* d_gains,
@@ -802,6 +838,13 @@ struct observation_options {
     // -A: one layer of gains for THIS rank's channels, host [freq][ant]{re, im}: as debug_run_options::gains.
     const double* gains = nullptr;
     const uint8_t* ant_flags = nullptr;   // -f with -A: uint8 [n_ant], flagged antennas get zero weights (needs gains)
+    // Full-Stokes follow-up beams (docs/STOKES.md; needs block_launch): the beams to follow (empty = off; 1 .. 16 distinct indices), the
+    // integration window in samples (0 = n_avg; must divide n_out_per_gemm * n_avg) and where every launch's set goes (may be NULL: the
+    // stage still runs).  The stage holds (MAX_TOTAL_SEP + 2) x launches-per-block result sets of a block's entries each, on the device and
+    // pinned: the run logs that amount and is refused (BF_ERR_INVALID, nothing allocated) beyond 8 GiB per side.  On a sharded run every rank follows the beams in its own channels and has a sink of its own.
+    std::vector<int> stokes_beams;
+    int stokes_int = 0;
+    dsabf::stokes_sink* stokes_sink = nullptr;
 };
 struct observation_result {
     float observation_time_ms = 0;
@@ -815,6 +858,7 @@ struct observation_result {
     uint64_t sps_candidates = 0;    // candidates the search stage found (sps_widths > 0)
     uint64_t vis_dumps = 0;         // integrations the correlator dumped (corr_blocks > 0)
     uint64_t sk_dumps = 0;          // integrations the moments stage dumped (sk_blocks > 0)
+    uint64_t stokes_units = 0;      // gemm-units the Stokes stage delivered (stokes_beams non-empty)
     int cond_masked = -1;           // channels the conditioner masked in the last push (cond_baseline > 0 and a block analysed), else -1
 };
 // The reference's production main() loop on top of the C-ABI.  pos/dir: antenna positions and beam directions.
