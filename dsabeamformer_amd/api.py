@@ -269,7 +269,7 @@ class Beamformer(_Owner):
         check(self._lib.bf_set_switch(self._h, name.encode(), int(value)))
 
     def counter(self, name: str) -> int:
-        """bf_get_counter: "fused_launches", "queued_units"."""
+        """bf_get_counter: "fused_launches", "queued_units", "dm_ring_stages", "fold_stream"."""
         v = C.c_uint64()
         check(self._lib.bf_get_counter(self._h, name.encode(), C.byref(v)))
         return int(v.value)
@@ -279,8 +279,16 @@ class Beamformer(_Owner):
         check(self._lib.bf_kernel_info(self._h, n_units, C.byref(g), C.byref(b), C.byref(l), C.byref(v)))
         name = C.create_string_buffer(160)
         check(self._lib.bf_kernel_name(self._h, name, 160))
+        # "launch": the kernel template the fused launch instantiates; variant_key() and "kernel" name the antenna-fold FAMILY, whose
+        # launches of whole chunk spans are fused16_fold_stream_kernel
+        key = self.variant_key()
+        launch = key.split("<")[0]
+        if launch == "fused16_fold_kernel":
+            v64 = C.c_uint64()   # (an A/B library of an earlier build, DSABF_LIB_PATH, has neither the counter nor the streamed kernel)
+            if self._lib.bf_get_counter(self._h, b"fold_stream", C.byref(v64)) == 0 and v64.value:
+                launch = "fused16_fold_stream_kernel"
         return {"kernel": name.value.decode(), "grid": g.value, "block": b.value, "lds_bytes": l.value,
-                "vgprs": v.value}
+                "vgprs": v.value, "launch": launch}
 
     def variant_key(self, write_c: bool = False) -> str:
         """The instantiation this handle launches (after set_weights decided general / conjugate-pair)."""

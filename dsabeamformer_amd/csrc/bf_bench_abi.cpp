@@ -79,8 +79,10 @@ int bf_get_counter(const bf_handle* h, const char* name, uint64_t* value)
         uint64_t n = 0;
         for (const bf_stage* s : h->stages) n += s->ring ? 1 : 0;
         *value = n;
-    } else
-        return fail(BF_ERR_INVALID, "unknown counter \"%s\" (fused_launches, queued_units, dm_ring_stages)", name);
+    } else if (!strcmp(name, "fold_stream"))       // 1: the antenna-fold launch of this handle is fused16_fold_stream_kernel (whole chunk spans)
+        *value = dsabf::fold_streams(h->geom) ? 1 : 0;
+    else
+        return fail(BF_ERR_INVALID, "unknown counter \"%s\" (fused_launches, queued_units, dm_ring_stages, fold_stream)", name);
     return BF_OK;
 }
 

@@ -212,7 +212,7 @@ constexpr int fused_min_waves()
 template <int AIN, int NIPO, bool WRITE_C, int MODE = kDetCanonical, bool PAIRED = false, int WAVES = kWaves16, int NS = kColTiles16>
 __global__ __launch_bounds__(64 * WAVES, (fused_min_waves<AIN, NIPO, WRITE_C, NS>())) void fused16_kernel(FusedArgs a)
 {
-    constexpr bool FOLD = false;
+    constexpr bool FOLD = false, STREAM = false;
 #include "bf_fused16_body.inc"
 }
 
@@ -227,7 +227,23 @@ template <int NIPO, int MODE>
 __global__ __launch_bounds__(kThreads16, (fused_min_waves<kAntK1P16, NIPO, false>())) void fused16_fold_kernel(FusedArgs a)
 {
     constexpr int AIN = FoldShape<NIPO>::AIN, WAVES = FoldShape<NIPO>::WAVES, NS = FoldShape<NIPO>::NS;
-    constexpr bool WRITE_C = FoldShape<NIPO>::WRITE_C, PAIRED = FoldShape<NIPO>::PAIRED, FOLD = true;
+    constexpr bool WRITE_C = FoldShape<NIPO>::WRITE_C, PAIRED = FoldShape<NIPO>::PAIRED, FOLD = true, STREAM = false;
+#include "bf_fused16_body.inc"
+}
+
+// The antenna-fold kernel for gemm-units of whole chunk spans (T % 128 == 0; n_ipo 64: T % 256 == 0 -- every production geometry):
+// the same sums, detect and stores; the chunk addressing is scalar state that advances by a constant, both prefetch loads are
+// unconditional and back to back, and the chunk loop waits for global memory once, where the staging first reads the prefetched
+// registers (STREAM in bf_fused16_body.inc; tests/test_isa_fold_stream_cpu.py).  Other gemm-units keep fused16_fold_kernel and its
+// per-row addressing.  A kernel of its own name in a translation unit of its own (bf_fused16_k1p16_fold_stream.hip): the nine
+// fused16_fold_kernel instantiations and their code stay what they were.
+template <int NIPO>
+constexpr unsigned fold_stream_span() { return NIPO == 64 ? 256u : 128u; }
+template <int NIPO, int MODE>
+__global__ __launch_bounds__(kThreads16, (fused_min_waves<kAntK1P16, NIPO, false>())) void fused16_fold_stream_kernel(FusedArgs a)
+{
+    constexpr int AIN = FoldShape<NIPO>::AIN, WAVES = FoldShape<NIPO>::WAVES, NS = FoldShape<NIPO>::NS;
+    constexpr bool WRITE_C = FoldShape<NIPO>::WRITE_C, PAIRED = FoldShape<NIPO>::PAIRED, FOLD = true, STREAM = true;
 #include "bf_fused16_body.inc"
 }
 
@@ -263,6 +279,20 @@ hipError_t launch_fused16_fold_t(const FusedArgs& args, const LaunchShape& ls, h
     return hipGetLastError();
 }
 
+// (the streamed kernel never tests a sample against the launch's end: whole spans only, and chunks that hold nothing else)
+template <int NIPO, int MODE>
+hipError_t launch_fused16_fold_stream_t(const FusedArgs& args, const LaunchShape& ls, hipStream_t s)
+{
+    if (ls.block != kThreads16 || args.n_ant != 64 || (args.interleave && args.interleave != kColTiles16) || ls.lds_bytes > 48 * 1024)
+        return hipErrorInvalidValue;
+    if (args.T <= 0 || (unsigned)args.T % fold_stream_span<NIPO>() != 0 || args.chunks_total <= 0 ||
+        (unsigned long long)args.chunks_total * kRowsPerChunk != args.S)
+        return hipErrorInvalidValue;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL((fused16_fold_stream_kernel<NIPO, MODE>), dim3(ls.grid), dim3(ls.block), ls.lds_bytes, s, args);
+    return hipGetLastError();
+}
+
 // One entry of the variant table: the kernel symbol (for hipFuncGetAttributes) and its launcher.
 using fused_launch_fn = hipError_t (*)(const FusedArgs&, const LaunchShape&, hipStream_t);
 struct FusedVariant {
@@ -271,7 +301,7 @@ struct FusedVariant {
     // the instantiation's template arguments, in the kernel's own order: what the census (bf_variant_key, tests/test_census_cpu.py,
     // profiles/r06_instantiations.txt) compares with the kernel symbols of the shipped library
     int ain = 0, nipo = 0, write_c = 0, mode = 0, paired = 0, waves = 0, ns = 0;
-    int fold = 0;   // fused16_fold_kernel<nipo, mode>
+    int fold = 0;   // 1: fused16_fold_kernel<nipo, mode>; 2: fused16_fold_stream_kernel<nipo, mode> (the same family under the same key)
 };
 
 template <int AIN, int NIPO, bool WRITE_C, int MODE, bool PAIRED, int WAVES, int NS = kColTiles16>
@@ -415,6 +445,15 @@ FusedVariant make_fold_variant()
 }
 // The antenna-fold kernels: n_ipo 16 / 32 / 64 x the three detect readings (bf_fused16_k1p16_fold.hip); anything else: none.
 FusedVariant fused16_variant_k1p16_fold(int n_ipo, int mode);
+
+template <int NIPO, int MODE>
+FusedVariant make_fold_stream_variant()
+{
+    return FusedVariant{reinterpret_cast<const void*>(fused16_fold_stream_kernel<NIPO, MODE>), launch_fused16_fold_stream_t<NIPO, MODE>, kAntK1P16,
+                        NIPO, 0, MODE, 0, kWaves16, kColTiles16, 2};
+}
+// ... and their streamed twins for gemm-units of whole chunk spans (bf_fused16_k1p16_fold_stream.hip).
+FusedVariant fused16_variant_k1p16_fold_stream(int n_ipo, int mode);
 
 // One definition per antenna class, each in its own translation unit (bf_fused16_*.hip).
 FusedVariant fused16_variant_a100(int n_ipo, bool write_c, int mode, bool paired);

@@ -1,5 +1,6 @@
-// bf_fused16_body.inc -- the text of fused16_kernel and fused16_fold_kernel (bf_fused16.hpp), included into both.  In scope where it is
-// included: the kernel argument `FusedArgs a` and the compile-time parameters AIN, NIPO, WRITE_C, MODE, PAIRED, WAVES, NS, FOLD.
+// bf_fused16_body.inc -- the text of fused16_kernel, fused16_fold_kernel and fused16_fold_stream_kernel (bf_fused16.hpp), included into
+// all three.  In scope where it is included: the kernel argument `FusedArgs a` and the compile-time parameters AIN, NIPO, WRITE_C, MODE,
+// PAIRED, WAVES, NS, FOLD, STREAM.
     constexpr int THREADS = 64 * WAVES;
     constexpr bool FAST = MODE == kDetFast;
     constexpr bool CONTRACTED = MODE == kDetContracted;
@@ -16,6 +17,7 @@
     static_assert(!ant_deep<AIN>() || (WAVES == 8 && NIPO >= 16 && !WRITE_C), "deep classes: 8 waves, long windows");
     static_assert(!FOLD || (AIN == kAntK1P16 && NIPO >= 16 && !WRITE_C && !PAIRED && WAVES == kWaves16 && NS == kColTiles16),
                   "antenna fold: 64 antennas in 16-byte pieces, long compile-time windows, general tiles on the plain launch shape");
+    static_assert(!STREAM || FOLD, "the streamed chunk loop exists for the antenna-fold kernels");
     // the deep classes' operands count in units of the nibble value itself, not 16 x, staged as OFFSET nibbles v + 8 in [0, 15] with
     // the correction in the accumulator seeds (sign-extended nibbles cost 9 VALU per dword and the pipe holds a lower clock on them:
     // profiles/r04_ubench_encoding.txt)
@@ -157,11 +159,23 @@
     // in plane 0, before it in plane 1), and the swizzle only XORs the 3 piece bits, so its LDS offset is the re offset ^ 64.
     [[maybe_unused]] unsigned lane_off64[NIPO == 64 ? PPT : 1];
     int lds_re[PPT];                      // LDS byte offset (inside one buffer) of the piece's 16*re image
+    // FOLD: the chunk row a thread stages.  STREAM deals the rows so that the 8 lanes of a ds_write_b128 group (thread pairs q = tid / 2
+    // = 4 j ... 4 j + 3) hold rows that differ in bit 0 and in the LOW STREAM BIT (row / LR & 1) -- the two row bits that swz16 XORs
+    // into piece bits 2 and 1 -- and not, like rows 4 j ... 4 j + 3, in bits 0 and 1, of which bit 1 lands on the piece bit P itself:
+    // with P the 8 lanes then cover all eight 16-byte slots of the 128-byte bank window (no store conflict; the four stores of a
+    // thread XOR constants into the slot).  Which thread stages a row changes nothing else: offsets formed once, same LDS image.
+    [[maybe_unused]] const int fold_row = [&] {
+        const int q = tid >> 1;
+        if constexpr (!STREAM) return q;
+        else if constexpr (LR == 32) return (q & 1) | (((q >> 1) & 3) << 5) | (((q >> 3) & 15) << 1);
+        else return (q & 1) | (((q >> 1) & 3) << 4) | (((q >> 3) & 7) << 1) | ((q >> 6) << 6);
+    }();
 #pragma unroll
     for (int k = 0; k < PPT; k++) {
         int row, pi;
-        if constexpr (FOLD) {   // a thread takes piece P = tid & 1 of row tid / 2 (k = 0) and its mirror piece 3 - P (k = 1): antenna 16 P + j <-> byte 15 - j
-            row = tid >> 1;
+        if constexpr (FOLD) {   // a thread takes piece P = tid & 1 of row tid / 2 (STREAM: fold_row; k = 0) and its mirror piece 3 - P (k = 1): antenna 16 P + j <-> byte 15 - j
+            if constexpr (STREAM) row = fold_row;
+            else row = tid >> 1;
             pi = k == 0 ? (tid & 1) : 3 - (tid & 1);
         } else {
             const int pc = tid + k * THREADS;
@@ -175,6 +189,8 @@
     auto lane_off = [&](int k) -> unsigned {
         if constexpr (NIPO == 64)
             return lane_off64[k];
+        else if constexpr (STREAM)
+            return (unsigned)(64 * fold_row + 16 * (k == 0 ? (tid & 1) : 3 - (tid & 1)));
         else if constexpr (FOLD)
             return (unsigned)(64 * (tid >> 1) + 16 * (k == 0 ? (tid & 1) : 3 - (tid & 1)));
         else
@@ -231,6 +247,67 @@
             }
         }
     };
+    // STREAM (fused16_fold_stream_kernel; launched only when T % SPAN == 0, launch_fused16_fold_stream_t): the chunk addressing above
+    // as wave-uniform state that advances by a constant, and a prefetch with no predicate.
+    //  * Every chunk of [0, chunks_total) holds real samples only: T % SPAN == 0 makes S = n_units * T a multiple of SPAN, hence of
+    //    4 * n_ipo (SPAN = 128 for n_ipo 16 / 32, 256 for 64), so fused_launch_shape's rows = ceil(S / n_ipo / 4) * 4 * n_ipo == S and
+    //    chunks_total * 128 == S (the launcher refuses anything else).  `valid` is constant-true; so is piece_live (256 threads x 2
+    //    pieces = the chunk's 512 pieces).  No zero-initialisation, no branch around a load.
+    //  * st_base = first byte of chunk st_next, the chunk the next load_stream() requests: 64-bit and scalar (a launch may exceed
+    //    4 GiB); the per-lane part is lane_off(k), 32-bit and constant for the whole kernel.  One chunk on = 128 samples (n_ipo 64:
+    //    32 samples inside a span, 224 to the next span); a span that would start at sample T starts the next gemm-unit instead, which
+    //    lies (n_freq - 1) * T samples further on.
+    //  * The requests are clamped to the workgroup's last chunk: the last two requests of a workgroup re-read chunk c_end - 1 (real
+    //    samples, see above) and nobody reads what is staged from them.
+    [[maybe_unused]] unsigned long long st_base = 0;   // (bytes behind a.in)
+    [[maybe_unused]] unsigned st_t0 = 0;      // first sample of st_next's span inside its gemm-unit
+    [[maybe_unused]] int st_next = c_begin;
+    [[maybe_unused]] unsigned long long st_unit = 0;   // bytes from a gemm-unit's end to the same frequency's next gemm-unit
+    [[maybe_unused]] unsigned st_off[PPT];             // lane_off(k), formed once
+    if constexpr (STREAM) {
+        const unsigned s_c = (unsigned)(NIPO == 64 ? c_begin / 2 : c_begin) * SPAN;   // (n_ipo 64: c_begin is even, a whole group)
+        const unsigned u = a.t_shift >= 0 ? (s_c >> a.t_shift) : (s_c / (unsigned)a.T);
+        st_t0 = s_c - u * (unsigned)a.T;
+        // (64-bit products are formed on the vector unit, once per workgroup: the state goes back to scalar registers by name)
+        auto sgpr64 = [](unsigned long long v) {
+            return (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v) |
+                   ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32)) << 32);
+        };
+        st_base = sgpr64((unsigned long long)((size_t)((size_t)u * a.n_freq + f) * a.T + st_t0) * 64);
+        st_t0 = (unsigned)__builtin_amdgcn_readfirstlane((int)st_t0);
+        st_unit = sgpr64((unsigned long long)(unsigned)(a.n_freq - 1) * (unsigned)a.T * 64);
+#pragma unroll
+        for (int k = 0; k < PPT; k++) st_off[k] = lane_off(k);
+    }
+    auto load_stream = [&]() {
+        // (the base as a scalar register pair by name, the pointer global by type: global_load v, v_off, s[base] -- not a.in + lane_off
+        //  hoisted into four VGPRs and a 64-bit vector add per load)
+        unsigned long long base = (unsigned long long)a.in + st_base;
+        asm volatile("" : "+s"(base));
+#pragma unroll
+        for (int k = 0; k < PPT; k++) {
+            unsigned off = st_off[k];
+            asm volatile("" : "+v"(off));      // (its zero extension stays beside the load, where the instruction's 32-bit offset operand takes it)
+            stage[k] = *(const __attribute__((address_space(1))) stage_t*)(base + off);
+        }
+        if (st_next + 1 < c_end) {             // scalar: no memory operation depends on it
+            bool next_span = true;
+            if constexpr (NIPO == 64) {
+                next_span = (st_next & 1) != 0;
+                st_base += next_span ? (size_t)(SPAN - 32u) * 64 : (size_t)32 * 64;
+            } else {
+                st_base += (size_t)SPAN * 64;
+            }
+            if (next_span) {
+                st_t0 += SPAN;
+                if (st_t0 >= (unsigned)a.T) {
+                    st_t0 = 0;
+                    st_base += st_unit;
+                }
+            }
+            st_next++;
+        }
+    };
     auto write_chunk = [&](char* buf) {
         if constexpr (FOLD) {
             // stage[0] = antennas 16 P ... 16 P + 15 of the row, stage[1] = their mirror images in descending order.  Per dword pair:
@@ -240,6 +317,10 @@
             // (behind the launch's last sample) gives all-zero operands.  LDS row: Sr0 Sr1 Di0 Di1 | Dr0 Dr1 Si0 Si1 (pieces
             // P, P + 2, P + 4, P + 6: the swizzle only XORs the 3 piece bits).
             constexpr unsigned M = 0x78787878u, H = 0x80808080u;
+            if constexpr (STREAM) {   // the chunk loop's one wait for global memory: both prefetched pieces at once, stated here so that
+                __builtin_amdgcn_s_waitcnt(0x0F70);   // the compiler adds none of its own (vmcnt(0); expcnt and lgkmcnt left alone)
+                asm volatile("" : "+v"(stage[0]), "+v"(stage[PPT - 1]));
+            }
             v4i sr, si, dr, di;
 #pragma unroll
             for (int d = 0; d < 4; d++) {
@@ -337,7 +418,8 @@
                     const unsigned grp = (NIPO >= 32) ? (unsigned)(pend_chunk[gi] / CPG) : (2u * pend_chunk[gi] + gi);
                     float* ub = a.out + ((size_t)(4u * grp) * FB + (size_t)f * a.n_beams);  // wave-uniform part
                     const unsigned o = 4u * grp + (unsigned)g4;
-                    if (o * (unsigned)L < a.S) store_slots(ub + (size_t)g4 * FB, pend[gi]);
+                    // (STREAM: chunks_total * 128 == S, so every output of every chunk lies inside the launch: see load_stream)
+                    if (STREAM || o * (unsigned)L < a.S) store_slots(ub + (size_t)g4 * FB, pend[gi]);
                 }
                 pend_chunk[gi] = -1;
             }
@@ -349,17 +431,28 @@
     const unsigned long long probe_t0 = __builtin_amdgcn_s_memtime(), probe_r0 = __builtin_amdgcn_s_memrealtime();
 #endif
 
-    load_chunk(c_begin);
-    write_chunk(smem);
-    if (c_begin + 1 < c_end) load_chunk(c_begin + 1);
+    if constexpr (STREAM) {
+        load_stream();
+        write_chunk(smem);
+        load_stream();
+    } else {
+        load_chunk(c_begin);
+        write_chunk(smem);
+        if (c_begin + 1 < c_end) load_chunk(c_begin + 1);
+    }
     __syncthreads();
 
     // FOLD: a wave without beams only stages; its chunks run in a loop of their own, so that the tile loop holds the (longer) staging once
     const bool stage_only = FOLD && !wave_active;
     if (stage_only)
         for (int c = c_begin; c < c_end; c++) {
-            if (c + 1 < c_end) write_chunk(smem + ((c - c_begin + 1) & 1) * BUF);
-            if (c + 2 < c_end) load_chunk(c + 2);
+            if constexpr (STREAM) {   // (the last iteration stages a second image of chunk c_end - 1 into the buffer nobody reads any more)
+                write_chunk(smem + ((c - c_begin + 1) & 1) * BUF);
+                load_stream();
+            } else {
+                if (c + 1 < c_end) write_chunk(smem + ((c - c_begin + 1) & 1) * BUF);
+                if (c + 2 < c_end) load_chunk(c + 2);
+            }
             __syncthreads();
         }
     for (int c = stage_only ? c_end : c_begin; c < c_end; c++) {
@@ -564,11 +657,22 @@
             };
             // staging work in the shadow of the MFMA stream: the next chunk's LDS image after tile 1, the parked stores
             // of the previous chunk and the prefetch of chunk c+2 after tile 3
+            // (STREAM: neither depends on c -- the one wait for the prefetched registers is write_chunk's first read of them, six row
+            //  tiles after their request, and the request goes out before the parked stores, whose acknowledgement nothing waits for;
+            //  the workgroup's last iteration stages a second image of its last chunk into the buffer nobody reads any more)
             auto staging = [&](const int t8) {
-                if (t8 == 1 && c + 1 < c_end) write_chunk(nxt);
-                if (t8 == 3) {
-                    flush_pending();
-                    if (c + 2 < c_end) load_chunk(c + 2);
+                if constexpr (STREAM) {
+                    if (t8 == 1) write_chunk(nxt);
+                    if (t8 == 3) {
+                        load_stream();
+                        flush_pending();
+                    }
+                } else {
+                    if (t8 == 1 && c + 1 < c_end) write_chunk(nxt);
+                    if (t8 == 3) {
+                        flush_pending();
+                        if (c + 2 < c_end) load_chunk(c + 2);
+                    }
                 }
             };
 #pragma unroll

@@ -48,6 +48,8 @@ size_t weight_pair_image_bytes(const Geometry& g);
 // (64 antennas, n_ipo 16 / 32 / 64 have one).
 bool fold_supported(const Geometry& g);
 size_t weight_fold_image_bytes(const Geometry& g);
+// g.fold and gemm-units of whole chunk spans: the launch runs fused16_fold_stream_kernel (scalar chunk addressing), else fused16_fold_kernel
+bool fold_streams(const Geometry& g);
 
 // True if the fused kernel has an instantiation for this geometry; `why` (optional) explains a refusal.
 bool fused_supported(const Geometry& g, const char** why);

@@ -453,7 +453,8 @@ int detect_mode_of(const Geometry& g) { return g.fast_detect ? kDetFast : g.cont
 FusedVariant select_variant(const Geometry& g, bool write_c)
 {
     if (use_generic(g)) return FusedVariant{};
-    if (g.fold && !write_c) return fused16_variant_k1p16_fold(g.n_ipo, detect_mode_of(g));   // (fold_supported: 64 antennas, n_ipo 16 / 32 / 64)
+    if (g.fold && !write_c)   // (fold_supported: 64 antennas, n_ipo 16 / 32 / 64; gemm-units of whole chunk spans: the streamed kernel)
+        return fold_streams(g) ? fused16_variant_k1p16_fold_stream(g.n_ipo, detect_mode_of(g)) : fused16_variant_k1p16_fold(g.n_ipo, detect_mode_of(g));
     if (deep_class(g)) {
         if (write_c) return FusedVariant{};
         const bool paired = g.paired;
@@ -529,6 +530,12 @@ size_t weight_pair_image_bytes(const Geometry& g)
 bool fold_supported(const Geometry& g)
 {
     return !use_generic(g) && !deep_class(g) && !rtw_class(g) && g.n_ant == 64 && (g.n_ipo == 16 || g.n_ipo == 32 || g.n_ipo == 64);
+}
+// ... and which of its two kernels: gemm-units of whole chunk spans (128 samples; 256 for n_ipo 64) run fused16_fold_stream_kernel,
+// whose chunk addressing is scalar; any other n_time runs fused16_fold_kernel, which addresses such units row by row
+bool fold_streams(const Geometry& g)
+{
+    return g.fold && fold_supported(g) && g.n_time > 0 && g.n_time % (g.n_ipo == 64 ? 256 : 128) == 0;
 }
 size_t weight_fold_image_bytes(const Geometry& g)
 {
