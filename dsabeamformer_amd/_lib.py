@@ -13,6 +13,8 @@ BF_NOT_READY = 1
 BF_ERR_INVALID, BF_ERR_DEVICE, BF_ERR_NO_DEVICE, BF_ERR_STATE = -1, -2, -3, -4
 BF_DETECT_CANONICAL, BF_DETECT_FAST, BF_DETECT_CONTRACTED = 0, 1, 2
 BF_CAL_PHASE, BF_CAL_FULL = 0, 1
+BF_NULL_MAX = 4
+BF_NULL_SCALED, BF_NULL_CLIP = 0, 1
 BF_SK_DEAD, BF_SK_LOW, BF_SK_HIGH = 1, 2, 4   # cell codes of bf_sk_select (include/dsabf.h)
 BF_STOKES_MAX_BEAMS = 16
 
@@ -70,6 +72,12 @@ class BfCalOptions(C.Structure):
     """Mirror of ``bf_cal_options`` (include/dsabf.h)."""
 
     _fields_ = [("tol", C.c_double), ("max_iter", C.c_int), ("ref_ant", C.c_int), ("joint_pol", C.c_int)]
+
+
+class BfNullOptions(C.Structure):
+    """Mirror of ``bf_null_options`` (include/dsabf.h)."""
+
+    _fields_ = [("min_ratio", C.c_double), ("tol", C.c_double), ("n_null", C.c_int), ("max_iter", C.c_int), ("pol", C.c_int)]
 
 
 class BfSkOptions(C.Structure):
@@ -139,6 +147,11 @@ SIGNATURES = {
     "bf_solve_gains_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(BfCalOptions), C.c_void_p, C.c_void_p,
                                         C.c_void_p]),
     "bf_calibrate_weights_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "bf_null_default_options": (C.c_int, [C.POINTER(BfNullOptions)]),
+    "bf_null_vec_entries": (C.c_size_t, [C.POINTER(BfConfig), C.c_int]),
+    "bf_null_solve_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(BfNullOptions), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bf_null_weights_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]),
     "bf_sk_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "bf_sk_entries": (C.c_size_t, [C.POINTER(BfConfig)]),
     "bf_sk_default_options": (C.c_int, [C.POINTER(BfSkOptions)]),
@@ -313,6 +326,9 @@ SIGNATURES = {
     "bfh_run_debug_observation3": (C.c_int, [C.POINTER(BfConfig), C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p,
                                              C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_int),
                                              C.POINTER(C.c_float), C.c_int, C.c_char_p, C.c_void_p]),
+    "bfh_run_debug_observation4": (C.c_int, [C.POINTER(BfConfig), C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p,
+                                             C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_int),
+                                             C.POINTER(C.c_float), C.c_int, C.c_char_p, C.c_char_p, C.c_void_p]),
 }
 
 

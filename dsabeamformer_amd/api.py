@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-from ._lib import BF_CAL_FULL, BF_CAL_PHASE, BfCalOptions, BfCondOptions, BfConfig, BfSkOptions, DsabfError, BfSpsCandidate, BfSpsPeak, BfSpsStat, check, load
+from ._lib import BF_CAL_FULL, BF_CAL_PHASE, BF_NULL_CLIP, BF_NULL_SCALED, BfCalOptions, BfNullOptions, BfCondOptions, BfConfig, BfSkOptions, DsabfError, BfSpsCandidate, BfSpsPeak, BfSpsStat, check, load
 
 
 def debug_config(**over) -> BfConfig:
@@ -173,6 +173,30 @@ class Beamformer(_Owner):
     def gain_entries(self, joint_pol: bool = False) -> int:
         """bf_cal_gain_entries: (joint_pol ? 1 : n_pol) * n_freq * n_ant complex entries (two float64 each)."""
         return self._lib.bf_cal_gain_entries(C.byref(self.cfg), int(bool(joint_pol)))
+
+    def null_solve(self, d_vis, d_vecs, d_eig, d_info, flags=None, n_null: int = 1, min_ratio: float = 4.0, tol: float = 1e-6,
+                   max_iter: int = 200, pol: int = -1, stream: int = 0) -> None:
+        """bf_null_solve_device (docs/NULLING.md): the visibilities d_vis (as ``correlate`` leaves them) -> d_vecs, float64
+        [freq][n_null][ant]{re, im} (``null_vec_entries(n_null)`` complex entries; exact zeros where unused), d_eig, float64
+        [freq][n_null + 1] (the lambdas, then the trace), and d_info, int32 [freq][1 + 2 n_null] (n_used, then {iterations, status} per
+        vector).  ``flags``: uint8 [ant] on the device or None; ``pol`` -1: the polarisations are added first."""
+        opt = BfNullOptions(float(min_ratio), float(tol), int(n_null), int(max_iter), int(pol))
+        check(self._lib.bf_null_solve_device(self._h, _ptr(d_vis), _ptr(flags), C.byref(opt), _ptr(d_vecs), _ptr(d_eig), _ptr(d_info),
+                                             C.c_void_p(stream)))
+
+    def null_weights(self, d_w_in, d_vecs, d_info, d_w_out, n_null: int, flags=None, mode: str = "scaled", scale=None, stream: int = 0) -> None:
+        """bf_null_weights_device: d_w_out = d_w_in with the used vectors of every channel projected out, w' = w - sum_j conj(u_j) (u_j^T w),
+        times k_f = min(1, 127 / max |part|) (``mode`` "scaled") or 1 ("clip"), rounded half to even and clipped to +-127; int8
+        [freq][ant][beam]{re, im}, the array ``set_weights_device`` takes.  ``scale``: float64 [freq] on the device or None, receives k_f."""
+        modes = {"scaled": BF_NULL_SCALED, "clip": BF_NULL_CLIP}
+        if mode not in modes:
+            raise ValueError("mode must be 'scaled' or 'clip', not %r" % (mode,))
+        check(self._lib.bf_null_weights_device(self._h, _ptr(d_w_in), _ptr(d_vecs), _ptr(d_info), int(n_null), _ptr(flags), modes[mode],
+                                               _ptr(d_w_out), _ptr(scale), C.c_void_p(stream)))
+
+    def null_vec_entries(self, n_null: int = 1) -> int:
+        """bf_null_vec_entries: n_freq * n_null * n_ant complex entries (two float64 each); 0 for an n_null outside 1 ... 4."""
+        return self._lib.bf_null_vec_entries(C.byref(self.cfg), int(n_null))
 
     def expand(self, d_in, nbytes: int, d_out, stream: int = 0) -> None:
         check(self._lib.bf_expand_device(self._h, _ptr(d_in), int(nbytes), _ptr(d_out), C.c_void_p(stream)))

@@ -62,6 +62,14 @@
 //                                                   sample], one record per launch, to stokes_file.  With -R: stokes_file.<rank>.
 //   beam -E vis_file -G gains_file -f ant_file     the solver leaves the listed antennas out (their gains are exactly zero);
 //   beam ... -A gains_file -f ant_file              the listed antennas get zero weights.
+//   beam -E vis_file -Z null_file [-y n_null[:min_ratio]] [-f ant_file]
+//                                                   the spatial null (docs/NULLING.md), no observation: the dominant eigenvectors of every
+//                                                   record of a -V file (up to n_null [1] per channel, each used only if it stands min_ratio [4]
+//                                                   above the rest) written as one record of null_file.  -G may be given in the same run.
+//                                                   With -R world -r rank: vis_file.<rank> -> null_file.<rank>.
+//   beam ... -Z null_file [-f ant_file]             DEBUG run or observation mode: the vectors of the last record of null_file are projected
+//                                                   out of the steering weights before they are set (after -A's gains; -x follows the same
+//                                                   weights).  With -R: null_file.<rank>.
 //
 // With the reference's `make debug` geometry (default) it generates synthetic point-source voltages on the CPU,
 // streams them through the observation loop and writes bin/data.py (dedispersed beam responses, one row per source)
@@ -122,13 +130,16 @@ int main(int argc, char* argv[])
     bf_sk_options sk_opt;           // -t n_sigma, -m centre
     bf_sk_default_options(&sk_opt);
     bool sk_sigma_given = false, sk_centre_given = false;
-    std::string ant_flags_path;     // -f: antenna flags for -E or -A
+    std::string ant_flags_path;     // -f: antenna flags for -E, -A or -Z
+    std::string null_path, null_spec;   // -Z: the null file (written with -E, applied otherwise); -y n_null[:min_ratio]
+    bf_null_options null_opt;
+    bf_null_default_options(&null_opt);
     std::string stokes_path, stokes_list;   // -x: where the Stokes beams go; -b: the beams to follow
     int stokes_int = 0;                     // -l: samples per integration window (0: N_AVERAGING)
     bool stokes_int_given = false;
 
     int arg = 0;
-    while ((arg = getopt(argc, argv, "s:g:p:d:o:D:a:c:k:K:j:w:R:r:I:M:N:T:W:Q:S:B:C:i:V:L:E:G:A:n:U:F:Y:J:e:O:q:t:m:f:x:b:l:zPXuvhH")) != -1) {  // src/beamformer.cu:41-43 (+ -o -D -a -v)
+    while ((arg = getopt(argc, argv, "s:g:p:d:o:D:a:c:k:K:j:w:R:r:I:M:N:T:W:Q:S:B:C:i:V:L:E:G:A:n:U:F:Y:J:e:O:q:t:m:f:x:b:l:Z:y:zPXuvhH")) != -1) {  // src/beamformer.cu:41-43 (+ -o -D -a -v)
         switch (arg) {
             case 's': sources = optarg; break;                 // :77-89
             case 'g': opt.gpu = atoi(optarg); break;           // :92-100
@@ -171,6 +182,8 @@ int main(int argc, char* argv[])
             case 't': sk_opt.n_sigma = atof(optarg); sk_sigma_given = true; break;
             case 'm': sk_opt.centre = atof(optarg); sk_centre_given = true; break;
             case 'f': ant_flags_path = optarg; break;
+            case 'Z': null_path = optarg; break;
+            case 'y': null_spec = optarg; break;
             case 'x': stokes_path = optarg; break;
             case 'b': stokes_list = optarg; break;
             case 'l': stokes_int = atoi(optarg); stokes_int_given = true; break;
@@ -226,6 +239,13 @@ int main(int argc, char* argv[])
                              " -x file -b b0,b1,... [-l n_int]   observation mode: full-Stokes follow-up beams -- I, Q, U, V (exact int64) of up to 16\n"
                              "                         of the beams per window of n_int voltage samples [N_AVERAGING; 1 = full time resolution; must\n"
                              "                         divide N_OUTPUTS_PER_GEMM * N_AVERAGING], one record per launch, to file (with -R: file.<rank>)\n"
+                             " -E vis_file -Z null_file [-y n_null[:min_ratio]]   the spatial null, no observation: the dominant eigenvectors of\n"
+                             "                         every record of a -V file (power iteration on the device; up to n_null [1] of 1 .. 4 per channel,\n"
+                             "                         each used only if it stands min_ratio [4] above the mean of the rest) as one record of null_file;\n"
+                             "                         -G may be given too; -f leaves antennas out; with -R world -r rank: vis_file.<rank> -> null_file.<rank>\n"
+                             " -Z null_file            DEBUG run and observation mode: the vectors of the last record of null_file are projected out of\n"
+                             "                         the steering weights (after -A's gains; -x follows the same weights; -f zeroes antennas); its\n"
+                             "                         NANT / NFREQ / FIRST_CHANNEL must be the run's; with -R: null_file.<rank>\n"
                              " -H                      this text\n";
                 return EXIT_SUCCESS;
             default: usage(true, std::cerr); return EXIT_FAILURE;
@@ -348,13 +368,13 @@ int main(int argc, char* argv[])
         fprintf(stderr, "beam: -O / -q / -t / -m belong to the select mode: give -e moments_file\n");
         return EXIT_FAILURE;
     }
-    if (!ant_flags_path.empty() && solve_vis.empty() && apply_gains.empty()) {
-        fprintf(stderr, "beam: -f (antenna flags) belongs to the gain solver or to calibrated weights: give -E vis_file or -A gains_file\n");
+    if (!ant_flags_path.empty() && solve_vis.empty() && apply_gains.empty() && null_path.empty()) {
+        fprintf(stderr, "beam: -f (antenna flags) belongs to the solvers or to conditioned weights: give -E vis_file, -A gains_file or -Z null_file\n");
         return EXIT_FAILURE;
     }
     if (!select_path.empty()) {   // select mode: host only
-        if (observe_mode || !solve_vis.empty() || !apply_gains.empty()) {
-            fprintf(stderr, "beam: -e (select flags) runs nothing else: leave out -j / -k / -E / -A\n");
+        if (observe_mode || !solve_vis.empty() || !apply_gains.empty() || !null_path.empty()) {
+            fprintf(stderr, "beam: -e (select flags) runs nothing else: leave out -j / -k / -E / -A / -Z\n");
             return EXIT_FAILURE;
         }
         if (select_ant_path.empty()) {
@@ -376,14 +396,42 @@ int main(int argc, char* argv[])
         fprintf(stderr, "beam: -P (joint polarisations) belongs to the gain solver: give -E vis_file -G gains_file\n");
         return EXIT_FAILURE;
     }
-    std::vector<uint8_t> ant_flags;   // -f: read before any device is touched, against NANT of the vis file (-E) or of the run (-A)
+    if (!null_spec.empty()) {   // -y n_null[:min_ratio]: the solver's options
+        if (solve_vis.empty() || null_path.empty()) {
+            fprintf(stderr, "beam: -y (vectors per channel) belongs to the spatial null's solve mode: give -E vis_file -Z null_file\n");
+            return EXIT_FAILURE;
+        }
+        char* end = nullptr;
+        const long n = strtol(null_spec.c_str(), &end, 10);
+        double ratio = null_opt.min_ratio;
+        bool ok = end != null_spec.c_str() && n >= 1 && n <= BF_NULL_MAX;
+        if (ok && *end == ':') {
+            char* rend = nullptr;
+            ratio = strtod(end + 1, &rend);
+            ok = rend != end + 1 && !*rend && ratio >= 0.0;
+        } else if (ok && *end) {
+            ok = false;
+        }
+        if (!ok) {
+            fprintf(stderr, "beam: -y %s: n_null must be 1 .. %d and min_ratio, if given, a number >= 0\n", null_spec.c_str(), BF_NULL_MAX);
+            return EXIT_FAILURE;
+        }
+        null_opt.n_null = (int)n;
+        null_opt.min_ratio = ratio;
+    }
+    const bool sharded_files = world > 1 && rank >= 0 && rank < world;   // -R: the null's files carry the rank, as -V's do
+    if (!solve_vis.empty() && !null_path.empty() && sharded_files) {
+        solve_vis += "." + std::to_string(rank);
+        null_path += "." + std::to_string(rank);
+    }
+    std::vector<uint8_t> ant_flags;   // -f: read before any device is touched, against NANT of the vis file (-E) or of the run (-A, -Z)
     if (!solve_vis.empty()) {   // solve mode: no observation of either kind
         if (junk_blocks >= 0 || !ring_key.empty()) {
             fprintf(stderr, "beam: -E (gain solver) runs no observation: leave out -j / -k\n");
             return EXIT_FAILURE;
         }
-        if (solve_gains_path.empty()) {
-            fprintf(stderr, "beam: -E needs -G gains_file (where the gains go)\n");
+        if (solve_gains_path.empty() && null_path.empty()) {
+            fprintf(stderr, "beam: -E needs -G gains_file (where the gains go) or -Z null_file (where the interferer vectors go)\n");
             return EXIT_FAILURE;
         }
         if (!apply_gains.empty()) {
@@ -423,6 +471,29 @@ int main(int argc, char* argv[])
             opt.ant_flags = ant_flags.data();
         }
     }
+    // -Z without -E: read before any device is touched, against the same geometry as -A
+    null_vectors nulls;
+    if (!null_path.empty() && solve_vis.empty()) {
+        const bool observe = junk_blocks >= 0 || !ring_key.empty();
+        bf_config gcfg;
+        bf_config_default(&gcfg, observe ? 0 : 1);
+        const int n_freq = observe && world >= 1 && gcfg.n_freq % world == 0 ? gcfg.n_freq / world : gcfg.n_freq;
+        const int first = observe && rank >= 0 ? rank * n_freq : 0;
+        if (observe && sharded_files) null_path += "." + std::to_string(rank);
+        std::string why;
+        if (!read_null_vectors(null_path.c_str(), gcfg.n_ant, n_freq, first, &nulls, &why)) {
+            fprintf(stderr, "beam: -Z %s\n", why.c_str());
+            return EXIT_FAILURE;
+        }
+        opt.nulls = &nulls;
+        if (!ant_flags_path.empty() && ant_flags.empty()) {
+            if (!read_index_file(ant_flags_path.c_str(), gcfg.n_ant, &ant_flags, &why)) {
+                fprintf(stderr, "beam: -f %s\n", why.c_str());
+                return EXIT_FAILURE;
+            }
+        }
+        if (!ant_flags.empty()) opt.ant_flags = ant_flags.data();
+    }
     opt.positions = positions.empty() ? nullptr : positions.c_str();
     opt.directions = directions.empty() ? nullptr : directions.c_str();
     opt.sources = sources.empty() ? nullptr : sources.c_str();
@@ -437,15 +508,26 @@ int main(int argc, char* argv[])
     char name[256];
     if (bf_device_name(opt.device, name, sizeof name) == BF_OK) std::cout << "Selected: " << name << std::endl;
 
-    if (!solve_vis.empty()) {   // -E / -G: the gain solver on a file of visibilities
+    if (!solve_vis.empty()) {   // -E / -G / -Z: the gain solver and the spatial null on a file of visibilities
         uint64_t n_records = 0;
-        int src = solve_vis_file(solve_vis.c_str(), solve_gains_path.c_str(), solve_joint, opt.device, &n_records, std::cout,
-                                 ant_flags.empty() ? nullptr : ant_flags.data());
-        if (src != BF_OK) {
-            fprintf(stderr, "GPUassert: %s (%d)\n", bf_last_error(), src);
-            return EXIT_FAILURE;
+        if (!solve_gains_path.empty()) {
+            int src = solve_vis_file(solve_vis.c_str(), solve_gains_path.c_str(), solve_joint, opt.device, &n_records, std::cout,
+                                     ant_flags.empty() ? nullptr : ant_flags.data());
+            if (src != BF_OK) {
+                fprintf(stderr, "GPUassert: %s (%d)\n", bf_last_error(), src);
+                return EXIT_FAILURE;
+            }
+            std::cout << "Wrote " << n_records << " gain records to " << solve_gains_path << std::endl;
         }
-        std::cout << "Wrote " << n_records << " gain records to " << solve_gains_path << std::endl;
+        if (!null_path.empty()) {
+            int src = null_vis_file(solve_vis.c_str(), null_path.c_str(), null_opt, opt.device, &n_records, std::cout,
+                                    ant_flags.empty() ? nullptr : ant_flags.data());
+            if (src != BF_OK) {
+                fprintf(stderr, "GPUassert: %s (%d)\n", bf_last_error(), src);
+                return EXIT_FAILURE;
+            }
+            std::cout << "Wrote " << n_records << " null records to " << null_path << std::endl;
+        }
         return 0;
     }
 
@@ -545,7 +627,8 @@ int main(int argc, char* argv[])
         oopt.comm = comm;
         oopt.incoherent_beam = ib_beam;
         oopt.gains = gains_layer.empty() ? nullptr : gains_layer.data();
-        oopt.ant_flags = gains_layer.empty() || ant_flags.empty() ? nullptr : ant_flags.data();
+        oopt.nulls = opt.nulls;
+        oopt.ant_flags = (gains_layer.empty() && !opt.nulls) || ant_flags.empty() ? nullptr : ant_flags.data();
         const bf_config& sink_cfg = comm ? full_cfg : pcfg;
         if (comm && rank != 0) {          // only the gather root has a consumer
             out_ring.clear();

@@ -62,8 +62,10 @@ int bf_set_switch(bf_handle* h, const char* name, int value)
         h->dm_ring = value != 0;         // takes effect at the next bf_dm_stream_create
     } else if (!strcmp(name, "cal_resident")) {
         h->cal_resident = value != 0;    // 0: bf_solve_gains_device streams the visibilities at every antenna count (same bits)
+    } else if (!strcmp(name, "null_resident")) {
+        h->null_resident = value != 0;   // 0: bf_null_solve_device streams the visibilities at every antenna count (same bits)
     } else {
-        return fail(BF_ERR_INVALID, "unknown switch \"%s\" (tsplit, rtw_kout, lds_pad, dm_wide, dm_ring, paired, fold, coalesce, cal_resident)", name);
+        return fail(BF_ERR_INVALID, "unknown switch \"%s\" (tsplit, rtw_kout, lds_pad, dm_wide, dm_ring, paired, fold, coalesce, cal_resident, null_resident)", name);
     }
     return BF_OK;
 }

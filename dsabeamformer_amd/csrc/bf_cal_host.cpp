@@ -1,5 +1,6 @@
 // bf_cal_host.cpp -- host mirror of the gain solver (include/dsabf_host.hpp: gains_file_sink, read_gains_layer, solve_vis_file,
-// set_weights_calibrated, and the flag files that feed them: read_index_file, read_moments_sum, select_moments_file; docs/CALIBRATION.md).  The C-ABI's solver and weight calls take device pointers and the C-ABI has no device
+// set_weights_calibrated, and the flag files that feed them: read_index_file, read_moments_sum, select_moments_file; docs/CALIBRATION.md)
+// and of the spatial null (null_file_sink, read_null_vectors, null_vis_file, set_weights_conditioned; docs/NULLING.md).  The C-ABI's solver and weight calls take device pointers and the C-ABI has no device
 // allocator, so this is the one host-mirror file that allocates device memory itself.
 #include <fcntl.h>
 #include <hip/hip_runtime.h>
@@ -322,7 +323,14 @@ int select_moments_file(const char* moments_path, const bf_sk_options& opt, cons
 
 int set_weights_calibrated(bf_handle* h, int device, const int8_t* w, const double* gains_layer, int8_t* w_set, const uint8_t* ant_flags)
 {
-    if (!h || !w || !gains_layer) return set_error(BF_ERR_INVALID, "set_weights_calibrated: NULL argument");
+    if (!gains_layer) return set_error(BF_ERR_INVALID, "set_weights_calibrated: NULL argument");
+    return set_weights_conditioned(h, device, w, gains_layer, nullptr, w_set, ant_flags);
+}
+
+int set_weights_conditioned(bf_handle* h, int device, const int8_t* w, const double* gains_layer, const null_vectors* nulls, int8_t* w_set,
+                            const uint8_t* ant_flags)
+{
+    if (!h || !w || (!gains_layer && !nulls)) return set_error(BF_ERR_INVALID, "set_weights_conditioned: NULL argument");
     bf_config cfg;
     int rc = bf_get_config(h, &cfg);
     if (rc != BF_OK) return rc;
@@ -330,19 +338,165 @@ int set_weights_calibrated(bf_handle* h, int device, const int8_t* w, const doub
     device_scratch mem;
     hipError_t e = mem.begin(device);
     int8_t* d_w = nullptr;
-    double* d_g = nullptr;
+    double *d_g = nullptr, *d_vecs = nullptr;
+    int32_t* d_info = nullptr;
     uint8_t* d_flags = nullptr;
+    if (nulls && (nulls->n_null < 1 || nulls->n_null > BF_NULL_MAX || nulls->vecs.size() != (size_t)cfg.n_freq * nulls->n_null * cfg.n_ant * 2 ||
+                  nulls->info.size() != (size_t)cfg.n_freq * (1 + 2 * nulls->n_null)))
+        return set_error(BF_ERR_INVALID, "set_weights_conditioned: the vectors are not of this geometry");
     if (e == hipSuccess && ant_flags) e = mem.alloc(&d_flags, (size_t)cfg.n_ant);
     if (e == hipSuccess && ant_flags) e = hipMemcpy(d_flags, ant_flags, (size_t)cfg.n_ant, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = mem.alloc(&d_w, w_bytes);
-    if (e == hipSuccess) e = mem.alloc(&d_g, g_bytes);
     if (e == hipSuccess) e = hipMemcpy(d_w, w, w_bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_g, gains_layer, g_bytes, hipMemcpyHostToDevice);
-    if (e != hipSuccess) return hip_fail("set_weights_calibrated", e);
-    if ((rc = calibrate_weights(h, d_w, d_g, d_flags, BF_CAL_PHASE, d_w)) != BF_OK) return rc;   // (in place; the null stream)
+    if (e == hipSuccess && gains_layer) e = mem.alloc(&d_g, g_bytes);
+    if (e == hipSuccess && gains_layer) e = hipMemcpy(d_g, gains_layer, g_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess && nulls) e = mem.alloc(&d_vecs, nulls->vecs.size() * sizeof(double));
+    if (e == hipSuccess && nulls) e = hipMemcpy(d_vecs, nulls->vecs.data(), nulls->vecs.size() * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess && nulls) e = mem.alloc(&d_info, nulls->info.size() * sizeof(int32_t));
+    if (e == hipSuccess && nulls) e = hipMemcpy(d_info, nulls->info.data(), nulls->info.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return hip_fail("set_weights_conditioned", e);
+    // (in place, on the null stream: the calibration first, then the null)
+    if (gains_layer && (rc = calibrate_weights(h, d_w, d_g, d_flags, BF_CAL_PHASE, d_w)) != BF_OK) return rc;
+    if (nulls && (rc = null_weights(h, d_w, d_vecs, d_info, nulls->n_null, d_flags, BF_NULL_SCALED, d_w)) != BF_OK) return rc;
     if ((rc = bf_set_weights_device(h, d_w, nullptr)) != BF_OK) return rc;
-    if ((e = hipDeviceSynchronize()) != hipSuccess) return hip_fail("set_weights_calibrated", e);    // d_w is freed on return
-    if (w_set && (e = hipMemcpy(w_set, d_w, w_bytes, hipMemcpyDeviceToHost)) != hipSuccess) return hip_fail("set_weights_calibrated", e);
+    if ((e = hipDeviceSynchronize()) != hipSuccess) return hip_fail("set_weights_conditioned", e);    // d_w is freed on return
+    if (w_set && (e = hipMemcpy(w_set, d_w, w_bytes, hipMemcpyDeviceToHost)) != hipSuccess) return hip_fail("set_weights_conditioned", e);
+    return BF_OK;
+}
+
+// ---- the spatial null (docs/NULLING.md) ------------------------------------------------------------------------------------------
+
+null_file_sink::null_file_sink(int n_ant, int n_freq, int first_channel, int n_null, const char* path)
+    : n_vec_doubles((size_t)n_freq * n_null * n_ant * 2), n_eig((size_t)n_freq * (n_null + 1)), n_info((size_t)n_freq * (1 + 2 * n_null))
+{
+    fd = ::open(path, O_CREAT | O_TRUNC | O_WRONLY, 0644);
+    if (fd < 0) return;
+    char header[kHeaderBytes];
+    ::memset(header, 0, sizeof(header));
+    ::snprintf(header, sizeof(header),
+               "HDR_VERSION 1.0\nHDR_SIZE %zu\nINSTRUMENT DSA\nCONTENT nullvecs\nDTYPE float64\nENDIAN little\nLAYOUT freq,vec,ant,reim\n"
+               "RECORD_HEADER_BYTES %zu\nNANT %d\nNPOL 1\nNFREQ %d\nFIRST_CHANNEL %d\nNNULL %d\nEIG float64 freq,(lambdas,trace)\n"
+               "INFO int32 freq,(n_used,(iterations,status) per vector)\n",
+               kHeaderBytes, kRecordBytes, n_ant, n_freq, first_channel, n_null);
+    if (!write_all(fd, header, sizeof(header))) close();
+}
+
+null_file_sink::~null_file_sink() { close(); }
+
+bool null_file_sink::deliver(uint64_t first_block, uint64_t n_columns_per_pol, const double* vecs, const double* eig, const int32_t* info)
+{
+    if (fd < 0) return false;
+    const uint64_t rec[2] = {first_block, n_columns_per_pol};
+    static_assert(sizeof rec == kRecordBytes, "the record header is two uint64");
+    if (!write_all(fd, reinterpret_cast<const char*>(rec), sizeof rec) ||
+        !write_all(fd, reinterpret_cast<const char*>(vecs), n_vec_doubles * sizeof(double)) ||
+        !write_all(fd, reinterpret_cast<const char*>(eig), n_eig * sizeof(double)) ||
+        !write_all(fd, reinterpret_cast<const char*>(info), n_info * sizeof(int32_t)))
+        return false;
+    records++;
+    return true;
+}
+
+void null_file_sink::close()
+{
+    if (fd >= 0) ::close(fd);
+    fd = -1;
+}
+
+bool read_null_vectors(const char* path, int n_ant, int n_freq, int first_channel, null_vectors* out, std::string* why)
+{
+    record_file_header h;
+    if (!read_record_file_header(path, &h, why)) return false;
+    auto no = [&](const std::string& msg) {
+        if (why) *why = std::string(path) + ": " + msg;
+        return false;
+    };
+    if (h.content != "nullvecs" || h.dtype != "float64") return no("CONTENT " + h.content + " is not a file of interferer vectors");
+    if (h.n_ant != n_ant || h.n_freq != n_freq || h.first_channel != first_channel)
+        return no("NANT " + std::to_string(h.n_ant) + " NFREQ " + std::to_string(h.n_freq) + " FIRST_CHANNEL " + std::to_string(h.first_channel) +
+                  " do not match this run (" + std::to_string(n_ant) + " antennas, " + std::to_string(n_freq) + " channels from " +
+                  std::to_string(first_channel) + ")");
+    fd_guard f{::open(path, O_RDONLY)};
+    char text[4097];
+    if (f.fd < 0 || !pread_all(f.fd, text, 4096, 0)) return no("cannot be read");
+    text[4096] = 0;
+    const char* key = ::strstr(text, "\nNNULL ");
+    const int n_null = key ? atoi(key + 7) : 0;
+    if (n_null < 1 || n_null > BF_NULL_MAX) return no("its header has no NNULL 1 .. " + std::to_string(BF_NULL_MAX));
+    const size_t vec_bytes = (size_t)n_freq * n_null * n_ant * 2 * sizeof(double), eig_bytes = (size_t)n_freq * (n_null + 1) * sizeof(double);
+    const size_t info_bytes = (size_t)n_freq * (1 + 2 * n_null) * sizeof(int32_t);
+    const size_t rec_bytes = h.record_header_bytes + vec_bytes + eig_bytes + info_bytes, body = h.file_bytes - h.header_bytes;
+    if (body == 0 || body % rec_bytes) return no("holds no whole record");
+    const off_t last = (off_t)(h.header_bytes + body - rec_bytes + h.record_header_bytes);
+    out->n_null = n_null;
+    out->vecs.resize(vec_bytes / sizeof(double));
+    out->info.resize(info_bytes / sizeof(int32_t));
+    if (!pread_all(f.fd, out->vecs.data(), vec_bytes, last) || !pread_all(f.fd, out->info.data(), info_bytes, last + (off_t)(vec_bytes + eig_bytes)))
+        return no("its last record cannot be read");
+    return true;
+}
+
+int null_vis_file(const char* vis_path, const char* null_path, const bf_null_options& opt, int device, uint64_t* n_records, std::ostream& log,
+                  const uint8_t* ant_flags)
+{
+    record_file_header vh;
+    std::string why;
+    if (!read_record_file_header(vis_path, &vh, &why)) return set_error(BF_ERR_INVALID, why.c_str());
+    if (vh.content != "visibilities" || vh.dtype != "int64") return set_error(BF_ERR_INVALID, (std::string(vis_path) + " is not a file of visibilities").c_str());
+    bf_config cfg;
+    bf_config_default(&cfg, /*debug=*/0);   // the solver reads n_ant, n_pol and n_freq of the handle's geometry only
+    cfg.n_ant = vh.n_ant;
+    cfg.n_pol = vh.n_pol;
+    cfg.n_freq = vh.n_freq;
+    const size_t n_vis = 2 * bf_corr_entries(&cfg), n_vecs = 2 * bf_null_vec_entries(&cfg, opt.n_null);
+    if (!n_vecs) return set_error(BF_ERR_INVALID, "null_vis_file: n_null is outside 1 ... 4");
+    const size_t n_eig = (size_t)cfg.n_freq * (opt.n_null + 1), n_info = (size_t)cfg.n_freq * (1 + 2 * opt.n_null);
+    const size_t rec_bytes = vh.record_header_bytes + n_vis * sizeof(int64_t), body = vh.file_bytes - vh.header_bytes;
+    if (body % rec_bytes) return set_error(BF_ERR_INVALID, (std::string(vis_path) + " ends inside a record").c_str());
+    fd_guard in{::open(vis_path, O_RDONLY)};
+    if (in.fd < 0) return set_error(BF_ERR_INVALID, (std::string(vis_path) + " cannot be opened").c_str());
+    bf_handle* h = nullptr;
+    int rc = bf_create(&cfg, device, &h);
+    if (rc != BF_OK) return rc;
+    struct handle_guard {
+        bf_handle* h;
+        ~handle_guard() { bf_destroy(h); }
+    } hg{h};
+    null_file_sink sink(cfg.n_ant, cfg.n_freq, vh.first_channel, opt.n_null, null_path);
+    if (!sink.is_open()) return set_error(BF_ERR_INVALID, (std::string(null_path) + " cannot be created").c_str());
+    device_scratch mem;
+    hipError_t e = mem.begin(device);
+    int64_t* d_vis = nullptr;
+    double *d_vecs = nullptr, *d_eig = nullptr;
+    int32_t* d_info = nullptr;
+    uint8_t* d_flags = nullptr;
+    if (e == hipSuccess && ant_flags) e = mem.alloc(&d_flags, (size_t)cfg.n_ant);
+    if (e == hipSuccess && ant_flags) e = hipMemcpy(d_flags, ant_flags, (size_t)cfg.n_ant, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = mem.alloc(&d_vis, n_vis * sizeof(int64_t));
+    if (e == hipSuccess) e = mem.alloc(&d_vecs, n_vecs * sizeof(double));
+    if (e == hipSuccess) e = mem.alloc(&d_eig, n_eig * sizeof(double));
+    if (e == hipSuccess) e = mem.alloc(&d_info, n_info * sizeof(int32_t));
+    if (e != hipSuccess) return hip_fail("null_vis_file", e);
+    std::vector<int64_t> vis(n_vis);
+    std::vector<double> vecs(n_vecs), eig(n_eig);
+    std::vector<int32_t> info(n_info);
+    uint64_t used = 0, channels = 0;
+    for (size_t at = vh.header_bytes; at < vh.file_bytes; at += rec_bytes) {
+        uint64_t rec[2];
+        if (!pread_all(in.fd, rec, sizeof rec, (off_t)at) || !pread_all(in.fd, vis.data(), n_vis * sizeof(int64_t), (off_t)(at + sizeof rec)))
+            return set_error(BF_ERR_INVALID, (std::string(vis_path) + ": a record cannot be read").c_str());
+        if ((e = hipMemcpy(d_vis, vis.data(), n_vis * sizeof(int64_t), hipMemcpyHostToDevice)) != hipSuccess) return hip_fail("null_vis_file", e);
+        if ((rc = null_solve(h, d_vis, d_flags, opt, d_vecs, d_eig, d_info)) != BF_OK) return rc;
+        if ((e = hipMemcpy(vecs.data(), d_vecs, n_vecs * sizeof(double), hipMemcpyDeviceToHost)) != hipSuccess) return hip_fail("null_vis_file", e);
+        if ((e = hipMemcpy(eig.data(), d_eig, n_eig * sizeof(double), hipMemcpyDeviceToHost)) != hipSuccess) return hip_fail("null_vis_file", e);
+        if ((e = hipMemcpy(info.data(), d_info, n_info * sizeof(int32_t), hipMemcpyDeviceToHost)) != hipSuccess) return hip_fail("null_vis_file", e);
+        if (!sink.deliver(rec[0], rec[1], vecs.data(), eig.data(), info.data()))
+            return set_error(BF_ERR_INVALID, (std::string(null_path) + ": write failed").c_str());
+        for (size_t i = 0; i < n_info; i += 1 + 2 * (size_t)opt.n_null, channels++) used += (uint64_t)info[i];
+    }
+    if (n_records) *n_records = sink.get_records_written();
+    log << "Spatial null: " << sink.get_records_written() << " records of " << cfg.n_freq << " channels (" << cfg.n_ant << " antennas, up to " << opt.n_null
+        << " vectors each), " << used << " vectors used in " << channels << " channel solves" << std::endl;
     return BF_OK;
 }
 

@@ -357,9 +357,22 @@ int bfh_run_debug_observation3(const bf_config* cfg, int gpu, const char* positi
                                const char* output, int device, int verbose, float* ded_out, size_t ded_capacity, int* n_pt_sources,
                                float* observation_ms, int per_unit_launches, const char* gains_file, int8_t* weights_out)
 {
+    return bfh_run_debug_observation4(cfg, gpu, positions, directions, sources, output, device, verbose, ded_out, ded_capacity, n_pt_sources,
+                                      observation_ms, per_unit_launches, gains_file, nullptr, weights_out);
+}
+int bfh_run_debug_observation4(const bf_config* cfg, int gpu, const char* positions, const char* directions, const char* sources,
+                               const char* output, int device, int verbose, float* ded_out, size_t ded_capacity, int* n_pt_sources,
+                               float* observation_ms, int per_unit_launches, const char* gains_file, const char* null_file, int8_t* weights_out)
+{
     if (!cfg) return BF_ERR_INVALID;
     debug_run_options opt;
     std::vector<double> gains_layer;
+    null_vectors nulls;
+    if (null_file) {
+        std::string why;
+        if (!read_null_vectors(null_file, cfg->n_ant, cfg->n_freq, 0, &nulls, &why)) return set_error(BF_ERR_INVALID, why.c_str());
+        opt.nulls = &nulls;
+    }
     if (gains_file) {
         std::string why;
         if (!read_gains_layer(gains_file, cfg->n_ant, cfg->n_freq, 0, &gains_layer, &why)) return set_error(BF_ERR_INVALID, why.c_str());

@@ -38,6 +38,7 @@ struct bf_handle {
     bool no_fold = false;         // bf_set_switch("fold", 0): never select the antenna-fold kernel
     bool dm_ring = true;          // bf_set_switch("dm_ring", 0): the next bf_dm_stream_create takes the linear buffer (test switch)
     bool cal_resident = true;     // bf_set_switch("cal_resident", 0): the gain solver re-reads the visibilities at every antenna count (test switch)
+    bool null_resident = true;    // bf_set_switch("null_resident", 0): the same for bf_null_solve_device (test switch)
     // bf_enqueue_gemm_unit coalesces (see flush_units): the caller keeps the reference's one-unit-per-call loop
     // (src/beamformer.cu:454-519), the device sees one launch per run of consecutive gemm-units.
     struct pending_unit {

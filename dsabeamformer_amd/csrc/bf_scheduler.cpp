@@ -337,9 +337,10 @@ int run_debug_observation(const bf_config& cfg, const debug_run_options& opt, de
         std::vector<int8_t> fourier_coefficients((size_t)cfg.n_freq * cfg.n_ant * cfg.n_beams * 2);
         generate_fourier_coefficients(cfg.n_beams, cfg.n_ant, cfg.n_freq, 0, opt.gpu, pos.data(), dir.data(),
                                       fourier_coefficients.data());
-        if (opt.gains) {
-            rc = set_weights_calibrated(h, opt.device, fourier_coefficients.data(), opt.gains, opt.weights_out, opt.ant_flags);
-            if (rc == BF_OK) log << "Calibrated the weights with one layer of gains" << std::endl;
+        if (opt.gains || opt.nulls) {
+            rc = set_weights_conditioned(h, opt.device, fourier_coefficients.data(), opt.gains, opt.nulls, opt.weights_out, opt.ant_flags);
+            if (rc == BF_OK && opt.gains) log << "Calibrated the weights with one layer of gains" << std::endl;
+            if (rc == BF_OK && opt.nulls) log << "Projected up to " << opt.nulls->n_null << " interferer vectors per channel out of the weights" << std::endl;
         } else {
             rc = bf_set_weights(h, fourier_coefficients.data());
             if (rc == BF_OK && opt.weights_out) ::memcpy(opt.weights_out, fourier_coefficients.data(), fourier_coefficients.size());
@@ -629,11 +630,12 @@ struct production_run {
         std::vector<int8_t> fourier_coefficients((size_t)cfg.n_freq * cfg.n_ant * cfg.n_beams * 2);
         generate_fourier_coefficients(cfg.n_beams, cfg.n_ant, cfg.n_freq, opt.rank * cfg.n_freq, opt.gpu, pos, dir, fourier_coefficients.data());
         const bool follow = !opt.stokes_beams.empty();   // (the Stokes stage takes the weights as they were set: calibrated, in place)
-        if (opt.gains) {
-            if ((rc = set_weights_calibrated(dev.h, opt.device, fourier_coefficients.data(), opt.gains, follow ? fourier_coefficients.data() : nullptr,
-                                             opt.ant_flags)) != BF_OK)
+        if (opt.gains || opt.nulls) {
+            if ((rc = set_weights_conditioned(dev.h, opt.device, fourier_coefficients.data(), opt.gains, opt.nulls,
+                                              follow ? fourier_coefficients.data() : nullptr, opt.ant_flags)) != BF_OK)
                 return rc;
-            log << "Calibrated the weights with one layer of gains" << std::endl;
+            if (opt.gains) log << "Calibrated the weights with one layer of gains" << std::endl;
+            if (opt.nulls) log << "Projected up to " << opt.nulls->n_null << " interferer vectors per channel out of the weights" << std::endl;
         } else if ((rc = bf_set_weights(dev.h, fourier_coefficients.data())) != BF_OK) {
             return rc;
         }

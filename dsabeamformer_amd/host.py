@@ -205,19 +205,20 @@ class ObservationLoopState:
 def run_debug_observation(cfg: BfConfig, gpu: int = 0, positions: str | None = None, directions: str | None = None,
                           sources: str | None = None, output: str | None = None, device: int = 0,
                           verbose: bool = False, max_sources: int = 4096, per_unit_launches: bool = False,
-                          gains: str | None = None, return_weights: bool = False):
+                          gains: str | None = None, return_weights: bool = False, nulls: str | None = None):
     """The reference's `make debug` main() end to end; returns (dedispersed [n_src][n_beams], observation_ms).
     per_unit_launches: the reference's own launch pattern instead of one launch / copy / DM-0 launch per block.
     gains: a file of gains (read_gains_file) whose last record's layer 0 calibrates the steering weights, as `beam -A` does.
+    nulls: a file of interferer vectors (read_null_file) whose last record is projected out of the weights, after the gains, as `beam -Z` does.
     return_weights: return dict(dedispersed, ms, weights) instead, weights = the int8 [freq][ant][beam][2] array the run set."""
     ded = np.zeros((max_sources, cfg.n_beams), np.float32)
     n = C.c_int()
     ms = C.c_float()
     enc = lambda s: s.encode() if s else None  # noqa: E731
     w = np.zeros((cfg.n_freq, cfg.n_ant, cfg.n_beams, 2), np.int8) if return_weights else None
-    check(load().bfh_run_debug_observation3(C.byref(cfg), gpu, enc(positions), enc(directions), enc(sources), enc(output),
+    check(load().bfh_run_debug_observation4(C.byref(cfg), gpu, enc(positions), enc(directions), enc(sources), enc(output),
                                             device, 1 if verbose else 0, _p(ded), ded.size, C.byref(n), C.byref(ms),
-                                            1 if per_unit_launches else 0, enc(gains), _p(w) if return_weights else None))
+                                            1 if per_unit_launches else 0, enc(gains), enc(nulls), _p(w) if return_weights else None))
     if return_weights:
         return {"dedispersed": ded[:n.value].copy(), "ms": ms.value, "weights": w}
     return ded[:n.value].copy(), ms.value
@@ -388,6 +389,46 @@ def write_gains_file(path: str, n_ant: int, n_pol: int, n_freq: int, first_chann
             g, i = np.ascontiguousarray(gains, "<f8"), np.ascontiguousarray(info, "<i4")
             assert g.shape == (n_pol, n_freq, n_ant, 2) and i.shape == (n_pol, n_freq, 2)
             fp.write(np.array([first_block, n_columns], "<u8").tobytes() + g.tobytes() + i.tobytes())
+
+
+NULL_LAYOUT = "freq,vec,ant,reim"
+
+
+def read_null_file(path: str):
+    """Parse a dsabf::null_file_sink file (docs/NULLING.md): returns (header dict, list of (first_block, n_columns_per_pol, float64 vectors
+    [n_freq][n_null][n_ant][2], float64 eig [n_freq][n_null + 1], int32 info [n_freq][1 + 2 n_null]) per record)."""
+    raw = open(path, "rb").read()
+    text = raw[:DETECTED_HEADER_BYTES].split(b"\0", 1)[0].decode()
+    hdr = dict(line.split(None, 1) for line in text.splitlines() if line.strip())
+    assert hdr["CONTENT"] == "nullvecs" and hdr["DTYPE"] == "float64" and hdr["LAYOUT"] == NULL_LAYOUT, hdr
+    n_freq, n_null, n_ant = int(hdr["NFREQ"]), int(hdr["NNULL"]), int(hdr["NANT"])
+    n, n_eig, n_info = n_freq * n_null * n_ant * 2, n_freq * (n_null + 1), n_freq * (1 + 2 * n_null)
+    at, rec, records = int(hdr["HDR_SIZE"]), int(hdr["RECORD_HEADER_BYTES"]), []
+    while at < len(raw):
+        first_block, n_columns = (int(v) for v in np.frombuffer(raw, "<u8", 2, at))
+        at += rec
+        vecs = np.frombuffer(raw, "<f8", n, at).reshape(n_freq, n_null, n_ant, 2)
+        at += 8 * n
+        eig = np.frombuffer(raw, "<f8", n_eig, at).reshape(n_freq, n_null + 1)
+        at += 8 * n_eig
+        records.append((first_block, n_columns, vecs, eig, np.frombuffer(raw, "<i4", n_info, at).reshape(n_freq, 1 + 2 * n_null)))
+        at += 4 * n_info
+    return hdr, records
+
+
+def write_null_file(path: str, n_ant: int, n_freq: int, first_channel: int, n_null: int, records) -> None:
+    """Write a file of interferer vectors in dsabf::null_file_sink's format, e.g. vectors found elsewhere for `beam -Z`: records is a list
+    of (first_block, n_columns_per_pol, vectors [n_freq][n_null][n_ant][2], eig [n_freq][n_null + 1], info [n_freq][1 + 2 n_null])."""
+    text = ("HDR_VERSION 1.0\nHDR_SIZE %d\nINSTRUMENT DSA\nCONTENT nullvecs\nDTYPE float64\nENDIAN little\nLAYOUT %s\n"
+            "RECORD_HEADER_BYTES 16\nNANT %d\nNPOL 1\nNFREQ %d\nFIRST_CHANNEL %d\nNNULL %d\nEIG float64 freq,(lambdas,trace)\n"
+            "INFO int32 freq,(n_used,(iterations,status) per vector)\n"
+            % (DETECTED_HEADER_BYTES, NULL_LAYOUT, n_ant, n_freq, first_channel, n_null)).encode()
+    with open(path, "wb") as fp:
+        fp.write(text.ljust(DETECTED_HEADER_BYTES, b"\0"))
+        for first_block, n_columns, vecs, eig, info in records:
+            v, e, i = np.ascontiguousarray(vecs, "<f8"), np.ascontiguousarray(eig, "<f8"), np.ascontiguousarray(info, "<i4")
+            assert v.shape == (n_freq, n_null, n_ant, 2) and e.shape == (n_freq, n_null + 1) and i.shape == (n_freq, 1 + 2 * n_null)
+            fp.write(np.array([first_block, n_columns], "<u8").tobytes() + v.tobytes() + e.tobytes() + i.tobytes())
 
 
 def run_observation_junk_dm(cfg: BfConfig, n_blocks: int, delays, dm_path: str | None, detected_path: str | None = None,

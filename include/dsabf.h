@@ -325,6 +325,53 @@ int bf_solve_gains_device(bf_handle *h, const int64_t *d_vis, const double *d_mo
 int bf_calibrate_weights_device(bf_handle *h, const int8_t *d_w_in, const double *d_gains_layer, const uint8_t *d_flags, int mode,
                                 int8_t *d_w_out, void *hip_stream);
 
+/* ---- The spatial null: interferer vectors from visibilities, projected weights (docs/NULLING.md) ------------------------------
+ * Extends the weight upload as the gain solver does, src/beamformer.cu:230-241 (the steering weights), :251, :272 (their allocation
+ * and copy): an interferer that is strong in every antenna occupies ONE direction of antenna space per channel, the dominant
+ * eigenvector of the visibility matrix V[a1][a2] = sum v[a1] conj(v[a2]) that bf_correlate_device measures.  bf_null_solve_device finds
+ * the n_null dominant eigenvectors u_j per channel by power iteration with deflation, one workgroup per channel;
+ * bf_null_weights_device removes them from every beam: w' = w - sum_j conj(u_j) (u_j^T w), so that u_j^T w' = 0 -- the beam sample is
+ * sum_a v_a w_a, and v ~ s u for the interferer.  The fused kernels run unchanged with other weight bytes.
+ * The arithmetic is fp64, one rounding per operation (no fused multiply-add), every sum over antennas in the OSUM order of
+ * docs/CALIBRATION.md section 2, so the result is bit-equal to a numpy restatement (tests/support/null_oracle.py) on every path.
+ * bf_null_solve_device: d_vis as bf_correlate_device leaves it, d_flags NULL or uint8 [ant] (non-zero: the antenna's row and column
+ *   are zero, and so are its vector entries).  opt: n_null 1 ... BF_NULL_MAX vectors per channel; min_ratio: vector j is used only if
+ *   lambda_j >= min_ratio * max(rest_j, 0), rest_j = (trace - lambda_0 - ... - lambda_j) / (m - j - 1) the mean of what is left over the
+ *   m unflagged antennas (0: always), and only if every earlier vector is used, m > j + 1 and lambda_j > 0; tol: stop when
+ *   |u - u_prev| <= tol; max_iter >= 1 multiplications per vector; pol -1: the polarisations' integers are added first (the
+ *   beamformer has one weight per (f, a, b) for both), 0 ... n_pol - 1: that polarisation alone.
+ *   d_vecs: fp64 [freq][n_null][ant]{re, im} (bf_null_vec_entries complex entries), unit vectors, exact zeros where unused;
+ *   d_eig: fp64 [freq][n_null + 1], the lambdas and then the trace; d_info: int32 [freq][1 + 2 n_null], n_used and then
+ *   {iterations, status} per vector: status 1 = converged, 0 = max_iter ran out (the vector is used all the same: it lies in the
+ *   dominant subspace), 2 = nothing was left (this vector and all later ones are zero).  No NaN is produced.  d_vis and d_vecs
+ *   16-byte aligned.
+ * bf_null_weights_device: d_w_in / d_w_out int8 [freq][ant][beam]{re, im} as for bf_set_weights_device (4-byte aligned; they may be
+ *   the same array); d_vecs, d_info and n_null as the solver left them; d_flags as given to the solver.  Channels with n_used > 0:
+ *   each part of k_f w' is rounded half to even and clipped to [-127, 127]; BF_NULL_SCALED k_f = min(1, 127 / M_f) with M_f the
+ *   largest |part| of w' in the channel, BF_NULL_CLIP k_f = 1.  Channels with n_used == 0 are copied byte for byte, k_f = 1.  Flagged
+ *   antennas get (0, 0) in both.  d_scale NULL or fp64 [freq]: k_f (the channel's power gain is k_f^2).
+ * Both calls are asynchronous on hip_stream, need no weights set, leave the caller's current device as found and keep NO state or
+ *   scratch in the handle, so calls issued on different queues without synchronisation are independent.  Defined for n_ant a multiple
+ *   of 4 up to 256; beyond that, and for n_null outside 1 ... BF_NULL_MAX, max_iter < 1, tol or min_ratio negative or NaN, pol out of
+ *   range, a mode that is neither, or a NULL or misaligned pointer, they return BF_ERR_INVALID and launch nothing.
+ *   bf_null_default_options: min_ratio 4.0, tol 1e-6, n_null 1, max_iter 200, pol -1. */
+typedef struct {
+    double min_ratio;
+    double tol;
+    int n_null;
+    int max_iter;
+    int pol;
+} bf_null_options;
+#define BF_NULL_MAX 4
+#define BF_NULL_SCALED 0
+#define BF_NULL_CLIP 1
+int bf_null_default_options(bf_null_options *o);
+size_t bf_null_vec_entries(const bf_config *cfg, int n_null);
+int bf_null_solve_device(bf_handle *h, const int64_t *d_vis, const uint8_t *d_flags, const bf_null_options *opt, double *d_vecs,
+                         double *d_eig, int32_t *d_info, void *hip_stream);
+int bf_null_weights_device(bf_handle *h, const int8_t *d_w_in, const double *d_vecs, const int32_t *d_info, int n_null,
+                           const uint8_t *d_flags, int mode, int8_t *d_w_out, double *d_scale, void *hip_stream);
+
 /* ---- Voltage moments and spectral kurtosis (docs/SPECTRAL_KURTOSIS.md) --------------------------------------------------------
  * Reads what the loop's kernels read, src/beamformer.cu:454-488 (the packed voltages of the resident gemm-units), and produces what
  * the calibration path above takes and nothing else here makes: antenna flags.  Per (antenna, channel, polarisation) cell two power

@@ -51,7 +51,8 @@ int bf_rtw_plan(const bf_config *cfg, int n_units, int n_cus, int *windows_per_s
  *                       include/dsabf.h); what it selects instead is what "paired" and the weights decide
  *   "coalesce" 0 / 1    0: bf_enqueue_gemm_unit launches one kernel per call (the reference's literal launch pattern)
  *   "cal_resident" 0 / 1  0: bf_solve_gains_device re-reads the visibilities from memory every iteration at every antenna count,
- *                       instead of keeping them in LDS up to 64 antennas (docs/CALIBRATION.md; the same bits) */
+ *                       instead of keeping them in LDS up to 64 antennas (docs/CALIBRATION.md; the same bits)
+ *   "null_resident" 0 / 1  0: the same for bf_null_solve_device (docs/NULLING.md; the same bits) */
 int bf_set_switch(bf_handle *h, const char *name, int value);
 /* Counters of one handle: "fused_launches" = fused-kernel launches issued so far (what coalescing saves),
  * "queued_units" = gemm-units bf_enqueue_gemm_unit has queued and not launched yet, "dm_ring_stages" = live DM stages of the handle

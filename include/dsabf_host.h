@@ -96,6 +96,13 @@ int bfh_run_debug_observation2(const bf_config *cfg, int gpu, const char *positi
 int bfh_run_debug_observation3(const bf_config *cfg, int gpu, const char *positions, const char *directions, const char *sources,
                                const char *output, int device, int verbose, float *ded_out, size_t ded_capacity, int *n_pt_sources,
                                float *observation_ms, int per_unit_launches, const char *gains_file, int8_t *weights_out);
+/* The same with a spatial null as well (docs/NULLING.md; `beam -Z`): null_file (may be NULL) is a file of interferer vectors of the run's
+ * geometry (NANT, NFREQ, FIRST_CHANNEL 0; anything else: BF_ERR_INVALID before any device work); the vectors of its last record are
+ * projected out of the steering weights on the device (BF_NULL_SCALED) before they are set -- after the gains if both are given. */
+int bfh_run_debug_observation4(const bf_config *cfg, int gpu, const char *positions, const char *directions, const char *sources,
+                               const char *output, int device, int verbose, float *ded_out, size_t ded_capacity, int *n_pt_sources,
+                               float *observation_ms, int per_unit_launches, const char *gains_file, const char *null_file,
+                               int8_t *weights_out);
 
 /* Production observation loop (src/beamformer.cu:364-534 without -DDEBUG) fed by the in-memory dada_junkdb stand-in:
  * n_blocks pseudo-random PSRDADA-sized blocks from a pinned ring of ring_blocks distinct blocks, default linear

@@ -188,6 +188,8 @@ public:
     friend std::ostream& operator<<(std::ostream& out, const observation_loop_state& a);
 };
 
+struct null_vectors;   // what `beam -Z` applies (below, with the spatial null)
+
 // ---- the reference's DEBUG main() as a callable (src/beamformer.cu:12-621, `make debug` flow) -------------
 struct debug_run_options {
     int gpu = 0;                 // -g
@@ -207,6 +209,9 @@ struct debug_run_options {
     const double* gains = nullptr;
     const uint8_t* ant_flags = nullptr;   // -f with -A: uint8 [n_ant], flagged antennas get zero weights (needs gains)
     int8_t* weights_out = nullptr;
+    // -Z: the interferer vectors of one record (read_null_vectors): projected out of the steering weights (BF_NULL_SCALED) before they are set,
+    // after the gains if both are given (set_weights_conditioned); ant_flags then holds for both.
+    const null_vectors* nulls = nullptr;
 };
 struct debug_run_result {
     float observation_time_ms = 0;
@@ -760,6 +765,60 @@ bool read_moments_sum(const char* path, record_file_header* header, std::vector<
 // given) the flagged channel indices, offset by the file's FIRST_CHANNEL, to chan_path, both in the `-F` format.  No device is touched.
 int select_moments_file(const char* moments_path, const bf_sk_options& opt, const char* ant_path, const char* chan_path, std::ostream& log);
 
+// ---- The spatial null (include/dsabf.h: bf_null_solve_device, bf_null_weights_device; docs/NULLING.md) -------------------------
+// Thin wrappers: device pointers in, asynchronous on `stream`, the C-ABI's return codes.
+inline int null_solve(bf_handle* h, const int64_t* d_vis, const uint8_t* d_flags, const bf_null_options& opt, double* d_vecs, double* d_eig,
+                      int32_t* d_info, void* stream = nullptr)
+{
+    return bf_null_solve_device(h, d_vis, d_flags, &opt, d_vecs, d_eig, d_info, stream);
+}
+inline int null_weights(bf_handle* h, const int8_t* d_w_in, const double* d_vecs, const int32_t* d_info, int n_null, const uint8_t* d_flags, int mode,
+                        int8_t* d_w_out, double* d_scale = nullptr, void* stream = nullptr)
+{
+    return bf_null_weights_device(h, d_w_in, d_vecs, d_info, n_null, d_flags, mode, d_w_out, d_scale, stream);
+}
+
+// File of interferer vectors: the 4096-byte ASCII header (`KEY value` lines, NUL padded: CONTENT nullvecs, DTYPE float64, NANT, NFREQ,
+// FIRST_CHANNEL, NNULL, LAYOUT freq,vec,ant,reim; NPOL 1: one set for both polarisations), then one record per solve: uint64 first_block,
+// uint64 n_columns_per_pol (those of the visibility record it was solved from), the vectors (little-endian float64
+// [freq][n_null][ant]{re, im}), the eigenvalues (float64 [freq][n_null + 1]), the info (int32 [freq][1 + 2 n_null]).
+class null_file_sink {
+    int fd = -1;
+    uint64_t records = 0;
+    size_t n_vec_doubles = 0, n_eig = 0, n_info = 0;
+
+public:
+    static constexpr size_t kHeaderBytes = 4096;
+    static constexpr size_t kRecordBytes = 16;
+    null_file_sink(int n_ant, int n_freq, int first_channel, int n_null, const char* path);
+    ~null_file_sink();
+    null_file_sink(const null_file_sink&) = delete;
+    null_file_sink& operator=(const null_file_sink&) = delete;
+    bool is_open() const { return fd >= 0; }
+    bool deliver(uint64_t first_block, uint64_t n_columns_per_pol, const double* vecs, const double* eig, const int32_t* info);
+    void close();
+    uint64_t get_records_written() const { return records; }
+};
+// The vectors and the info of one record, as bf_null_weights_device takes them.
+struct null_vectors {
+    int n_null = 0;
+    std::vector<double> vecs;    // [freq][n_null][ant]{re, im}
+    std::vector<int32_t> info;   // [freq][1 + 2 n_null]
+};
+// The LAST record of a null file: what `beam -Z` applies.  The geometry must be n_ant x n_freq starting at first_channel; false + *why
+// otherwise.  No device is touched.
+bool read_null_vectors(const char* path, int n_ant, int n_freq, int first_channel, null_vectors* out, std::string* why);
+// `beam -E vis_file -Z null_file [-y n_null[:min_ratio]]`: every record of a vis_file_sink file uploaded, solved (bf_null_solve_device with
+// opt) and written as one record; the geometry comes from the file's header.  ant_flags (optional, host, uint8 [NANT of the file]).
+int null_vis_file(const char* vis_path, const char* null_path, const bf_null_options& opt, int device, uint64_t* n_records, std::ostream& log,
+                  const uint8_t* ant_flags = nullptr);
+// Weights `w` (host, the layout of bf_set_weights) conditioned on the device and set on the handle (bf_set_weights_device): first times
+// conj(g) / |g| of one layer of gains (gains_layer, may be NULL; bf_calibrate_weights_device, BF_CAL_PHASE), then the vectors of `nulls`
+// (may be NULL) projected out (bf_null_weights_device, BF_NULL_SCALED) -- the vectors were measured in the antenna domain that the
+// calibrated weights address.  w_set (optional, host) receives what was set; ant_flags (optional): zero weights for those antennas.
+int set_weights_conditioned(bf_handle* h, int device, const int8_t* w, const double* gains_layer, const null_vectors* nulls, int8_t* w_set = nullptr,
+                            const uint8_t* ant_flags = nullptr);
+
 struct observation_options {
     int gpu = 0;          // -g
     int device = 0;
@@ -838,6 +897,7 @@ struct observation_options {
     // -A: one layer of gains for THIS rank's channels, host [freq][ant]{re, im}: as debug_run_options::gains.
     const double* gains = nullptr;
     const uint8_t* ant_flags = nullptr;   // -f with -A: uint8 [n_ant], flagged antennas get zero weights (needs gains)
+    const null_vectors* nulls = nullptr;  // -Z: as debug_run_options::nulls, for THIS rank's channels; the Stokes stage gets the same weights
     // Full-Stokes follow-up beams (docs/STOKES.md; needs block_launch): the beams to follow (empty = off; 1 .. 16 distinct indices), the
     // integration window in samples (0 = n_avg; must divide n_out_per_gemm * n_avg) and where every launch's set goes (may be NULL: the
     // stage still runs).  The stage holds (MAX_TOTAL_SEP + 2) x launches-per-block result sets of a block's entries each, on the device and
