@@ -68,6 +68,26 @@ class BfSpsCandidate(C.Structure):
                 ("snr", C.c_double)]
 
 
+class BfEvtOptions(C.Structure):
+    """Mirror of ``bf_evt_options`` (include/dsabf.h)."""
+
+    _fields_ = [("t_tol", C.c_int32), ("dm_tol", C.c_int32), ("max_width", C.c_int32), ("max_beams", C.c_int32), ("ib_beam", C.c_int32),
+                ("ib_ratio", C.c_double)]
+
+
+class BfEvtEvent(C.Structure):
+    """Mirror of ``bf_evt_event`` (include/dsabf.h)."""
+
+    _fields_ = [("best", BfSpsCandidate), ("t_lo", C.c_uint64), ("t_hi", C.c_uint64), ("dm_lo", C.c_int32), ("dm_hi", C.c_int32),
+                ("n_members", C.c_int32), ("n_beams", C.c_int32), ("snr_ib", C.c_double), ("flags", C.c_uint32)]
+
+
+class BfStampRequest(C.Structure):
+    """Mirror of ``bf_stamp_request`` (include/dsabf.h)."""
+
+    _fields_ = [("t0", C.c_uint64), ("dm", C.c_int32), ("beam", C.c_int32)]
+
+
 class BfCalOptions(C.Structure):
     """Mirror of ``bf_cal_options`` (include/dsabf.h)."""
 
@@ -200,6 +220,16 @@ SIGNATURES = {
     "bf_cond_push": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "bf_cond_mask_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "bf_dm_stream_attach_conditioner": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "bf_evt_default_options": (None, [C.POINTER(BfEvtOptions)]),
+    "bf_evt_create": (C.c_int, [C.POINTER(BfEvtOptions), C.POINTER(C.c_void_p)]),
+    "bf_evt_destroy": (C.c_int, [C.c_void_p]),
+    "bf_evt_feed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "bf_evt_flush": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "bf_evt_open": (C.c_int, [C.c_void_p]),
+    "bf_dm_stream_create_history": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "bf_dm_stream_history": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "bf_dm_stream_cut": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bf_dm_stream_cut_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "bf_comm_unique_id": (C.c_int, [C.c_void_p]),
     "bf_comm_create": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
     "bf_comm_destroy": (C.c_int, [C.c_void_p]),
@@ -303,6 +333,12 @@ SIGNATURES = {
     "bfh_dm_sink_create": (C.c_int, [C.POINTER(BfConfig), C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "bfh_dm_sink_deliver": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "bfh_dm_sink_destroy": (C.c_int, [C.c_void_p]),
+    "bfh_event_sink_create": (C.c_int, [C.c_char_p, C.POINTER(C.c_void_p)]),
+    "bfh_event_sink_deliver": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "bfh_event_sink_destroy": (C.c_int, [C.c_void_p]),
+    "bfh_stamp_sink_create": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "bfh_stamp_sink_deliver": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_int, C.c_int]),
+    "bfh_stamp_sink_destroy": (C.c_int, [C.c_void_p]),
     "bfh_dm_trial_share": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "bfh_junk_fill": (C.c_int, [C.POINTER(BfConfig), C.c_int, C.c_uint64, C.c_void_p]),
     "bfh_shm_ring_create": (C.c_int, [C.c_char_p, C.c_uint64, C.c_uint64, C.c_char_p, C.POINTER(C.c_void_p)]),

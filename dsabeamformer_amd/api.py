@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-from ._lib import BF_CAL_FULL, BF_CAL_PHASE, BF_NULL_CLIP, BF_NULL_SCALED, BfCalOptions, BfNullOptions, BfCondOptions, BfConfig, BfSkOptions, DsabfError, BfSpsCandidate, BfSpsPeak, BfSpsStat, check, load
+from ._lib import BF_CAL_FULL, BF_CAL_PHASE, BF_NULL_CLIP, BF_NULL_SCALED, BfCalOptions, BfNullOptions, BfCondOptions, BfConfig, BfEvtEvent, BfEvtOptions, BfSkOptions, BfStampRequest, DsabfError, BfSpsCandidate, BfSpsPeak, BfSpsStat, check, load
 
 
 def debug_config(**over) -> BfConfig:
@@ -326,7 +326,7 @@ class DmStream(_Owner):
     device (include/dsabf.h).  delays: int32 host array [n_dm][n_freq_total]."""
     _ptr_attr, _destroy = "_s", "bf_dm_stream_destroy"
 
-    def __init__(self, bf: Beamformer, delays, n_freq_total: int, max_rows_per_push: int):
+    def __init__(self, bf: Beamformer, delays, n_freq_total: int, max_rows_per_push: int, history_rows: int = 0):
         import numpy as np
 
         self._lib = load()
@@ -334,7 +334,12 @@ class DmStream(_Owner):
         d = np.ascontiguousarray(delays, np.int32)
         assert d.ndim == 2 and d.shape[1] == n_freq_total
         self.n_dm, self.n_beams, self._bf = d.shape[0], bf.cfg.n_beams, bf
-        check(self._lib.bf_dm_stream_create(bf._h, _ptr(d), d.shape[0], n_freq_total, max_rows_per_push, C.byref(self._s)))
+        # history_rows: rows kept for cut(), beyond what the pushes in flight need.  0 goes through bf_dm_stream_create (the same
+        # stage): a measurement build of an earlier round beside the product (DSABF_LIB_PATH) has only that export.
+        if history_rows:
+            check(self._lib.bf_dm_stream_create_history(bf._h, _ptr(d), d.shape[0], n_freq_total, max_rows_per_push, history_rows, C.byref(self._s)))
+        else:
+            check(self._lib.bf_dm_stream_create(bf._h, _ptr(d), d.shape[0], n_freq_total, max_rows_per_push, C.byref(self._s)))
 
     @property
     def max_delay(self) -> int:
@@ -367,6 +372,93 @@ class DmStream(_Owner):
         """bf_dm_stream_attach_conditioner: every push from now on conditions its new rows in the stage's buffer (``cond``: a
         Conditioner; None detaches) before they are dedispersed."""
         check(self._lib.bf_dm_stream_attach_conditioner(self._s, cond._c if cond is not None else None))
+
+    def history(self):
+        """bf_dm_stream_history: (oldest_row, next_row, cap_rows) -- rows [oldest_row, next_row) of the series can be cut."""
+        a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        check(self._lib.bf_dm_stream_history(self._s, C.byref(a), C.byref(b), C.byref(c)))
+        return int(a.value), int(b.value), int(c.value)
+
+    def cut(self, requests, n_tau: int, tbin: int, fbin: int, d_out, stream: int = 0):
+        """bf_dm_stream_cut: dedispersed stamps [request][n_freq_total / fbin][n_tau] (fp32, device memory ``d_out``) of the
+        requests -- an iterable of (t0, local trial, beam), or a structured array with fields t0, dm, beam -- asynchronously on
+        ``stream``.  Returns the int32 status of every request: 0 cut, 1 too old, 2 not pushed yet (its cells stay untouched)."""
+        import numpy as np
+
+        reqs = np.zeros(len(requests), stamp_request_dtype())
+        if len(requests):
+            r = np.asarray(requests)
+            if r.dtype.names:
+                for k in ("t0", "dm", "beam"):
+                    reqs[k] = r[k]
+            else:
+                reqs["t0"], reqs["dm"], reqs["beam"] = [[int(q[k]) for q in requests] for k in range(3)]
+        status = np.full(len(reqs), -1, np.int32)
+        check(self._lib.bf_dm_stream_cut(self._s, _ptr(reqs), len(reqs), n_tau, tbin, fbin, _ptr(d_out), _ptr(status), C.c_void_p(stream)))
+        return status
+
+
+def stamp_request_dtype():
+    import numpy as np
+
+    dt = np.dtype([("t0", np.uint64), ("dm", np.int32), ("beam", np.int32)], align=True)
+    assert dt.itemsize == C.sizeof(BfStampRequest)
+    return dt
+
+
+def event_dtype():
+    """numpy mirror of ``bf_evt_event``: best (a candidate record), t_lo, t_hi, dm_lo, dm_hi, n_members, n_beams, snr_ib, flags."""
+    import numpy as np
+
+    dt = np.dtype([("best", _candidate_dtype()), ("t_lo", np.uint64), ("t_hi", np.uint64), ("dm_lo", np.int32), ("dm_hi", np.int32),
+                   ("n_members", np.int32), ("n_beams", np.int32), ("snr_ib", np.float64), ("flags", np.uint32)], align=True)
+    assert dt.itemsize == C.sizeof(BfEvtEvent)
+    return dt
+
+
+EVT_IB_ONLY, EVT_WIDE, EVT_INCOHERENT = 1, 2, 4
+
+
+class EventBuilder(_Owner):
+    """bf_evt: the search's candidates grouped into events (include/dsabf.h, docs/EVENTS.md) -- friends of friends in time and
+    trial, streaming, on the host.  Options as in ``bf_evt_options``: t_tol, dm_tol, max_width, max_beams, ib_beam, ib_ratio."""
+    _ptr_attr, _destroy = "_e", "bf_evt_destroy"
+
+    def __init__(self, **options):
+        self._lib = load()
+        self._e = C.c_void_p()
+        opt = BfEvtOptions()
+        self._lib.bf_evt_default_options(C.byref(opt))
+        for k, v in options.items():
+            if k not in dict(BfEvtOptions._fields_):
+                raise TypeError("EventBuilder: unknown option %r" % k)
+            setattr(opt, k, v)
+        self.options = opt
+        check(self._lib.bf_evt_create(C.byref(opt), C.byref(self._e)))
+
+    @property
+    def open(self) -> int:
+        return self._lib.bf_evt_open(self._e)
+
+    def _events(self, call, n_new: int):
+        import numpy as np
+
+        out = np.zeros(self.open + n_new, event_dtype())
+        n_out = C.c_size_t()
+        check(call(_ptr(out), out.size, C.byref(n_out)))
+        return out[:n_out.value].copy()
+
+    def feed(self, cands, next_t: int):
+        """The candidates of one collected push (a structured array as SinglePulseSearch.collect returns) and that push's
+        first_t + n_t; returns the events that close, a structured array of ``event_dtype()``."""
+        import numpy as np
+
+        c = np.ascontiguousarray(cands, _candidate_dtype())
+        return self._events(lambda out, n, n_out: self._lib.bf_evt_feed(self._e, _ptr(c), c.size, next_t, out, n, n_out), c.size)
+
+    def flush(self):
+        """Closes every open cluster and returns the events."""
+        return self._events(lambda out, n, n_out: self._lib.bf_evt_flush(self._e, out, n, n_out), 0)
 
 
 def _candidate_dtype():

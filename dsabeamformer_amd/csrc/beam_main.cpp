@@ -76,6 +76,7 @@
 // exactly like the reference's DEBUG build.  The PSRDADA observation mode (-c core, -k key) needs libpsrdada, which is
 // not part of this build; the options are accepted and reported.
 #include <fcntl.h>
+#include <getopt.h>
 #include <unistd.h>
 
 #include <chrono>
@@ -138,9 +139,62 @@ int main(int argc, char* argv[])
     int stokes_int = 0;                     // -l: samples per integration window (0: N_AVERAGING)
     bool stokes_int_given = false;
 
+    // events and stamps (docs/EVENTS.md): long options only -- every letter is taken
+    std::string events_path, stamps_path;   // --events FILE, --stamps FILE
+    bf_evt_options evt_opt;
+    bf_evt_default_options(&evt_opt);
+    int stamp_bins = 64, stamp_tbin = 0, stamp_fbin = 1;
+    bool event_tol_given = false, event_veto_given = false, stamp_shape_given = false, stamp_flagged = false, long_bad = false;
+    enum { kEvents = 1000, kEventTol, kEventVeto, kStamps, kStampShape, kStampFlagged };
+    static const option long_options[] = {{"events", required_argument, nullptr, kEvents},       {"event-tol", required_argument, nullptr, kEventTol},
+                                          {"event-veto", required_argument, nullptr, kEventVeto}, {"stamps", required_argument, nullptr, kStamps},
+                                          {"stamp-shape", required_argument, nullptr, kStampShape}, {"stamp-flagged", no_argument, nullptr, kStampFlagged},
+                                          {nullptr, 0, nullptr, 0}};
+    // a non-negative integer that fills its whole field; anything else marks the command line as malformed
+    auto number = [&long_bad](const char* text, const char** end, int* out) {
+        char* e = nullptr;
+        const long v = strtol(text, &e, 10);
+        if (e == text || v < 0 || v > 1000000000L || *text == '-' || *text == '+' || *text == ' ') long_bad = true;
+        *out = (int)v;
+        *end = e;
+    };
+
     int arg = 0;
-    while ((arg = getopt(argc, argv, "s:g:p:d:o:D:a:c:k:K:j:w:R:r:I:M:N:T:W:Q:S:B:C:i:V:L:E:G:A:n:U:F:Y:J:e:O:q:t:m:f:x:b:l:Z:y:zPXuvhH")) != -1) {  // src/beamformer.cu:41-43 (+ -o -D -a -v)
+    while ((arg = getopt_long(argc, argv, "s:g:p:d:o:D:a:c:k:K:j:w:R:r:I:M:N:T:W:Q:S:B:C:i:V:L:E:G:A:n:U:F:Y:J:e:O:q:t:m:f:x:b:l:Z:y:zPXuvhH", long_options, nullptr)) != -1) {  // src/beamformer.cu:41-43 (+ -o -D -a -v)
         switch (arg) {
+            case kEvents: events_path = optarg; break;
+            case kStamps: stamps_path = optarg; break;
+            case kStampFlagged: stamp_flagged = true; break;
+            case kEventTol: {   // T[,D]
+                const char* e = nullptr;
+                event_tol_given = true;
+                number(optarg, &e, &evt_opt.t_tol);
+                if (*e == ',') number(e + 1, &e, &evt_opt.dm_tol);
+                if (*e) long_bad = true;
+                break;
+            }
+            case kEventVeto: {   // MAXBEAMS[:IB_RATIO]
+                const char* e = nullptr;
+                event_veto_given = true;
+                number(optarg, &e, &evt_opt.max_beams);
+                if (*e == ':') {
+                    char* e2 = nullptr;
+                    evt_opt.ib_ratio = strtod(e + 1, &e2);
+                    if (e2 == e + 1 || *e2 || !(evt_opt.ib_ratio >= 0.0)) long_bad = true;
+                    e = e2;
+                }
+                if (*e) long_bad = true;
+                break;
+            }
+            case kStampShape: {   // BINS[:TBIN[:FBIN]]
+                const char* e = nullptr;
+                stamp_shape_given = true;
+                number(optarg, &e, &stamp_bins);
+                if (*e == ':') number(e + 1, &e, &stamp_tbin);
+                if (*e == ':') number(e + 1, &e, &stamp_fbin);
+                if (*e || stamp_bins < 1 || stamp_fbin < 1) long_bad = true;
+                break;
+            }
             case 's': sources = optarg; break;                 // :77-89
             case 'g': opt.gpu = atoi(optarg); break;           // :92-100
             case 'p': positions = optarg; break;               // :102-111
@@ -246,6 +300,15 @@ int main(int argc, char* argv[])
                              " -Z null_file            DEBUG run and observation mode: the vectors of the last record of null_file are projected out of\n"
                              "                         the steering weights (after -A's gains; -x follows the same weights; -f zeroes antennas); its\n"
                              "                         NANT / NFREQ / FIRST_CHANNEL must be the run's; with -R: null_file.<rank>\n"
+                             " --events FILE [--event-tol T[,D]] [--event-veto MAXBEAMS[:IB_RATIO]]   with -S: the candidates grouped into events,\n"
+                             "                         friends of friends within T samples [0] and D trials [1]; one line per event to FILE (t_start dm beam\n"
+                             "                         width snr peak n_members n_beams dm_lo dm_hi t_lo t_hi snr_ib flags; with -X: FILE.<rank>); flags: 1 only\n"
+                             "                         the -i column saw it, 2 more than MAXBEAMS [4] beams, 4 the -i column's S/N >= IB_RATIO [0.5] x the best\n"
+                             " --stamps FILE [--stamp-shape BINS[:TBIN[:FBIN]]] [--stamp-flagged]   with --events: the dedispersed dynamic spectrum of\n"
+                             "                         each unflagged event's best beam (--stamp-flagged: of flagged ones too), BINS [64] bins of TBIN samples\n"
+                             "                         [0: half the width] x channels in groups of FBIN [1, must divide the band], cut from the DM stage's ring\n"
+                             "                         --events without -S, --stamps without --events, the others without their parent, or malformed\n"
+                             "                         numbers: beam exits with a usage error\n"
                              " -H                      this text\n";
                 return EXIT_SUCCESS;
             default: usage(true, std::cerr); return EXIT_FAILURE;
@@ -258,6 +321,30 @@ int main(int argc, char* argv[])
     if (!sps_on && (sps_widths_given || !cand_path.empty())) {
         fprintf(stderr, "beam: -B / -C belong to the single-pulse search: give -S snr (and -M dm_max)\n");
         return EXIT_FAILURE;
+    }
+    if (long_bad) {
+        fprintf(stderr, "beam: --event-tol T[,D], --event-veto MAXBEAMS[:IB_RATIO], --stamp-shape BINS[:TBIN[:FBIN]]: malformed or negative number\n");
+        return EXIT_FAILURE;
+    }
+    if (!events_path.empty() && !sps_on) {
+        fprintf(stderr, "beam: --events groups the candidates of the single-pulse search: give -S snr (and -M dm_max)\n");
+        return EXIT_FAILURE;
+    }
+    if (events_path.empty() && (event_tol_given || event_veto_given || !stamps_path.empty())) {
+        fprintf(stderr, "beam: --event-tol / --event-veto / --stamps belong to the event builder: give --events FILE\n");
+        return EXIT_FAILURE;
+    }
+    if (stamps_path.empty() && (stamp_shape_given || stamp_flagged)) {
+        fprintf(stderr, "beam: --stamp-shape / --stamp-flagged belong to the stamps: give --stamps FILE\n");
+        return EXIT_FAILURE;
+    }
+    if (!stamps_path.empty()) {   // the band is the production geometry's, whatever -R
+        bf_config band;
+        bf_config_default(&band, /*debug=*/0);
+        if (band.n_freq % stamp_fbin != 0) {
+            fprintf(stderr, "beam: --stamp-shape: FBIN %d does not divide the band's %d channels\n", stamp_fbin, band.n_freq);
+            return EXIT_FAILURE;
+        }
     }
     if (sps_on && (sps_widths < 1 || sps_widths > 8)) {
         fprintf(stderr, "beam: -B %d: n_widths must be 1 .. 8\n", sps_widths);
@@ -660,6 +747,8 @@ int main(int argc, char* argv[])
         std::unique_ptr<dm_file_sink> dm_sink;
         std::unique_ptr<dm_ring_sink> dm_rsink;
         std::unique_ptr<sps_file_sink> cand_sink;
+        std::unique_ptr<event_file_sink> esink;
+        std::unique_ptr<stamp_file_sink> tsink;
         int n_dm = 0, my_trials = 0;
         if (dm_max > 0.0) {
             std::vector<double> dms = dm_trials(0.0, dm_max);
@@ -688,6 +777,8 @@ int main(int argc, char* argv[])
                 for (size_t i = (size_t)my_first * full_cfg.n_freq; i < (size_t)(my_first + my_count) * full_cfg.n_freq; i++) dmax = delays[i] > dmax ? delays[i] : dmax;
                 if (!dm_path.empty()) dm_path += "." + std::to_string(rank);
                 if (!cand_path.empty()) cand_path += "." + std::to_string(rank);
+                if (!events_path.empty()) events_path += "." + std::to_string(rank);
+                if (!stamps_path.empty()) stamps_path += "." + std::to_string(rank);
                 std::cout << "Shard " << rank << " dedisperses trials " << my_first << " .. " << my_first + my_count - 1 << std::endl;
             }
             my_trials = my_count;
@@ -720,6 +811,27 @@ int main(int argc, char* argv[])
                     return EXIT_FAILURE;
                 }
                 oopt.sps_sink = cand_sink.get();
+            }
+            if (!events_path.empty()) {   // --events / --stamps: where the search runs
+                esink.reset(new event_file_sink(events_path.c_str()));
+                if (!esink->is_open()) {
+                    fprintf(stderr, "beam: could not open %s\n", events_path.c_str());
+                    return EXIT_FAILURE;
+                }
+                oopt.evt = &evt_opt;
+                oopt.event_sink = esink.get();
+                oopt.stamp_bins = stamp_bins;
+                oopt.stamp_tbin = stamp_tbin;
+                oopt.stamp_fbin = stamp_fbin;
+                oopt.stamp_flagged = stamp_flagged;
+                if (!stamps_path.empty()) {
+                    tsink.reset(new stamp_file_sink(stamps_path.c_str(), full_cfg.n_freq / stamp_fbin, stamp_bins, stamp_fbin));
+                    if (!tsink->is_open()) {
+                        fprintf(stderr, "beam: could not open %s\n", stamps_path.c_str());
+                        return EXIT_FAILURE;
+                    }
+                    oopt.stamp_sink = tsink.get();
+                }
             }
         }
         if (cond_given && my_trials > 0 && (!comm || rank == 0 || oopt.dm_split_trials)) {   // -n: the conditioner runs where the DM stage runs
@@ -772,6 +884,8 @@ int main(int argc, char* argv[])
         if (sink) std::cout << "Wrote " << sink->get_delivered() << " gemm-units of detected powers to " << sink_name << std::endl;
         if (dm_sink) std::cout << "Wrote " << dm_sink->get_times_written() << " dedispersed samples x " << my_trials << " trials to " << dm_path << std::endl;
         if (cand_sink) std::cout << "Wrote " << cand_sink->get_candidates_written() << " candidates to " << cand_path << std::endl;
+        if (esink) std::cout << "Wrote " << esink->get_events_written() << " events to " << events_path << std::endl;
+        if (tsink) std::cout << "Wrote " << tsink->get_stamps_written() << " stamps to " << stamps_path << std::endl;
         if (vsink) std::cout << "Wrote " << vsink->get_dumps_written() << " visibility dumps of " << corr_blocks << " blocks to " << vis_path << std::endl;
         if (xsink) std::cout << "Wrote " << xsink->get_sets_written() << " sets of Stokes beams to " << stokes_path << std::endl;
         if (ksink) std::cout << "Wrote " << ksink->get_dumps_written() << " moment dumps of " << sk_blocks << " blocks to " << sk_path << std::endl;

@@ -5,6 +5,7 @@
 #include <numeric>
 
 #include "bf_runtime_internal.h"
+#include "stamp/bf_stamp_kernels.h"
 
 // ---- DM-trial dedispersion as a stage of the observation loop (include/dsabf.h) ---------------------------
 // The detected stream arrives block by block; out[dm][t][b] needs rows t .. t + max_delay.  The stream keeps the last
@@ -49,6 +50,14 @@ struct bf_dm_stream : bf_stage {
     int reserved_rows = 0;        // ... and how many (0: no reservation outstanding)
     bf_sps* search = nullptr;     // bf_dm_stream_attach_search: every chunk is also pushed into this stage, before `done` is recorded
     bf_cond* cond = nullptr;      // bf_dm_stream_attach_conditioner: every push's new rows are conditioned in place, before `rows_ready` is recorded
+    // bf_dm_stream_cut (docs/EVENTS.md section 2): the end of the most recent cut, recorded behind the cut before it.  The producer of
+    // the rows of a later push waits for it wherever it waits for done[old]: it cannot overwrite what a cut queued before it reads.
+    hipEvent_t cut_done = nullptr;
+    bool cut_recorded = false;    // false: no cut has ever been issued, and nothing waits for the event
+    hipStream_t cut_q = nullptr;  // bf_dm_stream_cut_host: a queue of the stage's own, made at the first call ...
+    float* d_cut = nullptr;       // ... and the device buffer its stamps land in, grown as needed
+    size_t cut_floats = 0;
+    std::vector<int32_t> trial_delay;   // [n_dm]: max over f of delay[dm][f] -- the rows a stamp of that trial needs beyond its times
 };
 
 // One link to an attached stage: the member of the DM stage (search, cond) and that stage's feeder, set and cleared together.
@@ -209,14 +218,23 @@ int bf_dedisperse_dm_band_device(bf_handle* h, const float* d_series, int n_t, i
 
 int bf_dm_stream_create(bf_handle* h, const int32_t* delays, int n_dm, int n_freq_total, int max_rows_per_push, bf_dm_stream** out)
 {
+    return bf_dm_stream_create_history(h, delays, n_dm, n_freq_total, max_rows_per_push, 0, out);
+}
+
+int bf_dm_stream_create_history(bf_handle* h, const int32_t* delays, int n_dm, int n_freq_total, int max_rows_per_push, int history_rows,
+                                bf_dm_stream** out)
+{
     if (!out) return fail(BF_ERR_INVALID, "out is NULL");
     *out = nullptr;
     if (!h || !delays) return fail(BF_ERR_INVALID, "NULL argument");
     if (n_dm <= 0 || n_freq_total <= 0 || max_rows_per_push <= 0) return fail(BF_ERR_INVALID, "need n_dm, n_freq_total, max_rows_per_push > 0");
+    if (history_rows < 0) return fail(BF_ERR_INVALID, "history_rows must be >= 0");
     int dmax = 0;
+    std::vector<int32_t> trial_delay((size_t)n_dm, 0);
     for (size_t i = 0; i < (size_t)n_dm * n_freq_total; i++) {
         if (delays[i] < 0) return fail(BF_ERR_INVALID, "a streamed dedispersion needs delays >= 0 (delay[%zu] = %d)", i, delays[i]);
         if (delays[i] > dmax) dmax = delays[i];
+        if (delays[i] > trial_delay[i / (size_t)n_freq_total]) trial_delay[i / (size_t)n_freq_total] = delays[i];
     }
     ON_DEVICE(h);
     bf_dm_stream* s = new (std::nothrow) bf_dm_stream();
@@ -227,9 +245,11 @@ int bf_dm_stream_create(bf_handle* h, const int32_t* delays, int n_dm, int n_fre
     s->max_delay = dmax;
     s->max_rows = max_rows_per_push;
     s->row_floats = (size_t)n_freq_total * h->cfg.n_beams;
+    s->trial_delay.swap(trial_delay);
     bf_resources& res = s->res;
     // the ring: the window of a push (<= max_delay + max_rows rows) + two more pushes' rows that may be written while it is read
-    if (!h->dm_ring || !dm_ring_create(s, h->device, (size_t)dmax + 3 * (size_t)max_rows_per_push)) {
+    // (+ the rows kept for bf_dm_stream_cut: the linear buffer keeps none)
+    if (!h->dm_ring || !dm_ring_create(s, h->device, (size_t)dmax + 3 * (size_t)max_rows_per_push + (size_t)history_rows)) {
         // linear: room for the carry and a push twice over -- when the end is reached the carry moves to the start without overlapping itself
         s->cap_rows = 2 * ((size_t)dmax + (size_t)max_rows_per_push);
         res.dev(&s->d_buf, s->cap_rows * s->row_floats * sizeof(float));
@@ -245,6 +265,7 @@ int bf_dm_stream_create(bf_handle* h, const int32_t* delays, int n_dm, int n_fre
         res.event(&s->done[k]);
         res.event(&s->rows_ready[k]);
     }
+    res.event(&s->cut_done);
     if (int rc = stage_adopt(s, "bf_dm_stream_create")) return rc;
     *out = s;
     return BF_OK;
@@ -296,6 +317,7 @@ static int dm_place_rows(bf_dm_stream* s, int n_rows, hipStream_t q, float** dst
     if (s->ring) {
         const int old = (int)(s->n_push % 3);        // the slot push j will record into: last recorded by push j - 3
         if (s->done_recorded[old]) HIP_TRY(hipStreamWaitEvent(q, s->done[old], 0));
+        if (s->cut_recorded) HIP_TRY(hipStreamWaitEvent(q, s->cut_done, 0));   // a cut queued before this producer may read the rows it overwrites
         *dst = s->d_buf + s->wpos * s->row_floats;   // (wpos + n_rows may pass cap_rows: the second mapping continues the first)
         return BF_OK;
     }
@@ -424,6 +446,120 @@ int bf_dm_stream_push(bf_dm_stream* s, const float* d_rows, int n_rows, float* h
     s->reserved_rows = 0;
     if (first_t) *first_t = emitted;
     if (n_t_out) *n_t_out = n_out;
+    return BF_OK;
+}
+
+// ---- stamps: dedispersed dynamic spectra of single beams, cut from the ring (docs/EVENTS.md section 2) ------------------------
+// Series row t lies in physical row t % cap_rows (wpos == pushed % cap_rows: the ring starts at row 0 and only ever advances).
+int bf_dm_stream_history(const bf_dm_stream* s, uint64_t* oldest_row, uint64_t* next_row, uint64_t* cap_rows)
+{
+    if (!s || !oldest_row || !next_row || !cap_rows) return fail(BF_ERR_INVALID, "NULL argument");
+    if (int rc = orphaned(s)) return rc;
+    *next_row = s->pushed;
+    *cap_rows = s->cap_rows;
+    // the linear buffer keeps no history: an empty range
+    const uint64_t taken = s->pushed + (uint64_t)s->reserved_rows;   // rows written, or being written by an outstanding reservation's producer
+    *oldest_row = !s->ring ? s->pushed : taken > s->cap_rows ? taken - s->cap_rows : 0;
+    return BF_OK;
+}
+
+int bf_dm_stream_cut(bf_dm_stream* s, const bf_stamp_request* reqs, int n_req, int n_tau, int tbin, int fbin, float* d_out, int32_t* status,
+                     void* hip_stream)
+{
+    if (!s) return fail(BF_ERR_INVALID, "NULL argument");
+    if (n_req < 0) return fail(BF_ERR_INVALID, "n_req must be >= 0");
+    if (n_req > 0 && (!reqs || !d_out || !status)) return fail(BF_ERR_INVALID, "NULL argument");
+    if (int rc = orphaned(s)) return rc;
+    if (!s->ring) return fail(BF_ERR_STATE, "bf_dm_stream_cut: this DM stage runs on the linear buffer, which keeps no history");
+    if (n_tau < 1 || tbin < 1 || fbin < 1 || s->n_freq % fbin != 0)
+        return fail(BF_ERR_INVALID, "need n_tau, tbin, fbin >= 1 and fbin (%d) dividing the band's %d channels", fbin, s->n_freq);
+    if (s->n_freq / fbin > 65535 * 4) return fail(BF_ERR_INVALID, "more than %d frequency groups", 65535 * 4);
+    bf_handle* h = s->h;
+    for (int r = 0; r < n_req; r++)
+        if (reqs[r].dm < 0 || reqs[r].dm >= s->n_dm || reqs[r].beam < 0 || reqs[r].beam >= h->cfg.n_beams)
+            return fail(BF_ERR_INVALID, "request %d: trial %d / beam %d outside [0, %d) / [0, %d)", r, reqs[r].dm, reqs[r].beam, s->n_dm, h->cfg.n_beams);
+    // the statuses: pure arithmetic on what the host knows
+    uint64_t oldest = 0, next = 0, cap = 0;
+    (void)bf_dm_stream_history(s, &oldest, &next, &cap);
+    int n_cut = 0;
+    for (int r = 0; r < n_req; r++) {
+        const uint64_t span = (uint64_t)n_tau * (uint64_t)tbin + (uint64_t)s->trial_delay[(size_t)reqs[r].dm];   // (< 2^62 + 2^31)
+        const uint64_t t0 = reqs[r].t0;
+        status[r] = t0 < oldest ? 1 : (t0 > next || span > next - t0) ? 2 : 0;
+        n_cut += status[r] == 0;
+    }
+    if (!n_cut) return BF_OK;
+    ON_DEVICE(h);
+    hipStream_t q = as_stream(hip_stream);
+    // The ordering, in three steps.  (1) rows_ready of the newest push: recorded behind its producer, its conditioner and rows_ready of
+    // the push before it -- every row < pushed is in place and conditioned.
+    const int newest = (int)((s->n_push + 2) % 3);
+    if (s->n_push && s->rows_recorded[newest]) HIP_TRY(hipStreamWaitEvent(q, s->rows_ready[newest], 0));
+    dsabf::StampBatch batch{};
+    hipError_t launch_err = hipSuccess;
+    int n_items = 0;
+    for (int r = 0; r < n_req; r++) {
+        if (status[r] == 0) {
+            dsabf::StampItem& it = batch.item[n_items++];
+            it.row = reqs[r].t0 % s->cap_rows;   // (the window is <= next - oldest <= cap_rows rows long: it ends inside the second mapping)
+            it.dm = reqs[r].dm;
+            it.beam = reqs[r].beam;
+            it.slot = r;
+        }
+        if (n_items == dsabf::kStampBatch || (r == n_req - 1 && n_items)) {
+            launch_err = dsabf::launch_stamp_cut(s->d_buf, s->row_floats, s->n_freq, h->cfg.n_beams, s->d_delays, batch, n_items, n_tau, tbin, fbin,
+                                                 d_out, q);
+            if (launch_err != hipSuccess) break;   // (what was launched before it is still recorded below)
+            n_items = 0;
+        }
+    }
+    // (2) cut_done, behind the cut before this one: the event then means "this cut and every earlier one have read their rows";
+    // (3) dm_place_rows waits for it in front of every later producer.
+    if (s->cut_recorded) HIP_TRY(hipStreamWaitEvent(q, s->cut_done, 0));
+    HIP_TRY(hipEventRecord(s->cut_done, q));
+    s->cut_recorded = true;
+    if (launch_err != hipSuccess) return fail(BF_ERR_DEVICE, "bf_dm_stream_cut: the launch failed: %s", hipGetErrorString(launch_err));
+    return BF_OK;
+}
+
+// The cut for a host consumer (run_observation): on a queue of the stage's own, into the stage's device buffer, copied to host_out
+// (pinned for an asynchronous copy) and waited for THERE -- the caller's queues keep running.  host_out: [n_req][n_freq / fbin][n_tau];
+// the stamps of requests with a non-zero status are not written.
+int bf_dm_stream_cut_host(bf_dm_stream* s, const bf_stamp_request* reqs, int n_req, int n_tau, int tbin, int fbin, float* host_out, int32_t* status)
+{
+    if (!s) return fail(BF_ERR_INVALID, "NULL argument");
+    if (n_req < 0) return fail(BF_ERR_INVALID, "n_req must be >= 0");
+    if (n_req > 0 && (!reqs || !host_out || !status)) return fail(BF_ERR_INVALID, "NULL argument");
+    if (int rc = orphaned(s)) return rc;
+    if (!s->ring) return fail(BF_ERR_STATE, "bf_dm_stream_cut_host: this DM stage runs on the linear buffer, which keeps no history");
+    if (n_tau < 1 || tbin < 1 || fbin < 1 || s->n_freq % fbin != 0)
+        return fail(BF_ERR_INVALID, "need n_tau, tbin, fbin >= 1 and fbin (%d) dividing the band's %d channels", fbin, s->n_freq);
+    if (!n_req) return BF_OK;
+    bf_handle* h = s->h;
+    ON_DEVICE(h);
+    const size_t stamp_floats = (size_t)(s->n_freq / fbin) * (size_t)n_tau, need = stamp_floats * (size_t)n_req;
+    if (!s->cut_q) {
+        s->res.queue(&s->cut_q);
+        if (s->res.err != hipSuccess) return fail(BF_ERR_DEVICE, "bf_dm_stream_cut_host: %s", hipGetErrorString(s->res.err));
+    }
+    if (need > s->cut_floats) {   // (nothing of an earlier call is in flight: every call ends with a wait for its queue)
+        float* p = nullptr;
+        HIP_TRY(hipMalloc((void**)&p, need * sizeof(float)));
+        for (void*& d : s->res.device)
+            if (d == s->d_cut && d) {
+                (void)hipFree(d);
+                d = nullptr;
+            }
+        s->res.device.push_back(p);
+        s->d_cut = p;
+        s->cut_floats = need;
+    }
+    if (int rc = bf_dm_stream_cut(s, reqs, n_req, n_tau, tbin, fbin, s->d_cut, status, s->cut_q)) return rc;
+    for (int r = 0; r < n_req; r++)
+        if (status[r] == 0)
+            HIP_TRY(hipMemcpyAsync(host_out + (size_t)r * stamp_floats, s->d_cut + (size_t)r * stamp_floats, stamp_floats * sizeof(float),
+                                   hipMemcpyDeviceToHost, s->cut_q));
+    HIP_TRY(hipStreamSynchronize(s->cut_q));
     return BF_OK;
 }
 

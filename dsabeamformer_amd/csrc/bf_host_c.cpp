@@ -692,4 +692,51 @@ int bfh_dm_sink_destroy(bfh_dm_sink* s)
     return BF_OK;
 }
 
+// the event and stamp file sinks on their own (tests, host consumers; no device needed)
+struct bfh_event_sink {
+    event_file_sink s;
+};
+int bfh_event_sink_create(const char* path, bfh_event_sink** out)
+{
+    if (!path || !out) return BF_ERR_INVALID;
+    *out = nullptr;
+    std::unique_ptr<bfh_event_sink> s(new bfh_event_sink{event_file_sink(path)});
+    if (!s->s.is_open()) return BF_ERR_INVALID;
+    *out = s.release();
+    return BF_OK;
+}
+int bfh_event_sink_deliver(bfh_event_sink* s, const bf_evt_event* events, size_t n)
+{
+    if (!s || (n && !events)) return BF_ERR_INVALID;
+    return s->s.deliver(events, n) ? BF_OK : BF_ERR_STATE;
+}
+int bfh_event_sink_destroy(bfh_event_sink* s)
+{
+    delete s;   // (the sink closes its file)
+    return BF_OK;
+}
+struct bfh_stamp_sink {
+    stamp_file_sink s;
+};
+int bfh_stamp_sink_create(const char* path, int n_freq_out, int n_bins, int fbin, bfh_stamp_sink** out)
+{
+    if (!path || !out || n_freq_out < 1 || n_bins < 1 || fbin < 1) return BF_ERR_INVALID;
+    *out = nullptr;
+    std::unique_ptr<bfh_stamp_sink> s(new bfh_stamp_sink{stamp_file_sink(path, n_freq_out, n_bins, fbin)});
+    if (!s->s.is_open()) return BF_ERR_INVALID;
+    *out = s.release();
+    return BF_OK;
+}
+int bfh_stamp_sink_deliver(bfh_stamp_sink* s, uint64_t t0, int dm, int beam, int tbin, int width, double snr, const float* data, int n_freq_out,
+                           int n_bins)
+{
+    if (!s || !data) return BF_ERR_INVALID;
+    return s->s.deliver(t0, dm, beam, tbin, width, snr, data, n_freq_out, n_bins) ? BF_OK : BF_ERR_STATE;
+}
+int bfh_stamp_sink_destroy(bfh_stamp_sink* s)
+{
+    delete s;
+    return BF_OK;
+}
+
 }  // extern "C"

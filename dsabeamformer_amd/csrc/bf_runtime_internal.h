@@ -1,5 +1,5 @@
 // bf_runtime_internal.h -- what the C-ABI runtime's translation units share (bf_runtime.cpp, bf_queues.cpp, bf_dm_stream.cpp,
-// bf_sps.cpp, bf_cond.cpp, bf_corr.cpp, bf_sk.cpp, bf_stokes.cpp, bf_bench_abi.cpp): the handle, the base of its stages, the error string, the device scope.
+// bf_sps.cpp, bf_cond.cpp, bf_corr.cpp, bf_sk.cpp, bf_stokes.cpp, bf_evt.cpp, bf_bench_abi.cpp): the handle, the base of its stages, the error string, the device scope.
 // Host-only and not installed: no .hip / .hpp file includes it.
 #pragma once
 #include "../../include/dsabf.h"

@@ -207,6 +207,7 @@ struct run_resources {
     bf_corr* corr = nullptr;
     bf_sk* sk = nullptr;
     bf_stokes* stokes = nullptr;
+    bf_evt* evt = nullptr;
     std::vector<void*> pinned;
     ~run_resources()
     {
@@ -215,6 +216,7 @@ struct run_resources {
         bf_sk_destroy(sk);
         bf_stokes_destroy(stokes);
         bf_sps_destroy(sps);
+        bf_evt_destroy(evt);
         bf_cond_destroy(cond);
         bf_dm_stream_destroy(dm);
         for (void* p : pinned) bf_free_pinned(p);
@@ -490,6 +492,11 @@ int check_options(const bf_config& cfg, const observation_options& opt)
     if (opt.sps_widths < 0 || opt.sps_widths > 8) return set_error(BF_ERR_INVALID, "run_observation: sps_widths must be 0 (off) .. 8");
     if ((opt.sps_widths || opt.sps_sink) && !opt.dm_delays) return set_error(BF_ERR_INVALID, "run_observation: the single-pulse search needs the DM stage (dm_delays)");
     if (opt.sps_sink && !opt.sps_widths) return set_error(BF_ERR_INVALID, "run_observation: a sps_sink needs sps_widths > 0");
+    if (opt.evt && !opt.sps_widths) return set_error(BF_ERR_INVALID, "run_observation: the event builder (evt) needs sps_widths > 0");
+    if ((opt.event_sink || opt.stamp_sink) && !opt.evt) return set_error(BF_ERR_INVALID, "run_observation: an event_sink or a stamp_sink needs evt");
+    if (opt.evt && (opt.stamp_bins < 1 || opt.stamp_tbin < 0 || opt.stamp_fbin < 1 || opt.stamp_max_per_deliver < 0 ||
+                    (cfg.n_freq * (opt.comm ? opt.world : 1)) % opt.stamp_fbin != 0))
+        return set_error(BF_ERR_INVALID, "run_observation: need stamp_bins >= 1, stamp_tbin >= 0, stamp_max_per_deliver >= 0 and stamp_fbin >= 1 dividing the band");
     if (opt.cond_baseline < 0 || opt.cond_baseline > 64) return set_error(BF_ERR_INVALID, "run_observation: cond_baseline must be 0 (off) .. 64");
     if (opt.cond_baseline && !opt.dm_delays) return set_error(BF_ERR_INVALID, "run_observation: the conditioner needs the DM stage (dm_delays)");
     if (!opt.cond_baseline && (opt.cond_mask || opt.cond_auto_threshold != 0.0))
@@ -569,6 +576,13 @@ int resolve_plan(const bf_config& cfg, const observation_options& opt, launch_pl
 
 constexpr size_t kStokesSetBytesMax = (size_t)8 << 30;   // all result sets of a run's Stokes stage, per side (device, pinned)
 
+// A stamp that is wanted: the request (local trial index), and what the sink is told about the event it belongs to.
+struct stamp_want {
+    bf_stamp_request rq;
+    int tbin, width, dm_global;
+    double snr;
+};
+
 struct dm_chunk {
     uint64_t block, first_t;
     int n_t;
@@ -594,6 +608,12 @@ struct production_run {
     uint64_t dm_seq = 0, dm_times = 0, dm_chunks = 0;
     std::vector<bf_sps_candidate> cands;  // what bf_sps_collect returns for one chunk
     uint64_t sps_candidates = 0;
+    bf_evt_options evt_opt{};              // opt.evt with max_width and ib_beam filled in
+    std::vector<bf_evt_event> events_out;  // what one feed closes
+    std::deque<stamp_want> stamp_pending;  // wanted, not yet cut: new ones, and those answered "not pushed yet"
+    float* stamp_host = nullptr;           // pinned: the stamps of one cut
+    size_t stamp_batch = 0;                // requests one cut takes
+    uint64_t events = 0, stamps = 0, stamps_dropped = 0, stamps_missed = 0, stamps_beyond_end = 0;
     float* cond_mask_host = nullptr;      // pinned, whole dwords: where the conditioner's mask of the last push is read back at the end
 
     // channels the conditioner masked in the last push (-1: no conditioner, or no push)
@@ -647,10 +667,22 @@ struct production_run {
     {
         int rc = BF_OK;
         if (plan.dm_run) {
-            rc = bf_dm_stream_create(dev.h, opt.dm_delays + (size_t)plan.dm_first * plan.n_freq_band, plan.dm_count, plan.n_freq_band, plan.dm_rows, &dev.dm);
-            if (rc != BF_OK) return gpu_error(log, rc);
             // chunks in flight: the launches of MAX_TOTAL_SEP blocks queued + the one being delivered
             const size_t n_buf = (size_t)(kMaxTotalSep + 2) * (size_t)(cfg.n_gemms_per_block / plan.upl);
+            int history_rows = 0;
+            if (opt.evt && opt.stamp_sink) {   // docs/EVENTS.md section 3: span / 2 + t_tol + max_width + (n_buf + 1) dm_rows
+                const int max_width = 1 << (opt.sps_widths - 1), tbin_max = opt.stamp_tbin ? opt.stamp_tbin : std::max(1, max_width / 2);
+                history_rows = opt.stamp_bins * tbin_max / 2 + opt.evt->t_tol + max_width + (int)(n_buf + 1) * plan.dm_rows;
+            }
+            rc = bf_dm_stream_create_history(dev.h, opt.dm_delays + (size_t)plan.dm_first * plan.n_freq_band, plan.dm_count, plan.n_freq_band,
+                                             plan.dm_rows, history_rows, &dev.dm);
+            if (rc != BF_OK) return gpu_error(log, rc);
+            if (history_rows) {
+                uint64_t oldest = 0, next = 0, cap = 0;
+                bf_dm_stream_history(dev.dm, &oldest, &next, &cap);
+                log << "Stamps: DM ring of " << cap << " rows (" << ((cap * (uint64_t)plan.n_freq_band * (uint64_t)cfg.n_beams * 4) >> 20) << " MiB), "
+                    << history_rows << " of them history" << std::endl;
+            }
             for (size_t i = 0; i < n_buf; i++) {
                 float* chunk = nullptr;
                 if ((rc = dev.alloc_pinned((size_t)plan.dm_count * plan.dm_rows * cfg.n_beams, &chunk)) != BF_OK) return rc;
@@ -674,6 +706,17 @@ struct production_run {
                 if (rc == BF_OK) rc = bf_dm_stream_attach_search(dev.dm, dev.sps);
                 if (rc != BF_OK) return gpu_error(log, rc);
                 cands.resize((size_t)plan.dm_count * cfg.n_beams);
+            }
+            if (opt.evt) {
+                evt_opt = *opt.evt;
+                evt_opt.max_width = 1 << (opt.sps_widths - 1);
+                if (evt_opt.ib_beam < 0) evt_opt.ib_beam = opt.incoherent_beam;
+                if ((rc = bf_evt_create(&evt_opt, &dev.evt)) != BF_OK) return gpu_error(log, rc);
+                if (opt.stamp_sink) {
+                    stamp_batch = (size_t)std::max(1, opt.stamp_max_per_deliver);
+                    const size_t stamp_floats = (size_t)(plan.n_freq_band / opt.stamp_fbin) * (size_t)opt.stamp_bins;
+                    if ((rc = dev.alloc_pinned(stamp_batch * stamp_floats, &stamp_host)) != BF_OK) return rc;
+                }
             }
         }
         if (opt.corr_blocks > 0) {   // dumps in flight: one per block queued at most, + the one being delivered
@@ -832,6 +875,86 @@ struct production_run {
         return rc;
     }
 
+    // The events one feed (or the flush) closed: to the sink; then the stamps that are wanted of them -- unflagged ones unless
+    // stamp_flagged, by snr descending, then event order, at most stamp_max_per_deliver; the rest are counted as dropped.
+    int take_events(size_t n)
+    {
+        events += n;
+        if (opt.event_sink && n && !opt.event_sink->deliver(events_out.data(), n)) {
+            log << "ERROR: event sink failed" << std::endl;
+            return BF_ERR_STATE;
+        }
+        if (!opt.stamp_sink) return BF_OK;
+        std::vector<size_t> pick;
+        for (size_t i = 0; i < n; i++)
+            if (opt.stamp_flagged || !events_out[i].flags) pick.push_back(i);
+        std::stable_sort(pick.begin(), pick.end(), [&](size_t a, size_t b) { return events_out[a].best.snr > events_out[b].best.snr; });
+        const size_t cap = (size_t)opt.stamp_max_per_deliver;
+        if (pick.size() > cap) {
+            stamps_dropped += pick.size() - cap;
+            pick.resize(cap);
+        }
+        for (size_t i : pick) {
+            const bf_sps_candidate& b = events_out[i].best;
+            const int tbin = opt.stamp_tbin ? opt.stamp_tbin : std::max(1, b.width / 2);
+            const uint64_t centre = b.t_start + (uint64_t)(b.width / 2), half = (uint64_t)opt.stamp_bins * (uint64_t)tbin / 2;
+            stamp_pending.push_back({{centre > half ? centre - half : 0, b.dm - plan.dm_first, b.beam}, tbin, b.width, b.dm, b.snr});
+        }
+        return BF_OK;
+    }
+
+    // One round of cuts over everything pending (a call per time binning, stamp_batch requests at most): cut ones go to the sink, those
+    // whose rows have left the ring are counted as missed, those not pushed yet stay -- at the end of the run they are counted as
+    // beyond it: their window passes the last row the run produced.
+    int cut_stamps(bool last)
+    {
+        if (stamp_pending.empty()) return BF_OK;
+        std::deque<stamp_want> todo;
+        todo.swap(stamp_pending);
+        const int n_freq_out = plan.n_freq_band / opt.stamp_fbin;
+        const size_t stamp_floats = (size_t)n_freq_out * (size_t)opt.stamp_bins;
+        while (!todo.empty()) {
+            const int tbin = todo.front().tbin;
+            std::vector<stamp_want> group;
+            std::deque<stamp_want> rest;
+            for (const stamp_want& w : todo)
+                if (w.tbin == tbin && group.size() < stamp_batch) group.push_back(w); else rest.push_back(w);
+            todo.swap(rest);
+            std::vector<bf_stamp_request> rq;
+            for (const stamp_want& w : group) rq.push_back(w.rq);
+            std::vector<int32_t> status(group.size(), -1);
+            const int rc = bf_dm_stream_cut_host(dev.dm, rq.data(), (int)rq.size(), opt.stamp_bins, tbin, opt.stamp_fbin, stamp_host, status.data());
+            if (rc != BF_OK) return gpu_error(log, rc);
+            for (size_t i = 0; i < group.size(); i++) {
+                const stamp_want& w = group[i];
+                if (status[i] == 2) {   // not pushed yet: retried at the next deliver -- or, at the end of the run, never there
+                    if (last) stamps_beyond_end++; else stamp_pending.push_back(w);
+                } else if (status[i] == 1) {
+                    stamps_missed++;
+                } else {
+                    stamps++;
+                    if (!opt.stamp_sink->deliver(w.rq.t0, w.dm_global, w.rq.beam, w.tbin, w.width, w.snr, stamp_host + i * stamp_floats, n_freq_out, opt.stamp_bins)) {
+                        log << "ERROR: stamp sink failed at time " << w.rq.t0 << std::endl;
+                        return BF_ERR_STATE;
+                    }
+                }
+            }
+        }
+        return BF_OK;
+    }
+
+    // The end of the run: every open cluster closes, and one last round of cuts.
+    int flush_events()
+    {
+        if (!dev.evt) return BF_OK;
+        size_t n = 0;
+        events_out.resize((size_t)bf_evt_open(dev.evt));
+        int rc = bf_evt_flush(dev.evt, events_out.data(), events_out.size(), &n);
+        if (rc != BF_OK) return gpu_error(log, rc);
+        if ((rc = take_events(n)) != BF_OK) return rc;
+        return opt.stamp_sink ? cut_stamps(/*last=*/true) : BF_OK;
+    }
+
     // What the blocks analysed so far finished: their DM chunks have landed (their copies sit on the queues the analysis event joins),
     // and so has every D2H copy of their gemm-units: hand those over, in order.
     int deliver(uint64_t blocks_analyzed)
@@ -849,6 +972,13 @@ struct production_run {
                     log << "ERROR: candidate sink failed at output time " << c.first_t << std::endl;
                     return BF_ERR_STATE;
                 }
+                if (dev.evt) {   // the chunk's candidates (global trial indices) into the builder; what closes goes to the sinks
+                    size_t n_ev = 0;
+                    events_out.resize((size_t)bf_evt_open(dev.evt) + n);
+                    const int rc_e = bf_evt_feed(dev.evt, cands.data(), n, c.first_t + (uint64_t)c.n_t, events_out.data(), events_out.size(), &n_ev);
+                    if (rc_e != BF_OK) return gpu_error(log, rc_e);
+                    if (int rc_t = take_events(n_ev)) return rc_t;
+                }
             }
             if (!opt.dm_sink) continue;
             dm_chunks++;
@@ -857,6 +987,8 @@ struct production_run {
                 return BF_ERR_STATE;
             }
         }
+        if (opt.stamp_sink)   // one round of cuts per deliver, on the stage's own queue: the compute queues keep running
+            if (int rc = cut_stamps(/*last=*/false)) return rc;
         while (!vis_pending.empty() && vis_pending.front().second < blocks_analyzed) {   // (the collect waits for the dump's own copy)
             const uint64_t first_block = vis_pending.front().first;
             vis_pending.pop_front();
@@ -955,6 +1087,9 @@ int run_observation(const bf_config& cfg, const observation_options& opt, block_
     float ms = 0;
     bf_timer_stop(h, &ms);
     bf_stream_sync(h, -1);  // :560-562
+    if ((rc = run.flush_events()) != BF_OK) return rc;
+    if (opt.event_sink) opt.event_sink->close();
+    if (opt.stamp_sink) opt.stamp_sink->close();
     if (opt.sink) opt.sink->close();
     if (opt.dm_sink) opt.dm_sink->close();
     if (opt.sps_sink) opt.sps_sink->close();
@@ -974,6 +1109,11 @@ int run_observation(const bf_config& cfg, const observation_options& opt, block_
         res->dm_times = run.dm_times;
         res->dm_chunks = run.dm_chunks;
         res->sps_candidates = run.sps_candidates;
+        res->events = run.events;
+        res->stamps = run.stamps;
+        res->stamps_dropped = run.stamps_dropped;
+        res->stamps_missed = run.stamps_missed;
+        res->stamps_beyond_end = run.stamps_beyond_end;
         res->vis_dumps = run.vis_dumps;
         res->sk_dumps = run.sk_dumps;
         res->stokes_units = run.stokes_units;
@@ -1005,6 +1145,13 @@ int run_observation(const bf_config& cfg, const observation_options& opt, block_
     if (run.dev.sps)
         log << "Single-pulse search: boxcar widths 1 .. " << (1 << (opt.sps_widths - 1)) << ", " << run.sps_candidates << " candidates at S/N >= "
             << opt.sps_threshold << std::endl;
+    if (run.dev.evt) {
+        log << "Events: " << run.events << " events";
+        if (opt.stamp_sink)
+            log << ", stamps " << run.stamps << ", stamps_dropped " << run.stamps_dropped << ", stamps_missed " << run.stamps_missed
+                << ", beyond the end of the run " << run.stamps_beyond_end;
+        log << std::endl;
+    }
     return BF_OK;
 }
 

@@ -269,6 +269,42 @@ def run_observation_junk_to_file(cfg: BfConfig, n_blocks: int, path: str, ring_b
     return {"ms": ms.value, "gemms_written": n.value, "ring": ring}
 
 
+def read_event_file(path: str):
+    """Parse a dsabf::event_file_sink file (docs/EVENTS.md): a structured array of ``api.event_dtype()``, one entry per line."""
+    from .api import event_dtype
+
+    lines = open(path).read().splitlines()
+    assert lines and lines[0].split() == "# t_start dm beam width snr peak n_members n_beams dm_lo dm_hi t_lo t_hi snr_ib flags".split(), path
+    out = np.zeros(len(lines) - 1, event_dtype())
+    for k, line in enumerate(lines[1:]):
+        v = line.split()
+        assert len(v) == 14, line
+        out["best"][k] = (int(v[0]), int(v[1]), int(v[2]), int(v[3]), float(v[5]), float(v[4]))   # (the record's order: ..., peak, snr)
+        out[k]["n_members"], out[k]["n_beams"], out[k]["dm_lo"], out[k]["dm_hi"] = (int(x) for x in v[6:10])
+        out[k]["t_lo"], out[k]["t_hi"], out[k]["snr_ib"], out[k]["flags"] = int(v[10]), int(v[11]), float(v[12]), int(v[13])
+    return out
+
+
+def read_stamp_file(path: str):
+    """Parse a dsabf::stamp_file_sink file: returns (header dict, list of dict(t0, dm, beam, tbin, width, snr, data float32
+    [NFREQ_OUT][NBINS])), in the order the stamps were written."""
+    raw = open(path, "rb").read()
+    text = raw[:DETECTED_HEADER_BYTES].split(b"\0", 1)[0].decode()
+    hdr = dict(line.split(None, 1) for line in text.splitlines() if line.strip())
+    assert hdr["CONTENT"] == "stamps" and hdr["DTYPE"] == "float32" and hdr["LAYOUT"] == "freq,time"
+    n_f, n_b, at, rec = int(hdr["NFREQ_OUT"]), int(hdr["NBINS"]), int(hdr["HDR_SIZE"]), int(hdr["RECORD_HEADER_BYTES"])
+    stamps = []
+    while at < len(raw):
+        t0 = int(np.frombuffer(raw, "<u8", 1, at)[0])
+        dm, beam, tbin, width = (int(v) for v in np.frombuffer(raw, "<i4", 4, at + 8))
+        snr = float(np.frombuffer(raw, "<f8", 1, at + 24)[0])
+        at += rec
+        stamps.append(dict(t0=t0, dm=dm, beam=beam, tbin=tbin, width=width, snr=snr, data=np.frombuffer(raw, "<f4", n_f * n_b, at).reshape(n_f, n_b)))
+        at += 4 * n_f * n_b
+    assert at == len(raw)
+    return hdr, stamps
+
+
 def read_dm_file(path: str):
     """Parse a dsabf::dm_file_sink file: returns (header dict, float32 array [n_dm][T][n_beams], list of (first_t, n_t) per
     chunk).  The chunks ([dm][t][beam] each) are joined along t; they follow each other without gaps."""

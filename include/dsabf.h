@@ -643,6 +643,77 @@ int bf_cond_push(bf_cond *c, float *d_rows, int n_rows, void *hip_stream);
 int bf_cond_mask_device(bf_cond *c, const uint8_t **d_mask);
 int bf_dm_stream_attach_conditioner(bf_dm_stream *dm, bf_cond *c);
 
+/* ---- Candidate events and dedispersed stamps behind the search (docs/EVENTS.md) -----------------------------------------
+ * The reference stops at a DM-0 collapse copied to the host (src/beamformer.cu:498-510); the search behind the DM stage ends
+ * in bf_sps_candidate records, one per (trial, beam) and push.  Two opt-in pieces turn those into "one thing happened" and
+ * into the evidence for it; with neither in use nothing changes.
+ * (1) bf_evt: a streaming friends-of-friends grouping of candidates -- host, fp64, no GPU, a pure function of the feeds.
+ *   A candidate covers the closed interval [a0, a1] = [t_start, t_start + width - 1].  A and B are LINKED iff
+ *   a0 <= b1 + t_tol, b0 <= a1 + t_tol and |dmA - dmB| <= dm_tol (beams play no part); a cluster is a connected component of
+ *   the links.  bf_evt_feed takes the candidates of one collected push; next_t = that push's first_t + n_t, and every LATER
+ *   candidate has t_start >= next_t - (max_width - 1).  A member is live while a1 + t_tol >= next_t - (max_width - 1); a
+ *   cluster closes at the first feed after which it has no live member, and leaves as one bf_evt_event.  A cluster that is
+ *   fed without pause stays one event.  bf_evt_flush closes everything; bf_evt_open: clusters still open.
+ *   best: the member with the largest snr among beams other than ib_beam (ties: smaller t_start, dm, beam, width); only
+ *   ib_beam members: the best of those and BF_EVT_IB_ONLY.  t_lo / t_hi: min a0 / max a1; dm_lo / dm_hi; n_members; n_beams:
+ *   distinct beams other than ib_beam; snr_ib: largest snr of an ib_beam member, 0.0 without one.  BF_EVT_WIDE: n_beams >
+ *   max_beams.  BF_EVT_INCOHERENT: ib_beam >= 0 and (IB_ONLY or snr_ib >= ib_ratio * best.snr).  The events of one call
+ *   leave sorted by (best.t_start, best.dm, best.beam).  BF_ERR_INVALID: negative tolerances, max_width < 1, max_beams < 0,
+ *   a NaN or negative ib_ratio, NULL pointers, max_out smaller than the events that close (nothing is consumed then).
+ * (2) stamps: bf_dm_stream_create_history is bf_dm_stream_create with a ring of at least max_delay + 3 max_rows_per_push +
+ *   history_rows rows (bf_dm_stream_create is that call with 0).  bf_dm_stream_history: rows [*oldest_row, *next_row) of the
+ *   series are readable; next_row = rows pushed, oldest_row = max(0, pushed + reserved rows - cap_rows) (the producer of an
+ *   outstanding reservation is already overwriting the oldest rows).  bf_dm_stream_cut, asynchronous on hip_stream:
+ *     out[r][g][tau] = sum over f = g fbin .. g fbin + fbin - 1, ascending, of
+ *                      ( sum over i = 0 .. tbin - 1, ascending, of x[t0 + tau tbin + i + delay[dm][f]][f][beam] ),
+ *   fp32, [n_req][n_freq_total / fbin][n_tau] on the device, every sum sequential from its first element, one rounding per
+ *   add; x is the row as it lies in the ring (conditioned behind an attached conditioner: what the search saw); dm is the
+ *   LOCAL trial index.  Request r needs rows [t0, t0 + n_tau tbin + max_f delay[dm][f]).  status[r] (host, filled before the
+ *   call returns): 0 cut, 1 a row is older than oldest_row, 2 a row is not pushed yet (1 wins where both hold); a request
+ *   with a non-zero status launches nothing and its cells stay untouched.  A producer queued after a cut waits for it.
+ *   bf_dm_stream_cut_host is the cut for a host consumer (run_observation): on a queue of the stage's own, into a device buffer of
+ *   the stage, copied to host_out ([n_req][n_freq_total / fbin][n_tau], pinned) and waited for THERE; the caller's queues keep running.
+ *   BF_ERR_INVALID, nothing launched: dm, beam or n_req out of range, n_tau, tbin or fbin < 1, fbin not dividing
+ *   n_freq_total, NULL pointers.  BF_ERR_STATE: the linear fallback buffer (it keeps no history), or an orphaned stage. */
+typedef struct bf_evt bf_evt;
+typedef struct bf_evt_options {
+    int32_t t_tol, dm_tol; /* samples, trials */
+    int32_t max_width;     /* 2^(n_widths - 1) of the search that feeds it */
+    int32_t max_beams;     /* more distinct beams than this: BF_EVT_WIDE */
+    int32_t ib_beam;       /* the incoherent column, -1: none */
+    double ib_ratio;
+} bf_evt_options;
+#define BF_EVT_IB_ONLY 1u
+#define BF_EVT_WIDE 2u
+#define BF_EVT_INCOHERENT 4u
+typedef struct bf_evt_event {
+    bf_sps_candidate best;
+    uint64_t t_lo, t_hi;
+    int32_t dm_lo, dm_hi;
+    int32_t n_members, n_beams;
+    double snr_ib;
+    uint32_t flags;
+} bf_evt_event;
+typedef struct bf_stamp_request {
+    uint64_t t0;
+    int32_t dm; /* local trial index */
+    int32_t beam;
+} bf_stamp_request;
+void bf_evt_default_options(bf_evt_options *o); /* 0, 1, 128, 4, -1, 0.5: design defaults (src/beamformer.cu:498-510 has no such step) */
+int bf_evt_create(const bf_evt_options *o, bf_evt **out);
+int bf_evt_destroy(bf_evt *e);
+int bf_evt_feed(bf_evt *e, const bf_sps_candidate *cands, size_t n, uint64_t next_t, bf_evt_event *out, size_t max_out,
+                size_t *n_out);
+int bf_evt_flush(bf_evt *e, bf_evt_event *out, size_t max_out, size_t *n_out);
+int bf_evt_open(const bf_evt *e);
+int bf_dm_stream_create_history(bf_handle *h, const int32_t *delays, int n_dm, int n_freq_total, int max_rows_per_push,
+                                int history_rows, bf_dm_stream **out);
+int bf_dm_stream_history(const bf_dm_stream *s, uint64_t *oldest_row, uint64_t *next_row, uint64_t *cap_rows);
+int bf_dm_stream_cut(bf_dm_stream *s, const bf_stamp_request *reqs, int n_req, int n_tau, int tbin, int fbin, float *d_out,
+                     int32_t *status, void *hip_stream);
+int bf_dm_stream_cut_host(bf_dm_stream *s, const bf_stamp_request *reqs, int n_req, int n_tau, int tbin, int fbin,
+                          float *host_out, int32_t *status);
+
 /* ---- Multi-GPU: frequency shards and the gather of their detected powers -------------------------------
  * The reference runs 8 independent processes, one sub-band per GPU (`-g`, src/beamformer.cu:92-100,233; README.md:168)
  * and never brings their outputs together.  Here a handle may own any contiguous range of frequencies (bf_config.n_freq

@@ -164,6 +164,19 @@ int bfh_dm_sink_create(const bf_config *cfg, const char *target, int n_freq_tota
 int bfh_dm_sink_deliver(bfh_dm_sink *s, uint64_t first_t, int n_t, int n_dm, int n_beams, const float *data);
 int bfh_dm_sink_destroy(bfh_dm_sink *s);
 
+/* The event and stamp file sinks on their own (docs/EVENTS.md section 3; tests and host consumers, no device): dsabf::event_file_sink
+ * writes one text line per event, dsabf::stamp_file_sink the 4096-byte header and one record per stamp (data: float32
+ * [n_freq_out][n_bins], the shape given at creation -- another one is refused with BF_ERR_STATE). */
+typedef struct bfh_event_sink bfh_event_sink;
+int bfh_event_sink_create(const char *path, bfh_event_sink **out);
+int bfh_event_sink_deliver(bfh_event_sink *s, const bf_evt_event *events, size_t n);
+int bfh_event_sink_destroy(bfh_event_sink *s);
+typedef struct bfh_stamp_sink bfh_stamp_sink;
+int bfh_stamp_sink_create(const char *path, int n_freq_out, int n_bins, int fbin, bfh_stamp_sink **out);
+int bfh_stamp_sink_deliver(bfh_stamp_sink *s, uint64_t t0, int dm, int beam, int tbin, int width, double snr, const float *data,
+                           int n_freq_out, int n_bins);
+int bfh_stamp_sink_destroy(bfh_stamp_sink *s);
+
 /* DM trial ladder and per-channel sample delays (sandbox/Dispersion Theory.ipynb cells 1-2 and 5; dsabf::dm_trials,
  * dsabf::dm_delays).  bfh_dm_trials returns the number of trials written (<= cap). */
 int bfh_dm_trials(double dm0, double dm_max, int nchan, double epsilon, double nu_ghz, double chan_bw_mhz, double ti_us,

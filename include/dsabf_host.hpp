@@ -583,6 +583,97 @@ public:
     uint64_t get_candidates_written() const { return written; }
 };
 
+// ---- Events and stamps behind the search (include/dsabf.h: bf_evt_*, bf_dm_stream_cut_host; docs/EVENTS.md) -------------------
+// With observation_options::evt set run_observation feeds every collected chunk's candidates to a bf_evt and hands the events that
+// close to an event_sink; with a stamp_sink it also cuts the dedispersed stamp of (at most stamp_max_per_deliver of) them out of the
+// DM stage's ring and hands each to the stamp_sink.
+struct event_sink {
+    virtual ~event_sink() {}
+    virtual bool deliver(const bf_evt_event* events, size_t n) = 0;
+    virtual void close() {}
+};
+
+// Text file: a `#` header line, then one line per event:
+// t_start dm beam width snr peak n_members n_beams dm_lo dm_hi t_lo t_hi snr_ib flags (the first six: the best member's record).
+class event_file_sink : public event_sink {
+    FILE* fp = nullptr;
+    uint64_t written = 0;
+
+public:
+    explicit event_file_sink(const char* path) : fp(fopen(path, "w"))
+    {
+        if (fp) fprintf(fp, "# t_start dm beam width snr peak n_members n_beams dm_lo dm_hi t_lo t_hi snr_ib flags\n");
+    }
+    ~event_file_sink() override { close(); }
+    event_file_sink(const event_file_sink&) = delete;
+    event_file_sink& operator=(const event_file_sink&) = delete;
+    bool is_open() const { return fp != nullptr; }
+    bool deliver(const bf_evt_event* e, size_t n) override
+    {
+        if (!fp) return false;
+        for (size_t i = 0; i < n; i++)
+            if (fprintf(fp, "%llu %d %d %d %.17g %.9g %d %d %d %d %llu %llu %.17g %u\n", (unsigned long long)e[i].best.t_start, e[i].best.dm, e[i].best.beam,
+                        e[i].best.width, e[i].best.snr, (double)e[i].best.peak, e[i].n_members, e[i].n_beams, e[i].dm_lo, e[i].dm_hi,
+                        (unsigned long long)e[i].t_lo, (unsigned long long)e[i].t_hi, e[i].snr_ib, e[i].flags) < 0)
+                return false;
+        written += n;
+        return true;
+    }
+    void close() override
+    {
+        if (fp) fclose(fp);
+        fp = nullptr;
+    }
+    uint64_t get_events_written() const { return written; }
+};
+
+// One stamp: the request it was cut for (t0, the GLOBAL trial index, beam), its time binning, the best member's width and S/N, and
+// data float32 [n_freq_out][n_bins].
+struct stamp_sink {
+    virtual ~stamp_sink() {}
+    virtual bool deliver(uint64_t t0, int dm, int beam, int tbin, int width, double snr, const float* data, int n_freq_out, int n_bins) = 0;
+    virtual void close() {}
+};
+
+// File: the 4096-byte ASCII header (`KEY value` lines, NUL padded: CONTENT stamps, DTYPE float32, NFREQ_OUT, NBINS, FBIN, LAYOUT
+// freq,time), then one record per stamp: uint64 t0; int32 dm, beam, tbin, width; double snr; the n_freq_out * n_bins floats.
+class stamp_file_sink : public stamp_sink {
+    FILE* fp = nullptr;
+    uint64_t written = 0;
+    int n_freq_out, n_bins;
+
+public:
+    static constexpr size_t kHeaderBytes = 4096;
+    static constexpr size_t kRecordBytes = 32;
+    stamp_file_sink(const char* path, int n_freq_out_, int n_bins_, int fbin) : fp(fopen(path, "wb")), n_freq_out(n_freq_out_), n_bins(n_bins_)
+    {
+        if (!fp) return;
+        char header[kHeaderBytes] = {0};
+        snprintf(header, sizeof header, "HDR_SIZE 4096\nCONTENT stamps\nDTYPE float32\nNFREQ_OUT %d\nNBINS %d\nFBIN %d\nLAYOUT freq,time\nRECORD_HEADER_BYTES 32\n",
+                 n_freq_out, n_bins, fbin);
+        if (fwrite(header, 1, sizeof header, fp) != sizeof header) close();
+    }
+    ~stamp_file_sink() override { close(); }
+    stamp_file_sink(const stamp_file_sink&) = delete;
+    stamp_file_sink& operator=(const stamp_file_sink&) = delete;
+    bool is_open() const { return fp != nullptr; }
+    bool deliver(uint64_t t0, int dm, int beam, int tbin, int width, double snr, const float* data, int nf, int nb) override
+    {
+        if (!fp || nf != n_freq_out || nb != n_bins) return false;
+        const int32_t ints[4] = {dm, beam, tbin, width};
+        const size_t n = (size_t)nf * (size_t)nb;
+        if (fwrite(&t0, 8, 1, fp) != 1 || fwrite(ints, 4, 4, fp) != 4 || fwrite(&snr, 8, 1, fp) != 1 || fwrite(data, sizeof(float), n, fp) != n) return false;
+        written++;
+        return true;
+    }
+    void close() override
+    {
+        if (fp) fclose(fp);
+        fp = nullptr;
+    }
+    uint64_t get_stamps_written() const { return written; }
+};
+
 // ---- The correlator inside the loop (include/dsabf.h: bf_corr_*; docs/CORRELATOR.md) ------------------------------------------
 // With observation_options::corr_blocks > 0 run_observation creates a bf_corr, pushes the gemm-units of every launch into it on the
 // launch's queue (behind the detect launch, from the resident block), dumps after the last launch of every corr_blocks-th analysed
@@ -870,6 +961,21 @@ struct observation_options {
     int sps_widths = 0;
     double sps_threshold = 8.0;
     sps_candidate_sink* sps_sink = nullptr;
+    // Events and stamps (docs/EVENTS.md; evt needs sps_widths > 0, stamp_sink needs evt).  evt: the builder's options (NULL = off);
+    // max_width is forced to the search's 2^(sps_widths-1), an ib_beam of -1 becomes incoherent_beam.  Closed events go to event_sink
+    // (may be NULL).  Of the events ONE FEED closes -- deliver() feeds one collected chunk at a time, so the rule does not depend on how
+    // many chunks a deliver happens to find -- at most stamp_max_per_deliver -- by snr descending, then event order; flagged ones only with
+    // stamp_flagged -- get a stamp of stamp_bins bins of stamp_tbin samples (0: max(1, best.width / 2)) and stamp_fbin channels per
+    // row, centred on the best member; the rest count in observation_result::stamps_dropped.  The DM stage is created with the
+    // history of docs/EVENTS.md section 3.  With dm_split_trials every rank builds and cuts its own trials.
+    const bf_evt_options* evt = nullptr;
+    dsabf::event_sink* event_sink = nullptr;
+    dsabf::stamp_sink* stamp_sink = nullptr;
+    int stamp_bins = 64;
+    int stamp_tbin = 0;
+    int stamp_fbin = 1;
+    bool stamp_flagged = false;
+    int stamp_max_per_deliver = 16;
     // Conditioning in front of the DM stage (docs/CONDITIONING.md; needs dm_delays): cond_baseline = pushes of the statistics' window
     // (1 .. 64), 0 = off.  A bf_cond is created next to the DM stage and attached to it: every pushed block is normalised per
     // (channel, beam), masked (cond_mask: host uint8 [cfg.n_freq * world], nonzero = masked, or NULL; cond_auto_threshold > 0 adds the
@@ -916,6 +1022,11 @@ struct observation_result {
     uint64_t dm_times = 0;          // output times the DM stage produced (dm_delays set): rows analysed - the largest delay
     uint64_t dm_chunks = 0;         // chunks handed to dm_sink
     uint64_t sps_candidates = 0;    // candidates the search stage found (sps_widths > 0)
+    uint64_t events = 0;            // events the builder closed (evt set), the final flush included
+    uint64_t stamps = 0;            // stamps cut and handed to stamp_sink
+    uint64_t stamps_dropped = 0;    // events beyond stamp_max_per_deliver of their deliver
+    uint64_t stamps_missed = 0;     // requests whose rows had left the ring (status 1)
+    uint64_t stamps_beyond_end = 0; // requests whose window passes the last row of the run: still "not pushed yet" at the last cut
     uint64_t vis_dumps = 0;         // integrations the correlator dumped (corr_blocks > 0)
     uint64_t sk_dumps = 0;          // integrations the moments stage dumped (sk_blocks > 0)
     uint64_t stokes_units = 0;      // gemm-units the Stokes stage delivered (stokes_beams non-empty)
