@@ -6,6 +6,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include "bf_fold_staging.h"
+
 #include <atomic>
 #include <type_traits>
 

@@ -264,20 +264,44 @@
     [[maybe_unused]] int st_next = c_begin;
     [[maybe_unused]] unsigned long long st_unit = 0;   // bytes from a gemm-unit's end to the same frequency's next gemm-unit
     [[maybe_unused]] unsigned st_off[PPT];             // lane_off(k), formed once
+    // (64-bit products are formed on the vector unit, once per workgroup: the state goes back to scalar registers by name)
+    [[maybe_unused]] auto sgpr64 = [](unsigned long long v) {
+        return (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v) |
+               ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32)) << 32);
+    };
     if constexpr (STREAM) {
         const unsigned s_c = (unsigned)(NIPO == 64 ? c_begin / 2 : c_begin) * SPAN;   // (n_ipo 64: c_begin is even, a whole group)
         const unsigned u = a.t_shift >= 0 ? (s_c >> a.t_shift) : (s_c / (unsigned)a.T);
         st_t0 = s_c - u * (unsigned)a.T;
-        // (64-bit products are formed on the vector unit, once per workgroup: the state goes back to scalar registers by name)
-        auto sgpr64 = [](unsigned long long v) {
-            return (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v) |
-                   ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32)) << 32);
-        };
         st_base = sgpr64((unsigned long long)((size_t)((size_t)u * a.n_freq + f) * a.T + st_t0) * 64);
         st_t0 = (unsigned)__builtin_amdgcn_readfirstlane((int)st_t0);
         st_unit = sgpr64((unsigned long long)(unsigned)(a.n_freq - 1) * (unsigned)a.T * 64);
 #pragma unroll
         for (int k = 0; k < PPT; k++) st_off[k] = lane_off(k);
+    }
+    // STREAM: what the chunk loop needs besides the samples, as per-lane registers formed once per workgroup (docs/LOG_r09.md).
+    //  * fk: the staging's masks and the byte-reversal selector (bf_fold_staging.h) -- operands, not 32-bit literals behind the opcode.
+    //  * wr_ptr / rd_ptr: the LDS addresses of the four staging stores (sr, di, dr, si) and of the two fragment reads of row tile 0,
+    //    INCLUDING the buffer -- no scalar buffer base added to a per-lane constant in front of every store and read.  Both start in
+    //    buffer 0.  wr_ptr moves by lds_step behind every staging (+BUF, -BUF, ...: the prologue stages into buffer 0, the first
+    //    chunk into buffer 1); rd_ptr moves the other way behind every chunk of the tile loop, towards the buffer that chunk's
+    //    staging filled; lds_step changes sign once per staged chunk, as its last use there (a negation in place, no copy).
+    //    Row tile t8 of a lane lies RB * lds_row16(t8, 0) bytes behind its row tile 0: the row splits into a t8 part and a lane
+    //    part, and the swizzle reads only row bits of the lane part.
+    using lds_ptr = __attribute__((address_space(3))) char*;
+    using lds_v4i = __attribute__((address_space(3))) v4i;
+    [[maybe_unused]] FoldStageMasks fk;
+    [[maybe_unused]] lds_ptr wr_ptr[4] = {nullptr, nullptr, nullptr, nullptr}, rd_ptr[2] = {nullptr, nullptr};
+    [[maybe_unused]] int lds_step = BUF;
+    if constexpr (STREAM) {
+        static_assert(KS == 1, "one plane per buffer");
+        asm volatile("" : "+v"(fk.m78), "+v"(fk.kC0), "+v"(fk.k40), "+v"(fk.f0f), "+v"(fk.k18), "+v"(fk.k08), "+v"(fk.h80), "+v"(fk.f8), "+v"(fk.rev),
+                     "+v"(lds_step));
+#pragma unroll
+        for (int j = 0; j < 4; j++) wr_ptr[j] = (lds_ptr)smem + (lds_re[0] ^ (32 * j));
+        const int row0 = lds_row16<MAPN>(0, c16);
+        rd_ptr[0] = (lds_ptr)smem + (row0 * RB + 16 * swz16<MAPN>(g4, row0));
+        rd_ptr[1] = (lds_ptr)smem + (row0 * RB + 16 * swz16<MAPN>(g4 + 4, row0));
     }
     auto load_stream = [&]() {
         // (the base as a scalar register pair by name, the pointer global by type: global_load v, v_off, s[base] -- not a.in + lane_off
@@ -286,9 +310,10 @@
         asm volatile("" : "+s"(base));
 #pragma unroll
         for (int k = 0; k < PPT; k++) {
-            unsigned off = st_off[k];
-            asm volatile("" : "+v"(off));      // (its zero extension stays beside the load, where the instruction's 32-bit offset operand takes it)
-            stage[k] = *(const __attribute__((address_space(1))) stage_t*)(base + off);
+            // (its zero extension stays beside the load, where the instruction's 32-bit offset operand takes it; pinned in its own
+            //  register, not in a copy: a copy is a v_mov per load and chunk)
+            asm volatile("" : "+v"(st_off[k]));
+            stage[k] = *(const __attribute__((address_space(1))) stage_t*)(base + st_off[k]);
         }
         if (st_next + 1 < c_end) {             // scalar: no memory operation depends on it
             bool next_span = true;
@@ -317,11 +342,26 @@
             // (behind the launch's last sample) gives all-zero operands.  LDS row: Sr0 Sr1 Di0 Di1 | Dr0 Dr1 Si0 Si1 (pieces
             // P, P + 2, P + 4, P + 6: the swizzle only XORs the 3 piece bits).
             constexpr unsigned M = 0x78787878u, H = 0x80808080u;
+            v4i sr, si, dr, di;
             if constexpr (STREAM) {   // the chunk loop's one wait for global memory: both prefetched pieces at once, stated here so that
                 __builtin_amdgcn_s_waitcnt(0x0F70);   // the compiler adds none of its own (vmcnt(0); expcnt and lgkmcnt left alone)
                 asm volatile("" : "+v"(stage[0]), "+v"(stage[PPT - 1]));
+                // the same bytes in 16 operations per dword pair (fold_stage_pair, bf_fold_staging.h), stored through wr_ptr; `buf` is
+                // the buffer wr_ptr already points into
+#pragma unroll
+                for (int d = 0; d < 4; d++) {
+                    unsigned xsr, xsi, xdr, xdi;
+                    fold_stage_pair((unsigned)stage[0][d], (unsigned)stage[PPT - 1][3 - d], fk, xsr, xsi, xdr, xdi);
+                    sr[d] = (int)xsr, si[d] = (int)xsi, dr[d] = (int)xdr, di[d] = (int)xdi;
+                }
+                *reinterpret_cast<lds_v4i*>(wr_ptr[0]) = sr;
+                *reinterpret_cast<lds_v4i*>(wr_ptr[1]) = di;
+                *reinterpret_cast<lds_v4i*>(wr_ptr[2]) = dr;
+                *reinterpret_cast<lds_v4i*>(wr_ptr[3]) = si;
+#pragma unroll
+                for (int j = 0; j < 4; j++) wr_ptr[j] += lds_step;
+                return;
             }
-            v4i sr, si, dr, di;
 #pragma unroll
             for (int d = 0; d < 4; d++) {
                 const unsigned ta = (unsigned)stage[0][d] ^ 0x88888888u;
@@ -380,6 +420,22 @@
     int pend_chunk[PEND];                  // chunk whose finished sums sit in pend[gi] (-1: none); tracked per entry
 #pragma unroll                             // because entry 0 of chunk c can be parked before entry 1 of chunk c-1 left
     for (int gi = 0; gi < PEND; gi++) pend_chunk[gi] = -1;
+    // STREAM: entry gi of a workgroup parks the groups grp0, grp0 + step, ... in that order and every parked group is stored before the
+    // next one is parked (flush_pending runs once per chunk), so the wave-uniform part of a store's address is scalar state like
+    // st_base: st_ub[gi] = bytes from a.out to (row 4 * group, frequency f, beam 0) of the group entry gi stores next, advanced by one
+    // add per store.  The per-lane part of an interleaved store, g4 * FB + the lane's first beam, is formed once (st_lane0, floats).
+    [[maybe_unused]] unsigned long long st_ub[PEND], st_ub_step = 0;
+    [[maybe_unused]] size_t st_lane0 = 0;
+    if constexpr (STREAM) {
+        constexpr unsigned GSTEP = (NIPO >= 32) ? 1u : 2u;   // groups between two stores of one entry
+#pragma unroll
+        for (int gi = 0; gi < PEND; gi++) {
+            const unsigned grp0 = (NIPO >= 32) ? (unsigned)(c_begin / CPG) : (2u * (unsigned)c_begin + gi);
+            st_ub[gi] = sgpr64((unsigned long long)((size_t)(4u * grp0) * FB + (size_t)f * a.n_beams) * sizeof(float));
+        }
+        st_ub_step = sgpr64((unsigned long long)(4u * GSTEP) * FB * sizeof(float));
+        st_lane0 = (size_t)g4 * FB + (size_t)slot_beam[0];
+    }
     // x[sl] -> row[beam of slot sl]; `row` points at beam 0 of one output's frequency row.  Interleaved tiles give every
     // lane consecutive beams: vector stores.
     auto store_slots = [&](float* row, const float (&x)[NS]) {
@@ -414,12 +470,21 @@
         if constexpr (LONG && !WRITE_C) {
 #pragma unroll
             for (int gi = 0; gi < PEND; gi++) {
-                if (pend_chunk[gi] >= 0 && wave_active) {
+                if constexpr (STREAM) {
+                    // (chunks_total * 128 == S, so every output of every chunk lies inside the launch: see load_stream)
+                    if (pend_chunk[gi] >= 0 && wave_active) {
+                        float* ub = reinterpret_cast<float*>(reinterpret_cast<char*>(a.out) + st_ub[gi]);
+                        if (a.interleave)   // (store_slots' vector store of four neighbouring beams: NS == 4, not PAIRED)
+                            __builtin_nontemporal_store(v4f{pend[gi][0], pend[gi][1], pend[gi][2], pend[gi][3]}, reinterpret_cast<v4f*>(ub + st_lane0));
+                        else
+                            store_slots(ub + (size_t)g4 * FB, pend[gi]);
+                        st_ub[gi] += st_ub_step;
+                    }
+                } else if (pend_chunk[gi] >= 0 && wave_active) {
                     const unsigned grp = (NIPO >= 32) ? (unsigned)(pend_chunk[gi] / CPG) : (2u * pend_chunk[gi] + gi);
                     float* ub = a.out + ((size_t)(4u * grp) * FB + (size_t)f * a.n_beams);  // wave-uniform part
                     const unsigned o = 4u * grp + (unsigned)g4;
-                    // (STREAM: chunks_total * 128 == S, so every output of every chunk lies inside the launch: see load_stream)
-                    if (STREAM || o * (unsigned)L < a.S) store_slots(ub + (size_t)g4 * FB, pend[gi]);
+                    if (o * (unsigned)L < a.S) store_slots(ub + (size_t)g4 * FB, pend[gi]);
                 }
                 pend_chunk[gi] = -1;
             }
@@ -441,6 +506,7 @@
         if (c_begin + 1 < c_end) load_chunk(c_begin + 1);
     }
     __syncthreads();
+    if constexpr (STREAM) lds_step = -lds_step;   // (behind every staged chunk, as the last use of the step: the next staging goes the other way)
 
     // FOLD: a wave without beams only stages; its chunks run in a loop of their own, so that the tile loop holds the (longer) staging once
     const bool stage_only = FOLD && !wave_active;
@@ -454,10 +520,11 @@
                 if (c + 2 < c_end) load_chunk(c + 2);
             }
             __syncthreads();
+            if constexpr (STREAM) lds_step = -lds_step;
         }
     for (int c = stage_only ? c_end : c_begin; c < c_end; c++) {
-        char* cur = smem + ((c - c_begin) & 1) * BUF;
-        char* nxt = smem + ((c - c_begin + 1) & 1) * BUF;
+        [[maybe_unused]] char* cur = smem + ((c - c_begin) & 1) * BUF;   // (STREAM: rd_ptr / wr_ptr hold the buffers)
+        [[maybe_unused]] char* nxt = smem + ((c - c_begin + 1) & 1) * BUF;
         if (!FOLD && !wave_active) {
             if (c + 1 < c_end) write_chunk(nxt);
             if (c + 2 < c_end) load_chunk(c + 2);
@@ -613,6 +680,11 @@
 
             // LDS fragments of row-tile t8: a0[h] = 16*re, a1[h] = 16*im of 16 antennas x 16 samples per lane group, k-step h
             auto read_frag = [&](const int t8, v4i (&a0)[KS], v4i (&a1)[KS]) {
+                if constexpr (STREAM) {   // (rd_ptr: the current buffer's row tile 0 of this lane; see its declaration)
+                    a0[0] = *reinterpret_cast<const lds_v4i*>(rd_ptr[0] + RB * lds_row16<MAPN>(t8, 0));
+                    a1[0] = *reinterpret_cast<const lds_v4i*>(rd_ptr[1] + RB * lds_row16<MAPN>(t8, 0));
+                    return;
+                }
                 const int row = lds_row16<MAPN>(t8, c16);
 #pragma unroll
                 for (int h = 0; h < KS; h++) {  // plane 1 keeps (im | re): the two planes' staging writes then never collide
@@ -675,10 +747,33 @@
                     }
                 }
             };
+            // STREAM: row tile t8 + 1's fragments are requested behind the last MFMA of tile t8 and in front of that MFMA's detect (nothing
+            // crosses the scheduling barrier), into registers of their own; tile t8 + 1 opens with ONE stated wait for both of them, so
+            // the compiler adds none between its MFMAs.  121 - 124 registers (docs/LOG_r09.md section 3; requesting them behind ALL of a
+            // tile's MFMAs, issued before any detect, takes 128 and scratch).
+            [[maybe_unused]] v4i pf0[KS], pf1[KS];
+            if constexpr (STREAM) read_frag(0, pf0, pf1);
 #pragma unroll
             for (int t8 = 0; t8 < 8; t8++) {   // (requesting tile t8+1's LDS fragments one tile early was tried: pair kernel
                 v4i a0[KS], a1[KS];            //  -2 % (129 VGPRs: 3 instead of 4 waves per SIMD), general +-0, r02 variants log;
-                read_frag(t8, a0, a1);         //  deep classes, requested and pinned one tile early: +-0.5 %, r04 variants log)
+                if constexpr (STREAM) {        //  deep classes, requested and pinned one tile early: +-0.5 %, r04 variants log)
+                    __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0); vmcnt and expcnt left alone
+                    a0[0] = pf0[0], a1[0] = pf1[0];
+                    asm volatile("" : "+v"(a0[0]), "+v"(a1[0]));
+#pragma unroll
+                    for (int t = 0; t < NT; t++) {
+                        v4i re[SPS], im[SPS];
+                        issue(a0, a1, t, re, im);
+                        if (t == NT - 1 && t8 + 1 < 8) {
+                            read_frag(t8 + 1, pf0, pf1);
+                            __builtin_amdgcn_sched_barrier(0);
+                        }
+                        consume(t8, t, re, im);
+                    }
+                    staging(t8);
+                    continue;
+                }
+                read_frag(t8, a0, a1);
                 if constexpr (RTW) {
 #pragma unroll
                     for (int r = 0; r < 4; r++) {
@@ -708,6 +803,12 @@
                 }
                 store_short(t8);
                 staging(t8);
+            }
+            if constexpr (STREAM) {   // (towards the buffer the staging of this chunk has just filled)
+                rd_ptr[0] -= lds_step;
+                rd_ptr[1] -= lds_step;
+                asm volatile("" : "+v"(lds_step), "+v"(rd_ptr[0]), "+v"(rd_ptr[1]));   // (negate behind its last use, in its own register)
+                lds_step = -lds_step;
             }
         }
         __syncthreads();
