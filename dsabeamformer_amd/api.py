@@ -578,80 +578,72 @@ class Conditioner(_Owner):
         return out
 
 
-class Correlator(_Owner):
-    """bf_corr: the correlator as a stage (include/dsabf.h, docs/CORRELATOR.md): one int64 accumulator on the device that pushes add
-    to and a dump snapshots and zeroes; the stage orders its pushes and dumps itself, whatever queues they are issued on."""
-    _ptr_attr, _destroy = "_c", "bf_corr_destroy"
+class _AccumStage(_Owner):
+    """What ``Correlator`` and ``SpectralKurtosis`` share: the bf_<_abi>_* entry points of an accumulator stage, whose results have
+    the shape ``_shape(cfg)``."""
+    _ptr_attr = "_c"
+    _abi = None
 
     def __init__(self, bf: Beamformer, max_in_flight: int = 2):
         self._lib = load()
         self._c = C.c_void_p()
         self._bf = bf
-        cfg = bf.cfg
-        self.shape = (cfg.n_freq, cfg.n_pol, cfg.n_ant * (cfg.n_ant + 1) // 2, 2)
-        check(self._lib.bf_corr_create(bf._h, int(max_in_flight), C.byref(self._c)))
+        self.shape = self._shape(bf.cfg)
+        check(self._call("create")(bf._h, int(max_in_flight), C.byref(self._c)))
+
+    def _call(self, name: str):
+        return getattr(self._lib, "bf_%s_%s" % (self._abi, name))
 
     def push(self, d_packed, n_units: int, stream: int = 0) -> None:
-        check(self._lib.bf_corr_push(self._c, _ptr(d_packed), int(n_units), C.c_void_p(stream)))
+        check(self._call("push")(self._c, _ptr(d_packed), int(n_units), C.c_void_p(stream)))
 
     def push_block(self, stream_idx: int, slot: int, first_unit: int, n_units: int) -> None:
         """The gemm-units [first_unit, first_unit + n_units) of ring slot ``slot`` (what enqueue_block reads), on compute queue stream_idx."""
-        check(self._lib.bf_corr_push_block(self._c, int(stream_idx), int(slot), int(first_unit), int(n_units)))
+        check(self._call("push_block")(self._c, int(stream_idx), int(slot), int(first_unit), int(n_units)))
 
     def dump(self, stream: int = 0) -> None:
         """Snapshot the accumulator to pinned host memory, then zero it (BF_ERR_STATE beyond max_in_flight uncollected dumps)."""
-        check(self._lib.bf_corr_dump(self._c, C.c_void_p(stream)))
+        check(self._call("dump")(self._c, C.c_void_p(stream)))
 
     @property
     def pending(self) -> int:
-        return self._lib.bf_corr_pending(self._c)
+        return self._call("pending")(self._c)
+
+    def collect(self):
+        import numpy as np
+
+        out = np.empty(self.shape, np.int64)
+        n = C.c_uint64()
+        check(self._call("collect")(self._c, _ptr(out), C.byref(n)))
+        return out, int(n.value)
+
+
+class Correlator(_AccumStage):
+    """bf_corr: the correlator as a stage (include/dsabf.h, docs/CORRELATOR.md): one int64 accumulator on the device that pushes add
+    to and a dump snapshots and zeroes; the stage orders its pushes and dumps itself, whatever queues they are issued on."""
+    _abi, _destroy = "corr", "bf_corr_destroy"
+
+    @staticmethod
+    def _shape(cfg):
+        return (cfg.n_freq, cfg.n_pol, cfg.n_ant * (cfg.n_ant + 1) // 2, 2)
 
     def collect(self):
         """Waits for the oldest uncollected dump; returns (int64 array [freq][pol][baseline][2], columns per polarisation)."""
-        import numpy as np
-
-        out = np.empty(self.shape, np.int64)
-        n = C.c_uint64()
-        check(self._lib.bf_corr_collect(self._c, _ptr(out), C.byref(n)))
-        return out, int(n.value)
+        return super().collect()
 
 
-class SpectralKurtosis(_Owner):
+class SpectralKurtosis(_AccumStage):
     """bf_sk: the voltage moments as a stage (include/dsabf.h, docs/SPECTRAL_KURTOSIS.md), a twin of ``Correlator``: one int64
     accumulator on the device that pushes add to and a dump snapshots and zeroes; the stage orders its pushes and dumps itself."""
-    _ptr_attr, _destroy = "_c", "bf_sk_destroy"
+    _abi, _destroy = "sk", "bf_sk_destroy"
 
-    def __init__(self, bf: Beamformer, max_in_flight: int = 2):
-        self._lib = load()
-        self._c = C.c_void_p()
-        self._bf = bf
-        cfg = bf.cfg
-        self.shape = (cfg.n_freq, cfg.n_pol, cfg.n_ant, 2)
-        check(self._lib.bf_sk_create(bf._h, int(max_in_flight), C.byref(self._c)))
-
-    def push(self, d_packed, n_units: int, stream: int = 0) -> None:
-        check(self._lib.bf_sk_push(self._c, _ptr(d_packed), int(n_units), C.c_void_p(stream)))
-
-    def push_block(self, stream_idx: int, slot: int, first_unit: int, n_units: int) -> None:
-        """The gemm-units [first_unit, first_unit + n_units) of ring slot ``slot`` (what enqueue_block reads), on compute queue stream_idx."""
-        check(self._lib.bf_sk_push_block(self._c, int(stream_idx), int(slot), int(first_unit), int(n_units)))
-
-    def dump(self, stream: int = 0) -> None:
-        """Snapshot the accumulator to pinned host memory, then zero it (BF_ERR_STATE beyond max_in_flight uncollected dumps)."""
-        check(self._lib.bf_sk_dump(self._c, C.c_void_p(stream)))
-
-    @property
-    def pending(self) -> int:
-        return self._lib.bf_sk_pending(self._c)
+    @staticmethod
+    def _shape(cfg):
+        return (cfg.n_freq, cfg.n_pol, cfg.n_ant, 2)
 
     def collect(self):
         """Waits for the oldest uncollected dump; returns (int64 array [freq][pol][ant][2] = {m1, m2}, columns per polarisation)."""
-        import numpy as np
-
-        out = np.empty(self.shape, np.int64)
-        n = C.c_uint64()
-        check(self._lib.bf_sk_collect(self._c, _ptr(out), C.byref(n)))
-        return out, int(n.value)
+        return super().collect()
 
 
 class StokesBeams(_Owner):

@@ -24,6 +24,23 @@ static int check_units(const bf_handle* h, int first_unit, int n_units)
     return fail(BF_ERR_INVALID, "gemm-units [%d, %d) are not inside a block of %d", first_unit, first_unit + n_units, h->cfg.n_gemms_per_block);
 }
 
+// a launch on compute queue q that reads ring slot `slot`
+static int check_queue_and_slot(const bf_handle* h, int q, int slot)
+{
+    if (int rc = check_queue(h, q)) return rc;
+    if (slot < 0 || slot >= h->cfg.n_blocks_on_gpu) return fail(BF_ERR_INVALID, "slot %d out of range", slot);
+    return BF_OK;
+}
+
+int dsabf::rt::resident_units(const bf_handle* h, int stream_idx, int slot, int first_unit, int n_units, const uint8_t** in)
+{
+    if (int rc = check_queue_and_slot(h, stream_idx, slot)) return rc;
+    if (int rc = check_units(h, first_unit, n_units)) return rc;
+    // src/beamformer.cu:464: &d_data[N_BYTES_PRE_EXPANSION_PER_GEMM*(N_GEMMS_PER_BLOCK*block + timeSlice)]
+    *in = h->d_data + bf_bytes_per_gemm(&h->cfg) * ((size_t)h->cfg.n_gemms_per_block * slot + first_unit);
+    return BF_OK;
+}
+
 // One of a queue's block buffers (bf_handle::queue_bufs): n_floats of device memory, allocated at its first use.
 static int ensure_buf(float*& p, size_t n_floats)
 {
@@ -161,8 +178,7 @@ int bf_enqueue_gemm_unit(bf_handle* h, int stream_idx, int slot, int time_slice,
 {
     if (!h) return fail(BF_ERR_INVALID, "handle is NULL");
     if (int rc = check_weights(h)) return rc;
-    if (int rc = check_queue(h, stream_idx)) return rc;
-    if (slot < 0 || slot >= h->cfg.n_blocks_on_gpu) return fail(BF_ERR_INVALID, "slot %d out of range", slot);
+    if (int rc = check_queue_and_slot(h, stream_idx, slot)) return rc;
     if (time_slice < 0 || time_slice >= h->cfg.n_gemms_per_block)
         return fail(BF_ERR_INVALID, "time_slice %d out of range", time_slice);
     ON_DEVICE(h);
@@ -174,10 +190,9 @@ int bf_enqueue_gemm_unit(bf_handle* h, int stream_idx, int slot, int time_slice,
         h->pending.push_back({stream_idx, slot, time_slice, host_out, nullptr, false});
         return BF_OK;
     }
-    const size_t per_gemm = bf_bytes_per_gemm(&h->cfg);
     const size_t per_det = bf_floats_per_detect(&h->cfg);
-    // src/beamformer.cu:464: &d_data[N_BYTES_PRE_EXPANSION_PER_GEMM*(N_GEMMS_PER_BLOCK*block + timeSlice)]
-    const uint8_t* in = h->d_data + per_gemm * ((size_t)h->cfg.n_gemms_per_block * slot + time_slice);
+    const uint8_t* in = nullptr;
+    if (int rc = resident_units(h, stream_idx, slot, time_slice, 1, &in)) return rc;   // (in range, see above: this asks where the unit is)
     float* out = h->d_out + per_det * (size_t)stream_idx;
     hipStream_t s = h->streams[stream_idx];
     if (h->last_out[stream_idx] == out) {
@@ -197,12 +212,10 @@ static int enqueue_block_impl(bf_handle* h, int stream_idx, int slot, int first_
 {
     if (!h) return fail(BF_ERR_INVALID, "handle is NULL");
     if (int rc = check_weights(h)) return rc;
-    if (int rc = check_queue(h, stream_idx)) return rc;
-    if (slot < 0 || slot >= h->cfg.n_blocks_on_gpu) return fail(BF_ERR_INVALID, "slot %d out of range", slot);
-    if (int rc = check_units(h, first_unit, n_units)) return rc;
+    const uint8_t* in = nullptr;
+    if (int rc = resident_units(h, stream_idx, slot, first_unit, n_units, &in)) return rc;
     ON_DEVICE(h);
     FLUSH_UNITS(h);
-    const size_t per_gemm = bf_bytes_per_gemm(&h->cfg);
     const size_t per_det = bf_floats_per_detect(&h->cfg);
     float* out = d_dst;
     if (!d_dst) {
@@ -216,7 +229,6 @@ static int enqueue_block_impl(bf_handle* h, int stream_idx, int slot, int first_
         if (int rc = preserve_last_units(h, stream_idx, (size_t)first_unit, (size_t)first_unit + (size_t)n_units, nullptr)) return rc;
         out = b.out_blk + per_det * (size_t)first_unit;
     }
-    const uint8_t* in = h->d_data + per_gemm * ((size_t)h->cfg.n_gemms_per_block * slot + first_unit);
     hipStream_t s = h->streams[stream_idx];
     if (int rc = launch_detect(h, in, n_units, out, s)) return rc;
     if (!host_out) return BF_OK;

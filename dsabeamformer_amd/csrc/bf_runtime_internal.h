@@ -1,11 +1,13 @@
 // bf_runtime_internal.h -- what the C-ABI runtime's translation units share (bf_runtime.cpp, bf_queues.cpp, bf_dm_stream.cpp,
-// bf_sps.cpp, bf_cond.cpp, bf_corr.cpp, bf_sk.cpp, bf_stokes.cpp, bf_evt.cpp, bf_bench_abi.cpp): the handle, the base of its stages, the error string, the device scope.
+// bf_sps.cpp, bf_cond.cpp, bf_accum.cpp, bf_corr.cpp, bf_sk.cpp, bf_stokes.cpp, bf_evt.cpp, bf_bench_abi.cpp): the handle, the base of its stages,
+// the accumulator stage under the correlator and the voltage moments, the error string, the device scope.
 // Host-only and not installed: no .hip / .hpp file includes it.
 #pragma once
 #include "../../include/dsabf.h"
 
 #include <hip/hip_runtime.h>
 
+#include <new>
 #include <string>
 #include <utility>
 #include <vector>
@@ -105,6 +107,39 @@ struct bf_stage {
     virtual void attached() {}                          // a DM stage has just become the feeder
 };
 
+// What differs between the two kinds of accumulator stage, the correlator (bf_corr.cpp) and the voltage moments (bf_sk.cpp).
+struct bf_accum_kind {
+    const char* noun;                              // bf_stage::noun
+    const char* abi;                               // "bf_corr" / "bf_sk": the prefix of the stage's entry points, as its messages name them
+    size_t (*entries)(const bf_config* cfg);       // cells of a result; the accumulator holds two int64 per cell
+    int (*check_create)(const bf_handle* h);       // what bf_*_create refuses about the geometry
+    int (*check_launch)(const bf_handle* h, int n_units, const char* who);   // the bounds of one launch
+    int (*launch)(bf_handle* h, const void* d_packed, int n_units, long long* d_acc, bool accumulate, hipStream_t q);
+};
+
+// The base of bf_corr and bf_sk (bf_accum.cpp): the accumulator, the chain of events that orders its pushes and dumps, the result sets.
+struct bf_accum_stage : bf_stage {
+    const bf_accum_kind& kind;
+    explicit bf_accum_stage(const bf_accum_kind& k) : bf_stage(k.noun), kind(k) {}
+    int max_in_flight = 0;
+    size_t n_int64 = 0;                // 2 * kind.entries
+    long long* d_acc = nullptr;        // the integration in progress: every push adds to it, a dump copies it out and zeroes it
+    uint64_t columns = 0;              // columns per polarisation pushed since the last dump
+    // Pushes and dumps share d_acc, so each waits for the one before it, whatever queue that was issued on: `last` is the event
+    // behind the most recent kernel (push_done, two taking turns) or behind the most recent dump's copy and memset (its set's).
+    hipEvent_t push_done[2] = {nullptr, nullptr};
+    hipEvent_t last = nullptr;
+    uint64_t n_push = 0;
+    struct result_set {
+        long long* h_acc = nullptr;    // pinned
+        hipEvent_t copied = nullptr;
+        uint64_t columns = 0;
+    };
+    std::vector<result_set> sets;      // dump j leaves its snapshot in set j % max_in_flight
+    hipStream_t copy_q = nullptr;
+    uint64_t n_dump = 0, n_collected = 0;
+};
+
 // (hidden: shared by the runtime's translation units, not exported from libdsabf.so)
 #pragma GCC visibility push(hidden)
 namespace dsabf::rt {
@@ -118,12 +153,32 @@ int flush_units(bf_handle* h);                          // bf_queues.cpp
 // Every detect launch of a handle: the fused kernel over n_units gemm-units at `in` -> out [unit][o][f][b] and, behind it on the same
 // queue, the incoherent beam into column h->ib_beam of the same `out` if one is set (bf_queues.cpp)
 int launch_detect(bf_handle* h, const void* in, int n_units, float* out, hipStream_t s);
+// The resident gemm-units [first_unit, first_unit + n_units) of ring slot `slot`, for a launch on compute queue stream_idx: refuses a
+// queue, a slot or units that are out of range, else *in is where the first of them starts (bf_queues.cpp)
+int resident_units(const bf_handle* h, int stream_idx, int slot, int first_unit, int n_units, const uint8_t** in);
 
 int orphaned(const bf_stage* s);                        // BF_ERR_STATE "the handle of this <noun> has been destroyed", or BF_OK
 // End of every create: `s` (s->h set) joins its handle's list; a HIP error in s->res destroys it and fails as "<who>: <error>".
 int stage_adopt(bf_stage* s, const char* who);
 void stage_release(bf_stage* s);                        // device side of a stage; the object stays, detached from its handle
 int stage_destroy(bf_stage* s);                         // every bf_*_destroy: unlinked from its feeder and its handle, released, deleted
+// The accumulator stages' entry points (bf_accum.cpp); bf_corr_* and bf_sk_* are these.  accum_init takes over `fresh` (NULL: out of
+// host memory): the handle adopts it, or it is deleted.
+int accum_init(bf_accum_stage* fresh, bf_handle* h, int max_in_flight);
+int accum_pending(const bf_accum_stage* s);
+int accum_push(bf_accum_stage* s, const void* d_packed, int n_units, void* hip_stream);
+int accum_push_block(bf_accum_stage* s, int stream_idx, int slot, int first_unit, int n_units);
+int accum_dump(bf_accum_stage* s);
+int accum_collect(bf_accum_stage* s, int64_t* out, uint64_t* n_columns_per_pol);
+template <class Stage> int accum_create(bf_handle* h, int max_in_flight, Stage** out)
+{
+    if (!out) return fail(BF_ERR_INVALID, "out is NULL");
+    *out = nullptr;
+    Stage* s = new (std::nothrow) Stage();
+    if (int rc = accum_init(s, h, max_in_flight)) return rc;
+    *out = s;
+    return BF_OK;
+}
 // The link "attached to a DM stage" has two ends: a member of the DM stage (search, cond) and the feeder of the stage it points at.
 bf_stage* as_stage(struct bf_sps* s);                   // bf_sps.cpp
 bf_stage* as_stage(struct bf_cond* c);                  // bf_cond.cpp

@@ -232,6 +232,22 @@ struct run_resources {
     }
 };
 
+// The weights of a run onto its handle: `w` as it is, or -- with gains and / or nulls -- calibrated and projected first.  w_set (optional,
+// may be `w` itself) receives what was set.  Returns the C-ABI's code; the caller reports a failure its own way.
+int set_run_weights(bf_handle* h, int device, const std::vector<int8_t>& w, const double* gains, const null_vectors* nulls, const uint8_t* ant_flags,
+                    int8_t* w_set, std::ostream& log)
+{
+    if (!gains && !nulls) {
+        const int rc = bf_set_weights(h, w.data());
+        if (rc == BF_OK && w_set && w_set != w.data()) ::memcpy(w_set, w.data(), w.size());
+        return rc;
+    }
+    const int rc = set_weights_conditioned(h, device, w.data(), gains, nulls, w_set, ant_flags);
+    if (rc == BF_OK && gains) log << "Calibrated the weights with one layer of gains" << std::endl;
+    if (rc == BF_OK && nulls) log << "Projected up to " << nulls->n_null << " interferer vectors per channel out of the weights" << std::endl;
+    return rc;
+}
+
 // The reference's launch pattern for one block (src/beamformer.cu:454-519): one gemm-unit per launch, round-robin over the compute
 // queues.  timeSlice[st] is the unit that stream st takes next (:319); it is back at st when the block is through.  dst(st, unit)
 // names the unit's D2H destination (nullptr, already logged: no destination, BF_ERR_STATE); after(st, unit), if any, is what
@@ -339,14 +355,7 @@ int run_debug_observation(const bf_config& cfg, const debug_run_options& opt, de
         std::vector<int8_t> fourier_coefficients((size_t)cfg.n_freq * cfg.n_ant * cfg.n_beams * 2);
         generate_fourier_coefficients(cfg.n_beams, cfg.n_ant, cfg.n_freq, 0, opt.gpu, pos.data(), dir.data(),
                                       fourier_coefficients.data());
-        if (opt.gains || opt.nulls) {
-            rc = set_weights_conditioned(h, opt.device, fourier_coefficients.data(), opt.gains, opt.nulls, opt.weights_out, opt.ant_flags);
-            if (rc == BF_OK && opt.gains) log << "Calibrated the weights with one layer of gains" << std::endl;
-            if (rc == BF_OK && opt.nulls) log << "Projected up to " << opt.nulls->n_null << " interferer vectors per channel out of the weights" << std::endl;
-        } else {
-            rc = bf_set_weights(h, fourier_coefficients.data());
-            if (rc == BF_OK && opt.weights_out) ::memcpy(opt.weights_out, fourier_coefficients.data(), fourier_coefficients.size());
-        }
+        rc = set_run_weights(h, opt.device, fourier_coefficients, opt.gains, opt.nulls, opt.ant_flags, opt.weights_out, log);
         if (rc != BF_OK) return gpu_error(log, rc);
     }
 
@@ -589,6 +598,23 @@ struct dm_chunk {
     float* host;
 };
 
+// A tap on the resident voltage blocks that integrates over whole blocks -- the correlator, the voltage moments: a push per launch on
+// the launch's queue, a dump after every `blocks`-th analysed block, each dump collected and delivered once that block's analysis
+// event has fired.  What the stage is comes as calls of the C-ABI; the bookkeeping is written once, in production_run.
+struct accum_tap {
+    const char* title;   // "Correlator": the closing line
+    const char* noun;    // "visibility": the sink's error line
+    int blocks;          // blocks per dump (0: off)
+    std::function<int(int max_in_flight, size_t* n_int64)> create;   // the stage, and the size of one dump
+    std::function<int(int q, int slot, int first_unit, int n_units)> push_block;
+    std::function<int()> dump;
+    std::function<int(int64_t* out, uint64_t* n_columns)> collect;
+    std::function<bool(uint64_t first_block, uint64_t n_columns, const int64_t* data, size_t n_int64)> deliver;   // to the sink, if there is one
+    std::deque<std::pair<uint64_t, uint64_t>> pending;   // dumps issued and not yet collected -- {first block of the integration, its last block}
+    std::vector<int64_t> host;                           // what collect returns for one dump
+    uint64_t blocks_pushed = 0, dumps = 0;
+};
+
 // One production run: its resources, its plan and what the steps of the loop hand to each other.
 struct production_run {
     const bf_config& cfg;
@@ -627,14 +653,19 @@ struct production_run {
         for (int f = 0; f < plan.n_freq_band; f++) n += reinterpret_cast<const uint8_t*>(cond_mask_host)[f] != 0;
         return n;
     }
-    // the correlator (corr_blocks > 0): dumps issued and not yet collected -- {first block of the integration, its last block}
-    std::deque<std::pair<uint64_t, uint64_t>> vis_pending;
-    std::vector<int64_t> vis;             // what bf_corr_collect returns for one dump
-    uint64_t corr_blocks_pushed = 0, vis_dumps = 0;
-    // the voltage moments (sk_blocks > 0): the same bookkeeping
-    std::deque<std::pair<uint64_t, uint64_t>> sk_pending;
-    std::vector<int64_t> moments;         // what bf_sk_collect returns for one dump
-    uint64_t sk_blocks_pushed = 0, sk_dumps = 0;
+    accum_tap corr{"Correlator", "visibility", opt.corr_blocks,
+                   [this](int n, size_t* n_int64) { *n_int64 = 2 * bf_corr_entries(&cfg); return bf_corr_create(dev.h, n, &dev.corr); },
+                   [this](int q, int slot, int first, int n) { return bf_corr_push_block(dev.corr, q, slot, first, n); },
+                   [this] { return bf_corr_dump(dev.corr, nullptr); },
+                   [this](int64_t* out, uint64_t* n) { return bf_corr_collect(dev.corr, out, n); },
+                   [this](uint64_t b, uint64_t n, const int64_t* d, size_t k) { return !opt.vis_sink || opt.vis_sink->deliver(b, n, d, k); }};
+    accum_tap sk{"Voltage moments", "moments", opt.sk_blocks,
+                 [this](int n, size_t* n_int64) { *n_int64 = 2 * bf_sk_entries(&cfg); return bf_sk_create(dev.h, n, &dev.sk); },
+                 [this](int q, int slot, int first, int n) { return bf_sk_push_block(dev.sk, q, slot, first, n); },
+                 [this] { return bf_sk_dump(dev.sk, nullptr); },
+                 [this](int64_t* out, uint64_t* n) { return bf_sk_collect(dev.sk, out, n); },
+                 [this](uint64_t b, uint64_t n, const int64_t* d, size_t k) { return !opt.sk_sink || opt.sk_sink->deliver(b, n, d, k); }};
+    accum_tap* const taps[2] = {&corr, &sk};   // in the order they follow the detect launch on its queue
     // the Stokes stage (stokes_beams non-empty): pushes issued and not yet collected -- {block of the launch, its first gemm-unit}
     std::deque<std::pair<uint64_t, uint64_t>> stokes_pending;
     std::vector<int8_t> stokes_weights;   // the host weights the handle got: what the stage's beams are picked from
@@ -650,15 +681,8 @@ struct production_run {
         std::vector<int8_t> fourier_coefficients((size_t)cfg.n_freq * cfg.n_ant * cfg.n_beams * 2);
         generate_fourier_coefficients(cfg.n_beams, cfg.n_ant, cfg.n_freq, opt.rank * cfg.n_freq, opt.gpu, pos, dir, fourier_coefficients.data());
         const bool follow = !opt.stokes_beams.empty();   // (the Stokes stage takes the weights as they were set: calibrated, in place)
-        if (opt.gains || opt.nulls) {
-            if ((rc = set_weights_conditioned(dev.h, opt.device, fourier_coefficients.data(), opt.gains, opt.nulls,
-                                              follow ? fourier_coefficients.data() : nullptr, opt.ant_flags)) != BF_OK)
-                return rc;
-            if (opt.gains) log << "Calibrated the weights with one layer of gains" << std::endl;
-            if (opt.nulls) log << "Projected up to " << opt.nulls->n_null << " interferer vectors per channel out of the weights" << std::endl;
-        } else if ((rc = bf_set_weights(dev.h, fourier_coefficients.data())) != BF_OK) {
-            return rc;
-        }
+        rc = set_run_weights(dev.h, opt.device, fourier_coefficients, opt.gains, opt.nulls, opt.ant_flags, follow ? fourier_coefficients.data() : nullptr, log);
+        if (rc != BF_OK) return rc;
         if (follow) stokes_weights.swap(fourier_coefficients);
         return opt.incoherent_beam >= 0 ? bf_set_incoherent_beam(dev.h, opt.incoherent_beam) : BF_OK;
     }
@@ -719,13 +743,11 @@ struct production_run {
                 }
             }
         }
-        if (opt.corr_blocks > 0) {   // dumps in flight: one per block queued at most, + the one being delivered
-            if ((rc = bf_corr_create(dev.h, kMaxTotalSep + 2, &dev.corr)) != BF_OK) return gpu_error(log, rc);
-            vis.resize(2 * bf_corr_entries(&cfg));
-        }
-        if (opt.sk_blocks > 0) {
-            if ((rc = bf_sk_create(dev.h, kMaxTotalSep + 2, &dev.sk)) != BF_OK) return gpu_error(log, rc);
-            moments.resize(2 * bf_sk_entries(&cfg));
+        for (accum_tap* t : taps) {
+            if (t->blocks <= 0) continue;
+            size_t n_int64 = 0;   // dumps in flight: one per block queued at most, + the one being delivered
+            if ((rc = t->create(kMaxTotalSep + 2, &n_int64)) != BF_OK) return gpu_error(log, rc);
+            t->host.resize(n_int64);
         }
         if (!opt.stokes_beams.empty()) {   // sets in flight: as the DM chunks -- the launches of the blocks queued + the one being delivered
             const int n_int = opt.stokes_int ? opt.stokes_int : cfg.n_avg, n_sel = (int)opt.stokes_beams.size();
@@ -795,14 +817,11 @@ struct production_run {
         unit_dst.assign((size_t)n_units, nullptr);
         for (int first = 0; first < n_units; first += plan.upl)
             if (const int rc = launch_units(block_index, gpu_block, first)) return rc;
-        if (dev.corr && ++corr_blocks_pushed % (uint64_t)opt.corr_blocks == 0) {   // the integration is complete: snapshot and zero
-            if (const int rc = bf_corr_dump(dev.corr, nullptr)) return gpu_error(log, rc);
-            vis_pending.emplace_back((uint64_t)block_index + 1 - (uint64_t)opt.corr_blocks, (uint64_t)block_index);
-        }
-        if (dev.sk && ++sk_blocks_pushed % (uint64_t)opt.sk_blocks == 0) {
-            if (const int rc = bf_sk_dump(dev.sk, nullptr)) return gpu_error(log, rc);
-            sk_pending.emplace_back((uint64_t)block_index + 1 - (uint64_t)opt.sk_blocks, (uint64_t)block_index);
-        }
+        for (accum_tap* t : taps)
+            if (t->blocks > 0 && ++t->blocks_pushed % (uint64_t)t->blocks == 0) {   // the integration is complete: snapshot and zero
+                if (const int rc = t->dump()) return gpu_error(log, rc);
+                t->pending.emplace_back((uint64_t)block_index + 1 - (uint64_t)t->blocks, (uint64_t)block_index);
+            }
         return BF_OK;
     }
 
@@ -830,10 +849,10 @@ struct production_run {
                                             : bf_enqueue_block(dev.h, q, gpu_block, first, upl, opt.comm ? nullptr : &unit_dst[first]);
         if (rc == BF_OK && opt.comm) rc = gather_block(q, d_rows);
         if (rc == BF_OK && plan.dm_run) rc = push_dm_rows(block_index, d_rows, dm_qs);
-        // the correlator reads the same resident units on the same queue, behind the detect launch and what follows it
-        if (rc == BF_OK && dev.corr) rc = bf_corr_push_block(dev.corr, q, gpu_block, first, upl);
-        if (rc == BF_OK && dev.sk) rc = bf_sk_push_block(dev.sk, q, gpu_block, first, upl);   // and so do the voltage moments
-        if (rc == BF_OK && dev.stokes) {                                                      // and the Stokes beams, one set per launch
+        // the correlator reads the same resident units on the same queue, behind the detect launch and what follows it; so do the voltage moments
+        for (accum_tap* t : taps)
+            if (rc == BF_OK && t->blocks > 0) rc = t->push_block(q, gpu_block, first, upl);
+        if (rc == BF_OK && dev.stokes) {   // and the Stokes beams, one set per launch
             rc = bf_stokes_push_block(dev.stokes, q, gpu_block, first, upl);
             if (rc == BF_OK) stokes_pending.emplace_back((uint64_t)block_index, (uint64_t)block_index * (uint64_t)n_units + (uint64_t)first);
         }
@@ -989,30 +1008,19 @@ struct production_run {
         }
         if (opt.stamp_sink)   // one round of cuts per deliver, on the stage's own queue: the compute queues keep running
             if (int rc = cut_stamps(/*last=*/false)) return rc;
-        while (!vis_pending.empty() && vis_pending.front().second < blocks_analyzed) {   // (the collect waits for the dump's own copy)
-            const uint64_t first_block = vis_pending.front().first;
-            vis_pending.pop_front();
-            uint64_t n_columns = 0;
-            const int rc = bf_corr_collect(dev.corr, vis.data(), &n_columns);
-            if (rc != BF_OK) return gpu_error(log, rc);
-            vis_dumps++;
-            if (opt.vis_sink && !opt.vis_sink->deliver(first_block, n_columns, vis.data(), vis.size())) {
-                log << "ERROR: visibility sink failed at block " << first_block << std::endl;
-                return BF_ERR_STATE;
+        for (accum_tap* t : taps)
+            while (!t->pending.empty() && t->pending.front().second < blocks_analyzed) {   // (the collect waits for the dump's own copy)
+                const uint64_t first_block = t->pending.front().first;
+                t->pending.pop_front();
+                uint64_t n_columns = 0;
+                const int rc = t->collect(t->host.data(), &n_columns);
+                if (rc != BF_OK) return gpu_error(log, rc);
+                t->dumps++;
+                if (!t->deliver(first_block, n_columns, t->host.data(), t->host.size())) {
+                    log << "ERROR: " << t->noun << " sink failed at block " << first_block << std::endl;
+                    return BF_ERR_STATE;
+                }
             }
-        }
-        while (!sk_pending.empty() && sk_pending.front().second < blocks_analyzed) {
-            const uint64_t first_block = sk_pending.front().first;
-            sk_pending.pop_front();
-            uint64_t n_columns = 0;
-            const int rc = bf_sk_collect(dev.sk, moments.data(), &n_columns);
-            if (rc != BF_OK) return gpu_error(log, rc);
-            sk_dumps++;
-            if (opt.sk_sink && !opt.sk_sink->deliver(first_block, n_columns, moments.data(), moments.size())) {
-                log << "ERROR: moments sink failed at block " << first_block << std::endl;
-                return BF_ERR_STATE;
-            }
-        }
         while (!stokes_pending.empty() && stokes_pending.front().first < blocks_analyzed) {   // (the collect waits for the set's own copy)
             const uint64_t first_unit = stokes_pending.front().second;
             stokes_pending.pop_front();
@@ -1114,8 +1122,8 @@ int run_observation(const bf_config& cfg, const observation_options& opt, block_
         res->stamps_dropped = run.stamps_dropped;
         res->stamps_missed = run.stamps_missed;
         res->stamps_beyond_end = run.stamps_beyond_end;
-        res->vis_dumps = run.vis_dumps;
-        res->sk_dumps = run.sk_dumps;
+        res->vis_dumps = run.corr.dumps;
+        res->sk_dumps = run.sk.dumps;
         res->stokes_units = run.stokes_units;
         res->cond_masked = run.cond_masked_channels();
     }
@@ -1133,12 +1141,9 @@ int run_observation(const bf_config& cfg, const observation_options& opt, block_
         if (opt.verbose) log << "Conditioner: " << run.cond_masked_channels() << " of " << run.plan.n_freq_band << " channels masked in the last push" << std::endl;
     }
     if (opt.incoherent_beam >= 0) log << "Incoherent beam: in beam column " << opt.incoherent_beam << " of the detected stream" << std::endl;
-    if (run.dev.corr)
-        log << "Correlator: " << run.vis_dumps << " dumps of " << opt.corr_blocks << " blocks each (an incomplete integration at the end is dropped)"
-            << std::endl;
-    if (run.dev.sk)
-        log << "Voltage moments: " << run.sk_dumps << " dumps of " << opt.sk_blocks << " blocks each (an incomplete integration at the end is dropped)"
-            << std::endl;
+    for (const accum_tap* t : run.taps)
+        if (t->blocks > 0)
+            log << t->title << ": " << t->dumps << " dumps of " << t->blocks << " blocks each (an incomplete integration at the end is dropped)" << std::endl;
     if (run.dev.stokes)
         log << "Stokes beams: " << opt.stokes_beams.size() << " beams, windows of " << (opt.stokes_int ? opt.stokes_int : cfg.n_avg) << " samples, "
             << run.stokes_units << " gemm-units" << std::endl;

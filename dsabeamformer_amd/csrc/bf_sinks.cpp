@@ -281,119 +281,61 @@ void dm_file_sink::close()
     fd = -1;
 }
 
-// ---- visibilities ------------------------------------------------------------------------------------------------------
-vis_file_sink::vis_file_sink(const bf_config& cfg, const char* path, int first_channel, int gpu)
+// ---- the int64 record files: visibilities, voltage moments, Stokes beams -------------------------------------------------
+int64_record_file::int64_record_file(const bf_config& cfg, const char* path, const char* content, const char* layout, int first_channel,
+                                     const std::string& extra, int gpu)
 {
     fd = ::open(path, O_CREAT | O_TRUNC | O_WRONLY, 0644);
     if (fd < 0) return;
     char header[kHeaderBytes];
     ::memset(header, 0, sizeof(header));
     ::snprintf(header, sizeof(header),
-               "HDR_VERSION 1.0\nHDR_SIZE %zu\nINSTRUMENT DSA\nCONTENT visibilities\nDTYPE int64\nENDIAN little\n"
-               "LAYOUT freq,pol,baseline(lower triangle a1*(a1+1)/2+a2),reim\nRECORD_HEADER_BYTES %zu\nNANT %d\nNPOL %d\nNFREQ %d\n"
-               "FIRST_CHANNEL %d\nN_OUTPUTS_PER_GEMM %d\nN_GEMMS_PER_BLOCK %d\nN_AVERAGING %d\nGPU %d\n",
-               kHeaderBytes, kRecordBytes, cfg.n_ant, cfg.n_pol, cfg.n_freq, first_channel, cfg.n_out_per_gemm, cfg.n_gemms_per_block, cfg.n_avg, gpu);
-    if (!pwrite_all(fd, header, sizeof(header), 0) || ::lseek(fd, (off_t)kHeaderBytes, SEEK_SET) < 0) {
-        ::close(fd);
-        fd = -1;
-    }
+               "HDR_VERSION 1.0\nHDR_SIZE %zu\nINSTRUMENT DSA\nCONTENT %s\nDTYPE int64\nENDIAN little\n"
+               "LAYOUT %s\nRECORD_HEADER_BYTES %zu\nNANT %d\nNPOL %d\nNFREQ %d\n"
+               "FIRST_CHANNEL %d\nN_OUTPUTS_PER_GEMM %d\nN_GEMMS_PER_BLOCK %d\nN_AVERAGING %d\n%sGPU %d\n",
+               kHeaderBytes, content, layout, kRecordBytes, cfg.n_ant, cfg.n_pol, cfg.n_freq, first_channel, cfg.n_out_per_gemm, cfg.n_gemms_per_block,
+               cfg.n_avg, extra.c_str(), gpu);
+    if (!pwrite_all(fd, header, sizeof(header), 0) || ::lseek(fd, (off_t)kHeaderBytes, SEEK_SET) < 0) close_file();
 }
 
-vis_file_sink::~vis_file_sink() { close(); }
-
-bool vis_file_sink::deliver(uint64_t first_block, uint64_t n_columns_per_pol, const int64_t* vis, size_t n_int64)
+bool int64_record_file::write_record(uint64_t first, uint64_t count, const int64_t* data, size_t n_int64)
 {
     if (fd < 0) return false;
-    const uint64_t rec[2] = {first_block, n_columns_per_pol};
+    const uint64_t rec[2] = {first, count};
     static_assert(sizeof rec == kRecordBytes, "the record header is two uint64");
     if (!write_all(fd, reinterpret_cast<const char*>(rec), sizeof rec) ||
-        !write_all(fd, reinterpret_cast<const char*>(vis), n_int64 * sizeof(int64_t)))
+        !write_all(fd, reinterpret_cast<const char*>(data), n_int64 * sizeof(int64_t)))
         return false;
-    dumps++;
+    records++;
     return true;
 }
 
-void vis_file_sink::close()
+void int64_record_file::close_file()
 {
     if (fd >= 0) ::close(fd);
     fd = -1;
+}
+
+vis_file_sink::vis_file_sink(const bf_config& cfg, const char* path, int first_channel, int gpu)
+    : int64_record_file(cfg, path, "visibilities", "freq,pol,baseline(lower triangle a1*(a1+1)/2+a2),reim", first_channel, "", gpu)
+{
 }
 
 sk_file_sink::sk_file_sink(const bf_config& cfg, const char* path, int first_channel, int gpu)
+    : int64_record_file(cfg, path, "voltage_moments", "freq,pol,ant,m1m2", first_channel, "", gpu)
 {
-    fd = ::open(path, O_CREAT | O_TRUNC | O_WRONLY, 0644);
-    if (fd < 0) return;
-    char header[kHeaderBytes];
-    ::memset(header, 0, sizeof(header));
-    ::snprintf(header, sizeof(header),
-               "HDR_VERSION 1.0\nHDR_SIZE %zu\nINSTRUMENT DSA\nCONTENT voltage_moments\nDTYPE int64\nENDIAN little\n"
-               "LAYOUT freq,pol,ant,m1m2\nRECORD_HEADER_BYTES %zu\nNANT %d\nNPOL %d\nNFREQ %d\n"
-               "FIRST_CHANNEL %d\nN_OUTPUTS_PER_GEMM %d\nN_GEMMS_PER_BLOCK %d\nN_AVERAGING %d\nGPU %d\n",
-               kHeaderBytes, kRecordBytes, cfg.n_ant, cfg.n_pol, cfg.n_freq, first_channel, cfg.n_out_per_gemm, cfg.n_gemms_per_block, cfg.n_avg, gpu);
-    if (!pwrite_all(fd, header, sizeof(header), 0) || ::lseek(fd, (off_t)kHeaderBytes, SEEK_SET) < 0) {
-        ::close(fd);
-        fd = -1;
-    }
 }
 
-sk_file_sink::~sk_file_sink() { close(); }
-
-bool sk_file_sink::deliver(uint64_t first_block, uint64_t n_columns_per_pol, const int64_t* moments, size_t n_int64)
+static std::string stokes_header_lines(const std::vector<int>& beams, int n_int)
 {
-    if (fd < 0) return false;
-    const uint64_t rec[2] = {first_block, n_columns_per_pol};
-    static_assert(sizeof rec == kRecordBytes, "the record header is two uint64");
-    if (!write_all(fd, reinterpret_cast<const char*>(rec), sizeof rec) ||
-        !write_all(fd, reinterpret_cast<const char*>(moments), n_int64 * sizeof(int64_t)))
-        return false;
-    dumps++;
-    return true;
-}
-
-void sk_file_sink::close()
-{
-    if (fd >= 0) ::close(fd);
-    fd = -1;
+    std::string list;
+    for (size_t i = 0; i < beams.size(); i++) list += (i ? "," : "") + std::to_string(beams[i]);
+    return "NINT " + std::to_string(n_int) + "\nNSEL " + std::to_string(beams.size()) + "\nBEAMS " + list + "\n";
 }
 
 stokes_file_sink::stokes_file_sink(const bf_config& cfg, const char* path, int first_channel, int gpu, const std::vector<int>& beams, int n_int)
+    : int64_record_file(cfg, path, "stokes", "unit,time,freq,beam,iquv", first_channel, stokes_header_lines(beams, n_int), gpu)
 {
-    fd = ::open(path, O_CREAT | O_TRUNC | O_WRONLY, 0644);
-    if (fd < 0) return;
-    std::string list;
-    for (size_t i = 0; i < beams.size(); i++) list += (i ? "," : "") + std::to_string(beams[i]);
-    char header[kHeaderBytes];
-    ::memset(header, 0, sizeof(header));
-    ::snprintf(header, sizeof(header),
-               "HDR_VERSION 1.0\nHDR_SIZE %zu\nINSTRUMENT DSA\nCONTENT stokes\nDTYPE int64\nENDIAN little\n"
-               "LAYOUT unit,time,freq,beam,iquv\nRECORD_HEADER_BYTES %zu\nNANT %d\nNPOL %d\nNFREQ %d\n"
-               "FIRST_CHANNEL %d\nN_OUTPUTS_PER_GEMM %d\nN_GEMMS_PER_BLOCK %d\nN_AVERAGING %d\nNINT %d\nNSEL %zu\nBEAMS %s\nGPU %d\n",
-               kHeaderBytes, kRecordBytes, cfg.n_ant, cfg.n_pol, cfg.n_freq, first_channel, cfg.n_out_per_gemm, cfg.n_gemms_per_block, cfg.n_avg, n_int,
-               beams.size(), list.c_str(), gpu);
-    if (!pwrite_all(fd, header, sizeof(header), 0) || ::lseek(fd, (off_t)kHeaderBytes, SEEK_SET) < 0) {
-        ::close(fd);
-        fd = -1;
-    }
-}
-
-stokes_file_sink::~stokes_file_sink() { close(); }
-
-bool stokes_file_sink::deliver(uint64_t first_unit, uint64_t n_units, const int64_t* stokes, size_t n_int64)
-{
-    if (fd < 0) return false;
-    const uint64_t rec[2] = {first_unit, n_units};
-    static_assert(sizeof rec == kRecordBytes, "the record header is two uint64");
-    if (!write_all(fd, reinterpret_cast<const char*>(rec), sizeof rec) ||
-        !write_all(fd, reinterpret_cast<const char*>(stokes), n_int64 * sizeof(int64_t)))
-        return false;
-    sets++;
-    return true;
-}
-
-void stokes_file_sink::close()
-{
-    if (fd >= 0) ::close(fd);
-    fd = -1;
 }
 
 bool parse_beam_list(const char* text, int n_beams, std::vector<int>* beams, std::string* why)

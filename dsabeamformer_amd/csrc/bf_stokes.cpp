@@ -265,11 +265,8 @@ int bf_stokes_push_block(bf_stokes* s, int stream_idx, int slot, int first_unit,
     if (!s) return fail(BF_ERR_INVALID, "the stage is NULL");
     if (int rc = orphaned(s)) return rc;
     bf_handle* h = s->h;
-    if (stream_idx < 0 || stream_idx >= h->cfg.n_streams) return fail(BF_ERR_INVALID, "stream %d out of range", stream_idx);
-    if (slot < 0 || slot >= h->cfg.n_blocks_on_gpu) return fail(BF_ERR_INVALID, "slot %d out of range", slot);
-    if (first_unit < 0 || n_units <= 0 || first_unit + n_units > h->cfg.n_gemms_per_block)
-        return fail(BF_ERR_INVALID, "gemm-units [%d, %d) are not inside a block of %d", first_unit, first_unit + n_units, h->cfg.n_gemms_per_block);
-    const uint8_t* in = h->d_data + bf_bytes_per_gemm(&h->cfg) * ((size_t)h->cfg.n_gemms_per_block * slot + first_unit);
+    const uint8_t* in = nullptr;
+    if (int rc = resident_units(h, stream_idx, slot, first_unit, n_units, &in)) return rc;
     // (a unit of a small geometry may start on any multiple of 4 bytes -- n_ant % 4 == 0 -- and the kernel then loads 4-byte words)
     if (int rc = check_push(s, in, n_units, "bf_stokes_push_block")) return rc;
     ON_DEVICE(h);

@@ -326,22 +326,29 @@ def read_dm_file(path: str):
     return hdr, data, chunks
 
 
-def read_vis_file(path: str):
-    """Parse a dsabf::vis_file_sink file (docs/CORRELATOR.md): returns (header dict, list of (first_block, n_columns_per_pol,
-    int64 array [n_freq][n_pol][n_ant (n_ant + 1) / 2][2]) per dump)."""
+def _read_int64_records(path: str, payload, content=None, layout=None):
+    """What the three int64 record files share: the 4096-byte text header as a dict (asserted to carry ``content`` and ``layout`` if
+    given), then the records -- two uint64 and an int64 payload whose shape ``payload(hdr, second)`` names (``second``: the record's
+    second uint64).  Returns (hdr, list of (first, second, int64 array))."""
     raw = open(path, "rb").read()
     text = raw[:DETECTED_HEADER_BYTES].split(b"\0", 1)[0].decode()
     hdr = dict(line.split(None, 1) for line in text.splitlines() if line.strip())
-    n_ant, shape = int(hdr["NANT"]), None
-    shape = (int(hdr["NFREQ"]), int(hdr["NPOL"]), n_ant * (n_ant + 1) // 2, 2)
-    n = shape[0] * shape[1] * shape[2] * 2
-    at, rec, dumps = int(hdr["HDR_SIZE"]), int(hdr["RECORD_HEADER_BYTES"]), []
+    assert content is None or (hdr["CONTENT"] == content and hdr["DTYPE"] == "int64" and hdr["LAYOUT"] == layout), hdr
+    at, rec, records = int(hdr["HDR_SIZE"]), int(hdr["RECORD_HEADER_BYTES"]), []
     while at < len(raw):
-        first_block, n_columns = (int(v) for v in np.frombuffer(raw, "<u8", 2, at))
+        first, second = (int(v) for v in np.frombuffer(raw, "<u8", 2, at))
         at += rec
-        dumps.append((first_block, n_columns, np.frombuffer(raw, "<i8", n, at).reshape(shape)))
+        shape = payload(hdr, second)
+        n = int(np.prod(shape))
+        records.append((first, second, np.frombuffer(raw, "<i8", n, at).reshape(shape)))
         at += 8 * n
-    return hdr, dumps
+    return hdr, records
+
+
+def read_vis_file(path: str):
+    """Parse a dsabf::vis_file_sink file (docs/CORRELATOR.md): returns (header dict, list of (first_block, n_columns_per_pol,
+    int64 array [n_freq][n_pol][n_ant (n_ant + 1) / 2][2]) per dump)."""
+    return _read_int64_records(path, lambda hdr, _: (int(hdr["NFREQ"]), int(hdr["NPOL"]), int(hdr["NANT"]) * (int(hdr["NANT"]) + 1) // 2, 2))
 
 
 MOMENTS_LAYOUT = "freq,pol,ant,m1m2"
@@ -350,19 +357,7 @@ MOMENTS_LAYOUT = "freq,pol,ant,m1m2"
 def read_moments_file(path: str):
     """Parse a dsabf::sk_file_sink file (docs/SPECTRAL_KURTOSIS.md): returns (header dict, list of (first_block, n_columns_per_pol,
     int64 array [n_freq][n_pol][n_ant][2] = {m1, m2}) per dump)."""
-    raw = open(path, "rb").read()
-    text = raw[:DETECTED_HEADER_BYTES].split(b"\0", 1)[0].decode()
-    hdr = dict(line.split(None, 1) for line in text.splitlines() if line.strip())
-    assert hdr["CONTENT"] == "voltage_moments" and hdr["DTYPE"] == "int64" and hdr["LAYOUT"] == MOMENTS_LAYOUT, hdr
-    shape = (int(hdr["NFREQ"]), int(hdr["NPOL"]), int(hdr["NANT"]), 2)
-    n = shape[0] * shape[1] * shape[2] * 2
-    at, rec, dumps = int(hdr["HDR_SIZE"]), int(hdr["RECORD_HEADER_BYTES"]), []
-    while at < len(raw):
-        first_block, n_columns = (int(v) for v in np.frombuffer(raw, "<u8", 2, at))
-        at += rec
-        dumps.append((first_block, n_columns, np.frombuffer(raw, "<i8", n, at).reshape(shape)))
-        at += 8 * n
-    return hdr, dumps
+    return _read_int64_records(path, lambda hdr, _: (int(hdr["NFREQ"]), int(hdr["NPOL"]), int(hdr["NANT"]), 2), "voltage_moments", MOMENTS_LAYOUT)
 
 
 STOKES_LAYOUT = "unit,time,freq,beam,iquv"
@@ -371,22 +366,13 @@ STOKES_LAYOUT = "unit,time,freq,beam,iquv"
 def read_stokes_file(path: str):
     """Parse a dsabf::stokes_file_sink file (docs/STOKES.md): returns (header dict, with BEAMS as a list of ints, and a list of
     (first_unit, n_units, int64 array [n_units][T][n_freq][n_sel][4] = {I, Q, U, V}) per record)."""
-    raw = open(path, "rb").read()
-    text = raw[:DETECTED_HEADER_BYTES].split(b"\0", 1)[0].decode()
-    hdr = dict(line.split(None, 1) for line in text.splitlines() if line.strip())
-    assert hdr["CONTENT"] == "stokes" and hdr["DTYPE"] == "int64" and hdr["LAYOUT"] == STOKES_LAYOUT, hdr
+    def payload(hdr, n_units):
+        n_int, n_sel = int(hdr["NINT"]), int(hdr["NSEL"])
+        return (n_units, int(hdr["N_OUTPUTS_PER_GEMM"]) * int(hdr["N_AVERAGING"]) // n_int, int(hdr["NFREQ"]), n_sel, 4)
+
+    hdr, records = _read_int64_records(path, payload, "stokes", STOKES_LAYOUT)
     hdr["BEAMS"] = [int(b) for b in hdr["BEAMS"].split(",")]
-    n_int, n_sel = int(hdr["NINT"]), int(hdr["NSEL"])
-    assert n_sel == len(hdr["BEAMS"]), hdr
-    T = int(hdr["N_OUTPUTS_PER_GEMM"]) * int(hdr["N_AVERAGING"]) // n_int
-    cell = (T, int(hdr["NFREQ"]), n_sel, 4)
-    per_unit = T * cell[1] * n_sel * 4
-    at, rec, records = int(hdr["HDR_SIZE"]), int(hdr["RECORD_HEADER_BYTES"]), []
-    while at < len(raw):
-        first_unit, n_units = (int(v) for v in np.frombuffer(raw, "<u8", 2, at))
-        at += rec
-        records.append((first_unit, n_units, np.frombuffer(raw, "<i8", n_units * per_unit, at).reshape((n_units,) + cell)))
-        at += 8 * n_units * per_unit
+    assert int(hdr["NSEL"]) == len(hdr["BEAMS"]), hdr
     return hdr, records
 
 

@@ -674,6 +674,29 @@ public:
     uint64_t get_stamps_written() const { return written; }
 };
 
+// ---- What the int64 record files of the three stages below share (vis_file_sink, sk_file_sink, stokes_file_sink) ---------------
+// The 4096-byte ASCII header (`KEY value` lines, NUL padded), then one record per delivery: two uint64, the entries (little-endian
+// int64).  A sink supplies the header's CONTENT and LAYOUT and, if it has any, lines of its own (`extra`, in front of the GPU line).
+class int64_record_file {
+    int fd = -1;
+    uint64_t records = 0;
+
+protected:
+    int64_record_file(const bf_config& cfg, const char* path, const char* content, const char* layout, int first_channel, const std::string& extra,
+                      int gpu);
+    ~int64_record_file() { close_file(); }
+    bool write_record(uint64_t first, uint64_t count, const int64_t* data, size_t n_int64);
+    void close_file();
+    uint64_t records_written() const { return records; }
+
+public:
+    static constexpr size_t kHeaderBytes = 4096;
+    static constexpr size_t kRecordBytes = 16;
+    int64_record_file(const int64_record_file&) = delete;
+    int64_record_file& operator=(const int64_record_file&) = delete;
+    bool is_open() const { return fd >= 0; }
+};
+
 // ---- The correlator inside the loop (include/dsabf.h: bf_corr_*; docs/CORRELATOR.md) ------------------------------------------
 // With observation_options::corr_blocks > 0 run_observation creates a bf_corr, pushes the gemm-units of every launch into it on the
 // launch's queue (behind the detect launch, from the resident block), dumps after the last launch of every corr_blocks-th analysed
@@ -689,21 +712,15 @@ struct vis_sink {
 // File: the 4096-byte ASCII header (`KEY value` lines, NUL padded: CONTENT visibilities, DTYPE int64, NANT, NPOL, NFREQ,
 // FIRST_CHANNEL, LAYOUT freq,pol,baseline(lower triangle a1*(a1+1)/2+a2),reim), then one record per dump: uint64 first_block,
 // uint64 n_columns_per_pol, the entries (little-endian int64).
-class vis_file_sink : public vis_sink {
-    int fd = -1;
-    uint64_t dumps = 0;
-
+class vis_file_sink : public vis_sink, public int64_record_file {
 public:
-    static constexpr size_t kHeaderBytes = 4096;
-    static constexpr size_t kRecordBytes = 16;
     vis_file_sink(const bf_config& cfg, const char* path, int first_channel, int gpu);
-    ~vis_file_sink() override;
-    vis_file_sink(const vis_file_sink&) = delete;
-    vis_file_sink& operator=(const vis_file_sink&) = delete;
-    bool is_open() const { return fd >= 0; }
-    bool deliver(uint64_t first_block, uint64_t n_columns_per_pol, const int64_t* vis, size_t n_int64) override;
-    void close() override;
-    uint64_t get_dumps_written() const { return dumps; }
+    bool deliver(uint64_t first_block, uint64_t n_columns_per_pol, const int64_t* vis, size_t n_int64) override
+    {
+        return write_record(first_block, n_columns_per_pol, vis, n_int64);
+    }
+    void close() override { close_file(); }
+    uint64_t get_dumps_written() const { return records_written(); }
 };
 
 // Keeps the dumps in host memory (tests, small runs).
@@ -736,21 +753,15 @@ struct sk_sink {
 // File: the 4096-byte ASCII header (`KEY value` lines, NUL padded: CONTENT voltage_moments, DTYPE int64, NANT, NPOL, NFREQ,
 // FIRST_CHANNEL, LAYOUT freq,pol,ant,m1m2), then one record per dump: uint64 first_block, uint64 n_columns_per_pol, the entries
 // (little-endian int64).
-class sk_file_sink : public sk_sink {
-    int fd = -1;
-    uint64_t dumps = 0;
-
+class sk_file_sink : public sk_sink, public int64_record_file {
 public:
-    static constexpr size_t kHeaderBytes = 4096;
-    static constexpr size_t kRecordBytes = 16;
     sk_file_sink(const bf_config& cfg, const char* path, int first_channel, int gpu);
-    ~sk_file_sink() override;
-    sk_file_sink(const sk_file_sink&) = delete;
-    sk_file_sink& operator=(const sk_file_sink&) = delete;
-    bool is_open() const { return fd >= 0; }
-    bool deliver(uint64_t first_block, uint64_t n_columns_per_pol, const int64_t* moments, size_t n_int64) override;
-    void close() override;
-    uint64_t get_dumps_written() const { return dumps; }
+    bool deliver(uint64_t first_block, uint64_t n_columns_per_pol, const int64_t* moments, size_t n_int64) override
+    {
+        return write_record(first_block, n_columns_per_pol, moments, n_int64);
+    }
+    void close() override { close_file(); }
+    uint64_t get_dumps_written() const { return records_written(); }
 };
 
 // ---- Full-Stokes follow-up beams inside the loop (include/dsabf.h: bf_stokes_*; docs/STOKES.md) --------------------------------
@@ -768,21 +779,15 @@ struct stokes_sink {
 // File: the 4096-byte ASCII header (`KEY value` lines, NUL padded: CONTENT stokes, DTYPE int64, NANT, NFREQ, FIRST_CHANNEL, NINT, NSEL,
 // BEAMS b0,b1,..., LAYOUT unit,time,freq,beam,iquv), then one record per collected set: uint64 first_unit, uint64 n_units, the entries
 // (little-endian int64).
-class stokes_file_sink : public stokes_sink {
-    int fd = -1;
-    uint64_t sets = 0;
-
+class stokes_file_sink : public stokes_sink, public int64_record_file {
 public:
-    static constexpr size_t kHeaderBytes = 4096;
-    static constexpr size_t kRecordBytes = 16;
     stokes_file_sink(const bf_config& cfg, const char* path, int first_channel, int gpu, const std::vector<int>& beams, int n_int);
-    ~stokes_file_sink() override;
-    stokes_file_sink(const stokes_file_sink&) = delete;
-    stokes_file_sink& operator=(const stokes_file_sink&) = delete;
-    bool is_open() const { return fd >= 0; }
-    bool deliver(uint64_t first_unit, uint64_t n_units, const int64_t* stokes, size_t n_int64) override;
-    void close() override;
-    uint64_t get_sets_written() const { return sets; }
+    bool deliver(uint64_t first_unit, uint64_t n_units, const int64_t* stokes, size_t n_int64) override
+    {
+        return write_record(first_unit, n_units, stokes, n_int64);
+    }
+    void close() override { close_file(); }
+    uint64_t get_sets_written() const { return records_written(); }
 };
 
 // `beam -b`: a comma-separated list of beam indices -> beams.  false + *why if it is empty, holds anything but indices 0 .. n_beams - 1,

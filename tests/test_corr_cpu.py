@@ -145,3 +145,28 @@ def test_python_surface_and_signature_table():
     assert callable(api.Beamformer.correlate) and callable(api.vis_to_square) and callable(host.read_vis_file)
     assert all(callable(getattr(api.Correlator, m)) for m in ("push", "push_block", "dump", "collect", "close"))
     assert isinstance(api.Correlator.pending, property)
+
+
+def test_vis_file_round_trip(tmp_path):
+    """A file in dsabf::vis_file_sink's layout (include/dsabf_host.hpp), written here with numpy: the 4096-byte `KEY value` header, NUL
+    padded, then per dump two uint64 and the int64 entries.  host.read_vis_file returns exactly the header and the records."""
+    from dsabeamformer_amd import host
+
+    n_ant, n_pol, n_freq = 5, 2, 3
+    shape = (n_freq, n_pol, n_ant * (n_ant + 1) // 2, 2)
+    rng = np.random.default_rng(31)
+    records = [(0, 4096, rng.integers(-2**62, 2**62, shape, dtype=np.int64)), (6, 1, rng.integers(-2**62, 2**62, shape, dtype=np.int64))]
+    text = ("HDR_VERSION 1.0\nHDR_SIZE 4096\nINSTRUMENT DSA\nCONTENT visibilities\nDTYPE int64\nENDIAN little\n"
+            "LAYOUT freq,pol,baseline(lower triangle a1*(a1+1)/2+a2),reim\nRECORD_HEADER_BYTES 16\nNANT %d\nNPOL %d\nNFREQ %d\n"
+            "FIRST_CHANNEL 128\nN_OUTPUTS_PER_GEMM 2\nN_GEMMS_PER_BLOCK 4\nN_AVERAGING 16\nGPU 1\n" % (n_ant, n_pol, n_freq)).encode()
+    path = str(tmp_path / "v.bin")
+    with open(path, "wb") as fp:
+        fp.write(text.ljust(4096, b"\0"))
+        for first_block, n_columns, vis in records:
+            fp.write(np.array([first_block, n_columns], "<u8").tobytes() + vis.astype("<i8").tobytes())
+    hdr, dumps = host.read_vis_file(path)
+    assert hdr["CONTENT"] == "visibilities" and hdr["DTYPE"] == "int64" and hdr["LAYOUT"] == "freq,pol,baseline(lower triangle a1*(a1+1)/2+a2),reim"
+    assert (int(hdr["NANT"]), int(hdr["NPOL"]), int(hdr["NFREQ"]), int(hdr["FIRST_CHANNEL"]), int(hdr["HDR_SIZE"]), int(hdr["GPU"])) == (5, 2, 3, 128, 4096, 1)
+    assert [(d[0], d[1]) for d in dumps] == [(0, 4096), (6, 1)]
+    assert all(d[2].dtype == np.int64 and d[2].shape == shape and np.array_equal(d[2], r[2]) for d, r in zip(dumps, records))
+    assert os.path.getsize(path) == 4096 + 2 * (16 + records[0][2].nbytes)

@@ -1,8 +1,17 @@
 """GPU tests (-m gpu) of what the four stage objects of a handle share: their place on the handle, the order in which handle and
 stages may be destroyed, and that a create / destroy cycle gives back what it took.  Public API only (dsabeamformer_amd.api): the
 file says nothing about how the runtime keeps its stages, and every comparison of device output is np.array_equal."""
+import os
+import sys
+
 import numpy as np
 import pytest
+
+from conftest import ROOT
+
+sys.path.insert(0, os.path.join(ROOT, "tests", "support"))
+import corr_oracle  # noqa: E402
+import sk_oracle  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -173,3 +182,50 @@ def test_four_cycles_give_back_what_they_took(torch, bfmod):
         free.append(torch.cuda.mem_get_info()[0])
     print("free device memory after each cycle:", free, "drop from cycle 2 to cycle 4: %d bytes" % (free[1] - free[3]))
     assert free[1] - free[3] <= CYCLE_DROP_BEFORE_THE_SHARED_BASE, free
+
+
+def test_a_correlator_and_a_moments_stage_on_one_handle_keep_their_own_state(torch, bfmod):
+    """The correlator and the moments stage are one accumulator stage underneath: whatever that base kept per kind and not per
+    instance -- an accumulator, a column count, the event chain, the dump counters -- would show here.  One of each on one handle, both
+    with max_in_flight 1, two ring slots of different voltages: slot 0 into both on queue 0, a dump of the correlator alone, slot 1
+    into both on queue 1, a dump of both.  Bit for bit the correlator's dumps are slot 0 alone and slot 1 alone, the moments' single
+    dump is the sum of both with the summed column count; the correlator's full set refuses its second dump and leaves the moments
+    stage with nothing pending."""
+    from dsabeamformer_amd import api
+
+    rng = np.random.default_rng(43)
+    cfg = bfmod.debug_config(n_ant=100, n_pol=2, n_avg=2, n_beams=8, n_freq=3, n_out_per_gemm=8, n_gemms_per_block=4, n_blocks_on_gpu=2,
+                             n_streams=4)                                        # tests/test_gpu_sk.py's push_block geometry
+    n_u, cols = cfg.n_gemms_per_block, cfg.n_gemms_per_block * cfg.n_out_per_gemm * cfg.n_avg
+    blocks = rng.integers(0, 256, size=(2, n_u, cfg.n_freq, cfg.n_out_per_gemm * cfg.n_pol * cfg.n_avg, cfg.n_ant), dtype=np.uint8)
+    want_vis = [corr_oracle.visibilities(b, 2) for b in blocks]
+    want_mom = sk_oracle.moments(blocks.reshape((2 * n_u,) + blocks.shape[2:]), 2)
+    assert not np.array_equal(want_vis[0], want_vis[1])
+    bf = bfmod.Beamformer(cfg)
+    corr, sk = api.Correlator(bf, 1), api.SpectralKurtosis(bf, 1)
+    pin = torch.from_numpy(blocks).pin_memory()
+    for slot in (0, 1):
+        bf.submit_block(slot, pin[slot], blocks[slot].nbytes)
+    bf.sync(-1)
+    for stage in (corr, sk):
+        stage.push_block(0, 0, 0, n_u)
+    corr.dump()
+    for stage in (corr, sk):
+        stage.push_block(1, 1, 0, n_u)
+    with pytest.raises(bfmod.DsabfError) as e:
+        corr.dump()
+    assert e.value.code == BF_ERR_STATE and "bf_corr_dump" in str(e.value) and "uncollected" in str(e.value), str(e.value)
+    assert corr.pending == 1 and sk.pending == 0
+    vis, n_columns = corr.collect()                                              # makes room for the correlator's second dump
+    assert n_columns == cols and np.array_equal(vis, want_vis[0])
+    corr.dump()
+    sk.dump()
+    assert corr.pending == 1 and sk.pending == 1
+    vis, n_columns = corr.collect()
+    assert n_columns == cols and np.array_equal(vis, want_vis[1])
+    mom, n_columns = sk.collect()
+    assert n_columns == 2 * cols and np.array_equal(mom, want_mom)
+    assert corr.pending == 0 and sk.pending == 0
+    for s in (corr, sk):
+        s.close()
+    bf.close()
