@@ -56,6 +56,11 @@ class BfSpsStat(C.Structure):
     _fields_ = [("sum", C.c_double), ("sumsq", C.c_double)]
 
 
+class BfPsrModel(C.Structure):
+    """Mirror of ``bf_psr_model`` (include/dsabf.h)."""
+    _fields_ = [("phase0", C.c_uint64), ("dphase", C.c_uint64), ("ddphase", C.c_int64), ("epoch_row", C.c_int64)]
+
+
 class BfCondOptions(C.Structure):
     """Mirror of ``bf_cond_options`` (include/dsabf.h)."""
     _fields_ = [("baseline_pushes", C.c_int), ("zero_dm", C.c_int), ("auto_threshold", C.c_double)]
@@ -230,6 +235,16 @@ SIGNATURES = {
     "bf_dm_stream_history": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "bf_dm_stream_cut": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bf_dm_stream_cut_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "bf_psr_model_from_spin": (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_double, C.c_int64, C.POINTER(BfPsrModel)]),
+    "bf_psr_entries": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "bf_psr_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "bf_psr_destroy": (C.c_int, [C.c_void_p]),
+    "bf_psr_push": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "bf_psr_dump": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "bf_psr_collect": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "bf_psr_pending": (C.c_int, [C.c_void_p]),
+    "bf_psr_beam_snr": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bf_dm_stream_attach_folder": (C.c_int, [C.c_void_p, C.c_void_p]),
     "bf_comm_unique_id": (C.c_int, [C.c_void_p]),
     "bf_comm_create": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
     "bf_comm_destroy": (C.c_int, [C.c_void_p]),
@@ -339,6 +354,9 @@ SIGNATURES = {
     "bfh_stamp_sink_create": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "bfh_stamp_sink_deliver": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_int, C.c_int]),
     "bfh_stamp_sink_destroy": (C.c_int, [C.c_void_p]),
+    "bfh_psr_sink_create": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "bfh_psr_sink_deliver": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "bfh_psr_sink_destroy": (C.c_int, [C.c_void_p]),
     "bfh_dm_trial_share": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "bfh_junk_fill": (C.c_int, [C.POINTER(BfConfig), C.c_int, C.c_uint64, C.c_void_p]),
     "bfh_shm_ring_create": (C.c_int, [C.c_char_p, C.c_uint64, C.c_uint64, C.c_char_p, C.POINTER(C.c_void_p)]),

@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-from ._lib import BF_CAL_FULL, BF_CAL_PHASE, BF_NULL_CLIP, BF_NULL_SCALED, BfCalOptions, BfNullOptions, BfCondOptions, BfConfig, BfEvtEvent, BfEvtOptions, BfSkOptions, BfStampRequest, DsabfError, BfSpsCandidate, BfSpsPeak, BfSpsStat, check, load
+from ._lib import BF_CAL_FULL, BF_CAL_PHASE, BF_NULL_CLIP, BF_NULL_SCALED, BfCalOptions, BfNullOptions, BfCondOptions, BfConfig, BfPsrModel, BfEvtEvent, BfEvtOptions, BfSkOptions, BfStampRequest, DsabfError, BfSpsCandidate, BfSpsPeak, BfSpsStat, check, load
 
 
 def debug_config(**over) -> BfConfig:
@@ -373,6 +373,11 @@ class DmStream(_Owner):
         Conditioner; None detaches) before they are dedispersed."""
         check(self._lib.bf_dm_stream_attach_conditioner(self._s, cond._c if cond is not None else None))
 
+    def attach_folder(self, folder) -> None:
+        """bf_dm_stream_attach_folder: every push from now on also folds its new rows where they lie in the stage's buffer
+        (``folder``: a PulsarFolder; None detaches), behind an attached conditioner."""
+        check(self._lib.bf_dm_stream_attach_folder(self._s, folder._c if folder is not None else None))
+
     def history(self):
         """bf_dm_stream_history: (oldest_row, next_row, cap_rows) -- rows [oldest_row, next_row) of the series can be cut."""
         a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
@@ -576,6 +581,73 @@ class Conditioner(_Owner):
         if hip.hipDeviceSynchronize() != 0 or hip.hipMemcpy(_ptr(out), p, C.c_size_t(out.size), 2) != 0:
             raise DsabfError(-3, "Conditioner.mask: the copy from the device failed")
         return out
+
+
+class PulsarFolder(_Owner):
+    """bf_psr: the detected rows [t][f][b] folded at known spin models into fp64 profiles [pulsar][freq][bin][beam] and uint64 hits
+    [pulsar][freq][bin], every cell summed in row order (include/dsabf.h, docs/PULSAR_FOLDING.md).  ``models``: BfPsrModel objects or
+    (phase0, dphase, ddphase, epoch_row) tuples; ``delays``: int32 host array [n_psr][n_freq_total].  Attach it with
+    ``DmStream.attach_folder`` or push rows yourself."""
+    _ptr_attr, _destroy = "_c", "bf_psr_destroy"
+
+    def __init__(self, bf: Beamformer, n_freq_total: int, max_rows: int, n_bins: int, models, delays, max_in_flight: int = 2):
+        import numpy as np
+
+        self._lib = load()
+        self._c = C.c_void_p()
+        self._bf = bf
+        ms = (BfPsrModel * max(len(models), 1))()
+        for i, m in enumerate(models):
+            ms[i] = m if isinstance(m, BfPsrModel) else BfPsrModel(*[int(v) for v in m])
+        d = np.ascontiguousarray(delays, np.int32)
+        assert d.ndim == 2 and d.shape == (len(models), n_freq_total)
+        self.n_psr, self.n_freq_total, self.n_bins, self.n_beams = len(models), n_freq_total, n_bins, bf.cfg.n_beams
+        check(self._lib.bf_psr_create(bf._h, n_freq_total, max_rows, n_bins, C.cast(ms, C.c_void_p), _ptr(d), len(models), int(max_in_flight),
+                                      C.byref(self._c)))
+
+    @staticmethod
+    def model_from_spin(f0_hz: float, f1_hz_s: float = 0.0, phase0_turns: float = 0.0, row_seconds: float = 1.0, epoch_row: int = 0) -> BfPsrModel:
+        """bf_psr_model_from_spin: the fixed-point oscillator of a spin frequency and its derivative (host, no GPU)."""
+        m = BfPsrModel()
+        check(load().bf_psr_model_from_spin(f0_hz, f1_hz_s, phase0_turns, row_seconds, int(epoch_row), C.byref(m)))
+        return m
+
+    @staticmethod
+    def beam_snr(profile_k, hits_k, chan_mask=None):
+        """bf_psr_beam_snr: (snr float64 [n_beams], peak_bin int32 [n_beams]) of one pulsar's profile [f][bin][beam] and hits [f][bin]
+        (host, no GPU); chan_mask: nonzero = channel left out."""
+        import numpy as np
+
+        p = np.ascontiguousarray(profile_k, np.float64)
+        h = np.ascontiguousarray(hits_k, np.uint64)
+        assert p.ndim == 3 and h.shape == p.shape[:2]
+        m = None if chan_mask is None else np.ascontiguousarray(np.asarray(chan_mask) != 0, np.uint8)
+        assert m is None or m.shape == (p.shape[0],)
+        snr, peak = np.zeros(p.shape[2], np.float64), np.zeros(p.shape[2], np.int32)
+        check(load().bf_psr_beam_snr(_ptr(p), _ptr(h), p.shape[0], p.shape[1], p.shape[2], _ptr(m), _ptr(snr), _ptr(peak)))
+        return snr, peak
+
+    def push(self, d_rows, n_rows: int, stream: int = 0) -> None:
+        check(self._lib.bf_psr_push(self._c, _ptr(d_rows), int(n_rows), C.c_void_p(stream)))
+
+    def dump(self, stream: int = 0) -> None:
+        """Snapshot profile and hits to pinned host memory, then zero them (BF_ERR_STATE beyond max_in_flight uncollected dumps)."""
+        check(self._lib.bf_psr_dump(self._c, C.c_void_p(stream)))
+
+    @property
+    def pending(self) -> int:
+        return self._lib.bf_psr_pending(self._c)
+
+    def collect(self):
+        """Waits for the oldest uncollected dump; returns (profile float64 [n_psr][freq][bin][beam], hits uint64 [n_psr][freq][bin],
+        first_row, n_rows) of that integration."""
+        import numpy as np
+
+        prof = np.empty((self.n_psr, self.n_freq_total, self.n_bins, self.n_beams), np.float64)
+        hits = np.empty((self.n_psr, self.n_freq_total, self.n_bins), np.uint64)
+        first, n = C.c_uint64(), C.c_uint64()
+        check(self._lib.bf_psr_collect(self._c, _ptr(prof), _ptr(hits), C.byref(first), C.byref(n)))
+        return prof, hits, int(first.value), int(n.value)
 
 
 class _AccumStage(_Owner):

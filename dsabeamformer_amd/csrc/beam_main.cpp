@@ -145,10 +145,23 @@ int main(int argc, char* argv[])
     bf_evt_default_options(&evt_opt);
     int stamp_bins = 64, stamp_tbin = 0, stamp_fbin = 1;
     bool event_tol_given = false, event_veto_given = false, stamp_shape_given = false, stamp_flagged = false, long_bad = false;
-    enum { kEvents = 1000, kEventTol, kEventVeto, kStamps, kStampShape, kStampFlagged };
+    // pulsar folding (docs/PULSAR_FOLDING.md): --fold f0[:f1[:phase0]] up to 4 times, --fold-dm dm (the k-th belongs to the k-th --fold),
+    // --fold-bins n, --fold-rows rows_per_dump, --fold-out FILE
+    struct fold_spec {
+        double f0 = 0.0, f1 = 0.0, phase0 = 0.0, dm = 0.0;
+    };
+    std::vector<fold_spec> folds;
+    std::vector<double> fold_dms;
+    int fold_bins = 64, fold_rows = 0;
+    std::string fold_path;
+    bool fold_extra_given = false, fold_bad = false;
+    enum { kEvents = 1000, kEventTol, kEventVeto, kStamps, kStampShape, kStampFlagged, kFold, kFoldDm, kFoldBins, kFoldRows, kFoldOut };
     static const option long_options[] = {{"events", required_argument, nullptr, kEvents},       {"event-tol", required_argument, nullptr, kEventTol},
                                           {"event-veto", required_argument, nullptr, kEventVeto}, {"stamps", required_argument, nullptr, kStamps},
                                           {"stamp-shape", required_argument, nullptr, kStampShape}, {"stamp-flagged", no_argument, nullptr, kStampFlagged},
+                                          {"fold", required_argument, nullptr, kFold},           {"fold-dm", required_argument, nullptr, kFoldDm},
+                                          {"fold-bins", required_argument, nullptr, kFoldBins},   {"fold-rows", required_argument, nullptr, kFoldRows},
+                                          {"fold-out", required_argument, nullptr, kFoldOut},
                                           {nullptr, 0, nullptr, 0}};
     // a non-negative integer that fills its whole field; anything else marks the command line as malformed
     auto number = [&long_bad](const char* text, const char** end, int* out) {
@@ -162,6 +175,45 @@ int main(int argc, char* argv[])
     int arg = 0;
     while ((arg = getopt_long(argc, argv, "s:g:p:d:o:D:a:c:k:K:j:w:R:r:I:M:N:T:W:Q:S:B:C:i:V:L:E:G:A:n:U:F:Y:J:e:O:q:t:m:f:x:b:l:Z:y:zPXuvhH", long_options, nullptr)) != -1) {  // src/beamformer.cu:41-43 (+ -o -D -a -v)
         switch (arg) {
+            case kFold: {   // f0[:f1[:phase0]]
+                fold_spec fs;
+                double* field[3] = {&fs.f0, &fs.f1, &fs.phase0};
+                const char* at = optarg;
+                for (int i = 0; i < 3; i++) {
+                    char* e = nullptr;
+                    *field[i] = strtod(at, &e);
+                    if (e == at) fold_bad = true;
+                    at = e;
+                    if (*at != ':') break;
+                    at++;
+                    if (i == 2) fold_bad = true;
+                }
+                if (*at) fold_bad = true;
+                folds.push_back(fs);
+                break;
+            }
+            case kFoldDm: {
+                char* e = nullptr;
+                fold_dms.push_back(strtod(optarg, &e));
+                if (e == optarg || *e || !(fold_dms.back() >= 0.0)) fold_bad = true;
+                fold_extra_given = true;
+                break;
+            }
+            case kFoldBins:
+            case kFoldRows: {
+                const char* e = nullptr;
+                bool bad = long_bad;
+                long_bad = false;
+                number(optarg, &e, arg == kFoldBins ? &fold_bins : &fold_rows);
+                if (*e || long_bad) fold_bad = true;
+                long_bad = bad;
+                fold_extra_given = true;
+                break;
+            }
+            case kFoldOut:
+                fold_path = optarg;
+                fold_extra_given = true;
+                break;
             case kEvents: events_path = optarg; break;
             case kStamps: stamps_path = optarg; break;
             case kStampFlagged: stamp_flagged = true; break;
@@ -309,6 +361,11 @@ int main(int argc, char* argv[])
                              "                         [0: half the width] x channels in groups of FBIN [1, must divide the band], cut from the DM stage's ring\n"
                              "                         --events without -S, --stamps without --events, the others without their parent, or malformed\n"
                              "                         numbers: beam exits with a usage error\n"
+                             " --fold F0[:F1[:PHASE0]] [--fold-dm DM] [--fold-bins N] [--fold-rows ROWS] [--fold-out FILE]   with -M: the detected stream of\n"
+                             "                         every beam folded at spin frequency F0 Hz, derivative F1 Hz/s [0] and phase PHASE0 turns [0] at the first row,\n"
+                             "                         dedispersed at DM pc/cc [0] (the k-th --fold-dm belongs to the k-th --fold; up to 4 --fold), into N [64] phase\n"
+                             "                         bins (2 .. 4096); a dump to FILE whenever ROWS [one block's] rows or more have been folded (with -X: FILE.<rank>);\n"
+                             "                         --fold without -M, the others without --fold, more than 4 --fold or malformed numbers: a usage error\n"
                              " -H                      this text\n";
                 return EXIT_SUCCESS;
             default: usage(true, std::cerr); return EXIT_FAILURE;
@@ -320,6 +377,20 @@ int main(int argc, char* argv[])
     }
     if (!sps_on && (sps_widths_given || !cand_path.empty())) {
         fprintf(stderr, "beam: -B / -C belong to the single-pulse search: give -S snr (and -M dm_max)\n");
+        return EXIT_FAILURE;
+    }
+    if (!folds.empty() && !(dm_max > 0.0)) {
+        fprintf(stderr, "beam: --fold (pulsar folding) requires the DM stage: give -M dm_max\n");
+        return EXIT_FAILURE;
+    }
+    if (folds.empty() && fold_extra_given) {
+        fprintf(stderr, "beam: --fold-dm / --fold-bins / --fold-rows / --fold-out belong to the pulsar folder: give --fold F0[:F1[:PHASE0]]\n");
+        return EXIT_FAILURE;
+    }
+    if (fold_bad || folds.size() > (size_t)BF_PSR_MAX_PULSARS || fold_dms.size() > folds.size() ||
+        (!folds.empty() && (fold_bins < 2 || fold_bins > BF_PSR_MAX_BINS || fold_rows < 0))) {
+        fprintf(stderr, "beam: --fold F0[:F1[:PHASE0]] (at most %d), --fold-dm DM >= 0 (one per --fold at most), --fold-bins 2 .. %d, --fold-rows ROWS: "
+                        "malformed, too many or out of range\n", BF_PSR_MAX_PULSARS, BF_PSR_MAX_BINS);
         return EXIT_FAILURE;
     }
     if (long_bad) {
@@ -843,6 +914,40 @@ int main(int argc, char* argv[])
                 return EXIT_FAILURE;
             }
             oopt.cond_mask = cond_mask.empty() ? nullptr : cond_mask.data();
+        }
+        std::vector<bf_psr_model> fold_models;
+        std::vector<int32_t> fold_delays;
+        std::unique_ptr<psr_file_sink> fsink;
+        if (!folds.empty() && my_trials > 0 && (!comm || rank == 0 || oopt.dm_split_trials)) {   // --fold: the folder runs where the DM stage runs
+            const int n_psr = (int)folds.size();
+            std::vector<double> dms((size_t)n_psr, 0.0);
+            for (size_t k = 0; k < fold_dms.size(); k++) dms[k] = fold_dms[k];
+            std::vector<float> freq((size_t)full_cfg.n_freq);
+            for (int c = 0; c < full_cfg.n_freq; c++) freq[(size_t)c] = channel_frequency_weights(opt.gpu, c);
+            fold_delays.resize((size_t)n_psr * full_cfg.n_freq);
+            dm_delays(dms.data(), n_psr, freq.data(), full_cfg.n_freq, freq[0], tsamp_ms, fold_delays.data());
+            fold_models.resize((size_t)n_psr);
+            for (int k = 0; k < n_psr; k++)
+                if (bf_psr_model_from_spin(folds[(size_t)k].f0, folds[(size_t)k].f1, folds[(size_t)k].phase0, tsamp_ms * 1e-3, 0, &fold_models[(size_t)k]) != BF_OK) {
+                    fprintf(stderr, "beam: --fold %d: %s\n", k, bf_last_error());
+                    return EXIT_FAILURE;
+                }
+            oopt.psr_models = fold_models.data();
+            oopt.psr_delays = fold_delays.data();
+            oopt.n_psr = n_psr;
+            oopt.psr_bins = fold_bins;
+            oopt.psr_dump_rows = fold_rows > 0 ? fold_rows : pcfg.n_gemms_per_block * pcfg.n_out_per_gemm;
+            if (!fold_path.empty()) {
+                if (oopt.dm_split_trials) fold_path += "." + std::to_string(rank);
+                fsink.reset(new psr_file_sink(fold_path.c_str(), n_psr, full_cfg.n_freq, fold_bins, pcfg.n_beams));
+                if (!fsink->is_open()) {
+                    fprintf(stderr, "beam: could not open %s\n", fold_path.c_str());
+                    return EXIT_FAILURE;
+                }
+                oopt.psr_sink = fsink.get();
+            }
+            std::cout << "Pulsar folder: " << n_psr << " pulsars, " << fold_bins << " bins, a dump every " << oopt.psr_dump_rows << " rows of " << tsamp_ms
+                      << " ms" << std::endl;
         }
         std::unique_ptr<vis_file_sink> vsink;
         if (!vis_path.empty()) {   // -V: every shard correlates its own channels

@@ -50,6 +50,7 @@ struct bf_dm_stream : bf_stage {
     int reserved_rows = 0;        // ... and how many (0: no reservation outstanding)
     bf_sps* search = nullptr;     // bf_dm_stream_attach_search: every chunk is also pushed into this stage, before `done` is recorded
     bf_cond* cond = nullptr;      // bf_dm_stream_attach_conditioner: every push's new rows are conditioned in place, before `rows_ready` is recorded
+    bf_psr* fold = nullptr;       // bf_dm_stream_attach_folder: every push's new rows are also folded where they lie, before `done` is recorded
     // bf_dm_stream_cut (docs/EVENTS.md section 2): the end of the most recent cut, recorded behind the cut before it.  The producer of
     // the rows of a later push waits for it wherever it waits for done[old]: it cannot overwrite what a cut queued before it reads.
     hipEvent_t cut_done = nullptr;
@@ -60,7 +61,7 @@ struct bf_dm_stream : bf_stage {
     std::vector<int32_t> trial_delay;   // [n_dm]: max over f of delay[dm][f] -- the rows a stamp of that trial needs beyond its times
 };
 
-// One link to an attached stage: the member of the DM stage (search, cond) and that stage's feeder, set and cleared together.
+// One link to an attached stage: the member of the DM stage (search, cond, fold) and that stage's feeder, set and cleared together.
 template <class T>
 static void set_link(bf_dm_stream* dm, T*& member, T* to)
 {
@@ -75,6 +76,7 @@ void dsabf::rt::dm_stream_drop(bf_dm_stream* dm, bf_stage* attached)
 {
     if (dm->search && as_stage(dm->search) == attached) set_link<bf_sps>(dm, dm->search, nullptr);
     if (dm->cond && as_stage(dm->cond) == attached) set_link<bf_cond>(dm, dm->cond, nullptr);
+    if (dm->fold && as_stage(dm->fold) == attached) set_link<bf_psr>(dm, dm->fold, nullptr);
 }
 
 // The ring is no hipMalloc: it is unmapped and released here, behind the wait for everything in flight, and the stage's resource
@@ -83,6 +85,7 @@ void bf_dm_stream::release_device()
 {
     set_link<bf_sps>(this, search, nullptr);
     set_link<bf_cond>(this, cond, nullptr);
+    set_link<bf_psr>(this, fold, nullptr);
     res.wait();
     if (mapped0) (void)hipMemUnmap(d_buf, phys_bytes);
     if (mapped1) (void)hipMemUnmap(reinterpret_cast<char*>(d_buf) + phys_bytes, phys_bytes);
@@ -298,6 +301,17 @@ int bf_dm_stream_attach_conditioner(bf_dm_stream* dm, bf_cond* c)
     return BF_OK;
 }
 
+int bf_dm_stream_attach_folder(bf_dm_stream* dm, bf_psr* p)
+{
+    if (!dm) return fail(BF_ERR_INVALID, "NULL argument");
+    if (int rc = orphaned(dm)) return rc;
+    if (p == dm->fold) return BF_OK;
+    if (p)
+        if (int rc = psr_check_attach(p, dm->h, dm->n_freq, dm->max_rows)) return rc;
+    set_link(dm, dm->fold, p);
+    return BF_OK;
+}
+
 int bf_dm_stream_output_device(bf_dm_stream* s, float** d_out)
 {
     if (!s || !d_out) return fail(BF_ERR_INVALID, "NULL argument");
@@ -372,6 +386,9 @@ int bf_dm_stream_push(bf_dm_stream* s, const float* d_rows, int n_rows, float* h
     if (s->search && s->pushed + (uint64_t)n_rows > (uint64_t)s->max_delay && bf_sps_pending(s->search) >= sps_max_in_flight(s->search))
         return fail(BF_ERR_STATE, "bf_dm_stream_push: the attached search stage has %d uncollected pushes (max_in_flight): bf_sps_collect first",
                     bf_sps_pending(s->search));
+    // an attached folder refuses what it would refuse of these rows (its oscillator's range) HERE too
+    if (s->fold)
+        if (int rc = psr_check_push(s->fold, n_rows)) return rc;
     bf_handle* h = s->h;
     ON_DEVICE(h);
     hipStream_t q = as_stream(hip_stream);
@@ -431,6 +448,12 @@ int bf_dm_stream_push(bf_dm_stream* s, const float* d_rows, int n_rows, float* h
         if (s->search)
             if (int rc = bf_sps_push(s->search, s->d_out[set], n_out, emitted, q)) return rc;
     }
+    // The folder's hook (docs/PULSAR_FOLDING.md section 2): the new rows are read where they lie, on this queue -- behind the copy-in and
+    // the conditioner, so it folds what the dedispersion reads; behind rows_ready and the chunk, so neither the push after this one
+    // nor this push's chunk waits for the fold -- and before `done` below, the event every producer that may overwrite these rows
+    // waits for.
+    if (s->fold)
+        if (int rc = bf_psr_push(s->fold, new_rows, n_rows, q)) return rc;
     // the end of push j implies the end of every push before it (chunks leave in order; a producer that waits for push j - 3 knows
     // that nothing older reads the rows it overwrites)
     if (s->ring && s->n_push && s->done_recorded[prev]) HIP_TRY(hipStreamWaitEvent(q, s->done[prev], 0));

@@ -739,4 +739,28 @@ int bfh_stamp_sink_destroy(bfh_stamp_sink* s)
     return BF_OK;
 }
 
+struct bfh_psr_sink {
+    psr_file_sink s;
+    int n_psr, n_freq, n_bins, n_beams;
+};
+int bfh_psr_sink_create(const char* path, int n_psr, int n_freq, int n_bins, int n_beams, bfh_psr_sink** out)
+{
+    if (!path || !out || n_psr < 1 || n_freq < 1 || n_bins < 1 || n_beams < 1) return BF_ERR_INVALID;
+    *out = nullptr;
+    std::unique_ptr<bfh_psr_sink> s(new bfh_psr_sink{psr_file_sink(path, n_psr, n_freq, n_bins, n_beams), n_psr, n_freq, n_bins, n_beams});
+    if (!s->s.is_open()) return BF_ERR_INVALID;
+    *out = s.release();
+    return BF_OK;
+}
+int bfh_psr_sink_deliver(bfh_psr_sink* s, uint64_t first_row, uint64_t n_rows, const uint64_t* hits, const double* profile)
+{
+    if (!s || !hits || !profile) return BF_ERR_INVALID;
+    return s->s.deliver(first_row, n_rows, s->n_psr, s->n_freq, s->n_bins, s->n_beams, hits, profile) ? BF_OK : BF_ERR_STATE;
+}
+int bfh_psr_sink_destroy(bfh_psr_sink* s)
+{
+    delete s;
+    return BF_OK;
+}
+
 }  // extern "C"

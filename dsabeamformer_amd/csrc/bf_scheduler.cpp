@@ -204,6 +204,7 @@ struct run_resources {
     bf_dm_stream* dm = nullptr;
     bf_sps* sps = nullptr;
     bf_cond* cond = nullptr;
+    bf_psr* psr = nullptr;
     bf_corr* corr = nullptr;
     bf_sk* sk = nullptr;
     bf_stokes* stokes = nullptr;
@@ -218,6 +219,7 @@ struct run_resources {
         bf_sps_destroy(sps);
         bf_evt_destroy(evt);
         bf_cond_destroy(cond);
+        bf_psr_destroy(psr);
         bf_dm_stream_destroy(dm);
         for (void* p : pinned) bf_free_pinned(p);
         bf_destroy(h);
@@ -515,6 +517,12 @@ int check_options(const bf_config& cfg, const observation_options& opt)
     if (opt.corr_blocks < 0) return set_error(BF_ERR_INVALID, "run_observation: corr_blocks must be 0 (off) or the blocks per dump");
     if (opt.vis_sink && !opt.corr_blocks) return set_error(BF_ERR_INVALID, "run_observation: a vis_sink needs corr_blocks > 0");
     if (opt.corr_blocks && !opt.block_launch) return set_error(BF_ERR_INVALID, "run_observation: the correlator needs block-granular launches");
+    if (opt.n_psr < 0 || opt.n_psr > BF_PSR_MAX_PULSARS) return set_error(BF_ERR_INVALID, "run_observation: n_psr must be 0 (off) .. 4");
+    if (opt.n_psr && !opt.dm_delays) return set_error(BF_ERR_INVALID, "run_observation: the pulsar folder needs the DM stage (dm_delays)");
+    if (opt.n_psr && (!opt.psr_models || !opt.psr_delays)) return set_error(BF_ERR_INVALID, "run_observation: n_psr > 0 needs psr_models and psr_delays");
+    if (opt.n_psr && (opt.psr_bins < 2 || opt.psr_bins > BF_PSR_MAX_BINS || opt.psr_dump_rows < 1))
+        return set_error(BF_ERR_INVALID, "run_observation: the pulsar folder needs psr_bins in 2 .. 4096 and psr_dump_rows >= 1");
+    if (!opt.n_psr && opt.psr_sink) return set_error(BF_ERR_INVALID, "run_observation: a psr_sink needs n_psr > 0");
     if (opt.sk_blocks < 0) return set_error(BF_ERR_INVALID, "run_observation: sk_blocks must be 0 (off) or the blocks per dump");
     if (opt.sk_sink && !opt.sk_blocks) return set_error(BF_ERR_INVALID, "run_observation: a sk_sink needs sk_blocks > 0");
     if (opt.sk_blocks && !opt.block_launch) return set_error(BF_ERR_INVALID, "run_observation: the voltage moments need block-granular launches");
@@ -640,6 +648,10 @@ struct production_run {
     float* stamp_host = nullptr;           // pinned: the stamps of one cut
     size_t stamp_batch = 0;                // requests one cut takes
     uint64_t events = 0, stamps = 0, stamps_dropped = 0, stamps_missed = 0, stamps_beyond_end = 0;
+    uint64_t psr_rows_folded = 0, psr_dumps = 0;   // the pulsar folder: rows folded since the last dump; dumps delivered
+    std::deque<uint64_t> psr_pending;              // the block behind whose last launch each uncollected dump was issued
+    std::vector<double> psr_prof;
+    std::vector<uint64_t> psr_hits;
     float* cond_mask_host = nullptr;      // pinned, whole dwords: where the conditioner's mask of the last push is read back at the end
 
     // channels the conditioner masked in the last push (-1: no conditioner, or no push)
@@ -723,6 +735,13 @@ struct production_run {
                 if (rc == BF_OK) rc = bf_dm_stream_attach_conditioner(dev.dm, dev.cond);
                 if (rc != BF_OK) return gpu_error(log, rc);
                 if ((rc = dev.alloc_pinned(((size_t)plan.n_freq_band + 3) / 4, &cond_mask_host)) != BF_OK) return rc;
+            }
+            if (opt.n_psr > 0) {   // the pulsar folder: behind the conditioner, on the rows in the stage's buffer (docs/PULSAR_FOLDING.md); a dump per launch at most
+                rc = bf_psr_create(dev.h, plan.n_freq_band, plan.dm_rows, opt.psr_bins, opt.psr_models, opt.psr_delays, opt.n_psr, (int)n_buf, &dev.psr);
+                if (rc == BF_OK) rc = bf_dm_stream_attach_folder(dev.dm, dev.psr);
+                if (rc != BF_OK) return gpu_error(log, rc);
+                psr_prof.resize(bf_psr_entries(opt.n_psr, plan.n_freq_band, opt.psr_bins, cfg.n_beams));
+                psr_hits.resize(psr_prof.size() / (size_t)cfg.n_beams);
             }
             if (opt.sps_widths > 0) {   // the search stage: as many result sets as chunk buffers (a chunk in flight = a search push in flight)
                 rc = bf_sps_create(dev.h, plan.dm_count, plan.dm_first, opt.sps_widths, plan.dm_rows, (int)n_buf, /*baseline_pushes=*/8,
@@ -889,8 +908,13 @@ struct production_run {
         uint64_t first_t = 0;
         int n_t = 0;
         float* chunk = dm_host[(size_t)(dm_seq++ % dm_host.size())];
-        const int rc = bf_dm_stream_push(dev.dm, d_rows, plan.dm_rows, chunk, &first_t, &n_t, dm_qs);
+        int rc = bf_dm_stream_push(dev.dm, d_rows, plan.dm_rows, chunk, &first_t, &n_t, dm_qs);
         if (rc == BF_OK && n_t > 0) dm_pending.push_back({(uint64_t)block_index, first_t, n_t, chunk});
+        if (rc == BF_OK && dev.psr && (psr_rows_folded += (uint64_t)plan.dm_rows) >= (uint64_t)opt.psr_dump_rows) {   // the attached folder has folded these rows
+            rc = bf_psr_dump(dev.psr, dm_qs);
+            psr_pending.push_back((uint64_t)block_index);
+            psr_rows_folded = 0;
+        }
         return rc;
     }
 
@@ -1021,6 +1045,17 @@ struct production_run {
                     return BF_ERR_STATE;
                 }
             }
+        while (!psr_pending.empty() && psr_pending.front() < blocks_analyzed) {   // (the collect waits for the dump's own copy)
+            psr_pending.pop_front();
+            uint64_t first_row = 0, n_rows = 0;
+            const int rc = bf_psr_collect(dev.psr, psr_prof.data(), psr_hits.data(), &first_row, &n_rows);
+            if (rc != BF_OK) return gpu_error(log, rc);
+            psr_dumps++;
+            if (opt.psr_sink && !opt.psr_sink->deliver(first_row, n_rows, opt.n_psr, plan.n_freq_band, opt.psr_bins, cfg.n_beams, psr_hits.data(), psr_prof.data())) {
+                log << "ERROR: fold sink failed at row " << first_row << std::endl;
+                return BF_ERR_STATE;
+            }
+        }
         while (!stokes_pending.empty() && stokes_pending.front().first < blocks_analyzed) {   // (the collect waits for the set's own copy)
             const uint64_t first_unit = stokes_pending.front().second;
             stokes_pending.pop_front();
@@ -1104,6 +1139,7 @@ int run_observation(const bf_config& cfg, const observation_options& opt, block_
     if (opt.vis_sink) opt.vis_sink->close();
     if (opt.sk_sink) opt.sk_sink->close();
     if (opt.stokes_sink) opt.stokes_sink->close();
+    if (opt.psr_sink) opt.psr_sink->close();
     const uint64_t chunks = obs_state.get_current_transfer_gemm() * cfg.n_out_per_gemm;  // :552
     const double rate = (double)source.get_block_size() * obs_state.get_blocks_transfer_queue() / ms / 1e6;  // :554
     closing_report(log, ms, chunks, ms / (chunks ? chunks : 1), rate, run.plan.block_launch ? "bf_enqueue_block" : kUnitLaunchPattern);
@@ -1125,6 +1161,7 @@ int run_observation(const bf_config& cfg, const observation_options& opt, block_
         res->vis_dumps = run.corr.dumps;
         res->sk_dumps = run.sk.dumps;
         res->stokes_units = run.stokes_units;
+        res->psr_dumps = run.psr_dumps;
         res->cond_masked = run.cond_masked_channels();
     }
     if (run.plan.dm_run)
@@ -1147,6 +1184,9 @@ int run_observation(const bf_config& cfg, const observation_options& opt, block_
     if (run.dev.stokes)
         log << "Stokes beams: " << opt.stokes_beams.size() << " beams, windows of " << (opt.stokes_int ? opt.stokes_int : cfg.n_avg) << " samples, "
             << run.stokes_units << " gemm-units" << std::endl;
+    if (run.dev.psr)
+        log << "Pulsar folder: " << opt.n_psr << " pulsars, " << opt.psr_bins << " bins, " << run.psr_dumps << " dumps of at least " << opt.psr_dump_rows
+            << " rows each (an incomplete integration at the end is dropped)" << std::endl;
     if (run.dev.sps)
         log << "Single-pulse search: boxcar widths 1 .. " << (1 << (opt.sps_widths - 1)) << ", " << run.sps_candidates << " candidates at S/N >= "
             << opt.sps_threshold << std::endl;

@@ -714,6 +714,62 @@ int bf_dm_stream_cut(bf_dm_stream *s, const bf_stamp_request *reqs, int n_req, i
 int bf_dm_stream_cut_host(bf_dm_stream *s, const bf_stamp_request *reqs, int n_req, int n_tau, int tbin, int fbin,
                           float *host_out, int32_t *status);
 
+/* ---- Pulsar folding: phase-binned profiles of every beam (docs/PULSAR_FOLDING.md) -------------------------------------------
+ * The reference stops at a DM-0 collapse copied to the host (src/beamformer.cu:498-510) and keeps nothing across blocks; the
+ * search behind the DM stage looks at one push at a time.  A bf_psr integrates the detected rows x[row][freq][beam] (fp32, the
+ * layout bf_dm_stream_push takes, n_beams = the handle's) at a KNOWN spin frequency and dispersion, for all beams at once;
+ * docs/PULSAR_FOLDING.md section 1 is the contract, to the bit:
+ *   phase model, integers only (turns in units of 2^-64, per row): rows r count from the first row the stage was given; for
+ *     pulsar k, channel f:  n = r - epoch_row - delay[k][f],
+ *     phase = phase0 + (uint64)n dphase + (uint64)(n (n - 1) / 2) (uint64)ddphase  (mod 2^64),  bin = ((phase >> 32) n_bins) >> 32;
+ *   delay: HOST int32 [n_psr][n_freq_total], all >= 0, sign and meaning of one row of dsabf::dm_delays / bfh_dm_delays;
+ *   profile[k][f][bin][beam] (fp64): acc = acc + (double)x[r][f][beam] over the rows of that bin IN ASCENDING ROW ORDER, from +0.0
+ *     at the last dump; hits[k][f][bin] (uint64): the number of those rows.  No fp32 sums, no atomics, no partial sums: the
+ *     bits do not depend on how the series is cut into pushes, on queues or on launch shapes.
+ *   n_bins 2 .. BF_PSR_MAX_BINS, n_psr 1 .. BF_PSR_MAX_PULSARS (they share one read of the rows).
+ * bf_psr_entries: the doubles of a profile, n_psr * n_freq_total * n_bins * n_beams (hits: that / n_beams); 0 out of range.
+ * bf_psr_push is asynchronous on hip_stream; pushes and dumps of one stage are ordered by the stage itself, whichever queues
+ *   they are issued on (they share the accumulators).  A push that would reach |n| >= 2^31 is refused: re-anchor epoch_row.
+ * bf_psr_dump snapshots profile and hits into pinned set j % max_in_flight and zeroes the accumulators, on a queue of the
+ *   stage's own, behind the pushes issued before it (hip_stream is not held); a dump whose set is uncollected: BF_ERR_STATE.
+ * bf_psr_collect waits for the OLDEST uncollected dump and copies it to profile / hits (host) and the integration's first row and
+ *   row count to *first_row / *n_rows (may be NULL); nothing pending: BF_ERR_STATE.  bf_psr_pending: dumps not yet collected.
+ * BF_ERR_INVALID, with nothing launched: n_rows outside 1 .. max_rows_per_push, NULL pointers, n_bins, n_psr or
+ *   max_in_flight out of range, a negative delay, the |n| limit.  Lifetime as for a bf_cond: a handle that goes first releases
+ *   the device memory, the stage then answers BF_ERR_STATE and can still be destroyed.
+ * bf_psr_model_from_spin (host, fp64, no GPU): x = f0 row_seconds; dphase = (uint64)ldexp(x - floor(x), 64) (a fraction that
+ *   rounds to 1.0: 0); ddphase = (int64)nearbyint(ldexp((f1 row_seconds) row_seconds, 64)), refused at |.| >= 2^62; phase0 from
+ *   phase0_turns like dphase; then dphase += (uint64)(ddphase >> 1), so that the phase follows f0 t + f1 t^2 / 2.  NaN, infinite
+ *   or row_seconds <= 0: BF_ERR_INVALID.
+ * bf_psr_beam_snr (host, fp64, no GPU), for one pulsar's profile [f][bin][beam] and hits [f][bin], per beam: over the channels
+ *   with chan_mask[f] == 0 (NULL: all), ascending: S[j] = sum profile, H[j] = sum hits; m[j] = S[j] / H[j] on the bins with H[j] > 0;
+ *   fewer than 4 such bins: snr 0, peak_bin -1; med = median of m (even count: (a + b) 0.5), sigma = 1.4826 median |m - med|;
+ *   sigma not > 0: snr 0, peak_bin -1; else snr = (max m - med) / sigma and peak_bin = the first bin that attains the maximum.
+ * bf_dm_stream_attach_folder(dm, p) (p == NULL detaches): from then on every bf_dm_stream_push also folds its new rows where they
+ *   lie in the DM stage's buffer, on the push's queue -- behind an attached conditioner (it folds what is dedispersed), and before
+ *   the ring can hand those rows' place to a later push.  Same handle, same n_freq_total, max_rows_per_push >= the DM stage's. */
+#define BF_PSR_MAX_PULSARS 4
+#define BF_PSR_MAX_BINS 4096
+typedef struct bf_psr bf_psr;
+typedef struct bf_psr_model {
+    uint64_t phase0, dphase; /* turns in units of 2^-64, per row of the detected stream */
+    int64_t ddphase;
+    int64_t epoch_row;       /* the row (counted from the first row pushed) at which phase = phase0 */
+} bf_psr_model;
+int bf_psr_model_from_spin(double f0_hz, double f1_hz_s, double phase0_turns, double row_seconds, int64_t epoch_row,
+                           bf_psr_model *model);
+size_t bf_psr_entries(int n_psr, int n_freq_total, int n_bins, int n_beams);
+int bf_psr_create(bf_handle *h, int n_freq_total, int max_rows_per_push, int n_bins, const bf_psr_model *models,
+                  const int32_t *delays, int n_psr, int max_in_flight, bf_psr **out);
+int bf_psr_destroy(bf_psr *p);
+int bf_psr_push(bf_psr *p, const float *d_rows, int n_rows, void *hip_stream);
+int bf_psr_dump(bf_psr *p, void *hip_stream);
+int bf_psr_collect(bf_psr *p, double *profile, uint64_t *hits, uint64_t *first_row, uint64_t *n_rows);
+int bf_psr_pending(const bf_psr *p);
+int bf_psr_beam_snr(const double *profile_k, const uint64_t *hits_k, int n_freq_total, int n_bins, int n_beams,
+                    const uint8_t *chan_mask, double *snr, int32_t *peak_bin);
+int bf_dm_stream_attach_folder(bf_dm_stream *dm, bf_psr *p);
+
 /* ---- Multi-GPU: frequency shards and the gather of their detected powers -------------------------------
  * The reference runs 8 independent processes, one sub-band per GPU (`-g`, src/beamformer.cu:92-100,233; README.md:168)
  * and never brings their outputs together.  Here a handle may own any contiguous range of frequencies (bf_config.n_freq

@@ -177,6 +177,14 @@ int bfh_stamp_sink_deliver(bfh_stamp_sink *s, uint64_t t0, int dm, int beam, int
                            int n_freq_out, int n_bins);
 int bfh_stamp_sink_destroy(bfh_stamp_sink *s);
 
+/* The fold file sink on its own (docs/PULSAR_FOLDING.md section 5; tests and host consumers, no device): dsabf::psr_file_sink
+ * writes the 4096-byte header and one record per dump -- hits uint64 [n_psr][n_freq][n_bins], profile float64
+ * [n_psr][n_freq][n_bins][n_beams], the shape given at creation. */
+typedef struct bfh_psr_sink bfh_psr_sink;
+int bfh_psr_sink_create(const char *path, int n_psr, int n_freq, int n_bins, int n_beams, bfh_psr_sink **out);
+int bfh_psr_sink_deliver(bfh_psr_sink *s, uint64_t first_row, uint64_t n_rows, const uint64_t *hits, const double *profile);
+int bfh_psr_sink_destroy(bfh_psr_sink *s);
+
 /* DM trial ladder and per-channel sample delays (sandbox/Dispersion Theory.ipynb cells 1-2 and 5; dsabf::dm_trials,
  * dsabf::dm_delays).  bfh_dm_trials returns the number of trials written (<= cap). */
 int bfh_dm_trials(double dm0, double dm_max, int nchan, double epsilon, double nu_ghz, double chan_bw_mhz, double ti_us,

@@ -674,6 +674,59 @@ public:
     uint64_t get_stamps_written() const { return written; }
 };
 
+// ---- Pulsar folding behind the DM stage (include/dsabf.h: bf_psr_*, bf_dm_stream_attach_folder; docs/PULSAR_FOLDING.md) -------
+// With observation_options::n_psr > 0 run_observation creates a bf_psr next to the DM stage, attaches it, dumps whenever
+// psr_dump_rows rows or more have been folded (an incomplete integration at the end is dropped) and hands every collected dump to a psr_sink.
+// One dump: hits uint64 [n_psr][n_freq][n_bins] and profile float64 [n_psr][n_freq][n_bins][n_beams] of the n_rows rows from first_row.
+struct psr_sink {
+    virtual ~psr_sink() {}
+    virtual bool deliver(uint64_t first_row, uint64_t n_rows, int n_psr, int n_freq, int n_bins, int n_beams, const uint64_t* hits,
+                         const double* profile) = 0;
+    virtual void close() {}
+};
+
+// File: the 4096-byte ASCII header (`KEY value` lines, NUL padded: CONTENT folds, DTYPE float64, NPSR, NFREQ, NBINS, NBEAMS, LAYOUT),
+// then one record per dump: uint64 first_row, n_rows; uint32 n_psr, n_freq, n_bins, n_beams; the hits (uint64); the profile (float64).
+class psr_file_sink : public psr_sink {
+    FILE* fp = nullptr;
+    uint64_t written = 0;
+
+public:
+    static constexpr size_t kHeaderBytes = 4096;
+    static constexpr size_t kRecordBytes = 32;
+    psr_file_sink(const char* path, int n_psr, int n_freq, int n_bins, int n_beams) : fp(fopen(path, "wb"))
+    {
+        if (!fp) return;
+        char header[kHeaderBytes] = {0};
+        snprintf(header, sizeof header,
+                 "HDR_SIZE 4096\nCONTENT folds\nDTYPE float64\nNPSR %d\nNFREQ %d\nNBINS %d\nNBEAMS %d\nLAYOUT hits[psr,freq,bin],profile[psr,freq,bin,beam]\n"
+                 "RECORD_HEADER_BYTES 32\n",
+                 n_psr, n_freq, n_bins, n_beams);
+        if (fwrite(header, 1, sizeof header, fp) != sizeof header) close();
+    }
+    ~psr_file_sink() override { close(); }
+    psr_file_sink(const psr_file_sink&) = delete;
+    psr_file_sink& operator=(const psr_file_sink&) = delete;
+    bool is_open() const { return fp != nullptr; }
+    bool deliver(uint64_t first_row, uint64_t n_rows, int n_psr, int n_freq, int n_bins, int n_beams, const uint64_t* hits, const double* profile) override
+    {
+        if (!fp || n_psr < 1 || n_freq < 1 || n_bins < 1 || n_beams < 1) return false;
+        const uint64_t rows[2] = {first_row, n_rows};
+        const uint32_t dims[4] = {(uint32_t)n_psr, (uint32_t)n_freq, (uint32_t)n_bins, (uint32_t)n_beams};
+        const size_t n_hits = (size_t)n_psr * (size_t)n_freq * (size_t)n_bins, n_prof = n_hits * (size_t)n_beams;
+        if (fwrite(rows, 8, 2, fp) != 2 || fwrite(dims, 4, 4, fp) != 4 || fwrite(hits, 8, n_hits, fp) != n_hits || fwrite(profile, 8, n_prof, fp) != n_prof)
+            return false;
+        written++;
+        return true;
+    }
+    void close() override
+    {
+        if (fp) fclose(fp);
+        fp = nullptr;
+    }
+    uint64_t get_dumps_written() const { return written; }
+};
+
 // ---- What the int64 record files of the three stages below share (vis_file_sink, sk_file_sink, stokes_file_sink) ---------------
 // The 4096-byte ASCII header (`KEY value` lines, NUL padded), then one record per delivery: two uint64, the entries (little-endian
 // int64).  A sink supplies the header's CONTENT and LAYOUT and, if it has any, lines of its own (`extra`, in front of the GPU line).
@@ -991,6 +1044,18 @@ struct observation_options {
     bool cond_zero_dm = true;
     double cond_auto_threshold = 0.0;
     const uint8_t* cond_mask = nullptr;
+    // Pulsar folding behind the DM stage (docs/PULSAR_FOLDING.md; needs dm_delays): n_psr = 1 .. 4 pulsars (0 = off) with their
+    // oscillators psr_models [n_psr] (bf_psr_model_from_spin) and delays psr_delays (host int32 [n_psr][cfg.n_freq * world], >= 0, a row
+    // of dm_delays each), psr_bins phase bins.  A bf_psr is created next to the DM stage and attached to it: it folds every pushed block
+    // where it lies in the stage's buffer (conditioned, if cond_baseline > 0).  After every launch that brings the rows folded since the
+    // last dump to psr_dump_rows or more the folder is dumped; every dump goes to psr_sink once its block has been analysed (an incomplete
+    // integration at the end is dropped).  On a sharded run the ranks that dedisperse each fold the whole band: redundant and identical.
+    const bf_psr_model* psr_models = nullptr;
+    const int32_t* psr_delays = nullptr;
+    int n_psr = 0;
+    int psr_bins = 64;
+    int psr_dump_rows = 0;
+    dsabf::psr_sink* psr_sink = nullptr;
     // The incoherent beam (docs/INCOHERENT_BEAM.md): beam column `incoherent_beam` of the detected stream carries the antenna powers
     // summed over the antennas instead of a tied beam (bf_set_incoherent_beam, set on the handle before the loop); -1 = off.  On a
     // sharded run every rank gives the same index: the sum is per channel, each shard fills its own slice of the column.
@@ -1035,6 +1100,7 @@ struct observation_result {
     uint64_t vis_dumps = 0;         // integrations the correlator dumped (corr_blocks > 0)
     uint64_t sk_dumps = 0;          // integrations the moments stage dumped (sk_blocks > 0)
     uint64_t stokes_units = 0;      // gemm-units the Stokes stage delivered (stokes_beams non-empty)
+    uint64_t psr_dumps = 0;         // integrations the pulsar folder dumped (n_psr > 0)
     int cond_masked = -1;           // channels the conditioner masked in the last push (cond_baseline > 0 and a block analysed), else -1
 };
 // The reference's production main() loop on top of the C-ABI.  pos/dir: antenna positions and beam directions.
