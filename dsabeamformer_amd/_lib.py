@@ -61,6 +61,23 @@ class BfPsrModel(C.Structure):
     _fields_ = [("phase0", C.c_uint64), ("dphase", C.c_uint64), ("ddphase", C.c_int64), ("epoch_row", C.c_int64)]
 
 
+class BfFfaPeak(C.Structure):
+    """Mirror of ``bf_ffa_peak`` (include/dsabf.h)."""
+    _fields_ = [("value", C.c_float), ("shift", C.c_uint16), ("bin", C.c_uint16)]
+
+
+class BfFfaStat(C.Structure):
+    """Mirror of ``bf_ffa_stat`` (include/dsabf.h)."""
+    _fields_ = [("sum", C.c_double), ("sumsq", C.c_double)]
+
+
+class BfFfaCandidate(C.Structure):
+    """Mirror of ``bf_ffa_candidate`` (include/dsabf.h)."""
+    _fields_ = [("first_row", C.c_uint64), ("n_rows", C.c_uint64), ("period_rows", C.c_double), ("dm", C.c_int32), ("beam", C.c_int32),
+                ("octave", C.c_int32), ("p", C.c_int32), ("shift", C.c_int32), ("bin", C.c_int32), ("width", C.c_int32), ("snr", C.c_double),
+                ("value", C.c_float)]
+
+
 class BfCondOptions(C.Structure):
     """Mirror of ``bf_cond_options`` (include/dsabf.h)."""
     _fields_ = [("baseline_pushes", C.c_int), ("zero_dm", C.c_int), ("auto_threshold", C.c_double)]
@@ -245,6 +262,18 @@ SIGNATURES = {
     "bf_psr_pending": (C.c_int, [C.c_void_p]),
     "bf_psr_beam_snr": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bf_dm_stream_attach_folder": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "bf_ffa_entries": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "bf_ffa_rows_of": (C.c_int, [C.c_int, C.c_int]),
+    "bf_ffa_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
+                                C.POINTER(C.c_void_p)]),
+    "bf_ffa_destroy": (C.c_int, [C.c_void_p]),
+    "bf_ffa_push": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p]),
+    "bf_ffa_collect": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "bf_ffa_pending": (C.c_int, [C.c_void_p]),
+    "bf_ffa_last_records": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "bf_ffa_select": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64,
+                                C.c_int, C.c_double, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "bf_dm_stream_attach_periodicity": (C.c_int, [C.c_void_p, C.c_void_p]),
     "bf_comm_unique_id": (C.c_int, [C.c_void_p]),
     "bf_comm_create": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
     "bf_comm_destroy": (C.c_int, [C.c_void_p]),
@@ -357,6 +386,9 @@ SIGNATURES = {
     "bfh_psr_sink_create": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "bfh_psr_sink_deliver": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]),
     "bfh_psr_sink_destroy": (C.c_int, [C.c_void_p]),
+    "bfh_ffa_sink_create": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_void_p)]),
+    "bfh_ffa_sink_deliver": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "bfh_ffa_sink_destroy": (C.c_int, [C.c_void_p]),
     "bfh_dm_trial_share": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "bfh_junk_fill": (C.c_int, [C.POINTER(BfConfig), C.c_int, C.c_uint64, C.c_void_p]),
     "bfh_shm_ring_create": (C.c_int, [C.c_char_p, C.c_uint64, C.c_uint64, C.c_char_p, C.POINTER(C.c_void_p)]),

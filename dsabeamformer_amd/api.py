@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-from ._lib import BF_CAL_FULL, BF_CAL_PHASE, BF_NULL_CLIP, BF_NULL_SCALED, BfCalOptions, BfNullOptions, BfCondOptions, BfConfig, BfPsrModel, BfEvtEvent, BfEvtOptions, BfSkOptions, BfStampRequest, DsabfError, BfSpsCandidate, BfSpsPeak, BfSpsStat, check, load
+from ._lib import BF_CAL_FULL, BF_CAL_PHASE, BF_NULL_CLIP, BF_NULL_SCALED, BfCalOptions, BfNullOptions, BfCondOptions, BfConfig, BfFfaCandidate, BfFfaPeak, BfFfaStat, BfPsrModel, BfEvtEvent, BfEvtOptions, BfSkOptions, BfStampRequest, DsabfError, BfSpsCandidate, BfSpsPeak, BfSpsStat, check, load
 
 
 def debug_config(**over) -> BfConfig:
@@ -378,6 +378,11 @@ class DmStream(_Owner):
         (``folder``: a PulsarFolder; None detaches), behind an attached conditioner."""
         check(self._lib.bf_dm_stream_attach_folder(self._s, folder._c if folder is not None else None))
 
+    def attach_periodicity(self, ffa) -> None:
+        """bf_dm_stream_attach_periodicity: every chunk a push emits from now on also goes into ``ffa`` (a PeriodicitySearch; None
+        detaches), behind an attached search stage."""
+        check(self._lib.bf_dm_stream_attach_periodicity(self._s, ffa._s if ffa is not None else None))
+
     def history(self):
         """bf_dm_stream_history: (oldest_row, next_row, cap_rows) -- rows [oldest_row, next_row) of the series can be cut."""
         a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
@@ -539,6 +544,86 @@ class SinglePulseSearch(_Owner):
         stats = np.ctypeslib.as_array(C.cast(st, C.POINTER(BfSpsStat)), (n_db,)).reshape(self.n_dm, self.n_beams)
         return {"value": peaks["value"].copy(), "t_end": peaks["t_end"].copy(), "sum": stats["sum"].copy(), "sumsq": stats["sumsq"].copy(),
                 "first_t": int(first.value), "n_t": int(n_t.value)}
+
+
+def _ffa_candidate_dtype():
+    import numpy as np
+
+    return np.dtype([("first_row", np.uint64), ("n_rows", np.uint64), ("period_rows", np.float64), ("dm", np.int32), ("beam", np.int32),
+                     ("octave", np.int32), ("p", np.int32), ("shift", np.int32), ("bin", np.int32), ("width", np.int32), ("snr", np.float64),
+                     ("value", np.float32)], align=True)
+
+
+class PeriodicitySearch(_Owner):
+    """bf_ffa: a blind periodicity search (Fast Folding Algorithm) over the chunks [n_dm][n_t][beam] of a DmStream, on the device
+    (include/dsabf.h, docs/PERIODICITY.md): the series of every (trial, beam) decimated by ``tdec``, cut into segments of ``n_seg``
+    samples, folded at every base period p_lo <= p < p_hi of ``n_oct`` octaves, boxcar-filtered at ``n_widths`` widths.  Attach it
+    with ``DmStream.attach_periodicity`` or push chunks yourself."""
+    _ptr_attr, _destroy = "_s", "bf_ffa_destroy"
+
+    def __init__(self, bf: Beamformer, n_dm: int, tdec: int, n_seg: int, n_oct: int, p_lo: int, p_hi: int, n_widths: int, max_t_per_push: int,
+                 dm_first: int = 0, max_in_flight: int = 2, threshold: float = 8.0):
+        self._lib = load()
+        self._s = C.c_void_p()
+        self.n_dm, self.n_beams, self._bf = n_dm, bf.cfg.n_beams, bf
+        self.tdec, self.n_seg, self.n_oct, self.p_lo, self.p_hi, self.n_widths, self.dm_first = tdec, n_seg, n_oct, p_lo, p_hi, n_widths, dm_first
+        check(self._lib.bf_ffa_create(bf._h, n_dm, dm_first, tdec, n_seg, n_oct, p_lo, p_hi, n_widths, max_t_per_push, max_in_flight, threshold,
+                                      C.byref(self._s)))
+
+    @staticmethod
+    def rows_of(length: int, p: int) -> int:
+        """bf_ffa_rows_of: the rows M of the fold of ``length`` samples at base period p (host, no GPU)."""
+        return load().bf_ffa_rows_of(int(length), int(p))
+
+    @staticmethod
+    def select(peaks, stats, tdec: int, n_seg: int, p_lo: int, first_row: int = 0, dm_first: int = 0, threshold: float = 8.0):
+        """bf_ffa_select, the candidate selection as a pure host function (no GPU).  peaks: (value float32, shift, bin)
+        [n_oct][n_p][K][n_dm][n_beams]; stats: (sum, sumsq) [n_dm][n_beams] float64 of the segment.  Returns a numpy structured array."""
+        import numpy as np
+
+        value, shift, bin_ = peaks
+        n_oct, n_p, n_widths, n_dm, n_beams = np.shape(value)
+        pk = np.empty(np.shape(value), np.dtype([("value", np.float32), ("shift", np.uint16), ("bin", np.uint16)]))
+        pk["value"], pk["shift"], pk["bin"] = value, shift, bin_
+        st = np.empty((n_dm, n_beams), np.dtype([("sum", np.float64), ("sumsq", np.float64)]))
+        st["sum"], st["sumsq"] = stats
+        assert pk.dtype.itemsize == C.sizeof(BfFfaPeak) and st.dtype.itemsize == C.sizeof(BfFfaStat)
+        out = np.zeros(n_dm * n_beams, _ffa_candidate_dtype())
+        assert out.dtype.itemsize == C.sizeof(BfFfaCandidate)
+        n_out = C.c_size_t()
+        check(load().bf_ffa_select(_ptr(pk), _ptr(st), tdec, n_seg, n_oct, p_lo, p_lo + n_p, n_widths, n_dm, n_beams, first_row, n_seg * tdec,
+                                   dm_first, threshold, _ptr(out), out.size, C.byref(n_out)))
+        return out[:n_out.value].copy()
+
+    def push(self, d_chunk, n_t: int, first_t: int, stream: int = 0) -> None:
+        check(self._lib.bf_ffa_push(self._s, _ptr(d_chunk), n_t, first_t, C.c_void_p(stream)))
+
+    @property
+    def pending(self) -> int:
+        return self._lib.bf_ffa_pending(self._s)
+
+    def collect(self):
+        """Waits for the oldest uncollected segment and returns its candidates (numpy structured array, one per (trial, beam) at most)."""
+        import numpy as np
+
+        out = np.zeros(self.n_dm * self.n_beams, _ffa_candidate_dtype())
+        n_out = C.c_size_t()
+        check(self._lib.bf_ffa_collect(self._s, _ptr(out), out.size, C.byref(n_out)))
+        return out[:n_out.value].copy()
+
+    def last_records(self) -> dict:
+        """The raw records of the segment just collected (copies): value / shift / bin [n_oct][n_p][K][n_dm][n_beams], sum / sumsq
+        [n_dm][n_beams], first_row, n_rows."""
+        import numpy as np
+
+        pk, st, first, n_rows = C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_uint64()
+        check(self._lib.bf_ffa_last_records(self._s, C.byref(pk), C.byref(st), C.byref(first), C.byref(n_rows)))
+        n_db = self.n_dm * self.n_beams
+        shape = (self.n_oct, self.p_hi - self.p_lo, self.n_widths, self.n_dm, self.n_beams)
+        peaks = np.ctypeslib.as_array(C.cast(pk, C.POINTER(BfFfaPeak)), (int(np.prod(shape)),)).reshape(shape)
+        stats = np.ctypeslib.as_array(C.cast(st, C.POINTER(BfFfaStat)), (n_db,)).reshape(self.n_dm, self.n_beams)
+        return {"value": peaks["value"].copy(), "shift": peaks["shift"].copy(), "bin": peaks["bin"].copy(), "sum": stats["sum"].copy(),
+                "sumsq": stats["sumsq"].copy(), "first_row": int(first.value), "n_rows": int(n_rows.value)}
 
 
 class Conditioner(_Owner):

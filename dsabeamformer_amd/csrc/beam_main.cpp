@@ -155,13 +155,23 @@ int main(int argc, char* argv[])
     int fold_bins = 64, fold_rows = 0;
     std::string fold_path;
     bool fold_extra_given = false, fold_bad = false;
-    enum { kEvents = 1000, kEventTol, kEventVeto, kStamps, kStampShape, kStampFlagged, kFold, kFoldDm, kFoldBins, kFoldRows, kFoldOut };
+    // periodicity search (docs/PERIODICITY.md): --ffa p_lo:p_hi, --ffa-seg n_seg, --ffa-dec tdec, --ffa-oct n, --ffa-widths K, --ffa-snr threshold,
+    // --ffa-out FILE
+    int ffa_p_lo = 0, ffa_p_hi = 0, ffa_seg = 1024, ffa_dec = 1, ffa_oct = 1, ffa_widths = 3;
+    double ffa_snr = 8.0;
+    std::string ffa_path;
+    bool ffa_given = false, ffa_extra_given = false, ffa_bad = false;
+    enum { kEvents = 1000, kEventTol, kEventVeto, kStamps, kStampShape, kStampFlagged, kFold, kFoldDm, kFoldBins, kFoldRows, kFoldOut, kFfa, kFfaSeg, kFfaDec, kFfaOct, kFfaWidths, kFfaSnr, kFfaOut };
     static const option long_options[] = {{"events", required_argument, nullptr, kEvents},       {"event-tol", required_argument, nullptr, kEventTol},
                                           {"event-veto", required_argument, nullptr, kEventVeto}, {"stamps", required_argument, nullptr, kStamps},
                                           {"stamp-shape", required_argument, nullptr, kStampShape}, {"stamp-flagged", no_argument, nullptr, kStampFlagged},
                                           {"fold", required_argument, nullptr, kFold},           {"fold-dm", required_argument, nullptr, kFoldDm},
                                           {"fold-bins", required_argument, nullptr, kFoldBins},   {"fold-rows", required_argument, nullptr, kFoldRows},
                                           {"fold-out", required_argument, nullptr, kFoldOut},
+                                          {"ffa", required_argument, nullptr, kFfa},             {"ffa-seg", required_argument, nullptr, kFfaSeg},
+                                          {"ffa-dec", required_argument, nullptr, kFfaDec},       {"ffa-oct", required_argument, nullptr, kFfaOct},
+                                          {"ffa-widths", required_argument, nullptr, kFfaWidths}, {"ffa-snr", required_argument, nullptr, kFfaSnr},
+                                          {"ffa-out", required_argument, nullptr, kFfaOut},
                                           {nullptr, 0, nullptr, 0}};
     // a non-negative integer that fills its whole field; anything else marks the command line as malformed
     auto number = [&long_bad](const char* text, const char** end, int* out) {
@@ -213,6 +223,44 @@ int main(int argc, char* argv[])
             case kFoldOut:
                 fold_path = optarg;
                 fold_extra_given = true;
+                break;
+            case kFfa: {   // p_lo:p_hi
+                const char* e = nullptr;
+                bool bad = long_bad;
+                long_bad = false;
+                number(optarg, &e, &ffa_p_lo);
+                if (*e == ':')
+                    number(e + 1, &e, &ffa_p_hi);
+                else
+                    ffa_bad = true;
+                if (*e || long_bad) ffa_bad = true;
+                long_bad = bad;
+                ffa_given = true;
+                break;
+            }
+            case kFfaSeg:
+            case kFfaDec:
+            case kFfaOct:
+            case kFfaWidths: {
+                const char* e = nullptr;
+                bool bad = long_bad;
+                long_bad = false;
+                number(optarg, &e, arg == kFfaSeg ? &ffa_seg : arg == kFfaDec ? &ffa_dec : arg == kFfaOct ? &ffa_oct : &ffa_widths);
+                if (*e || long_bad) ffa_bad = true;
+                long_bad = bad;
+                ffa_extra_given = true;
+                break;
+            }
+            case kFfaSnr: {
+                char* e = nullptr;
+                ffa_snr = strtod(optarg, &e);
+                if (e == optarg || *e || !(ffa_snr == ffa_snr)) ffa_bad = true;
+                ffa_extra_given = true;
+                break;
+            }
+            case kFfaOut:
+                ffa_path = optarg;
+                ffa_extra_given = true;
                 break;
             case kEvents: events_path = optarg; break;
             case kStamps: stamps_path = optarg; break;
@@ -366,6 +414,12 @@ int main(int argc, char* argv[])
                              "                         dedispersed at DM pc/cc [0] (the k-th --fold-dm belongs to the k-th --fold; up to 4 --fold), into N [64] phase\n"
                              "                         bins (2 .. 4096); a dump to FILE whenever ROWS [one block's] rows or more have been folded (with -X: FILE.<rank>);\n"
                              "                         --fold without -M, the others without --fold, more than 4 --fold or malformed numbers: a usage error\n"
+                             " --ffa P_LO:P_HI [--ffa-seg N] [--ffa-dec N] [--ffa-oct N] [--ffa-widths K] [--ffa-snr SNR] [--ffa-out FILE]   with -M: a blind\n"
+                             "                         periodicity search (Fast Folding Algorithm) of every DM trial and beam: the chunks decimated by --ffa-dec [1],\n"
+                             "                         cut into segments of --ffa-seg [1024] samples, folded at the base periods P_LO <= p < P_HI (8 .. 512 samples)\n"
+                             "                         of --ffa-oct [1] octaves, boxcar widths 1 .. 2^(K-1) [K = 3]; one line per candidate at S/N >= SNR [8] to FILE\n"
+                             "                         (with -X: FILE.<rank>, trials numbered over the whole ladder); --ffa without -M, the others without --ffa or\n"
+                             "                         malformed numbers: a usage error\n"
                              " -H                      this text\n";
                 return EXIT_SUCCESS;
             default: usage(true, std::cerr); return EXIT_FAILURE;
@@ -391,6 +445,18 @@ int main(int argc, char* argv[])
         (!folds.empty() && (fold_bins < 2 || fold_bins > BF_PSR_MAX_BINS || fold_rows < 0))) {
         fprintf(stderr, "beam: --fold F0[:F1[:PHASE0]] (at most %d), --fold-dm DM >= 0 (one per --fold at most), --fold-bins 2 .. %d, --fold-rows ROWS: "
                         "malformed, too many or out of range\n", BF_PSR_MAX_PULSARS, BF_PSR_MAX_BINS);
+        return EXIT_FAILURE;
+    }
+    if (ffa_given && !(dm_max > 0.0)) {
+        fprintf(stderr, "beam: --ffa (periodicity search) requires the DM stage: give -M dm_max\n");
+        return EXIT_FAILURE;
+    }
+    if (!ffa_given && ffa_extra_given) {
+        fprintf(stderr, "beam: --ffa-seg / --ffa-dec / --ffa-oct / --ffa-widths / --ffa-snr / --ffa-out belong to the periodicity search: give --ffa P_LO:P_HI\n");
+        return EXIT_FAILURE;
+    }
+    if (ffa_bad) {
+        fprintf(stderr, "beam: --ffa P_LO:P_HI, --ffa-seg N, --ffa-dec N, --ffa-oct N, --ffa-widths N, --ffa-snr SNR: malformed number\n");
         return EXIT_FAILURE;
     }
     if (long_bad) {
@@ -949,6 +1015,25 @@ int main(int argc, char* argv[])
             std::cout << "Pulsar folder: " << n_psr << " pulsars, " << fold_bins << " bins, a dump every " << oopt.psr_dump_rows << " rows of " << tsamp_ms
                       << " ms" << std::endl;
         }
+        std::unique_ptr<ffa_file_sink> ffa_out;
+        if (ffa_given && my_trials > 0 && (!comm || rank == 0 || oopt.dm_split_trials)) {   // --ffa: the search runs where the DM stage runs
+            oopt.ffa_p_lo = ffa_p_lo;
+            oopt.ffa_p_hi = ffa_p_hi;
+            oopt.ffa_seg = ffa_seg;
+            oopt.ffa_dec = ffa_dec;
+            oopt.ffa_oct = ffa_oct;
+            oopt.ffa_widths = ffa_widths;
+            oopt.ffa_threshold = ffa_snr;
+            if (!ffa_path.empty()) {
+                if (oopt.dm_split_trials) ffa_path += "." + std::to_string(rank);   // one file per shard; the trials are numbered over the whole ladder
+                ffa_out.reset(new ffa_file_sink(ffa_path.c_str(), ffa_dec, ffa_seg, ffa_oct, ffa_p_lo, ffa_p_hi, ffa_widths, ffa_snr));
+                if (!ffa_out->is_open()) {
+                    fprintf(stderr, "beam: could not open %s\n", ffa_path.c_str());
+                    return EXIT_FAILURE;
+                }
+                oopt.ffa_sink = ffa_out.get();
+            }
+        }
         std::unique_ptr<vis_file_sink> vsink;
         if (!vis_path.empty()) {   // -V: every shard correlates its own channels
             if (comm) vis_path += "." + std::to_string(rank);
@@ -989,6 +1074,7 @@ int main(int argc, char* argv[])
         if (sink) std::cout << "Wrote " << sink->get_delivered() << " gemm-units of detected powers to " << sink_name << std::endl;
         if (dm_sink) std::cout << "Wrote " << dm_sink->get_times_written() << " dedispersed samples x " << my_trials << " trials to " << dm_path << std::endl;
         if (cand_sink) std::cout << "Wrote " << cand_sink->get_candidates_written() << " candidates to " << cand_path << std::endl;
+        if (ffa_out) std::cout << "Wrote " << ffa_out->get_candidates_written() << " periodicity candidates to " << ffa_path << std::endl;
         if (esink) std::cout << "Wrote " << esink->get_events_written() << " events to " << events_path << std::endl;
         if (tsink) std::cout << "Wrote " << tsink->get_stamps_written() << " stamps to " << stamps_path << std::endl;
         if (vsink) std::cout << "Wrote " << vsink->get_dumps_written() << " visibility dumps of " << corr_blocks << " blocks to " << vis_path << std::endl;

@@ -51,6 +51,7 @@ struct bf_dm_stream : bf_stage {
     bf_sps* search = nullptr;     // bf_dm_stream_attach_search: every chunk is also pushed into this stage, before `done` is recorded
     bf_cond* cond = nullptr;      // bf_dm_stream_attach_conditioner: every push's new rows are conditioned in place, before `rows_ready` is recorded
     bf_psr* fold = nullptr;       // bf_dm_stream_attach_folder: every push's new rows are also folded where they lie, before `done` is recorded
+    bf_ffa* ffa = nullptr;        // bf_dm_stream_attach_periodicity: every chunk is also pushed into this stage, before `done` is recorded
     // bf_dm_stream_cut (docs/EVENTS.md section 2): the end of the most recent cut, recorded behind the cut before it.  The producer of
     // the rows of a later push waits for it wherever it waits for done[old]: it cannot overwrite what a cut queued before it reads.
     hipEvent_t cut_done = nullptr;
@@ -61,7 +62,7 @@ struct bf_dm_stream : bf_stage {
     std::vector<int32_t> trial_delay;   // [n_dm]: max over f of delay[dm][f] -- the rows a stamp of that trial needs beyond its times
 };
 
-// One link to an attached stage: the member of the DM stage (search, cond, fold) and that stage's feeder, set and cleared together.
+// One link to an attached stage: the member of the DM stage (search, cond, fold, ffa) and that stage's feeder, set and cleared together.
 template <class T>
 static void set_link(bf_dm_stream* dm, T*& member, T* to)
 {
@@ -77,6 +78,7 @@ void dsabf::rt::dm_stream_drop(bf_dm_stream* dm, bf_stage* attached)
     if (dm->search && as_stage(dm->search) == attached) set_link<bf_sps>(dm, dm->search, nullptr);
     if (dm->cond && as_stage(dm->cond) == attached) set_link<bf_cond>(dm, dm->cond, nullptr);
     if (dm->fold && as_stage(dm->fold) == attached) set_link<bf_psr>(dm, dm->fold, nullptr);
+    if (dm->ffa && as_stage(dm->ffa) == attached) set_link<bf_ffa>(dm, dm->ffa, nullptr);
 }
 
 // The ring is no hipMalloc: it is unmapped and released here, behind the wait for everything in flight, and the stage's resource
@@ -86,6 +88,7 @@ void bf_dm_stream::release_device()
     set_link<bf_sps>(this, search, nullptr);
     set_link<bf_cond>(this, cond, nullptr);
     set_link<bf_psr>(this, fold, nullptr);
+    set_link<bf_ffa>(this, ffa, nullptr);
     res.wait();
     if (mapped0) (void)hipMemUnmap(d_buf, phys_bytes);
     if (mapped1) (void)hipMemUnmap(reinterpret_cast<char*>(d_buf) + phys_bytes, phys_bytes);
@@ -312,6 +315,17 @@ int bf_dm_stream_attach_folder(bf_dm_stream* dm, bf_psr* p)
     return BF_OK;
 }
 
+int bf_dm_stream_attach_periodicity(bf_dm_stream* dm, bf_ffa* f)
+{
+    if (!dm) return fail(BF_ERR_INVALID, "NULL argument");
+    if (int rc = orphaned(dm)) return rc;
+    if (f == dm->ffa) return BF_OK;
+    if (f)
+        if (int rc = ffa_check_attach(f, dm->h, dm->n_dm, dm->max_rows)) return rc;
+    set_link(dm, dm->ffa, f);
+    return BF_OK;
+}
+
 int bf_dm_stream_output_device(bf_dm_stream* s, float** d_out)
 {
     if (!s || !d_out) return fail(BF_ERR_INVALID, "NULL argument");
@@ -389,6 +403,14 @@ int bf_dm_stream_push(bf_dm_stream* s, const float* d_rows, int n_rows, float* h
     // an attached folder refuses what it would refuse of these rows (its oscillator's range) HERE too
     if (s->fold)
         if (int rc = psr_check_push(s->fold, n_rows)) return rc;
+    // an attached periodicity stage takes the chunk this push emits: what it would refuse of it (no free result set for the
+    // segments the chunk completes) is refused HERE too
+    if (s->ffa) {
+        const uint64_t D = (uint64_t)s->max_delay, after = s->pushed + (uint64_t)n_rows;
+        const uint64_t emits = (after > D ? after - D : 0) - (s->pushed > D ? s->pushed - D : 0);   // the chunk's times: n_out below
+        if (emits)
+            if (int rc = ffa_check_push(s->ffa, (int)emits)) return rc;
+    }
     bf_handle* h = s->h;
     ON_DEVICE(h);
     hipStream_t q = as_stream(hip_stream);
@@ -447,6 +469,9 @@ int bf_dm_stream_push(bf_dm_stream* s, const float* d_rows, int n_rows, float* h
         // the search reads the chunk where it lies, on this queue and BEFORE `done` below: only that event keeps push j + 3 out of set j % 3
         if (s->search)
             if (int rc = bf_sps_push(s->search, s->d_out[set], n_out, emitted, q)) return rc;
+        // ... and so does the periodicity search (docs/PERIODICITY.md section 3), behind the search stage's kernels on this queue
+        if (s->ffa)
+            if (int rc = bf_ffa_push(s->ffa, s->d_out[set], n_out, emitted, q)) return rc;
     }
     // The folder's hook (docs/PULSAR_FOLDING.md section 2): the new rows are read where they lie, on this queue -- behind the copy-in and
     // the conditioner, so it folds what the dedispersion reads; behind rows_ready and the chunk, so neither the push after this one

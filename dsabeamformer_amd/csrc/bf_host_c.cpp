@@ -763,4 +763,27 @@ int bfh_psr_sink_destroy(bfh_psr_sink* s)
     return BF_OK;
 }
 
+struct bfh_ffa_sink {
+    ffa_file_sink s;
+};
+int bfh_ffa_sink_create(const char* path, int tdec, int n_seg, int n_oct, int p_lo, int p_hi, int n_widths, double threshold, bfh_ffa_sink** out)
+{
+    if (!path || !out) return BF_ERR_INVALID;
+    *out = nullptr;
+    std::unique_ptr<bfh_ffa_sink> s(new bfh_ffa_sink{ffa_file_sink(path, tdec, n_seg, n_oct, p_lo, p_hi, n_widths, threshold)});
+    if (!s->s.is_open()) return BF_ERR_INVALID;
+    *out = s.release();
+    return BF_OK;
+}
+int bfh_ffa_sink_deliver(bfh_ffa_sink* s, const bf_ffa_candidate* cands, size_t n)
+{
+    if (!s || (!cands && n)) return BF_ERR_INVALID;
+    return s->s.deliver(cands, n) ? BF_OK : BF_ERR_STATE;
+}
+int bfh_ffa_sink_destroy(bfh_ffa_sink* s)
+{
+    delete s;
+    return BF_OK;
+}
+
 }  // extern "C"

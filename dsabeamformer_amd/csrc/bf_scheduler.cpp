@@ -205,6 +205,7 @@ struct run_resources {
     bf_sps* sps = nullptr;
     bf_cond* cond = nullptr;
     bf_psr* psr = nullptr;
+    bf_ffa* ffa = nullptr;
     bf_corr* corr = nullptr;
     bf_sk* sk = nullptr;
     bf_stokes* stokes = nullptr;
@@ -220,6 +221,7 @@ struct run_resources {
         bf_evt_destroy(evt);
         bf_cond_destroy(cond);
         bf_psr_destroy(psr);
+        bf_ffa_destroy(ffa);
         bf_dm_stream_destroy(dm);
         for (void* p : pinned) bf_free_pinned(p);
         bf_destroy(h);
@@ -523,6 +525,9 @@ int check_options(const bf_config& cfg, const observation_options& opt)
     if (opt.n_psr && (opt.psr_bins < 2 || opt.psr_bins > BF_PSR_MAX_BINS || opt.psr_dump_rows < 1))
         return set_error(BF_ERR_INVALID, "run_observation: the pulsar folder needs psr_bins in 2 .. 4096 and psr_dump_rows >= 1");
     if (!opt.n_psr && opt.psr_sink) return set_error(BF_ERR_INVALID, "run_observation: a psr_sink needs n_psr > 0");
+    if (opt.ffa_p_hi < 0) return set_error(BF_ERR_INVALID, "run_observation: ffa_p_hi must be 0 (off) or the end of the period range");
+    if (opt.ffa_p_hi && !opt.dm_delays) return set_error(BF_ERR_INVALID, "run_observation: the periodicity search needs the DM stage (dm_delays)");
+    if (!opt.ffa_p_hi && opt.ffa_sink) return set_error(BF_ERR_INVALID, "run_observation: an ffa_sink needs ffa_p_hi > 0");
     if (opt.sk_blocks < 0) return set_error(BF_ERR_INVALID, "run_observation: sk_blocks must be 0 (off) or the blocks per dump");
     if (opt.sk_sink && !opt.sk_blocks) return set_error(BF_ERR_INVALID, "run_observation: a sk_sink needs sk_blocks > 0");
     if (opt.sk_blocks && !opt.block_launch) return set_error(BF_ERR_INVALID, "run_observation: the voltage moments need block-granular launches");
@@ -650,6 +655,8 @@ struct production_run {
     uint64_t events = 0, stamps = 0, stamps_dropped = 0, stamps_missed = 0, stamps_beyond_end = 0;
     uint64_t psr_rows_folded = 0, psr_dumps = 0;   // the pulsar folder: rows folded since the last dump; dumps delivered
     std::deque<uint64_t> psr_pending;              // the block behind whose last launch each uncollected dump was issued
+    uint64_t ffa_times = 0, ffa_segments = 0, ffa_candidates = 0;   // the periodicity search: output times of the delivered chunks; segments collected
+    std::vector<bf_ffa_candidate> ffa_cands;
     std::vector<double> psr_prof;
     std::vector<uint64_t> psr_hits;
     float* cond_mask_host = nullptr;      // pinned, whole dwords: where the conditioner's mask of the last push is read back at the end
@@ -742,6 +749,17 @@ struct production_run {
                 if (rc != BF_OK) return gpu_error(log, rc);
                 psr_prof.resize(bf_psr_entries(opt.n_psr, plan.n_freq_band, opt.psr_bins, cfg.n_beams));
                 psr_hits.resize(psr_prof.size() / (size_t)cfg.n_beams);
+            }
+            if (opt.ffa_p_hi > 0) {   // the periodicity search (docs/PERIODICITY.md)
+                // a result set for every segment the chunks in flight can complete: at most n_buf chunks of dm_rows times are pushed
+                // and not yet delivered, and X times behind a segment in progress complete at most X / seg_rows + 1 segments
+                const uint64_t seg_rows = (uint64_t)std::max(opt.ffa_seg, 1) * (uint64_t)std::max(opt.ffa_dec, 1);
+                const int in_flight = (int)((uint64_t)n_buf * (uint64_t)plan.dm_rows / seg_rows + 1);
+                rc = bf_ffa_create(dev.h, plan.dm_count, plan.dm_first, opt.ffa_dec, opt.ffa_seg, opt.ffa_oct, opt.ffa_p_lo, opt.ffa_p_hi, opt.ffa_widths,
+                                   plan.dm_rows, in_flight, opt.ffa_threshold, &dev.ffa);
+                if (rc == BF_OK) rc = bf_dm_stream_attach_periodicity(dev.dm, dev.ffa);
+                if (rc != BF_OK) return gpu_error(log, rc);
+                ffa_cands.resize((size_t)plan.dm_count * cfg.n_beams);
             }
             if (opt.sps_widths > 0) {   // the search stage: as many result sets as chunk buffers (a chunk in flight = a search push in flight)
                 rc = bf_sps_create(dev.h, plan.dm_count, plan.dm_first, opt.sps_widths, plan.dm_rows, (int)n_buf, /*baseline_pushes=*/8,
@@ -1023,6 +1041,21 @@ struct production_run {
                     if (int rc_t = take_events(n_ev)) return rc_t;
                 }
             }
+            if (dev.ffa) {   // the segments this chunk completed: their kernels ran behind the chunk's on its queue; the collect waits for their records
+                ffa_times += (uint64_t)c.n_t;
+                const uint64_t seg_rows = (uint64_t)opt.ffa_seg * (uint64_t)opt.ffa_dec;
+                while (ffa_segments < ffa_times / seg_rows) {
+                    size_t n = 0;
+                    const int rc = bf_ffa_collect(dev.ffa, ffa_cands.data(), ffa_cands.size(), &n);
+                    if (rc != BF_OK) return gpu_error(log, rc);
+                    ffa_segments++;
+                    ffa_candidates += n;
+                    if (opt.ffa_sink && !opt.ffa_sink->deliver(ffa_cands.data(), n)) {
+                        log << "ERROR: periodicity sink failed at segment " << ffa_segments - 1 << std::endl;
+                        return BF_ERR_STATE;
+                    }
+                }
+            }
             if (!opt.dm_sink) continue;
             dm_chunks++;
             if (!opt.dm_sink->deliver(c.first_t, c.n_t, plan.dm_count, cfg.n_beams, c.host)) {
@@ -1140,6 +1173,7 @@ int run_observation(const bf_config& cfg, const observation_options& opt, block_
     if (opt.sk_sink) opt.sk_sink->close();
     if (opt.stokes_sink) opt.stokes_sink->close();
     if (opt.psr_sink) opt.psr_sink->close();
+    if (opt.ffa_sink) opt.ffa_sink->close();
     const uint64_t chunks = obs_state.get_current_transfer_gemm() * cfg.n_out_per_gemm;  // :552
     const double rate = (double)source.get_block_size() * obs_state.get_blocks_transfer_queue() / ms / 1e6;  // :554
     closing_report(log, ms, chunks, ms / (chunks ? chunks : 1), rate, run.plan.block_launch ? "bf_enqueue_block" : kUnitLaunchPattern);
@@ -1162,6 +1196,8 @@ int run_observation(const bf_config& cfg, const observation_options& opt, block_
         res->sk_dumps = run.sk.dumps;
         res->stokes_units = run.stokes_units;
         res->psr_dumps = run.psr_dumps;
+        res->ffa_segments = run.ffa_segments;
+        res->ffa_candidates = run.ffa_candidates;
         res->cond_masked = run.cond_masked_channels();
     }
     if (run.plan.dm_run)
@@ -1187,6 +1223,10 @@ int run_observation(const bf_config& cfg, const observation_options& opt, block_
     if (run.dev.psr)
         log << "Pulsar folder: " << opt.n_psr << " pulsars, " << opt.psr_bins << " bins, " << run.psr_dumps << " dumps of at least " << opt.psr_dump_rows
             << " rows each (an incomplete integration at the end is dropped)" << std::endl;
+    if (run.dev.ffa)
+        log << "Periodicity search: periods " << opt.ffa_p_lo << " .. " << opt.ffa_p_hi - 1 << " samples x " << opt.ffa_oct << " octaves at decimation "
+            << opt.ffa_dec << ", " << run.ffa_segments << " segments of " << opt.ffa_seg << " samples, " << run.ffa_candidates << " candidates at S/N >= "
+            << opt.ffa_threshold << " (an incomplete segment at the end is dropped)" << std::endl;
     if (run.dev.sps)
         log << "Single-pulse search: boxcar widths 1 .. " << (1 << (opt.sps_widths - 1)) << ", " << run.sps_candidates << " candidates at S/N >= "
             << opt.sps_threshold << std::endl;

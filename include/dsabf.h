@@ -770,6 +770,81 @@ int bf_psr_beam_snr(const double *profile_k, const uint64_t *hits_k, int n_freq_
                     const uint8_t *chan_mask, double *snr, int32_t *peak_bin);
 int bf_dm_stream_attach_folder(bf_dm_stream *dm, bf_psr *p);
 
+/* ---- Periodicity search: the Fast Folding Algorithm behind the DM trials (docs/PERIODICITY.md) ------------------------------
+ * The reference has no search of any kind (its output is the detected stream and a DM-0 collapse, src/beamformer.cu:498-510).
+ * A bf_ffa consumes the chunks x[n_dm][n_t][n_beams] (fp32, contiguous, 16-byte aligned, n_beams = the handle's, n_beams % 4 == 0)
+ * that bf_dm_stream_push emits, and finds periodic signals nobody predicted; docs/PERIODICITY.md section 1 is the contract, to the bit:
+ *   decimation: y[u] = ((x[u tdec] + x[u tdec + 1]) + ...) + x[u tdec + tdec - 1], fp32, ascending time, the first term as it is;
+ *     a push that ends inside a group carries the running value and the count over.  tdec 1 .. BF_FFA_MAX_DEC.
+ *   segments: consecutive n_seg decimated samples, no overlap; n_seg <= BF_FFA_MAX_SEG.
+ *   octaves o < n_oct (1 .. BF_FFA_MAX_OCT): y_0 = y, y_{o+1}[u] = y_o[2u] + y_o[2u + 1], L_o = n_seg >> o; n_seg % 2^(n_oct-1) == 0.
+ *   fold, per octave and base period p_lo <= p < p_hi (BF_FFA_MIN_PERIOD <= p_lo < p_hi <= BF_FFA_MAX_PERIOD, samples of the
+ *     octave): M = bf_ffa_rows_of(L_o, p) = the largest power of two <= L_o / p, M >= 2 required for every (o, p); the first M p
+ *     samples are M rows of p bins, each a group of one row; a merge of two adjacent groups A (earlier), B (later) of g rows:
+ *       out[i][j] = A[i >> 1][j] + B[i >> 1][(j + ((i + 1) >> 1)) mod p],   i < 2g,   fp32, A's term the left operand,
+ *     log2 M times.  Row i of the last group is the profile at period p + i / (M - 1) samples.
+ *   circular boxcars per profile P_i, widths 2^k, k < n_widths (1 .. BF_FFA_MAX_WIDTHS, 2^(n_widths-1) <= p_lo / 2):
+ *     C_0 = P_i,  C_k[j] = C_{k-1}[j] + C_{k-1}[(j + 2^(k-1)) mod p].
+ *   per segment and (o, p, k, trial, beam) one bf_ffa_peak: the maximum of C_k over (i, j), the smallest i attaining it, the
+ *     smallest j at that i -- layout [n_oct][p_hi - p_lo][n_widths][n_dm][n_beams];
+ *   per segment and (trial, beam) one bf_ffa_stat: fp64 sum and sum of squares of the n_seg samples of y_0 (order free).
+ *   Nothing depends on how the series is cut into pushes, on queues or on launch shapes.
+ * bf_ffa_entries: peak records of a segment, n_oct (p_hi - p_lo) n_widths n_dm n_beams (statistics: n_dm n_beams); 0 out of range.
+ * bf_ffa_push is asynchronous on hip_stream; first_t is the row of the chunk's first time (bf_dm_stream_push's *first_t).  Pushes
+ *   of one stage are ordered by the stage itself, whichever queues they come on.  A push may complete none, one or several
+ *   segments; each is searched in order on the push's queue, its records go to result set segment % max_in_flight and are copied
+ *   to pinned memory on a queue of the stage's own.  A push whose completed segments would not all find a free set -- uncollected
+ *   segments + the push's > max_in_flight -- is refused with BF_ERR_STATE before anything is queued.
+ * bf_ffa_collect waits for the OLDEST uncollected segment and selects its candidates (bf_ffa_select); max_out >= n_dm * n_beams
+ *   (BF_ERR_INVALID, nothing consumed); nothing pending: BF_ERR_STATE.  bf_ffa_pending: segments searched and not yet collected.
+ * bf_ffa_last_records: host pointers to the records of the segment last collected, valid until the next collect or destroy.
+ * bf_ffa_select (host, fp64, no GPU, no contraction), per (trial, beam): mu = sum / n_seg, sigma = sqrt(max(sumsq / n_seg - mu mu, 0)),
+ *   skipped at sigma == 0; per record w = 2^k, snr = (value - (w M) (2^o mu)) / ((sigma sqrt(2^o)) sqrt(w M)); at most one
+ *   candidate: the largest snr (ties: lowest o, then p, then k), if >= threshold; period_rows = tdec 2^o (p + shift / (M - 1)) in
+ *   input samples; candidates leave in (trial, beam) order.
+ * BF_ERR_INVALID, with nothing launched: any bound above, NULL pointers, a misaligned chunk, n_t outside 1 .. max_t_per_push,
+ *   n_beams % 4 != 0, n_dm outside 1 .. 65535, max_in_flight < 1, a NaN threshold.  Lifetime as for a bf_sps.
+ * bf_dm_stream_attach_periodicity(dm, s) (s == NULL detaches): from then on every bf_dm_stream_push that emits a chunk also pushes
+ *   it into s, behind the dedispersion kernels (and an attached search stage) and before the push's `done` event; a push the
+ *   stage would refuse is refused by bf_dm_stream_push before it queues anything.  Same handle, same n_dm, max_t_per_push >= the
+ *   DM stage's max_rows_per_push. */
+#define BF_FFA_MAX_DEC 256
+#define BF_FFA_MAX_SEG 16384
+#define BF_FFA_MAX_OCT 6
+#define BF_FFA_MAX_WIDTHS 6
+#define BF_FFA_MIN_PERIOD 8
+#define BF_FFA_MAX_PERIOD 512
+typedef struct bf_ffa bf_ffa;
+typedef struct bf_ffa_peak {
+    float value;
+    uint16_t shift; /* the row i of the last group: period p + i / (M - 1) */
+    uint16_t bin;   /* the first bin j of the boxcar */
+} bf_ffa_peak;
+typedef struct bf_ffa_stat {
+    double sum, sumsq;
+} bf_ffa_stat;
+typedef struct bf_ffa_candidate {
+    uint64_t first_row, n_rows; /* the segment, in input samples (rows of the detected stream) */
+    double period_rows;
+    int32_t dm, beam, octave, p, shift, bin, width;
+    double snr;
+    float value;
+} bf_ffa_candidate;
+size_t bf_ffa_entries(int n_oct, int p_lo, int p_hi, int n_widths, int n_dm, int n_beams);
+int bf_ffa_rows_of(int len, int p);
+int bf_ffa_create(bf_handle *h, int n_dm, int dm_first, int tdec, int n_seg, int n_oct, int p_lo, int p_hi, int n_widths,
+                  int max_t_per_push, int max_in_flight, double threshold, bf_ffa **out);
+int bf_ffa_destroy(bf_ffa *s);
+int bf_ffa_push(bf_ffa *s, const float *d_chunk, int n_t, uint64_t first_t, void *hip_stream);
+int bf_ffa_collect(bf_ffa *s, bf_ffa_candidate *out, size_t max_out, size_t *n_out);
+int bf_ffa_pending(const bf_ffa *s);
+int bf_ffa_last_records(const bf_ffa *s, const bf_ffa_peak **peaks, const bf_ffa_stat **stats, uint64_t *first_row,
+                        uint64_t *n_rows);
+int bf_ffa_select(const bf_ffa_peak *peaks, const bf_ffa_stat *stats, int tdec, int n_seg, int n_oct, int p_lo, int p_hi,
+                  int n_widths, int n_dm, int n_beams, uint64_t first_row, uint64_t n_rows, int dm_first, double threshold,
+                  bf_ffa_candidate *out, size_t max_out, size_t *n_out);
+int bf_dm_stream_attach_periodicity(bf_dm_stream *dm, bf_ffa *s);
+
 /* ---- Multi-GPU: frequency shards and the gather of their detected powers -------------------------------
  * The reference runs 8 independent processes, one sub-band per GPU (`-g`, src/beamformer.cu:92-100,233; README.md:168)
  * and never brings their outputs together.  Here a handle may own any contiguous range of frequencies (bf_config.n_freq

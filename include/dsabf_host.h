@@ -185,6 +185,14 @@ int bfh_psr_sink_create(const char *path, int n_psr, int n_freq, int n_bins, int
 int bfh_psr_sink_deliver(bfh_psr_sink *s, uint64_t first_row, uint64_t n_rows, const uint64_t *hits, const double *profile);
 int bfh_psr_sink_destroy(bfh_psr_sink *s);
 
+/* The periodicity candidates' file sink on its own (docs/PERIODICITY.md section 6; tests and host consumers, no device):
+ * dsabf::ffa_file_sink writes the two `#` header lines and one text line per candidate. */
+typedef struct bfh_ffa_sink bfh_ffa_sink;
+int bfh_ffa_sink_create(const char *path, int tdec, int n_seg, int n_oct, int p_lo, int p_hi, int n_widths, double threshold,
+                        bfh_ffa_sink **out);
+int bfh_ffa_sink_deliver(bfh_ffa_sink *s, const bf_ffa_candidate *cands, size_t n);
+int bfh_ffa_sink_destroy(bfh_ffa_sink *s);
+
 /* DM trial ladder and per-channel sample delays (sandbox/Dispersion Theory.ipynb cells 1-2 and 5; dsabf::dm_trials,
  * dsabf::dm_delays).  bfh_dm_trials returns the number of trials written (<= cap). */
 int bfh_dm_trials(double dm0, double dm_max, int nchan, double epsilon, double nu_ghz, double chan_bw_mhz, double ti_us,

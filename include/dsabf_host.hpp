@@ -727,6 +727,53 @@ public:
     uint64_t get_dumps_written() const { return written; }
 };
 
+// ---- Periodicity search behind the DM stage (include/dsabf.h: bf_ffa_*, bf_dm_stream_attach_periodicity; docs/PERIODICITY.md) ----
+// With observation_options::ffa_p_hi > 0 run_observation creates a bf_ffa next to the DM stage, attaches it (every chunk is decimated
+// into the stage's series on the queue that produced it; a chunk that completes a segment also searches it) and hands the
+// candidates of every segment to an ffa_sink, in segment order, once the block whose chunk completed the segment has been analysed.
+struct ffa_sink {
+    virtual ~ffa_sink() {}
+    virtual bool deliver(const bf_ffa_candidate* cands, size_t n) = 0;
+    virtual void close() {}
+};
+
+// Text file (docs/PERIODICITY.md section 6): `#` header lines (the search's parameters as key=value words, then the column names),
+// then one line per candidate: first_row n_rows period_rows dm beam octave p shift bin width snr value (dm: the global trial index;
+// period_rows and snr with 17 significant digits, value with 9: they read back to the same bits).
+class ffa_file_sink : public ffa_sink {
+    FILE* fp = nullptr;
+    uint64_t written = 0;
+
+public:
+    ffa_file_sink(const char* path, int tdec, int n_seg, int n_oct, int p_lo, int p_hi, int n_widths, double threshold) : fp(fopen(path, "w"))
+    {
+        if (fp)
+            fprintf(fp, "# periodicity tdec=%d n_seg=%d n_oct=%d p_lo=%d p_hi=%d n_widths=%d threshold=%.17g\n"
+                        "# first_row n_rows period_rows dm beam octave p shift bin width snr value\n",
+                    tdec, n_seg, n_oct, p_lo, p_hi, n_widths, threshold);
+    }
+    ~ffa_file_sink() override { close(); }
+    ffa_file_sink(const ffa_file_sink&) = delete;
+    ffa_file_sink& operator=(const ffa_file_sink&) = delete;
+    bool is_open() const { return fp != nullptr; }
+    bool deliver(const bf_ffa_candidate* c, size_t n) override
+    {
+        if (!fp) return false;
+        for (size_t i = 0; i < n; i++)
+            if (fprintf(fp, "%llu %llu %.17g %d %d %d %d %d %d %d %.17g %.9g\n", (unsigned long long)c[i].first_row, (unsigned long long)c[i].n_rows,
+                        c[i].period_rows, c[i].dm, c[i].beam, c[i].octave, c[i].p, c[i].shift, c[i].bin, c[i].width, c[i].snr, (double)c[i].value) < 0)
+                return false;
+        written += n;
+        return true;
+    }
+    void close() override
+    {
+        if (fp) fclose(fp);
+        fp = nullptr;
+    }
+    uint64_t get_candidates_written() const { return written; }
+};
+
 // ---- What the int64 record files of the three stages below share (vis_file_sink, sk_file_sink, stokes_file_sink) ---------------
 // The 4096-byte ASCII header (`KEY value` lines, NUL padded), then one record per delivery: two uint64, the entries (little-endian
 // int64).  A sink supplies the header's CONTENT and LAYOUT and, if it has any, lines of its own (`extra`, in front of the GPU line).
@@ -1056,6 +1103,15 @@ struct observation_options {
     int psr_bins = 64;
     int psr_dump_rows = 0;
     dsabf::psr_sink* psr_sink = nullptr;
+    // Periodicity search behind the DM stage (docs/PERIODICITY.md; needs dm_delays): ffa_p_hi > 0 switches it on.  The chunks of this
+    // rank's trials are decimated by ffa_dec and cut into segments of ffa_seg samples; every segment is folded at the base periods
+    // ffa_p_lo <= p < ffa_p_hi of ffa_oct octaves with ffa_widths boxcar widths (the bounds of bf_ffa_create).  The stage is created
+    // next to the DM stage with dm_first from the plan and attached; every segment's candidates at or above ffa_threshold go to
+    // ffa_sink (may be NULL: the stage still runs).  A segment that is incomplete when the run ends is dropped.
+    int ffa_p_lo = 0, ffa_p_hi = 0;
+    int ffa_seg = 1024, ffa_dec = 1, ffa_oct = 1, ffa_widths = 3;
+    double ffa_threshold = 8.0;
+    dsabf::ffa_sink* ffa_sink = nullptr;
     // The incoherent beam (docs/INCOHERENT_BEAM.md): beam column `incoherent_beam` of the detected stream carries the antenna powers
     // summed over the antennas instead of a tied beam (bf_set_incoherent_beam, set on the handle before the loop); -1 = off.  On a
     // sharded run every rank gives the same index: the sum is per channel, each shard fills its own slice of the column.
@@ -1101,6 +1157,8 @@ struct observation_result {
     uint64_t sk_dumps = 0;          // integrations the moments stage dumped (sk_blocks > 0)
     uint64_t stokes_units = 0;      // gemm-units the Stokes stage delivered (stokes_beams non-empty)
     uint64_t psr_dumps = 0;         // integrations the pulsar folder dumped (n_psr > 0)
+    uint64_t ffa_segments = 0;      // segments the periodicity search collected (ffa_p_hi > 0)
+    uint64_t ffa_candidates = 0;    // ... and the candidates they gave
     int cond_masked = -1;           // channels the conditioner masked in the last push (cond_baseline > 0 and a block analysed), else -1
 };
 // The reference's production main() loop on top of the C-ABI.  pos/dir: antenna positions and beam directions.
