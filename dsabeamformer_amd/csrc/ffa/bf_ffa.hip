@@ -171,7 +171,7 @@ __global__ __launch_bounds__(kThreads) void ffa_search_kernel(const float* __res
 #pragma unroll
         for (int k = 0; k < K; k++) {
             bv[k] = -INFINITY;
-            bi[k] = 0x7fffffff;
+            bi[k] = 0;   // a column of NaN alone never passes peak_take: its record stays at cell (0, 0), inside M x p
         }
         if (K == 1) {
             const float* src = work + cur * cap;

@@ -786,7 +786,8 @@ int bf_dm_stream_attach_folder(bf_dm_stream *dm, bf_psr *p);
  *   circular boxcars per profile P_i, widths 2^k, k < n_widths (1 .. BF_FFA_MAX_WIDTHS, 2^(n_widths-1) <= p_lo / 2):
  *     C_0 = P_i,  C_k[j] = C_{k-1}[j] + C_{k-1}[(j + 2^(k-1)) mod p].
  *   per segment and (o, p, k, trial, beam) one bf_ffa_peak: the maximum of C_k over (i, j), the smallest i attaining it, the
- *     smallest j at that i -- layout [n_oct][p_hi - p_lo][n_widths][n_dm][n_beams];
+ *     smallest j at that i -- layout [n_oct][p_hi - p_lo][n_widths][n_dm][n_beams].  A (trial, beam) column with no finite sample in
+ *     the segment: value unspecified, shift < M and bin < p all the same, never a candidate; no other column changes;
  *   per segment and (trial, beam) one bf_ffa_stat: fp64 sum and sum of squares of the n_seg samples of y_0 (order free).
  *   Nothing depends on how the series is cut into pushes, on queues or on launch shapes.
  * bf_ffa_entries: peak records of a segment, n_oct (p_hi - p_lo) n_widths n_dm n_beams (statistics: n_dm n_beams); 0 out of range.

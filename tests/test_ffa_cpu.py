@@ -13,7 +13,7 @@ from conftest import ROOT
 
 sys.path.insert(0, os.path.join(ROOT, "tests", "support"))
 import ffa_oracle  # noqa: E402
-from ffa_stage import PARITY_CASES, case_input  # noqa: E402
+from ffa_stage import EDGE_CASES, PARITY_CASES, case_cfg, case_input, case_lds_bytes, case_max_rows  # noqa: E402
 
 BF_ERR_INVALID = -1
 
@@ -92,6 +92,51 @@ def test_every_parity_input_tells_a_left_fold_from_the_contract():
         assert ffa_oracle.association_matters(case_input(name), tdec, n_seg, n_oct, p_lo, p_hi, K), name
     x = ffa_oracle.parity_input(5, 2, 3 * 64, 64)                      # test_back_pressure_and_collect_order
     assert ffa_oracle.association_matters(x, 1, 64, 1, 8, 13, 2)
+
+
+def test_every_edge_input_tells_a_left_fold_from_the_contract():
+    """The inputs of tests/test_gpu_ffa_shapes.py, timed_geometry included.  max_seg is exempt: at M = 2048 fold_left's index table
+    is 2048 x 8 x 2048 int64, 268 MB; that case is there for its addressing (LDS size, rows, octaves), not for the association, which
+    max_seg_p511 covers at the same n_seg with M = 32."""
+    asked = [name for name in sorted(EDGE_CASES) if case_max_rows(name) <= 512]
+    assert sorted(set(EDGE_CASES) - set(asked)) == ["max_seg"]
+    for name in asked:
+        assert ffa_oracle.association_matters(case_input(name), *case_cfg(name)), name
+
+
+def test_the_long_decimation_groups_depend_on_the_order_of_their_adds():
+    """tdec 200 and 256: the same groups added in descending time give other bits in most decimated samples, so a kernel that
+    added a group in another order -- the carried part last, say -- would not pass on these inputs."""
+    for name in ("tdec200", "tdec256"):
+        tdec = case_cfg(name)[0]
+        x = case_input(name)
+        n = x.shape[1] // tdec
+        groups = x[:, :n * tdec].reshape(x.shape[0], n, tdec, x.shape[2])
+        back = np.ascontiguousarray(groups[:, :, ::-1]).reshape(x.shape[0], n * tdec, x.shape[2])
+        differ = np.mean(ffa_oracle.decimate(x, tdec).view(np.uint32) != ffa_oracle.decimate(back, tdec).view(np.uint32))
+        assert differ > 0.5, (name, differ)
+
+
+def test_the_edge_cases_sit_on_the_launchers_edges(lib):
+    """The dynamic LDS of ffa_search_kernel as launch_search_octave sizes it, 2 ((max_p M p + 3) & ~3) 4 bytes with M from
+    bf_ffa_rows_of, against the 48 KiB above which the launcher must raise hipFuncAttributeMaxDynamicSharedMemorySize.  Whoever
+    retunes the launcher learns here that the cases have left the edge."""
+    lds = {name: case_lds_bytes(name, lib.bf_ffa_rows_of) for name in EDGE_CASES}
+    assert lds["lds_48k_exact"] == 48 * 1024 and lds["lds_just_over"] == 48 * 1024 + 128
+    for name in ("lds_just_over", "timed_geometry", "max_seg", "max_seg_p511"):
+        assert lds[name] > 48 * 1024, name
+    assert (lds["timed_geometry"], lds["max_seg"], lds["max_seg_p511"]) == (64 * 1024, 128 * 1024, 130816)
+    # lds_just_over alone is above 48 KiB with two widths: the first launch of ffa_search_kernel<2> that needs the opt-in, in any order
+    assert [name for name in sorted(EDGE_CASES) if EDGE_CASES[name][7] == 2 and lds[name] > 48 * 1024] == ["lds_just_over"]
+    small = [name for name in sorted(EDGE_CASES) if name.startswith("k")]
+    assert len(small) == 6 and sorted(EDGE_CASES[name][7] for name in small) == [1, 2, 3, 4, 5, 6]
+    for name in small:
+        assert lds[name] <= 4096, name
+    # every case is one bf_ffa_create takes: each bound of the contract, and two rows at least in every octave
+    for name, (_, _, n_seg, p_lo, p_hi, tdec, n_oct, K, *_rest) in EDGE_CASES.items():
+        assert 1 <= tdec <= 256 and n_seg <= 16384 and n_seg % (1 << (n_oct - 1)) == 0 and 8 <= p_lo < p_hi <= 512 and (1 << (K - 1)) <= p_lo // 2, name
+        assert all(lib.bf_ffa_rows_of(n_seg >> o, p) >= 2 for o in range(n_oct) for p in range(p_lo, p_hi)), name
+    assert case_max_rows("max_seg") == 2048
 
 
 def test_decimation_and_octaves():

@@ -16,7 +16,7 @@ from conftest import ROOT
 sys.path.insert(0, os.path.join(ROOT, "tests", "support"))
 import ffa_oracle  # noqa: E402
 import sps_oracle  # noqa: E402
-from ffa_stage import PARITY_CASES, case_input, check_segment, run_stage, same_candidates  # noqa: E402
+from ffa_stage import PARITY_CASES, case_cfg, case_input, check_segment, run_stage, same_candidates  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -42,9 +42,7 @@ def _bf(bfmod, n_beams, n_freq=8):
     return bfmod.Beamformer(bfmod.debug_config(n_beams=n_beams, n_freq=n_freq))
 
 
-def _cfg(name):
-    _, _, n_seg, p_lo, p_hi, tdec, n_oct, K, *_ = PARITY_CASES[name]
-    return (tdec, n_seg, n_oct, p_lo, p_hi, K)
+_cfg = case_cfg          # (a name of either table of ffa_stage)
 
 
 @pytest.mark.sweep_cap(len(PARITY_CASES))

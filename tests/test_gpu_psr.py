@@ -67,14 +67,17 @@ def order_matters(x, models, delays, n_bins, first_row=0):
 
 
 def models_for(n_psr, n_bins, n_rows, which):
-    """The three kinds of model the shapes need, as (phase0, dphase, ddphase, epoch_row):
+    """The four kinds of model the shapes need, as (phase0, dphase, ddphase, epoch_row):
     fast:  0.37 turns per row -- more than one bin per row from 5 bins on (bins are skipped), ddphase > 0;
     slow:  about 30 rows per bin (long register runs), ddphase < 0, the epoch in the middle of the series (negative n);
-    still: dphase = ddphase = 0 -- every row of a channel lands in one bin."""
+    still: dphase = ddphase = 0 -- every row of a channel lands in one bin;
+    creep: three rows per bin at a constant step, from half a turn, the epoch at row 7 -- at 4096 bins the 203 rows of a channel stay in 68 bins.
+    One pulsar is `which`; two are slow + creep, three fast + slow + still, four all of them."""
     pool = {"fast": (int(0.1 * ONE), int(0.37 * ONE), 3 << 40, 0),
             "slow": (int(0.9 * ONE), ONE // (30 * n_bins), -(5 << 36), n_rows // 2),
-            "still": (int(0.77 * ONE), 0, 0, -12)}
-    return [pool[k] for k in (("fast", "slow", "still") if n_psr == 3 else (which,))]
+            "still": (int(0.77 * ONE), 0, 0, -12),
+            "creep": (ONE // 2, ONE // (3 * n_bins), 0, 7)}
+    return [pool[k] for k in {1: (which,), 2: ("slow", "creep"), 3: ("fast", "slow", "still"), 4: ("fast", "slow", "still", "creep")}[n_psr]]
 
 
 def delays_for(rng, n_psr, n_f, n_rows):
@@ -89,9 +92,12 @@ def push_all(torch, folder, d_x, row_bytes, cuts, streams):
         folder.push(d_x.data_ptr() + at * row_bytes, n, streams[k % len(streams)].cuda_stream)
 
 
-# every value of every axis: n_beams 4 60 64 68 256, n_freq_total 1 3 40, n_bins 2 5 64 1024, n_psr 1 3 (and every kind of model alone)
+# every value of every axis: n_beams 4 60 64 68 256 260 516, n_freq_total 1 3 40, n_bins 2 5 64 1024 4096, n_psr 1 2 3 4 -- every
+# compiled psr_fold_kernel<NPSR> -- (and every kind of model alone).  260 beams: a second beam block (blockIdx.y = 1) with 4 live
+# lanes; 516: three blocks; 4096 bins: the contract's maximum.
 SHAPES = [(4, 1, 2, 1, "fast"), (60, 3, 5, 3, None), (64, 40, 64, 1, "slow"), (68, 3, 1024, 3, None), (256, 40, 64, 3, None),
-          (256, 1, 1024, 1, "still"), (68, 40, 5, 1, "fast"), (64, 3, 2, 3, None), (60, 1, 64, 1, "slow"), (4, 40, 1024, 3, None)]
+          (256, 1, 1024, 1, "still"), (68, 40, 5, 1, "fast"), (64, 3, 2, 3, None), (60, 1, 64, 1, "slow"), (4, 40, 1024, 3, None),
+          (260, 3, 5, 2, None), (516, 1, 64, 4, None), (4, 3, 4096, 4, None), (64, 1, 2, 2, None)]
 
 
 @pytest.mark.sweep_cap(len(SHAPES))
