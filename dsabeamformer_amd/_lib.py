@@ -78,6 +78,12 @@ class BfFfaCandidate(C.Structure):
                 ("value", C.c_float)]
 
 
+class BfFfaGroup(C.Structure):
+    """Mirror of ``bf_ffa_group`` (include/dsabf.h)."""
+    _fields_ = [("head", BfFfaCandidate), ("n_members", C.c_int32), ("n_beams", C.c_int32), ("dm_lo", C.c_int32), ("dm_hi", C.c_int32),
+                ("n_harmonic", C.c_int32), ("reserved", C.c_int32)]
+
+
 class BfCondOptions(C.Structure):
     """Mirror of ``bf_cond_options`` (include/dsabf.h)."""
     _fields_ = [("baseline_pushes", C.c_int), ("zero_dm", C.c_int), ("auto_threshold", C.c_double)]
@@ -274,6 +280,9 @@ SIGNATURES = {
     "bf_ffa_select": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64,
                                 C.c_int, C.c_double, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "bf_dm_stream_attach_periodicity": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "bf_ffa_set_detrend": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "bf_ffa_detrend": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "bf_ffa_sift": (C.c_int, [C.c_void_p, C.c_size_t, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "bf_comm_unique_id": (C.c_int, [C.c_void_p]),
     "bf_comm_create": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
     "bf_comm_destroy": (C.c_int, [C.c_void_p]),
@@ -387,6 +396,8 @@ SIGNATURES = {
     "bfh_psr_sink_deliver": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]),
     "bfh_psr_sink_destroy": (C.c_int, [C.c_void_p]),
     "bfh_ffa_sink_create": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(C.c_void_p)]),
+    "bfh_ffa_sink_create_detrend": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int,
+                                              C.POINTER(C.c_void_p)]),
     "bfh_ffa_sink_deliver": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "bfh_ffa_sink_destroy": (C.c_int, [C.c_void_p]),
     "bfh_dm_trial_share": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),

@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-from ._lib import BF_CAL_FULL, BF_CAL_PHASE, BF_NULL_CLIP, BF_NULL_SCALED, BfCalOptions, BfNullOptions, BfCondOptions, BfConfig, BfFfaCandidate, BfFfaPeak, BfFfaStat, BfPsrModel, BfEvtEvent, BfEvtOptions, BfSkOptions, BfStampRequest, DsabfError, BfSpsCandidate, BfSpsPeak, BfSpsStat, check, load
+from ._lib import BF_CAL_FULL, BF_CAL_PHASE, BF_NULL_CLIP, BF_NULL_SCALED, BfCalOptions, BfNullOptions, BfCondOptions, BfConfig, BfFfaCandidate, BfFfaGroup, BfFfaPeak, BfFfaStat, BfPsrModel, BfEvtEvent, BfEvtOptions, BfSkOptions, BfStampRequest, DsabfError, BfSpsCandidate, BfSpsPeak, BfSpsStat, check, load
 
 
 def debug_config(**over) -> BfConfig:
@@ -554,21 +554,60 @@ def _ffa_candidate_dtype():
                      ("value", np.float32)], align=True)
 
 
+def _ffa_group_dtype():
+    import numpy as np
+
+    return np.dtype([("head", _ffa_candidate_dtype()), ("n_members", np.int32), ("n_beams", np.int32), ("dm_lo", np.int32), ("dm_hi", np.int32),
+                     ("n_harmonic", np.int32), ("reserved", np.int32)], align=True)
+
+
 class PeriodicitySearch(_Owner):
     """bf_ffa: a blind periodicity search (Fast Folding Algorithm) over the chunks [n_dm][n_t][beam] of a DmStream, on the device
     (include/dsabf.h, docs/PERIODICITY.md): the series of every (trial, beam) decimated by ``tdec``, cut into segments of ``n_seg``
     samples, folded at every base period p_lo <= p < p_hi of ``n_oct`` octaves, boxcar-filtered at ``n_widths`` widths.  Attach it
-    with ``DmStream.attach_periodicity`` or push chunks yourself."""
+    with ``DmStream.attach_periodicity`` or push chunks yourself.  ``detrend=(blk, win)`` (bf_ffa_set_detrend) removes a running
+    median over ``win`` means of ``blk`` decimated samples from every segment in front of the fold; None leaves it off."""
     _ptr_attr, _destroy = "_s", "bf_ffa_destroy"
 
     def __init__(self, bf: Beamformer, n_dm: int, tdec: int, n_seg: int, n_oct: int, p_lo: int, p_hi: int, n_widths: int, max_t_per_push: int,
-                 dm_first: int = 0, max_in_flight: int = 2, threshold: float = 8.0):
+                 dm_first: int = 0, max_in_flight: int = 2, threshold: float = 8.0, detrend: "tuple[int, int] | None" = None):
         self._lib = load()
         self._s = C.c_void_p()
         self.n_dm, self.n_beams, self._bf = n_dm, bf.cfg.n_beams, bf
         self.tdec, self.n_seg, self.n_oct, self.p_lo, self.p_hi, self.n_widths, self.dm_first = tdec, n_seg, n_oct, p_lo, p_hi, n_widths, dm_first
         check(self._lib.bf_ffa_create(bf._h, n_dm, dm_first, tdec, n_seg, n_oct, p_lo, p_hi, n_widths, max_t_per_push, max_in_flight, threshold,
                                       C.byref(self._s)))
+        if detrend is not None:
+            try:
+                self.set_detrend(*detrend)
+            except Exception:
+                self.close()
+                raise
+
+    def set_detrend(self, blk: int, win: int) -> None:
+        """bf_ffa_set_detrend: before the first push only; blk 0 switches the detrend off."""
+        check(self._lib.bf_ffa_set_detrend(self._s, int(blk), int(win)))
+
+    @property
+    def detrend(self):
+        """bf_ffa_detrend: (blk, win), or None while the detrend is off."""
+        blk, win = C.c_int(), C.c_int()
+        check(self._lib.bf_ffa_detrend(self._s, C.byref(blk), C.byref(win)))
+        return (blk.value, win.value) if blk.value else None
+
+    @staticmethod
+    def sift(cands, tol: float = 0.002, max_harm: int = 4, dm_tol: int = 2):
+        """bf_ffa_sift, the harmonic sift as a pure host function (no GPU): ``cands`` a candidate array as ``collect`` returns it (of
+        any number of segments, concatenated).  Returns a numpy structured array of groups (head, n_members, n_beams, dm_lo, dm_hi,
+        n_harmonic), in the order the groups were created."""
+        import numpy as np
+
+        cands = np.ascontiguousarray(cands, _ffa_candidate_dtype())
+        out = np.zeros(max(len(cands), 1), _ffa_group_dtype())
+        assert out.dtype.itemsize == C.sizeof(BfFfaGroup)
+        n_out = C.c_size_t()
+        check(load().bf_ffa_sift(_ptr(cands) if len(cands) else None, len(cands), tol, max_harm, dm_tol, _ptr(out), len(cands), C.byref(n_out)))
+        return out[:n_out.value].copy()
 
     @staticmethod
     def rows_of(length: int, p: int) -> int:

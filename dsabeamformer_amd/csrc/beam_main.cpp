@@ -156,12 +156,12 @@ int main(int argc, char* argv[])
     std::string fold_path;
     bool fold_extra_given = false, fold_bad = false;
     // periodicity search (docs/PERIODICITY.md): --ffa p_lo:p_hi, --ffa-seg n_seg, --ffa-dec tdec, --ffa-oct n, --ffa-widths K, --ffa-snr threshold,
-    // --ffa-out FILE
-    int ffa_p_lo = 0, ffa_p_hi = 0, ffa_seg = 1024, ffa_dec = 1, ffa_oct = 1, ffa_widths = 3;
+    // --ffa-out FILE, --ffa-detrend blk:win
+    int ffa_p_lo = 0, ffa_p_hi = 0, ffa_seg = 1024, ffa_dec = 1, ffa_oct = 1, ffa_widths = 3, ffa_det_blk = 0, ffa_det_win = 0;
     double ffa_snr = 8.0;
     std::string ffa_path;
     bool ffa_given = false, ffa_extra_given = false, ffa_bad = false;
-    enum { kEvents = 1000, kEventTol, kEventVeto, kStamps, kStampShape, kStampFlagged, kFold, kFoldDm, kFoldBins, kFoldRows, kFoldOut, kFfa, kFfaSeg, kFfaDec, kFfaOct, kFfaWidths, kFfaSnr, kFfaOut };
+    enum { kEvents = 1000, kEventTol, kEventVeto, kStamps, kStampShape, kStampFlagged, kFold, kFoldDm, kFoldBins, kFoldRows, kFoldOut, kFfa, kFfaSeg, kFfaDec, kFfaOct, kFfaWidths, kFfaSnr, kFfaOut, kFfaDetrend };
     static const option long_options[] = {{"events", required_argument, nullptr, kEvents},       {"event-tol", required_argument, nullptr, kEventTol},
                                           {"event-veto", required_argument, nullptr, kEventVeto}, {"stamps", required_argument, nullptr, kStamps},
                                           {"stamp-shape", required_argument, nullptr, kStampShape}, {"stamp-flagged", no_argument, nullptr, kStampFlagged},
@@ -171,7 +171,7 @@ int main(int argc, char* argv[])
                                           {"ffa", required_argument, nullptr, kFfa},             {"ffa-seg", required_argument, nullptr, kFfaSeg},
                                           {"ffa-dec", required_argument, nullptr, kFfaDec},       {"ffa-oct", required_argument, nullptr, kFfaOct},
                                           {"ffa-widths", required_argument, nullptr, kFfaWidths}, {"ffa-snr", required_argument, nullptr, kFfaSnr},
-                                          {"ffa-out", required_argument, nullptr, kFfaOut},
+                                          {"ffa-out", required_argument, nullptr, kFfaOut},       {"ffa-detrend", required_argument, nullptr, kFfaDetrend},
                                           {nullptr, 0, nullptr, 0}};
     // a non-negative integer that fills its whole field; anything else marks the command line as malformed
     auto number = [&long_bad](const char* text, const char** end, int* out) {
@@ -236,6 +236,20 @@ int main(int argc, char* argv[])
                 if (*e || long_bad) ffa_bad = true;
                 long_bad = bad;
                 ffa_given = true;
+                break;
+            }
+            case kFfaDetrend: {   // blk:win
+                const char* e = nullptr;
+                bool bad = long_bad;
+                long_bad = false;
+                number(optarg, &e, &ffa_det_blk);
+                if (*e == ':')
+                    number(e + 1, &e, &ffa_det_win);
+                else
+                    ffa_bad = true;
+                if (*e || long_bad) ffa_bad = true;
+                long_bad = bad;
+                ffa_extra_given = true;
                 break;
             }
             case kFfaSeg:
@@ -414,12 +428,14 @@ int main(int argc, char* argv[])
                              "                         dedispersed at DM pc/cc [0] (the k-th --fold-dm belongs to the k-th --fold; up to 4 --fold), into N [64] phase\n"
                              "                         bins (2 .. 4096); a dump to FILE whenever ROWS [one block's] rows or more have been folded (with -X: FILE.<rank>);\n"
                              "                         --fold without -M, the others without --fold, more than 4 --fold or malformed numbers: a usage error\n"
-                             " --ffa P_LO:P_HI [--ffa-seg N] [--ffa-dec N] [--ffa-oct N] [--ffa-widths K] [--ffa-snr SNR] [--ffa-out FILE]   with -M: a blind\n"
-                             "                         periodicity search (Fast Folding Algorithm) of every DM trial and beam: the chunks decimated by --ffa-dec [1],\n"
+                             " --ffa P_LO:P_HI [--ffa-seg N] [--ffa-dec N] [--ffa-oct N] [--ffa-widths K] [--ffa-snr SNR] [--ffa-out FILE] [--ffa-detrend BLK:WIN]\n"
+                             "                         with -M: a blind periodicity search (Fast Folding Algorithm) of every DM trial and beam: the chunks decimated by --ffa-dec [1],\n"
                              "                         cut into segments of --ffa-seg [1024] samples, folded at the base periods P_LO <= p < P_HI (8 .. 512 samples)\n"
                              "                         of --ffa-oct [1] octaves, boxcar widths 1 .. 2^(K-1) [K = 3]; one line per candidate at S/N >= SNR [8] to FILE\n"
                              "                         (with -X: FILE.<rank>, trials numbered over the whole ladder); --ffa without -M, the others without --ffa or\n"
-                             "                         malformed numbers: a usage error\n"
+                             "                         malformed numbers: a usage error.  --ffa-detrend BLK:WIN removes red noise from every segment in\n"
+                             "                         front of the fold: a running median over WIN (odd, 1 .. 129) means of BLK (a power of two, 1 .. 256, dividing\n"
+                             "                         --ffa-seg) decimated samples, interpolated between the block centres; the file's header then says detrend=BLK:WIN\n"
                              " -H                      this text\n";
                 return EXIT_SUCCESS;
             default: usage(true, std::cerr); return EXIT_FAILURE;
@@ -452,11 +468,11 @@ int main(int argc, char* argv[])
         return EXIT_FAILURE;
     }
     if (!ffa_given && ffa_extra_given) {
-        fprintf(stderr, "beam: --ffa-seg / --ffa-dec / --ffa-oct / --ffa-widths / --ffa-snr / --ffa-out belong to the periodicity search: give --ffa P_LO:P_HI\n");
+        fprintf(stderr, "beam: --ffa-seg / --ffa-dec / --ffa-oct / --ffa-widths / --ffa-snr / --ffa-out / --ffa-detrend belong to the periodicity search: give --ffa P_LO:P_HI\n");
         return EXIT_FAILURE;
     }
     if (ffa_bad) {
-        fprintf(stderr, "beam: --ffa P_LO:P_HI, --ffa-seg N, --ffa-dec N, --ffa-oct N, --ffa-widths N, --ffa-snr SNR: malformed number\n");
+        fprintf(stderr, "beam: --ffa P_LO:P_HI, --ffa-seg N, --ffa-dec N, --ffa-oct N, --ffa-widths N, --ffa-snr SNR, --ffa-detrend BLK:WIN: malformed number\n");
         return EXIT_FAILURE;
     }
     if (long_bad) {
@@ -1024,9 +1040,11 @@ int main(int argc, char* argv[])
             oopt.ffa_oct = ffa_oct;
             oopt.ffa_widths = ffa_widths;
             oopt.ffa_threshold = ffa_snr;
+            oopt.ffa_detrend_blk = ffa_det_blk;
+            oopt.ffa_detrend_win = ffa_det_win;
             if (!ffa_path.empty()) {
                 if (oopt.dm_split_trials) ffa_path += "." + std::to_string(rank);   // one file per shard; the trials are numbered over the whole ladder
-                ffa_out.reset(new ffa_file_sink(ffa_path.c_str(), ffa_dec, ffa_seg, ffa_oct, ffa_p_lo, ffa_p_hi, ffa_widths, ffa_snr));
+                ffa_out.reset(new ffa_file_sink(ffa_path.c_str(), ffa_dec, ffa_seg, ffa_oct, ffa_p_lo, ffa_p_hi, ffa_widths, ffa_snr, ffa_det_blk, ffa_det_win));
                 if (!ffa_out->is_open()) {
                     fprintf(stderr, "beam: could not open %s\n", ffa_path.c_str());
                     return EXIT_FAILURE;

@@ -2,6 +2,7 @@
 // docs/PERIODICITY.md).  The device code is csrc/ffa/bf_ffa.hip; this file owns the series and the carried decimation state, cuts
 // every push at the segment boundaries, orders the pushes whatever queues they come on, keeps the result sets and selects the
 // candidates.
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <new>
@@ -14,6 +15,7 @@ struct bf_ffa : bf_stage {
     bf_ffa() : bf_stage("periodicity stage") {}
     int n_dm = 0, dm_first = 0, tdec = 0, n_seg = 0, n_oct = 0, p_lo = 0, p_hi = 0, n_widths = 0, max_t = 0, max_in_flight = 0, n_beams = 0;
     double threshold = 0;
+    int det_blk = 0, det_win = 0;   // bf_ffa_set_detrend: samples per block and blocks per median window; det_blk == 0: off
     // Two series slots: segment s is decimated into slot s % 2 and searched there while the samples behind it go to the other one.
     // A slot holds the octaves one behind the other, each [n_dm][n_beams][n_seg >> o].
     float* d_slot[2] = {nullptr, nullptr};
@@ -150,6 +152,31 @@ int bf_ffa_create(bf_handle* h, int n_dm, int dm_first, int tdec, int n_seg, int
 
 int bf_ffa_destroy(bf_ffa* s) { return stage_destroy(s); }
 
+int bf_ffa_set_detrend(bf_ffa* s, int blk, int win)
+{
+    if (blk != 0) {   // (the bounds that need no stage first, as bf_ffa_create checks its shape before its handle)
+        if (blk < 1 || blk > BF_FFA_MAX_DETREND_BLK || (blk & (blk - 1)))
+            return fail(BF_ERR_INVALID, "bf_ffa_set_detrend: blk must be 0 (off) or a power of two 1 .. %d, not %d", BF_FFA_MAX_DETREND_BLK, blk);
+        if (win < 1 || win > BF_FFA_MAX_DETREND_WIN || !(win & 1))
+            return fail(BF_ERR_INVALID, "bf_ffa_set_detrend: win must be odd, 1 .. %d, not %d", BF_FFA_MAX_DETREND_WIN, win);
+    }
+    if (!s) return fail(BF_ERR_INVALID, "the stage is NULL");
+    if (int rc = orphaned(s)) return rc;
+    if (s->n_push) return fail(BF_ERR_STATE, "bf_ffa_set_detrend: the stage has taken a push; the detrend is set before the first");
+    if (blk != 0 && s->n_seg % blk) return fail(BF_ERR_INVALID, "bf_ffa_set_detrend: n_seg %d is no multiple of blk %d", s->n_seg, blk);
+    s->det_blk = blk;
+    s->det_win = blk ? win : 0;
+    return BF_OK;
+}
+
+int bf_ffa_detrend(const bf_ffa* s, int* blk, int* win)
+{
+    if (!s) return fail(BF_ERR_INVALID, "the stage is NULL");
+    if (blk) *blk = s->det_blk;
+    if (win) *win = s->det_win;
+    return BF_OK;
+}
+
 int bf_ffa_pending(const bf_ffa* s) { return s ? (int)(s->n_searched - s->n_collected) : fail(BF_ERR_INVALID, "the stage is NULL"); }
 
 int bf_ffa_push(bf_ffa* s, const float* d_chunk, int n_t, uint64_t first_t, void* hip_stream)
@@ -183,6 +210,7 @@ int bf_ffa_push(bf_ffa* s, const float* d_chunk, int n_t, uint64_t first_t, void
                                            pos, q));
         g += cnt + (with_open ? 1 : 0);
         if (closes) {
+            if (s->det_blk) HIP_TRY(dsabf::launch_ffa_detrend(slot, s->n_dm, s->n_beams, s->n_seg, s->det_blk, s->det_win, q));
             bf_ffa::result_set& r = s->sets[s->n_searched % (uint64_t)s->max_in_flight];
             HIP_TRY(dsabf::launch_ffa_search(slot, s->n_dm, s->n_beams, s->n_seg, s->n_oct, s->p_lo, s->p_hi, s->n_widths, r.d_peaks, r.d_stats, q));
             HIP_TRY(hipEventRecord(r.kernels_done, q));
@@ -290,6 +318,63 @@ int bf_ffa_select(const bf_ffa_peak* peaks, const bf_ffa_stat* stats, int tdec, 
         std::memcpy(&out[m++], &c, sizeof c);   // (the padding bytes too: zero)
     }
     *n_out = m;
+    return BF_OK;
+}
+
+int bf_ffa_sift(const bf_ffa_candidate* in, size_t n, double tol, int max_harm, int dm_tol, bf_ffa_group* out, size_t max_out, size_t* n_out)
+{
+    if (!n_out) return fail(BF_ERR_INVALID, "NULL argument");
+    *n_out = 0;
+    if (!(tol >= 0.0 && tol < 1.0)) return fail(BF_ERR_INVALID, "bf_ffa_sift: tol must be in [0, 1)");
+    if (max_harm < 1 || max_harm > BF_FFA_MAX_HARM) return fail(BF_ERR_INVALID, "bf_ffa_sift: max_harm must be 1 .. %d, not %d", BF_FFA_MAX_HARM, max_harm);
+    if (dm_tol < 0) return fail(BF_ERR_INVALID, "bf_ffa_sift: dm_tol must be >= 0, not %d", dm_tol);
+    if (n == 0) return BF_OK;
+    if (!in || !out) return fail(BF_ERR_INVALID, "NULL argument");
+    for (size_t i = 0; i < n; i++) {
+        if (!(in[i].snr == in[i].snr)) return fail(BF_ERR_INVALID, "bf_ffa_sift: candidate %zu has a NaN snr", i);
+        if (!(in[i].period_rows > 0.0)) return fail(BF_ERR_INVALID, "bf_ffa_sift: candidate %zu has a period_rows that is not > 0", i);
+    }
+    std::vector<size_t> order(n);
+    for (size_t i = 0; i < n; i++) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [in](size_t a, size_t b) { return in[a].snr > in[b].snr; });   // ties: the lower index first
+    std::vector<bf_ffa_group> groups;
+    std::vector<std::vector<int32_t>> beams;   // the distinct beams of a group
+    for (size_t idx : order) {
+        const bf_ffa_candidate& c = in[idx];
+        bool joined = false;
+        for (size_t g = 0; g < groups.size() && !joined; g++) {
+            bf_ffa_group& grp = groups[g];
+            const bf_ffa_candidate& hd = grp.head;
+            if (c.first_row != hd.first_row || c.n_rows != hd.n_rows) continue;
+            const int64_t ddm = (int64_t)c.dm - (int64_t)hd.dm;
+            if (ddm > dm_tol || -ddm > dm_tol) continue;
+            for (int a = 1; a <= max_harm && !joined; a++)
+                for (int b = 1; b <= max_harm; b++)
+                    if (std::fabs((c.period_rows * (double)b) / (hd.period_rows * (double)a) - 1.0) <= tol) {
+                        grp.n_members++;
+                        if (std::find(beams[g].begin(), beams[g].end(), c.beam) == beams[g].end()) beams[g].push_back(c.beam);
+                        grp.dm_lo = std::min(grp.dm_lo, c.dm);
+                        grp.dm_hi = std::max(grp.dm_hi, c.dm);
+                        if (a != 1 || b != 1) grp.n_harmonic++;
+                        joined = true;
+                        break;
+                    }
+        }
+        if (joined) continue;
+        bf_ffa_group grp;
+        std::memset(&grp, 0, sizeof grp);
+        std::memcpy(&grp.head, &c, sizeof c);
+        grp.n_members = 1;
+        grp.dm_lo = grp.dm_hi = c.dm;
+        groups.push_back(grp);
+        beams.push_back(std::vector<int32_t>(1, c.beam));
+    }
+    if (groups.size() > max_out) return fail(BF_ERR_INVALID, "bf_ffa_sift: %zu groups, room for max_out = %zu", groups.size(), max_out);
+    for (size_t g = 0; g < groups.size(); g++) {
+        groups[g].n_beams = (int32_t)beams[g].size();
+        std::memcpy(&out[g], &groups[g], sizeof(bf_ffa_group));
+    }
+    *n_out = groups.size();
     return BF_OK;
 }
 

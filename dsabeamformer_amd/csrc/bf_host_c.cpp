@@ -766,14 +766,19 @@ int bfh_psr_sink_destroy(bfh_psr_sink* s)
 struct bfh_ffa_sink {
     ffa_file_sink s;
 };
-int bfh_ffa_sink_create(const char* path, int tdec, int n_seg, int n_oct, int p_lo, int p_hi, int n_widths, double threshold, bfh_ffa_sink** out)
+int bfh_ffa_sink_create_detrend(const char* path, int tdec, int n_seg, int n_oct, int p_lo, int p_hi, int n_widths, double threshold, int detrend_blk,
+                                int detrend_win, bfh_ffa_sink** out)
 {
     if (!path || !out) return BF_ERR_INVALID;
     *out = nullptr;
-    std::unique_ptr<bfh_ffa_sink> s(new bfh_ffa_sink{ffa_file_sink(path, tdec, n_seg, n_oct, p_lo, p_hi, n_widths, threshold)});
+    std::unique_ptr<bfh_ffa_sink> s(new bfh_ffa_sink{ffa_file_sink(path, tdec, n_seg, n_oct, p_lo, p_hi, n_widths, threshold, detrend_blk, detrend_win)});
     if (!s->s.is_open()) return BF_ERR_INVALID;
     *out = s.release();
     return BF_OK;
+}
+int bfh_ffa_sink_create(const char* path, int tdec, int n_seg, int n_oct, int p_lo, int p_hi, int n_widths, double threshold, bfh_ffa_sink** out)
+{
+    return bfh_ffa_sink_create_detrend(path, tdec, n_seg, n_oct, p_lo, p_hi, n_widths, threshold, 0, 0, out);
 }
 int bfh_ffa_sink_deliver(bfh_ffa_sink* s, const bf_ffa_candidate* cands, size_t n)
 {

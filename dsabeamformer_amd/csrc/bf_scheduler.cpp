@@ -757,6 +757,7 @@ struct production_run {
                 const int in_flight = (int)((uint64_t)n_buf * (uint64_t)plan.dm_rows / seg_rows + 1);
                 rc = bf_ffa_create(dev.h, plan.dm_count, plan.dm_first, opt.ffa_dec, opt.ffa_seg, opt.ffa_oct, opt.ffa_p_lo, opt.ffa_p_hi, opt.ffa_widths,
                                    plan.dm_rows, in_flight, opt.ffa_threshold, &dev.ffa);
+                if (rc == BF_OK && (opt.ffa_detrend_blk || opt.ffa_detrend_win)) rc = bf_ffa_set_detrend(dev.ffa, opt.ffa_detrend_blk, opt.ffa_detrend_win);
                 if (rc == BF_OK) rc = bf_dm_stream_attach_periodicity(dev.dm, dev.ffa);
                 if (rc != BF_OK) return gpu_error(log, rc);
                 ffa_cands.resize((size_t)plan.dm_count * cfg.n_beams);

@@ -4,6 +4,8 @@
 // beam-lanes of a row on 256 contiguous bytes (the chunk is beam-contiguous); it adds the group's samples in ascending time, from
 // the carried value if an earlier push began the group, and writes the result TRANSPOSED: the series of a slot is
 // [trial][beam][time], one (trial, beam) contiguous in time, because that is the order every later step walks it in.
+// ffa_detrend_kernel (opt-in, bf_ffa_set_detrend; section 1a): one workgroup = one (trial, beam) of a complete segment; block means,
+// their running lower median by rank counting in LDS, and the piecewise linear trend through the block centres subtracted in place.
 // ffa_octave_kernel: y_{o+1}[u] = y_o[2u] + y_o[2u + 1], elementwise over a whole octave.
 // ffa_search_kernel: one workgroup = one (trial, beam) of one octave, all base periods.  The fold's working set, M rows of p bins
 // <= the octave's length, lives in LDS twice (the merge cannot run in place); the first merge level reads the series from memory
@@ -65,6 +67,84 @@ __global__ __launch_bounds__(256) void ffa_octave_kernel(const float2* __restric
     if (i < n) {
         const float2 v = lower[i];
         upper[i] = v.x + v.y;
+    }
+}
+
+// The total order of the running median (docs/PERIODICITY.md section 1a): fp32 bits as a uint32 that sorts like the value, -0 < +0.
+__device__ __forceinline__ uint32_t median_key(float v)
+{
+    const uint32_t b = __float_as_uint(v);
+    return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
+}
+__device__ __forceinline__ float median_unkey(uint32_t k) { return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xFFFFFFFFu)); }
+
+// One workgroup = one (trial, beam): the block means of its segment (a thread per block, a left fold in ascending time), their
+// running lower median (a thread per block: the rank of a window's element is the keys less than its own plus the equal keys in
+// front of it, so exactly one element of the window has the wanted rank, whatever order they are looked at in), then the piecewise
+// linear trend through the block centres subtracted in place (a thread per sample, the series read a second time out of the cache).
+// Means (as keys) and medians live in LDS, 8 nb bytes.
+__global__ __launch_bounds__(kThreads) void ffa_detrend_kernel(float* __restrict__ y, int n_seg, int lb, float inv_blk, int h)
+{
+    extern __shared__ uint32_t det_lds[];   // keys of the block means [nb], then the medians [nb] (fp32)
+    const int blk = 1 << lb, nb = n_seg >> lb;
+    uint32_t* __restrict__ key = det_lds;
+    float* __restrict__ med = reinterpret_cast<float*>(det_lds + nb);
+    float* __restrict__ s = y + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * (size_t)n_seg;
+
+    for (int c = threadIdx.x; c < nb; c += kThreads) {
+        const float* x = s + ((size_t)c << lb);
+        float acc;
+        if (blk >= 4) {   // (n_seg % blk == 0 and the series are 16-byte aligned: so is every block)
+            const float4 v = *reinterpret_cast<const float4*>(x);
+            acc = __fadd_rn(__fadd_rn(__fadd_rn(v.x, v.y), v.z), v.w);
+            for (int i = 4; i < blk; i += 4) {
+                const float4 w = *reinterpret_cast<const float4*>(x + i);
+                acc = __fadd_rn(__fadd_rn(__fadd_rn(__fadd_rn(acc, w.x), w.y), w.z), w.w);
+            }
+        } else {
+            acc = x[0];
+            for (int i = 1; i < blk; i++) acc = __fadd_rn(acc, x[i]);
+        }
+        key[c] = median_key(__fmul_rn(acc, inv_blk));
+    }
+    __syncthreads();
+
+    for (int c = threadIdx.x; c < nb; c += kThreads) {
+        const int lo = c - h > 0 ? c - h : 0, hi = c + h < nb - 1 ? c + h : nb - 1;
+        const int want = (hi - lo) >> 1;   // rank (n - 1) >> 1: the lower median
+        uint32_t sel = key[lo];
+        for (int i = lo; i <= hi; i++) {
+            const uint32_t ki = key[i];
+            int rank = 0;
+            for (int j = lo; j <= hi; j++) {
+                const uint32_t kj = key[j];
+                rank += (kj < ki || (kj == ki && j < i)) ? 1 : 0;
+            }
+            if (rank == want) {
+                sel = ki;
+                break;
+            }
+        }
+        med[c] = median_unkey(sel);
+    }
+    __syncthreads();
+
+    for (int u = threadIdx.x; u < n_seg; u += kThreads) {
+        const int k = 2 * u + 1 - blk;
+        float trend;
+        if (k < 0) {
+            trend = med[0];
+        } else {
+            const int c0 = k >> (lb + 1);
+            if (c0 >= nb - 1) {
+                trend = med[nb - 1];
+            } else {
+                const float a = __fmul_rn((float)(k & (2 * blk - 1)), 0.5f * inv_blk);   // (k - 2 blk c0) / (2 blk): dyadic, exact
+                const float r0 = med[c0];
+                trend = __fadd_rn(r0, __fmul_rn(a, __fsub_rn(med[c0 + 1], r0)));
+            }
+        }
+        s[u] = __fsub_rn(s[u], trend);
     }
 }
 
@@ -258,6 +338,24 @@ hipError_t launch_ffa_decimate(const float* d_chunk, int n_dm, int n_t, int n_be
     const dim3 grid((unsigned)((n_beams + 4 * kBeamLanes - 1) / (4 * kBeamLanes)), (unsigned)((n_groups + kGroupLanes - 1) / kGroupLanes), (unsigned)n_dm);
     hipLaunchKernelGGL(ffa_decimate_kernel, grid, dim3(kDecThreads), 0, stream, d_chunk, n_t, n_beams, tdec, c0, g0, n_groups, carry_in,
                        carry_out, y0, n_seg, pos0);
+    return hipGetLastError();
+}
+
+hipError_t launch_ffa_detrend(float* y0, int n_dm, int n_beams, int n_seg, int blk, int win, hipStream_t stream)
+{
+    if (n_dm <= 0 || n_dm > 65535 || n_beams <= 0 || n_seg < 1 || n_seg > kFfaMaxSeg || blk < 1 || blk > kFfaMaxDetrendBlk || (blk & (blk - 1)) ||
+        n_seg % blk || win < 1 || win > kFfaMaxDetrendWin || !(win & 1) || ((uintptr_t)y0 & 15))
+        return hipErrorInvalidValue;
+    int lb = 0;
+    while ((1 << lb) < blk) lb++;
+    const size_t lds = 2 * (size_t)(n_seg >> lb) * sizeof(float);   // 128 KiB at most (blk 1, n_seg 16384)
+    (void)hipGetLastError();
+    if (lds > 48 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(ffa_detrend_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(ffa_detrend_kernel, dim3((unsigned)n_beams, (unsigned)n_dm), dim3(kThreads), lds, stream, y0, n_seg, lb, 1.0f / (float)blk,
+                       (win - 1) / 2);
     return hipGetLastError();
 }
 

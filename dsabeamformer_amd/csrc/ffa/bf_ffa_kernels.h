@@ -13,6 +13,7 @@ namespace dsabf {
 
 constexpr int kFfaMaxDec = 256, kFfaMaxSeg = 16384, kFfaMaxOct = 6, kFfaMaxWidths = 6;
 constexpr int kFfaMinPeriod = 8, kFfaMaxPeriod = 512;
+constexpr int kFfaMaxDetrendBlk = 256, kFfaMaxDetrendWin = 129;
 
 // The rows M of the fold of an octave of `len` samples at base period p: the largest power of two <= len / p (0: none fits).
 __host__ __device__ inline int ffa_rows(int len, int p)
@@ -38,6 +39,11 @@ inline size_t ffa_octave_offset(int o, int n_seg, size_t n_db)
 // chunk: [n_dm][n_t][n_beams] fp32, 16-byte aligned, n_beams % 4 == 0.  carry_in and carry_out must differ.
 hipError_t launch_ffa_decimate(const float* d_chunk, int n_dm, int n_t, int n_beams, int tdec, int c0, int g0, int n_groups, const float* carry_in,
                                float* carry_out, float* y0, int n_seg, int pos0, hipStream_t stream);
+
+// The running-median detrend of one full segment, in place (docs/PERIODICITY.md section 1a): y0 is octave 0 of a slot,
+// [n_dm][n_beams][n_seg], 16-byte aligned; blk a power of two 1 .. 256 that divides n_seg, win odd 1 .. 129.  Behind the decimation
+// launch that closes the segment and in front of launch_ffa_search, on the same queue.
+hipError_t launch_ffa_detrend(float* y0, int n_dm, int n_beams, int n_seg, int blk, int win, hipStream_t stream);
 
 // One full segment in `slot` (octave 0 filled): the higher octaves, then per octave every base period p_lo <= p < p_hi folded, its
 // K boxcar widths, and the records peaks[o][p - p_lo][k][d][beam]; stats[d][beam] over octave 0.

@@ -808,13 +808,34 @@ int bf_dm_stream_attach_folder(bf_dm_stream *dm, bf_psr *p);
  * bf_dm_stream_attach_periodicity(dm, s) (s == NULL detaches): from then on every bf_dm_stream_push that emits a chunk also pushes
  *   it into s, behind the dedispersion kernels (and an attached search stage) and before the push's `done` event; a push the
  *   stage would refuse is refused by bf_dm_stream_push before it queues anything.  Same handle, same n_dm, max_t_per_push >= the
- *   DM stage's max_rows_per_push. */
+ *   DM stage's max_rows_per_push.
+ * bf_ffa_set_detrend(s, blk, win): red-noise removal in front of the fold (docs/PERIODICITY.md section 1a, to the bit).  Every complete
+ *   segment y_0 of every (trial, beam), after the decimation and before the octaves, the fold and the statistics, loses a trend:
+ *   the fp32 means of its nb = n_seg / blk blocks (a left fold times 2^-log2(blk)), their running LOWER median over win blocks
+ *   (windows truncated at the ends; the order of the keys bits ^ (bits >> 31 ? 0xFFFFFFFF : 0x80000000), so -0 < +0; a pure
+ *   selection), and through the block centres the piecewise linear r[c0] + a (r[c0 + 1] - r[c0]) in three fp32 roundings, constant
+ *   outside the first and last centre; y'[u] = y[u] - trend[u] in place.  Records and statistics are those of y'.  blk a power of
+ *   two 1 .. BF_FFA_MAX_DETREND_BLK that divides n_seg, win odd 1 .. BF_FFA_MAX_DETREND_WIN: BF_ERR_INVALID otherwise, nothing
+ *   allocated or launched; blk == 0 switches it off (the default: nothing is launched and no byte of anything changes).  Legal before
+ *   the first push only (BF_ERR_STATE afterwards, and for an orphaned stage).  bf_ffa_detrend reads the two back.  A column with a
+ *   non-finite sample in the segment: records and statistics unspecified, shift < M and bin < p all the same, no other column changes.
+ * bf_ffa_sift (host, fp64, pure, no GPU): groups candidates (what bf_ffa_collect gave, of any number of segments) that are one source
+ *   seen in neighbouring trials, several beams and at harmonically related periods.  Candidates are taken in descending snr (ties:
+ *   the lower index); each is tested against the existing group heads in the order they were created and joins the FIRST it
+ *   matches, else it becomes a head (links are to heads only).  A match: equal first_row and n_rows, |dm - head.dm| <= dm_tol, and
+ *   some a, then b, both ascending in 1 .. max_harm, with fabs((period_rows b) / (head.period_rows a) - 1.0) <= tol; the first
+ *   matching (a, b) other than (1, 1) counts in n_harmonic.  Groups leave in creation order.  BF_ERR_INVALID with *n_out = 0 and
+ *   nothing written: tol outside [0, 1) or NaN, max_harm outside 1 .. BF_FFA_MAX_HARM, dm_tol < 0, a NaN snr, a period_rows that
+ *   is not > 0, more groups than max_out, NULL pointers with n > 0.  n == 0: BF_OK, no group. */
 #define BF_FFA_MAX_DEC 256
 #define BF_FFA_MAX_SEG 16384
 #define BF_FFA_MAX_OCT 6
 #define BF_FFA_MAX_WIDTHS 6
 #define BF_FFA_MIN_PERIOD 8
 #define BF_FFA_MAX_PERIOD 512
+#define BF_FFA_MAX_DETREND_BLK 256
+#define BF_FFA_MAX_DETREND_WIN 129
+#define BF_FFA_MAX_HARM 16
 typedef struct bf_ffa bf_ffa;
 typedef struct bf_ffa_peak {
     float value;
@@ -845,6 +866,16 @@ int bf_ffa_select(const bf_ffa_peak *peaks, const bf_ffa_stat *stats, int tdec, 
                   int n_widths, int n_dm, int n_beams, uint64_t first_row, uint64_t n_rows, int dm_first, double threshold,
                   bf_ffa_candidate *out, size_t max_out, size_t *n_out);
 int bf_dm_stream_attach_periodicity(bf_dm_stream *dm, bf_ffa *s);
+typedef struct bf_ffa_group {
+    bf_ffa_candidate head;        /* the member with the largest snr */
+    int32_t n_members, n_beams;   /* head included; distinct beams among the members */
+    int32_t dm_lo, dm_hi;         /* extent in trials */
+    int32_t n_harmonic, reserved; /* members that joined at (a, b) != (1, 1); 0 */
+} bf_ffa_group;
+int bf_ffa_set_detrend(bf_ffa *s, int blk, int win);
+int bf_ffa_detrend(const bf_ffa *s, int *blk, int *win);
+int bf_ffa_sift(const bf_ffa_candidate *in, size_t n, double tol, int max_harm, int dm_tol, bf_ffa_group *out, size_t max_out,
+                size_t *n_out);
 
 /* ---- Multi-GPU: frequency shards and the gather of their detected powers -------------------------------
  * The reference runs 8 independent processes, one sub-band per GPU (`-g`, src/beamformer.cu:92-100,233; README.md:168)

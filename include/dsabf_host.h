@@ -190,6 +190,10 @@ int bfh_psr_sink_destroy(bfh_psr_sink *s);
 typedef struct bfh_ffa_sink bfh_ffa_sink;
 int bfh_ffa_sink_create(const char *path, int tdec, int n_seg, int n_oct, int p_lo, int p_hi, int n_widths, double threshold,
                         bfh_ffa_sink **out);
+/* The same with the stage's detrend (bf_ffa_set_detrend): blk > 0 appends ` detrend=blk:win` to the `# periodicity` line; blk == 0
+ * writes the file of bfh_ffa_sink_create, byte for byte. */
+int bfh_ffa_sink_create_detrend(const char *path, int tdec, int n_seg, int n_oct, int p_lo, int p_hi, int n_widths, double threshold,
+                                int detrend_blk, int detrend_win, bfh_ffa_sink **out);
 int bfh_ffa_sink_deliver(bfh_ffa_sink *s, const bf_ffa_candidate *cands, size_t n);
 int bfh_ffa_sink_destroy(bfh_ffa_sink *s);
 

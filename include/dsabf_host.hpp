@@ -745,12 +745,15 @@ class ffa_file_sink : public ffa_sink {
     uint64_t written = 0;
 
 public:
-    ffa_file_sink(const char* path, int tdec, int n_seg, int n_oct, int p_lo, int p_hi, int n_widths, double threshold) : fp(fopen(path, "w"))
+    // detrend_blk > 0 (the stage's bf_ffa_set_detrend) appends ` detrend=blk:win` to the first line; 0 leaves it as it always was
+    ffa_file_sink(const char* path, int tdec, int n_seg, int n_oct, int p_lo, int p_hi, int n_widths, double threshold, int detrend_blk = 0,
+                  int detrend_win = 0)
+        : fp(fopen(path, "w"))
     {
-        if (fp)
-            fprintf(fp, "# periodicity tdec=%d n_seg=%d n_oct=%d p_lo=%d p_hi=%d n_widths=%d threshold=%.17g\n"
-                        "# first_row n_rows period_rows dm beam octave p shift bin width snr value\n",
-                    tdec, n_seg, n_oct, p_lo, p_hi, n_widths, threshold);
+        if (!fp) return;
+        fprintf(fp, "# periodicity tdec=%d n_seg=%d n_oct=%d p_lo=%d p_hi=%d n_widths=%d threshold=%.17g", tdec, n_seg, n_oct, p_lo, p_hi, n_widths, threshold);
+        if (detrend_blk > 0) fprintf(fp, " detrend=%d:%d", detrend_blk, detrend_win);
+        fprintf(fp, "\n# first_row n_rows period_rows dm beam octave p shift bin width snr value\n");
     }
     ~ffa_file_sink() override { close(); }
     ffa_file_sink(const ffa_file_sink&) = delete;
@@ -1111,6 +1114,7 @@ struct observation_options {
     int ffa_p_lo = 0, ffa_p_hi = 0;
     int ffa_seg = 1024, ffa_dec = 1, ffa_oct = 1, ffa_widths = 3;
     double ffa_threshold = 8.0;
+    int ffa_detrend_blk = 0, ffa_detrend_win = 0;   // bf_ffa_set_detrend, applied right after the stage is created (0: off)
     dsabf::ffa_sink* ffa_sink = nullptr;
     // The incoherent beam (docs/INCOHERENT_BEAM.md): beam column `incoherent_beam` of the detected stream carries the antenna powers
     // summed over the antennas instead of a tied beam (bf_set_incoherent_beam, set on the handle before the loop); -1 = off.  On a
