@@ -110,6 +110,12 @@ class BfEvtEvent(C.Structure):
                 ("n_members", C.c_int32), ("n_beams", C.c_int32), ("snr_ib", C.c_double), ("flags", C.c_uint32)]
 
 
+class BfInjTruth(C.Structure):
+    """Mirror of ``bf_inj_truth`` (include/dsabf.h)."""
+
+    _fields_ = [("t_lo", C.c_uint64), ("t_hi", C.c_uint64), ("trial", C.c_int32), ("beam", C.c_int32)]
+
+
 class BfStampRequest(C.Structure):
     """Mirror of ``bf_stamp_request`` (include/dsabf.h)."""
 
@@ -283,6 +289,18 @@ SIGNATURES = {
     "bf_ffa_set_detrend": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "bf_ffa_detrend": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "bf_ffa_sift": (C.c_int, [C.c_void_p, C.c_size_t, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "bf_inj_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "bf_inj_destroy": (C.c_int, [C.c_void_p]),
+    "bf_inj_add_burst": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "bf_inj_add_train": (C.c_int, [C.c_void_p, C.POINTER(BfPsrModel), C.c_uint64, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.POINTER(C.c_uint64)]),
+    "bf_inj_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "bf_inj_next_row": (C.c_uint64, [C.c_void_p]),
+    "bf_inj_launches": (C.c_uint64, [C.c_void_p]),
+    "bf_inj_burst_profile": (C.c_int, [C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bf_inj_nearest_trial": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int)]),
+    "bf_inj_match": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint64, C.c_int32, C.c_void_p]),
+    "bf_dm_stream_attach_injector": (C.c_int, [C.c_void_p, C.c_void_p]),
     "bf_comm_unique_id": (C.c_int, [C.c_void_p]),
     "bf_comm_create": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
     "bf_comm_destroy": (C.c_int, [C.c_void_p]),

@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-from ._lib import BF_CAL_FULL, BF_CAL_PHASE, BF_NULL_CLIP, BF_NULL_SCALED, BfCalOptions, BfNullOptions, BfCondOptions, BfConfig, BfFfaCandidate, BfFfaGroup, BfFfaPeak, BfFfaStat, BfPsrModel, BfEvtEvent, BfEvtOptions, BfSkOptions, BfStampRequest, DsabfError, BfSpsCandidate, BfSpsPeak, BfSpsStat, check, load
+from ._lib import BF_CAL_FULL, BF_CAL_PHASE, BF_NULL_CLIP, BF_NULL_SCALED, BfCalOptions, BfNullOptions, BfCondOptions, BfConfig, BfFfaCandidate, BfFfaGroup, BfFfaPeak, BfFfaStat, BfInjTruth, BfPsrModel, BfEvtEvent, BfEvtOptions, BfSkOptions, BfStampRequest, DsabfError, BfSpsCandidate, BfSpsPeak, BfSpsStat, check, load
 
 
 def debug_config(**over) -> BfConfig:
@@ -382,6 +382,11 @@ class DmStream(_Owner):
         """bf_dm_stream_attach_periodicity: every chunk a push emits from now on also goes into ``ffa`` (a PeriodicitySearch; None
         detaches), behind an attached search stage."""
         check(self._lib.bf_dm_stream_attach_periodicity(self._s, ffa._s if ffa is not None else None))
+
+    def attach_injector(self, inj) -> None:
+        """bf_dm_stream_attach_injector: every push from now on adds the live pulses of ``inj`` (an Injector; None detaches) to its new
+        rows where they lie in the stage's buffer, in front of an attached conditioner."""
+        check(self._lib.bf_dm_stream_attach_injector(self._s, inj._c if inj is not None else None))
 
     def history(self):
         """bf_dm_stream_history: (oldest_row, next_row, cap_rows) -- rows [oldest_row, next_row) of the series can be cut."""
@@ -772,6 +777,108 @@ class PulsarFolder(_Owner):
         first, n = C.c_uint64(), C.c_uint64()
         check(self._lib.bf_psr_collect(self._c, _ptr(prof), _ptr(hits), C.byref(first), C.byref(n)))
         return prof, hits, int(first.value), int(n.value)
+
+
+def _truth_dtype():
+    import numpy as np
+
+    return np.dtype([("t_lo", np.uint64), ("t_hi", np.uint64), ("trial", np.int32), ("beam", np.int32)], align=True)
+
+
+class Injector(_Owner):
+    """bf_inj: synthetic bursts and pulse trains added in place to the detected rows [t][f][b], bit-equal to
+    tests/support/inj_oracle.py (include/dsabf.h, docs/INJECTION.md).  Tables are host arrays: ``delay`` int32 [n_freq_total],
+    ``profile`` float32 [n_freq_total][W or n_bins], ``response`` float32 [n_beams].  Attach it with ``DmStream.attach_injector`` or
+    apply it to rows yourself."""
+    _ptr_attr, _destroy = "_c", "bf_inj_destroy"
+
+    def __init__(self, bf: Beamformer, n_freq_total: int, max_rows: int, max_pulses: int = 64, max_width: int = 256):
+        self._lib = load()
+        self._c = C.c_void_p()
+        self.n_freq_total, self.n_beams, self._bf = n_freq_total, bf.cfg.n_beams, bf
+        check(self._lib.bf_inj_create(bf._h, n_freq_total, max_rows, max_pulses, max_width, C.byref(self._c)))
+
+    def _tables(self, width: int, delay, profile, response):
+        import numpy as np
+
+        d = np.ascontiguousarray(delay, np.int32)
+        p = np.ascontiguousarray(profile, np.float32)
+        r = np.ascontiguousarray(response, np.float32)
+        assert d.shape == (self.n_freq_total,) and p.shape == (self.n_freq_total, width) and r.shape == (self.n_beams,)
+        return d, p, r
+
+    def add_burst(self, t0: int, delay, profile, response) -> int:
+        """bf_inj_add_burst (W = profile.shape[1]); returns the pulse's id."""
+        import numpy as np
+
+        W = int(np.shape(profile)[1])
+        d, p, r = self._tables(W, delay, profile, response)
+        pid = C.c_uint64()
+        check(self._lib.bf_inj_add_burst(self._c, int(t0), W, _ptr(d), _ptr(p), _ptr(r), C.byref(pid)))
+        return int(pid.value)
+
+    def add_train(self, model, delay, profile, response, first_row: int = 0, n_rows: int | None = None) -> int:
+        """bf_inj_add_train (n_bins = profile.shape[1]; n_rows None: until the end); ``model``: a BfPsrModel or a (phase0, dphase,
+        ddphase, epoch_row) tuple.  Returns the pulse's id."""
+        import numpy as np
+
+        n_bins = int(np.shape(profile)[1])
+        d, p, r = self._tables(n_bins, delay, profile, response)
+        m = model if isinstance(model, BfPsrModel) else BfPsrModel(*[int(v) for v in model])
+        pid = C.c_uint64()
+        check(self._lib.bf_inj_add_train(self._c, C.byref(m), int(first_row), (1 << 64) - 1 if n_rows is None else int(n_rows), n_bins, _ptr(d),
+                                         _ptr(p), _ptr(r), C.byref(pid)))
+        return int(pid.value)
+
+    def apply(self, d_rows, n_rows: int, stream: int = 0) -> None:
+        check(self._lib.bf_inj_apply(self._c, _ptr(d_rows), int(n_rows), C.c_void_p(stream)))
+
+    @property
+    def next_row(self) -> int:
+        return int(self._lib.bf_inj_next_row(self._c))
+
+    @property
+    def launches(self) -> int:
+        return int(self._lib.bf_inj_launches(self._c))
+
+    @staticmethod
+    def burst_profile(n_freq_total: int, W: int, centre: float, sigma: float, fluence, smear=None):
+        """bf_inj_burst_profile: float32 [n_freq_total][W], a Gaussian of ``sigma`` rows around ``centre``, box-smeared over smear[f] rows,
+        each channel summing to fluence[f] (a scalar: every channel) (host, no GPU)."""
+        import numpy as np
+
+        fl = np.ascontiguousarray(np.broadcast_to(np.asarray(fluence, np.float64), (n_freq_total,)))
+        sm = None if smear is None else np.ascontiguousarray(np.broadcast_to(np.asarray(smear, np.int32), (n_freq_total,)))
+        out = np.zeros((n_freq_total, W), np.float32)
+        check(load().bf_inj_burst_profile(n_freq_total, W, float(centre), float(sigma), _ptr(sm), _ptr(fl), _ptr(out)))
+        return out
+
+    @staticmethod
+    def nearest_trial(ladder, delay) -> int:
+        """bf_inj_nearest_trial: the trial of ``ladder`` int32 [n_dm][n_freq_total] closest to ``delay`` in summed |difference| (host, no GPU)."""
+        import numpy as np
+
+        lad = np.ascontiguousarray(ladder, np.int32)
+        d = np.ascontiguousarray(delay, np.int32)
+        assert lad.ndim == 2 and d.shape == (lad.shape[1],)
+        trial = C.c_int(-1)
+        check(load().bf_inj_nearest_trial(_ptr(lad), lad.shape[0], lad.shape[1], _ptr(d), C.byref(trial)))
+        return int(trial.value)
+
+    @staticmethod
+    def match(truth, cands, t_tol: int = 0, dm_tol: int = 0):
+        """bf_inj_match: int32 [len(truth)], per truth record (t_lo, t_hi, trial, beam) the index of the matching candidate with the
+        largest snr, -1 if none (host, no GPU).  ``cands``: a structured array as ``SinglePulseSearch.collect`` returns."""
+        import numpy as np
+
+        tr = np.zeros(len(truth), _truth_dtype())
+        for i, t in enumerate(truth):
+            tr[i] = tuple(int(v) for v in t)
+        cd = np.ascontiguousarray(cands, _candidate_dtype())
+        assert tr.dtype.itemsize == C.sizeof(BfInjTruth) and cd.dtype.itemsize == C.sizeof(BfSpsCandidate)
+        best = np.full(len(tr), -1, np.int32)
+        check(load().bf_inj_match(_ptr(tr), len(tr), _ptr(cd), len(cd), int(t_tol), int(dm_tol), _ptr(best)))
+        return best
 
 
 class _AccumStage(_Owner):

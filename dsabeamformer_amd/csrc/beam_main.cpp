@@ -79,7 +79,9 @@
 #include <getopt.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <fstream>
 #include <thread>
@@ -161,7 +163,16 @@ int main(int argc, char* argv[])
     double ffa_snr = 8.0;
     std::string ffa_path;
     bool ffa_given = false, ffa_extra_given = false, ffa_bad = false;
-    enum { kEvents = 1000, kEventTol, kEventVeto, kStamps, kStampShape, kStampFlagged, kFold, kFoldDm, kFoldBins, kFoldRows, kFoldOut, kFfa, kFfaSeg, kFfaDec, kFfaOct, kFfaWidths, kFfaSnr, kFfaOut, kFfaDetrend };
+    // pulse injection (docs/INJECTION.md): --inject t0:dm:beam:fluence[:sigma[:w]] any number of times, --inject-train f0:dm:beam:amp[:duty[:bins]]
+    // up to 4 times, --inject-out FILE (one line of truth per pulse)
+    struct inject_spec {
+        double v[6] = {0, 0, 0, 0, 0, 0};
+        int n = 0;   // fields given
+    };
+    std::vector<inject_spec> inj_bursts, inj_trains;
+    std::string inj_path;
+    bool inj_bad = false;
+    enum { kEvents = 1000, kEventTol, kEventVeto, kStamps, kStampShape, kStampFlagged, kFold, kFoldDm, kFoldBins, kFoldRows, kFoldOut, kFfa, kFfaSeg, kFfaDec, kFfaOct, kFfaWidths, kFfaSnr, kFfaOut, kFfaDetrend, kInject, kInjectTrain, kInjectOut };
     static const option long_options[] = {{"events", required_argument, nullptr, kEvents},       {"event-tol", required_argument, nullptr, kEventTol},
                                           {"event-veto", required_argument, nullptr, kEventVeto}, {"stamps", required_argument, nullptr, kStamps},
                                           {"stamp-shape", required_argument, nullptr, kStampShape}, {"stamp-flagged", no_argument, nullptr, kStampFlagged},
@@ -172,6 +183,8 @@ int main(int argc, char* argv[])
                                           {"ffa-dec", required_argument, nullptr, kFfaDec},       {"ffa-oct", required_argument, nullptr, kFfaOct},
                                           {"ffa-widths", required_argument, nullptr, kFfaWidths}, {"ffa-snr", required_argument, nullptr, kFfaSnr},
                                           {"ffa-out", required_argument, nullptr, kFfaOut},       {"ffa-detrend", required_argument, nullptr, kFfaDetrend},
+                                          {"inject", required_argument, nullptr, kInject},       {"inject-train", required_argument, nullptr, kInjectTrain},
+                                          {"inject-out", required_argument, nullptr, kInjectOut},
                                           {nullptr, 0, nullptr, 0}};
     // a non-negative integer that fills its whole field; anything else marks the command line as malformed
     auto number = [&long_bad](const char* text, const char** end, int* out) {
@@ -202,6 +215,27 @@ int main(int argc, char* argv[])
                 folds.push_back(fs);
                 break;
             }
+            case kInject:
+            case kInjectTrain: {   // four to six numbers between colons
+                inject_spec sp;
+                const char* at = optarg;
+                for (;;) {
+                    char* e = nullptr;
+                    const double v = strtod(at, &e);
+                    if (e == at || sp.n == 6 || !std::isfinite(v)) {
+                        inj_bad = true;
+                        break;
+                    }
+                    sp.v[sp.n++] = v;
+                    at = e;
+                    if (*at != ':') break;
+                    at++;
+                }
+                if (*at || sp.n < 4) inj_bad = true;
+                (arg == kInject ? inj_bursts : inj_trains).push_back(sp);
+                break;
+            }
+            case kInjectOut: inj_path = optarg; break;
             case kFoldDm: {
                 char* e = nullptr;
                 fold_dms.push_back(strtod(optarg, &e));
@@ -428,6 +462,13 @@ int main(int argc, char* argv[])
                              "                         dedispersed at DM pc/cc [0] (the k-th --fold-dm belongs to the k-th --fold; up to 4 --fold), into N [64] phase\n"
                              "                         bins (2 .. 4096); a dump to FILE whenever ROWS [one block's] rows or more have been folded (with -X: FILE.<rank>);\n"
                              "                         --fold without -M, the others without --fold, more than 4 --fold or malformed numbers: a usage error\n"
+                             " --inject T0:DM:BEAM:FLUENCE[:SIGMA[:W]] [--inject-train F0:DM:BEAM:AMP[:DUTY[:BINS]]] [--inject-out FILE]   with -M: synthetic pulses\n"
+                             "                         added to the detected rows in front of the DM stage (and of -n): a burst whose window of W rows [the smallest\n"
+                             "                         power of two >= 8 SIGMA] starts at row T0 in the highest channel, dispersed at DM pc/cc, a Gaussian of SIGMA [1] rows\n"
+                             "                         of FLUENCE per channel in beam BEAM (any number of --inject); a pulse train at spin frequency F0 Hz, a boxcar of\n"
+                             "                         max(1, round(DUTY BINS)) of BINS [64] phase bins (DUTY [0.05]) of height AMP (up to 4 --inject-train); one line of\n"
+                             "                         truth per pulse to FILE (id kind t0|f0 dm trial beam ...; with -X: FILE.<rank>); an injection option without -M,\n"
+                             "                         --inject-out without a pulse, more than 4 trains or malformed numbers: a usage error\n"
                              " --ffa P_LO:P_HI [--ffa-seg N] [--ffa-dec N] [--ffa-oct N] [--ffa-widths K] [--ffa-snr SNR] [--ffa-out FILE] [--ffa-detrend BLK:WIN]\n"
                              "                         with -M: a blind periodicity search (Fast Folding Algorithm) of every DM trial and beam: the chunks decimated by --ffa-dec [1],\n"
                              "                         cut into segments of --ffa-seg [1024] samples, folded at the base periods P_LO <= p < P_HI (8 .. 512 samples)\n"
@@ -461,6 +502,37 @@ int main(int argc, char* argv[])
         (!folds.empty() && (fold_bins < 2 || fold_bins > BF_PSR_MAX_BINS || fold_rows < 0))) {
         fprintf(stderr, "beam: --fold F0[:F1[:PHASE0]] (at most %d), --fold-dm DM >= 0 (one per --fold at most), --fold-bins 2 .. %d, --fold-rows ROWS: "
                         "malformed, too many or out of range\n", BF_PSR_MAX_PULSARS, BF_PSR_MAX_BINS);
+        return EXIT_FAILURE;
+    }
+    const bool inj_given = !inj_bursts.empty() || !inj_trains.empty();
+    if ((inj_given || !inj_path.empty()) && !(dm_max > 0.0)) {
+        fprintf(stderr, "beam: --inject / --inject-train / --inject-out (pulse injection) require the DM stage: give -M dm_max\n");
+        return EXIT_FAILURE;
+    }
+    if (!inj_given && !inj_path.empty()) {
+        fprintf(stderr, "beam: --inject-out belongs to the pulse injection: give --inject T0:DM:BEAM:FLUENCE or --inject-train F0:DM:BEAM:AMP\n");
+        return EXIT_FAILURE;
+    }
+    {   // the ranges that need no geometry: whole numbers where whole numbers go, DM >= 0, SIGMA > 0, W and BINS within the stage's bounds
+        auto whole = [](double v, double lo, double hi) { return v >= lo && v <= hi && v == std::floor(v); };
+        for (inject_spec& sp : inj_bursts) {
+            if (sp.n < 5) sp.v[4] = 1.0;
+            if (sp.n < 6) {
+                double w = 1.0;
+                while (w < 8.0 * sp.v[4] && w <= (double)BF_INJ_MAX_WIDTH) w *= 2.0;
+                sp.v[5] = w;
+            }
+            if (!whole(sp.v[0], 0, 9e15) || !(sp.v[1] >= 0.0) || !whole(sp.v[2], 0, 1e9) || !(sp.v[4] > 0.0) || !whole(sp.v[5], 1, BF_INJ_MAX_WIDTH)) inj_bad = true;
+        }
+        for (inject_spec& sp : inj_trains) {
+            if (sp.n < 5) sp.v[4] = 0.05;
+            if (sp.n < 6) sp.v[5] = 64.0;
+            if (!(sp.v[1] >= 0.0) || !whole(sp.v[2], 0, 1e9) || !(sp.v[4] > 0.0 && sp.v[4] <= 1.0) || !whole(sp.v[5], 2, BF_PSR_MAX_BINS)) inj_bad = true;
+        }
+    }
+    if (inj_bad || inj_trains.size() > (size_t)BF_INJ_MAX_TRAINS || inj_bursts.size() + inj_trains.size() > (size_t)BF_INJ_MAX_PULSES) {
+        fprintf(stderr, "beam: --inject T0:DM:BEAM:FLUENCE[:SIGMA[:W]], --inject-train F0:DM:BEAM:AMP[:DUTY[:BINS]] (at most %d): malformed, too many or out of range\n",
+                BF_INJ_MAX_TRAINS);
         return EXIT_FAILURE;
     }
     if (ffa_given && !(dm_max > 0.0)) {
@@ -1030,6 +1102,73 @@ int main(int argc, char* argv[])
             }
             std::cout << "Pulsar folder: " << n_psr << " pulsars, " << fold_bins << " bins, a dump every " << oopt.psr_dump_rows << " rows of " << tsamp_ms
                       << " ms" << std::endl;
+        }
+        inj_plan iplan;
+        if (inj_given && my_trials > 0 && (!comm || rank == 0 || oopt.dm_split_trials)) {   // --inject: the injector runs where the DM stage runs
+            const int n_f = full_cfg.n_freq, n_b = pcfg.n_beams;
+            std::vector<float> freq((size_t)n_f);
+            for (int c = 0; c < n_f; c++) freq[(size_t)c] = channel_frequency_weights(opt.gpu, c);
+            FILE* truth = nullptr;
+            if (!inj_path.empty()) {
+                if (oopt.dm_split_trials) inj_path += "." + std::to_string(rank);
+                truth = fopen(inj_path.c_str(), "w");
+                if (!truth) {
+                    fprintf(stderr, "beam: could not open %s\n", inj_path.c_str());
+                    return EXIT_FAILURE;
+                }
+                fprintf(truth, "# id kind t0|f0 dm trial beam fluence|amp sigma|duty w|bins [t_lo t_hi]\n");
+            }
+            // delays of one pulse at the run's channel frequencies and -T, as --fold-dm takes them; its nearest trial of the whole ladder
+            auto delays_of = [&](double dm, std::vector<int32_t>* d, int* trial) {
+                d->resize((size_t)n_f);
+                dm_delays(&dm, 1, freq.data(), n_f, freq[0], tsamp_ms, d->data());
+                return bf_inj_nearest_trial(delays.data(), n_dm, n_f, d->data(), trial);
+            };
+            bool ok = true;
+            uint64_t id = 0;
+            for (const inject_spec& sp : inj_bursts) {
+                inj_plan::burst b;
+                int trial = -1;
+                b.t0 = (int64_t)sp.v[0];
+                b.W = (int)sp.v[5];
+                ok = ok && sp.v[2] < n_b && delays_of(sp.v[1], &b.delay, &trial) == BF_OK;
+                b.profile.resize((size_t)n_f * (size_t)b.W);
+                const std::vector<double> fluence((size_t)n_f, sp.v[3]);
+                ok = ok && bf_inj_burst_profile(n_f, b.W, (b.W - 1) / 2.0, sp.v[4], nullptr, fluence.data(), b.profile.data()) == BF_OK;
+                b.response.assign((size_t)n_b, 0.0f);
+                if (ok) b.response[(size_t)sp.v[2]] = 1.0f;
+                if (ok && truth)
+                    fprintf(truth, "%llu burst %lld %.17g %d %d %.17g %.17g %d %lld %lld\n", (unsigned long long)id, (long long)b.t0, sp.v[1], trial, (int)sp.v[2],
+                            sp.v[3], sp.v[4], b.W, (long long)b.t0, (long long)b.t0 + b.W - 1);
+                id++;
+                iplan.bursts.push_back(std::move(b));
+            }
+            for (const inject_spec& sp : inj_trains) {
+                inj_plan::train t;
+                int trial = -1;
+                t.n_bins = (int)sp.v[5];
+                ok = ok && sp.v[2] < n_b && delays_of(sp.v[1], &t.delay, &trial) == BF_OK;
+                ok = ok && bf_psr_model_from_spin(sp.v[0], 0.0, 0.0, tsamp_ms * 1e-3, 0, &t.model) == BF_OK;
+                const int on = std::max(1, (int)std::lround(sp.v[4] * t.n_bins));
+                t.profile.assign((size_t)n_f * (size_t)t.n_bins, 0.0f);
+                for (int f = 0; f < n_f; f++)
+                    for (int j = 0; j < on; j++) t.profile[(size_t)f * (size_t)t.n_bins + (size_t)j] = (float)sp.v[3];
+                t.response.assign((size_t)n_b, 0.0f);
+                if (ok) t.response[(size_t)sp.v[2]] = 1.0f;
+                if (ok && truth)
+                    fprintf(truth, "%llu train %.17g %.17g %d %d %.17g %.17g %d\n", (unsigned long long)id, sp.v[0], sp.v[1], trial, (int)sp.v[2], sp.v[3], sp.v[4],
+                            t.n_bins);
+                id++;
+                iplan.trains.push_back(std::move(t));
+            }
+            if (truth) fclose(truth);
+            if (!ok) {
+                fprintf(stderr, "beam: --inject / --inject-train: BEAM must be below the %d beams of this run, and the pulse must fit its window (%s)\n", n_b,
+                        bf_last_error());
+                return EXIT_FAILURE;
+            }
+            oopt.inj = &iplan;
+            std::cout << "Injector: " << iplan.bursts.size() << " bursts and " << iplan.trains.size() << " trains in front of the DM stage" << std::endl;
         }
         std::unique_ptr<ffa_file_sink> ffa_out;
         if (ffa_given && my_trials > 0 && (!comm || rank == 0 || oopt.dm_split_trials)) {   // --ffa: the search runs where the DM stage runs

@@ -52,6 +52,7 @@ struct bf_dm_stream : bf_stage {
     bf_cond* cond = nullptr;      // bf_dm_stream_attach_conditioner: every push's new rows are conditioned in place, before `rows_ready` is recorded
     bf_psr* fold = nullptr;       // bf_dm_stream_attach_folder: every push's new rows are also folded where they lie, before `done` is recorded
     bf_ffa* ffa = nullptr;        // bf_dm_stream_attach_periodicity: every chunk is also pushed into this stage, before `done` is recorded
+    bf_inj* inj = nullptr;        // bf_dm_stream_attach_injector: every push's new rows get the live pulses added in place, in front of the conditioner
     // bf_dm_stream_cut (docs/EVENTS.md section 2): the end of the most recent cut, recorded behind the cut before it.  The producer of
     // the rows of a later push waits for it wherever it waits for done[old]: it cannot overwrite what a cut queued before it reads.
     hipEvent_t cut_done = nullptr;
@@ -62,7 +63,7 @@ struct bf_dm_stream : bf_stage {
     std::vector<int32_t> trial_delay;   // [n_dm]: max over f of delay[dm][f] -- the rows a stamp of that trial needs beyond its times
 };
 
-// One link to an attached stage: the member of the DM stage (search, cond, fold, ffa) and that stage's feeder, set and cleared together.
+// One link to an attached stage: the member of the DM stage (search, cond, fold, ffa, inj) and that stage's feeder, set and cleared together.
 template <class T>
 static void set_link(bf_dm_stream* dm, T*& member, T* to)
 {
@@ -79,6 +80,7 @@ void dsabf::rt::dm_stream_drop(bf_dm_stream* dm, bf_stage* attached)
     if (dm->cond && as_stage(dm->cond) == attached) set_link<bf_cond>(dm, dm->cond, nullptr);
     if (dm->fold && as_stage(dm->fold) == attached) set_link<bf_psr>(dm, dm->fold, nullptr);
     if (dm->ffa && as_stage(dm->ffa) == attached) set_link<bf_ffa>(dm, dm->ffa, nullptr);
+    if (dm->inj && as_stage(dm->inj) == attached) set_link<bf_inj>(dm, dm->inj, nullptr);
 }
 
 // The ring is no hipMalloc: it is unmapped and released here, behind the wait for everything in flight, and the stage's resource
@@ -89,6 +91,7 @@ void bf_dm_stream::release_device()
     set_link<bf_cond>(this, cond, nullptr);
     set_link<bf_psr>(this, fold, nullptr);
     set_link<bf_ffa>(this, ffa, nullptr);
+    set_link<bf_inj>(this, inj, nullptr);
     res.wait();
     if (mapped0) (void)hipMemUnmap(d_buf, phys_bytes);
     if (mapped1) (void)hipMemUnmap(reinterpret_cast<char*>(d_buf) + phys_bytes, phys_bytes);
@@ -326,6 +329,17 @@ int bf_dm_stream_attach_periodicity(bf_dm_stream* dm, bf_ffa* f)
     return BF_OK;
 }
 
+int bf_dm_stream_attach_injector(bf_dm_stream* dm, bf_inj* inj)
+{
+    if (!dm) return fail(BF_ERR_INVALID, "NULL argument");
+    if (int rc = orphaned(dm)) return rc;
+    if (inj == dm->inj) return BF_OK;
+    if (inj)
+        if (int rc = inj_check_attach(inj, dm->h, dm->n_freq, dm->max_rows, dm->pushed)) return rc;
+    set_link(dm, dm->inj, inj);
+    return BF_OK;
+}
+
 int bf_dm_stream_output_device(bf_dm_stream* s, float** d_out)
 {
     if (!s || !d_out) return fail(BF_ERR_INVALID, "NULL argument");
@@ -411,6 +425,9 @@ int bf_dm_stream_push(bf_dm_stream* s, const float* d_rows, int n_rows, float* h
         if (emits)
             if (int rc = ffa_check_push(s->ffa, (int)emits)) return rc;
     }
+    // an attached injector refuses what it would refuse of these rows (a train's oscillator range) HERE too
+    if (s->inj)
+        if (int rc = inj_check_apply(s->inj, n_rows)) return rc;
     bf_handle* h = s->h;
     ON_DEVICE(h);
     hipStream_t q = as_stream(hip_stream);
@@ -446,6 +463,12 @@ int bf_dm_stream_push(bf_dm_stream* s, const float* d_rows, int n_rows, float* h
     // event, so they see them conditioned; and conditioner j + 1 runs behind conditioner j (the stage's own event chain, and this
     // wait).  In the ring the rows may run past cap_rows into the second mapping: one contiguous range, taken as such.  The linear
     // buffer has no rows_ready: there the whole push already runs behind the previous one.
+    // The injector's hook (docs/INJECTION.md section 2) stands in the same place, one step earlier: the live pulses are added to the
+    // new rows where they lie, so the conditioner -- and through rows_ready everything else -- sees them as it would see real ones.
+    // The argument above covers it word for word; the injector needs no chain of its own, it carries nothing from push to push.
+    // (Like the conditioner it has rewritten the rows once issued: if a LATER step of this call fails, detach or destroy.)
+    if (s->inj)
+        if (int rc = inj_apply(s->inj, new_rows, n_rows, q)) return rc;
     if (s->cond)
         if (int rc = bf_cond_push(s->cond, new_rows, n_rows, q)) return rc;
     if (s->ring) {

@@ -1,5 +1,5 @@
 // bf_runtime_internal.h -- what the C-ABI runtime's translation units share (bf_runtime.cpp, bf_queues.cpp, bf_dm_stream.cpp,
-// bf_sps.cpp, bf_cond.cpp, bf_accum.cpp, bf_corr.cpp, bf_sk.cpp, bf_stokes.cpp, bf_psr.cpp, bf_ffa.cpp, bf_evt.cpp, bf_bench_abi.cpp): the handle, the base of its stages,
+// bf_sps.cpp, bf_cond.cpp, bf_accum.cpp, bf_corr.cpp, bf_sk.cpp, bf_stokes.cpp, bf_psr.cpp, bf_ffa.cpp, bf_inj.cpp, bf_evt.cpp, bf_bench_abi.cpp): the handle, the base of its stages,
 // the accumulator stage under the correlator and the voltage moments, the error string, the device scope.
 // Host-only and not installed: no .hip / .hpp file includes it.
 #pragma once
@@ -94,11 +94,11 @@ struct bf_resources {
     void release();
 };
 
-// The base of the eight stage objects (bf_dm_stream, bf_sps, bf_cond, bf_corr, bf_sk, bf_stokes, bf_psr, bf_ffa: opaque to callers, each defined in its own file).
+// The base of the nine stage objects (bf_dm_stream, bf_sps, bf_cond, bf_corr, bf_sk, bf_stokes, bf_psr, bf_ffa, bf_inj: opaque to callers, each defined in its own file).
 struct bf_stage {
     bf_handle* h = nullptr;                 // NULL: the handle went first and took the device side with it
     const char* const noun;                 // "DM stage", "search stage", ...: the orphan check's message
-    struct bf_dm_stream* feeder = nullptr;  // search stage, conditioner, pulsar folder, periodicity stage: the DM stage it is attached to
+    struct bf_dm_stream* feeder = nullptr;  // search stage, conditioner, pulsar folder, periodicity stage, injector: the DM stage it is attached to
     bool ring = false;                      // DM stage: its buffer is the twice-mapped ring (bf_get_counter "dm_ring_stages")
     bf_resources res;
     explicit bf_stage(const char* noun_) : noun(noun_) {}
@@ -179,11 +179,12 @@ template <class Stage> int accum_create(bf_handle* h, int max_in_flight, Stage**
     *out = s;
     return BF_OK;
 }
-// The link "attached to a DM stage" has two ends: a member of the DM stage (search, cond, folder, periodicity) and the feeder of the stage it points at.
+// The link "attached to a DM stage" has two ends: a member of the DM stage (search, cond, folder, periodicity, injector) and the feeder of the stage it points at.
 bf_stage* as_stage(struct bf_sps* s);                   // bf_sps.cpp
 bf_stage* as_stage(struct bf_cond* c);                  // bf_cond.cpp
 bf_stage* as_stage(struct bf_psr* p);                   // bf_psr.cpp
 bf_stage* as_stage(struct bf_ffa* s);                   // bf_ffa.cpp
+bf_stage* as_stage(struct bf_inj* s);                   // bf_inj.cpp
 void dm_stream_drop(struct bf_dm_stream* dm, bf_stage* attached);   // bf_dm_stream.cpp: `attached` is going away
 int sps_check_attach(const struct bf_sps* s, const bf_handle* h, int n_dm, int max_rows);            // bf_dm_stream_attach_search's conditions
 int sps_max_in_flight(const struct bf_sps* s);
@@ -192,6 +193,10 @@ int psr_check_attach(const struct bf_psr* p, const bf_handle* h, int n_freq_tota
 int psr_check_push(const struct bf_psr* p, int n_rows);   // what bf_psr_push refuses about a push of n_rows rows, before anything is queued
 int ffa_check_attach(const struct bf_ffa* s, const bf_handle* h, int n_dm, int max_rows);            // bf_dm_stream_attach_periodicity's conditions
 int ffa_check_push(const struct bf_ffa* s, int n_t);      // what bf_ffa_push refuses about a push of n_t times, before anything is queued
+// bf_dm_stream_attach_injector's conditions: the three above, and that the injector has applied exactly the `pushed` rows of the DM stage
+int inj_check_attach(const struct bf_inj* s, const bf_handle* h, int n_freq_total, int max_rows, uint64_t pushed);
+int inj_check_apply(const struct bf_inj* s, int n_rows);   // what bf_inj_apply refuses about an apply of n_rows rows, before anything is queued
+int inj_apply(struct bf_inj* s, float* d_rows, int n_rows, hipStream_t q);   // the apply behind that check: bf_inj_apply, and the DM stage's hook
 
 // Makes `device` current for the duration of one entry point and puts the caller's device back afterwards: a library
 // call must not change the current device of a multi-device host process (torch's included).

@@ -206,6 +206,7 @@ struct run_resources {
     bf_cond* cond = nullptr;
     bf_psr* psr = nullptr;
     bf_ffa* ffa = nullptr;
+    bf_inj* inj = nullptr;
     bf_corr* corr = nullptr;
     bf_sk* sk = nullptr;
     bf_stokes* stokes = nullptr;
@@ -222,6 +223,7 @@ struct run_resources {
         bf_cond_destroy(cond);
         bf_psr_destroy(psr);
         bf_ffa_destroy(ffa);
+        bf_inj_destroy(inj);
         bf_dm_stream_destroy(dm);
         for (void* p : pinned) bf_free_pinned(p);
         bf_destroy(h);
@@ -525,6 +527,18 @@ int check_options(const bf_config& cfg, const observation_options& opt)
     if (opt.n_psr && (opt.psr_bins < 2 || opt.psr_bins > BF_PSR_MAX_BINS || opt.psr_dump_rows < 1))
         return set_error(BF_ERR_INVALID, "run_observation: the pulsar folder needs psr_bins in 2 .. 4096 and psr_dump_rows >= 1");
     if (!opt.n_psr && opt.psr_sink) return set_error(BF_ERR_INVALID, "run_observation: a psr_sink needs n_psr > 0");
+    if (opt.inj && !opt.dm_delays) return set_error(BF_ERR_INVALID, "run_observation: pulse injection needs the DM stage (dm_delays)");
+    if (opt.inj) {   // the tables' sizes: the whole band (every rank that dedisperses injects all of it), the handle's beams
+        const size_t band = (size_t)cfg.n_freq * (size_t)(opt.comm ? opt.world : 1);
+        for (const inj_plan::burst& b : opt.inj->bursts)
+            if (b.W < 1 || b.delay.size() != band || b.profile.size() != band * (size_t)b.W || b.response.size() != (size_t)cfg.n_beams)
+                return set_error(BF_ERR_INVALID, "run_observation: an injected burst needs W >= 1, delay [band], profile [band][W] and response [n_beams]");
+        for (const inj_plan::train& t : opt.inj->trains)
+            if (t.n_bins < 2 || t.delay.size() != band || t.profile.size() != band * (size_t)t.n_bins || t.response.size() != (size_t)cfg.n_beams)
+                return set_error(BF_ERR_INVALID, "run_observation: an injected train needs n_bins >= 2, delay [band], profile [band][n_bins] and response [n_beams]");
+        if (opt.inj->trains.size() > (size_t)BF_INJ_MAX_TRAINS || opt.inj->size() > (size_t)BF_INJ_MAX_PULSES)
+            return set_error(BF_ERR_INVALID, "run_observation: the injection plan holds more than BF_INJ_MAX_TRAINS trains or BF_INJ_MAX_PULSES pulses");
+    }
     if (opt.ffa_p_hi < 0) return set_error(BF_ERR_INVALID, "run_observation: ffa_p_hi must be 0 (off) or the end of the period range");
     if (opt.ffa_p_hi && !opt.dm_delays) return set_error(BF_ERR_INVALID, "run_observation: the periodicity search needs the DM stage (dm_delays)");
     if (!opt.ffa_p_hi && opt.ffa_sink) return set_error(BF_ERR_INVALID, "run_observation: an ffa_sink needs ffa_p_hi > 0");
@@ -730,6 +744,23 @@ struct production_run {
                 float* chunk = nullptr;
                 if ((rc = dev.alloc_pinned((size_t)plan.dm_count * plan.dm_rows * cfg.n_beams, &chunk)) != BF_OK) return rc;
                 dm_host.push_back(chunk);
+            }
+            if (opt.inj && opt.inj->size()) {   // the injector: in front of the conditioner, on the rows in the stage's buffer (docs/INJECTION.md)
+                int max_width = 1;
+                for (const inj_plan::burst& b : opt.inj->bursts) max_width = std::max(max_width, b.W);
+                for (const inj_plan::train& t : opt.inj->trains) max_width = std::max(max_width, t.n_bins);
+                rc = bf_inj_create(dev.h, plan.n_freq_band, plan.dm_rows, (int)opt.inj->size(), max_width, &dev.inj);
+                // every pulse before the first push: the bursts' ids first, then the trains'
+                for (size_t i = 0; rc == BF_OK && i < opt.inj->bursts.size(); i++) {
+                    const inj_plan::burst& b = opt.inj->bursts[i];
+                    rc = bf_inj_add_burst(dev.inj, b.t0, b.W, b.delay.data(), b.profile.data(), b.response.data(), nullptr);
+                }
+                for (size_t i = 0; rc == BF_OK && i < opt.inj->trains.size(); i++) {
+                    const inj_plan::train& t = opt.inj->trains[i];
+                    rc = bf_inj_add_train(dev.inj, &t.model, t.first_row, t.n_rows, t.n_bins, t.delay.data(), t.profile.data(), t.response.data(), nullptr);
+                }
+                if (rc == BF_OK) rc = bf_dm_stream_attach_injector(dev.dm, dev.inj);
+                if (rc != BF_OK) return gpu_error(log, rc);
             }
             if (opt.cond_baseline > 0) {   // the conditioner: in front of the DM stage, on the rows in its buffer (docs/CONDITIONING.md)
                 bf_cond_options co;
@@ -1197,6 +1228,7 @@ int run_observation(const bf_config& cfg, const observation_options& opt, block_
         res->sk_dumps = run.sk.dumps;
         res->stokes_units = run.stokes_units;
         res->psr_dumps = run.psr_dumps;
+        res->inj_pulses = run.dev.inj ? (uint64_t)opt.inj->size() : 0;
         res->ffa_segments = run.ffa_segments;
         res->ffa_candidates = run.ffa_candidates;
         res->cond_masked = run.cond_masked_channels();
@@ -1221,6 +1253,9 @@ int run_observation(const bf_config& cfg, const observation_options& opt, block_
     if (run.dev.stokes)
         log << "Stokes beams: " << opt.stokes_beams.size() << " beams, windows of " << (opt.stokes_int ? opt.stokes_int : cfg.n_avg) << " samples, "
             << run.stokes_units << " gemm-units" << std::endl;
+    if (run.dev.inj)
+        log << "Injector: " << opt.inj->bursts.size() << " bursts and " << opt.inj->trains.size() << " trains added to the rows in front of the DM stage, "
+            << bf_inj_launches(run.dev.inj) << " kernels launched" << std::endl;
     if (run.dev.psr)
         log << "Pulsar folder: " << opt.n_psr << " pulsars, " << opt.psr_bins << " bins, " << run.psr_dumps << " dumps of at least " << opt.psr_dump_rows
             << " rows each (an incomplete integration at the end is dropped)" << std::endl;

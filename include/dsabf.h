@@ -877,6 +877,68 @@ int bf_ffa_detrend(const bf_ffa *s, int *blk, int *win);
 int bf_ffa_sift(const bf_ffa_candidate *in, size_t n, double tol, int max_harm, int dm_tol, bf_ffa_group *out, size_t max_out,
                 size_t *n_out);
 
+/* ---- Pulse injection: test bursts and pulse trains in front of the DM stage (docs/INJECTION.md) -----------------------------
+ * The reference is there to "search for FRBs in real time" (README.md:11) and ends at a DM-0 collapse (src/beamformer.cu:498-510);
+ * nothing in it, and until here nothing in this library, puts a dispersed pulse into the stream to show that the chain finds it.
+ * A bf_inj adds synthetic pulses to the detected rows x[row][freq][beam] (fp32, the layout bf_dm_stream_push takes, n_beams = the
+ * handle's, n_beams % 4 == 0) in place; docs/INJECTION.md section 1 is the contract, to the bit:
+ *   rows r count from the first row the stage is given; bf_inj_next_row: the rows applied so far (host arithmetic).
+ *   burst (t0 >= 0, W 1 .. max_width, HOST tables delay int32 [n_freq_total] >= 0 -- one row of dsabf::dm_delays / bfh_dm_delays --,
+ *     profile float [n_freq_total][W], response float [n_beams]): every cell with i = r - t0 - delay[f], 0 <= i < W, becomes
+ *     x = fl(x + fl(profile[f][i] response[b])): one fp32 multiply, one fp32 add, never contracted, a zero response included.
+ *   train (a bf_psr_model, n_bins 2 .. min(max_width, BF_PSR_MAX_BINS), profile [n_freq_total][n_bins]): for first_row <= r <
+ *     first_row + n_rows (n_rows == UINT64_MAX: until the end)  x = fl(x + fl(profile[f][bin(r, f)] response[b])), bin the folder's
+ *     formula operation for operation (n = r - epoch_row - delay[f]); at most BF_INJ_MAX_TRAINS alive; an apply that would reach
+ *     |n| >= 2^31 on a covered row is refused as bf_psr_push refuses it.
+ *   a cell outside every window is NOT WRITTEN.  Order at a cell: the bursts that cover it in ascending id, then the trains in
+ *     ascending id; *id (may be NULL) counts adds of either kind from 0.  The bits do not depend on how the series is cut into
+ *     applies, on queues or on launch shapes.
+ *   lifetime of a pulse: an add whose first touched row (t0 + min delay; first_row) lies before bf_inj_next_row is refused with
+ *     BF_ERR_STATE, as is one beyond max_pulses (1 .. BF_INJ_MAX_PULSES) live pulses or BF_INJ_MAX_TRAINS live trains; a burst is
+ *     spent once next_row > t0 + max delay + W - 1, a train once its last row is behind next_row, and gives its slot back.  An add may
+ *     be called while earlier applies still run on the device: it never writes memory a queued kernel may read.
+ * bf_inj_apply takes rows [next_row, next_row + n_rows) at d_rows (16-byte aligned), asynchronously on hip_stream; the stage keeps no
+ *   device state from one apply to the next, so applies on different queues need no ordering among themselves.  An apply that no
+ *   live pulse overlaps launches nothing and reads nothing; one that bursts overlap reads and writes only rows inside some window.
+ *   bf_inj_launches: the kernels launched so far.  An attached injector is applied by the DM stage: bf_inj_apply then answers BF_ERR_STATE.
+ * bf_dm_stream_attach_injector(dm, inj) (NULL detaches): from then on every bf_dm_stream_push adds the live pulses to its new rows
+ *   where they lie in the DM stage's buffer, behind the copy-in and in front of an attached conditioner -- the caller's source rows
+ *   stay raw, everything downstream sees the pulses.  Same handle, same n_freq_total, max_rows_per_push >= the DM stage's, and
+ *   bf_inj_next_row == the rows the DM stage has been pushed (else BF_ERR_STATE).
+ * BF_ERR_INVALID, with nothing allocated or launched: NULL pointers, a negative delay, t0 < 0, W or n_bins out of range, max_pulses
+ *   or max_width outside 1 .. 4096, n_rows outside 1 .. max_rows_per_push.  Lifetime as for a bf_cond: a handle that goes first
+ *   releases the device memory, the stage then answers BF_ERR_STATE and can still be destroyed; destroying an attached injector detaches it.
+ * Host helpers (fp64, no GPU):
+ * bf_inj_burst_profile: per channel, s = smear[f] (rows of intra-channel smearing, >= 1; smear == NULL: 1),
+ *   g[i] = (1 / s) sum_{j < s} exp(-(i - centre - j + (s - 1) / 2)^2 / (2 sigma^2)), j ascending; N = sum_i g[i], i ascending;
+ *   profile[f][i] = (float)(fluence[f] (g[i] / N)).  N == 0 (the window misses the pulse), sigma not > 0, NaN: BF_ERR_INVALID.
+ * bf_inj_nearest_trial: the trial d of ladder int32 [n_dm][n_freq_total] that minimises sum_f |ladder[d][f] - delay[f]| (int64; ties: lowest d).
+ * bf_inj_match: candidate c matches truth k iff c.beam == beam, |c.dm - trial| <= dm_tol and [c.t_start, c.t_start + c.width - 1]
+ *   meets [t_lo - t_tol, t_hi + t_tol]; best[k] = the matching candidate with the largest snr (ties: lower index), -1 if none. */
+#define BF_INJ_MAX_PULSES 4096
+#define BF_INJ_MAX_WIDTH 4096
+#define BF_INJ_MAX_TRAINS 4
+typedef struct bf_inj bf_inj;
+typedef struct bf_inj_truth {
+    uint64_t t_lo, t_hi; /* first and last output time the pulse occupies at its trial */
+    int32_t trial, beam;
+} bf_inj_truth;
+int bf_inj_create(bf_handle *h, int n_freq_total, int max_rows_per_push, int max_pulses, int max_width, bf_inj **out);
+int bf_inj_destroy(bf_inj *s);
+int bf_inj_add_burst(bf_inj *s, int64_t t0, int W, const int32_t *delay, const float *profile, const float *response,
+                     uint64_t *id);
+int bf_inj_add_train(bf_inj *s, const bf_psr_model *model, uint64_t first_row, uint64_t n_rows, int n_bins,
+                     const int32_t *delay, const float *profile, const float *response, uint64_t *id);
+int bf_inj_apply(bf_inj *s, float *d_rows, int n_rows, void *hip_stream);
+uint64_t bf_inj_next_row(const bf_inj *s);
+uint64_t bf_inj_launches(const bf_inj *s);
+int bf_inj_burst_profile(int n_freq_total, int W, double centre, double sigma, const int32_t *smear, const double *fluence,
+                         float *profile);
+int bf_inj_nearest_trial(const int32_t *ladder, int n_dm, int n_freq_total, const int32_t *delay, int *trial);
+int bf_inj_match(const bf_inj_truth *truth, size_t n, const bf_sps_candidate *cands, size_t m, uint64_t t_tol,
+                 int32_t dm_tol, int32_t *best);
+int bf_dm_stream_attach_injector(bf_dm_stream *dm, bf_inj *inj);
+
 /* ---- Multi-GPU: frequency shards and the gather of their detected powers -------------------------------
  * The reference runs 8 independent processes, one sub-band per GPU (`-g`, src/beamformer.cu:92-100,233; README.md:168)
  * and never brings their outputs together.  Here a handle may own any contiguous range of frequencies (bf_config.n_freq

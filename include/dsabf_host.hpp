@@ -1018,6 +1018,30 @@ int null_vis_file(const char* vis_path, const char* null_path, const bf_null_opt
 int set_weights_conditioned(bf_handle* h, int device, const int8_t* w, const double* gains_layer, const null_vectors* nulls, int8_t* w_set = nullptr,
                             const uint8_t* ant_flags = nullptr);
 
+// ---- Pulse injection in front of the DM stage (include/dsabf.h: bf_inj_*, bf_dm_stream_attach_injector; docs/INJECTION.md) -------------
+// A plain container: the bursts and trains of a run with their host tables, as bf_inj_add_burst / bf_inj_add_train take them.
+// observation_options::inj points at one; run_observation adds the bursts in order (ids 0 ..), then the trains.
+struct inj_plan {
+    struct burst {
+        int64_t t0 = 0;
+        int W = 0;
+        std::vector<int32_t> delay;    // [band]: one row of dm_delays
+        std::vector<float> profile;    // [band][W]
+        std::vector<float> response;   // [n_beams]
+    };
+    struct train {
+        bf_psr_model model = {0, 0, 0, 0};
+        uint64_t first_row = 0, n_rows = UINT64_MAX;   // UINT64_MAX: until the end
+        int n_bins = 0;
+        std::vector<int32_t> delay;    // [band]
+        std::vector<float> profile;    // [band][n_bins]
+        std::vector<float> response;   // [n_beams]
+    };
+    std::vector<burst> bursts;
+    std::vector<train> trains;
+    size_t size() const { return bursts.size() + trains.size(); }
+};
+
 struct observation_options {
     int gpu = 0;          // -g
     int device = 0;
@@ -1106,6 +1130,12 @@ struct observation_options {
     int psr_bins = 64;
     int psr_dump_rows = 0;
     dsabf::psr_sink* psr_sink = nullptr;
+    // Pulse injection in front of the DM stage (docs/INJECTION.md; needs dm_delays): a plan of bursts and trains (NULL or empty = off) whose
+    // tables span the whole band (cfg.n_freq * world channels) and cfg.n_beams beams.  A bf_inj of exactly the plan's size is created next to
+    // the DM stage, every pulse is added before the first push (the bursts' ids first), and it is attached: the pulses are added to every
+    // pushed block where it lies in the stage's buffer, in front of the conditioner; the detected sinks keep the raw stream.  On a sharded
+    // run every rank that dedisperses injects the whole band: redundant and identical, as the folder folds.
+    const dsabf::inj_plan* inj = nullptr;
     // Periodicity search behind the DM stage (docs/PERIODICITY.md; needs dm_delays): ffa_p_hi > 0 switches it on.  The chunks of this
     // rank's trials are decimated by ffa_dec and cut into segments of ffa_seg samples; every segment is folded at the base periods
     // ffa_p_lo <= p < ffa_p_hi of ffa_oct octaves with ffa_widths boxcar widths (the bounds of bf_ffa_create).  The stage is created
@@ -1161,6 +1191,7 @@ struct observation_result {
     uint64_t sk_dumps = 0;          // integrations the moments stage dumped (sk_blocks > 0)
     uint64_t stokes_units = 0;      // gemm-units the Stokes stage delivered (stokes_beams non-empty)
     uint64_t psr_dumps = 0;         // integrations the pulsar folder dumped (n_psr > 0)
+    uint64_t inj_pulses = 0;        // pulses the injector was given (inj set and not empty)
     uint64_t ffa_segments = 0;      // segments the periodicity search collected (ffa_p_hi > 0)
     uint64_t ffa_candidates = 0;    // ... and the candidates they gave
     int cond_masked = -1;           // channels the conditioner masked in the last push (cond_baseline > 0 and a block analysed), else -1
