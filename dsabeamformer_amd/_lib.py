@@ -122,6 +122,12 @@ class BfStampRequest(C.Structure):
     _fields_ = [("t0", C.c_uint64), ("dm", C.c_int32), ("beam", C.c_int32)]
 
 
+class BfVcutRequest(C.Structure):
+    """Mirror of ``bf_vcut_request`` (include/dsabf.h)."""
+
+    _fields_ = [("t0", C.c_uint64), ("dm", C.c_int32), ("pad", C.c_int32)]
+
+
 class BfCalOptions(C.Structure):
     """Mirror of ``bf_cal_options`` (include/dsabf.h)."""
 
@@ -264,6 +270,14 @@ SIGNATURES = {
     "bf_dm_stream_history": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "bf_dm_stream_cut": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bf_dm_stream_cut_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "bf_vhist_units_needed": (C.c_int, [C.POINTER(BfConfig), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "bf_vhist_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "bf_vhist_destroy": (C.c_int, [C.c_void_p]),
+    "bf_vhist_push": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "bf_vhist_push_block": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "bf_vhist_history": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "bf_vhist_cut": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bf_vhist_cut_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "bf_psr_model_from_spin": (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_double, C.c_int64, C.POINTER(BfPsrModel)]),
     "bf_psr_entries": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "bf_psr_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
@@ -410,6 +424,9 @@ SIGNATURES = {
     "bfh_stamp_sink_create": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "bfh_stamp_sink_deliver": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_int, C.c_int]),
     "bfh_stamp_sink_destroy": (C.c_int, [C.c_void_p]),
+    "bfh_voltage_sink_create": (C.c_int, [C.c_char_p, C.POINTER(BfConfig), C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "bfh_voltage_sink_deliver": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_size_t]),
+    "bfh_voltage_sink_destroy": (C.c_int, [C.c_void_p]),
     "bfh_psr_sink_create": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "bfh_psr_sink_deliver": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]),
     "bfh_psr_sink_destroy": (C.c_int, [C.c_void_p]),

@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-from ._lib import BF_CAL_FULL, BF_CAL_PHASE, BF_NULL_CLIP, BF_NULL_SCALED, BfCalOptions, BfNullOptions, BfCondOptions, BfConfig, BfFfaCandidate, BfFfaGroup, BfFfaPeak, BfFfaStat, BfInjTruth, BfPsrModel, BfEvtEvent, BfEvtOptions, BfSkOptions, BfStampRequest, DsabfError, BfSpsCandidate, BfSpsPeak, BfSpsStat, check, load
+from ._lib import BF_CAL_FULL, BF_CAL_PHASE, BF_NULL_CLIP, BF_NULL_SCALED, BfCalOptions, BfNullOptions, BfCondOptions, BfConfig, BfFfaCandidate, BfFfaGroup, BfFfaPeak, BfFfaStat, BfInjTruth, BfPsrModel, BfEvtEvent, BfEvtOptions, BfSkOptions, BfStampRequest, BfVcutRequest, DsabfError, BfSpsCandidate, BfSpsPeak, BfSpsStat, check, load
 
 
 def debug_config(**over) -> BfConfig:
@@ -419,6 +419,85 @@ def stamp_request_dtype():
     dt = np.dtype([("t0", np.uint64), ("dm", np.int32), ("beam", np.int32)], align=True)
     assert dt.itemsize == C.sizeof(BfStampRequest)
     return dt
+
+
+def vcut_request_dtype():
+    import numpy as np
+
+    dt = np.dtype([("t0", np.uint64), ("dm", np.int32), ("pad", np.int32)], align=True)
+    assert dt.itemsize == C.sizeof(BfVcutRequest)
+    return dt
+
+
+def vhist_units_needed(cfg: BfConfig, max_delay_rows: int, dm_rows: int, n_buf: int, t_tol: int, max_width: int, cut_units: int) -> int:
+    """bf_vhist_units_needed: the history (whole gemm-units) with which a consumer that cuts ``cut_units`` units around an event when it
+    closes misses nothing (docs/VOLTAGE_CUTS.md section 3); 0 where undefined.  Host arithmetic, no device."""
+    return int(load().bf_vhist_units_needed(C.byref(cfg), max_delay_rows, dm_rows, n_buf, t_tol, max_width, cut_units))
+
+
+class VoltageHistory(_Owner):
+    """bf_vhist: a device ring of the last ``history_units`` whole gemm-units of packed voltages, and dedispersed cuts of it in the input
+    layout [unit][freq][time][ant] (include/dsabf.h, docs/VOLTAGE_CUTS.md).  delays: int32 host array [n_dm][n_freq], in samples."""
+    _ptr_attr, _destroy = "_c", "bf_vhist_destroy"
+
+    def __init__(self, bf: Beamformer, delays, history_units: int):
+        import numpy as np
+
+        self._lib = load()
+        self._c = C.c_void_p()
+        d = np.ascontiguousarray(delays, np.int32)
+        assert d.ndim == 2 and d.shape[1] == bf.cfg.n_freq
+        self.n_dm, self._bf = d.shape[0], bf
+        check(self._lib.bf_vhist_create(bf._h, _ptr(d), d.shape[0], int(history_units), C.byref(self._c)))
+
+    def push(self, d_packed, n_units: int, stream: int = 0) -> None:
+        """bf_vhist_push: ``n_units`` units at ``d_packed`` (device) take the next unit positions, asynchronously on ``stream``."""
+        check(self._lib.bf_vhist_push(self._c, _ptr(d_packed), int(n_units), C.c_void_p(stream)))
+
+    def push_block(self, stream_idx: int, slot: int, first_unit: int, n_units: int) -> None:
+        """bf_vhist_push_block: the resident units [first_unit, first_unit + n_units) of the handle's ring slot, on compute queue stream_idx."""
+        check(self._lib.bf_vhist_push_block(self._c, int(stream_idx), int(slot), int(first_unit), int(n_units)))
+
+    def history(self):
+        """bf_vhist_history: (oldest_unit, next_unit, cap_units) -- units [oldest_unit, next_unit) of the series can be cut."""
+        a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        check(self._lib.bf_vhist_history(self._c, C.byref(a), C.byref(b), C.byref(c)))
+        return int(a.value), int(b.value), int(c.value)
+
+    @staticmethod
+    def _requests(requests):
+        import numpy as np
+
+        reqs = np.zeros(len(requests), vcut_request_dtype())
+        if len(requests):
+            r = np.asarray(requests)
+            if r.dtype.names:
+                for k in ("t0", "dm"):
+                    reqs[k] = r[k]
+            else:
+                reqs["t0"], reqs["dm"] = [[int(q[k]) for q in requests] for k in range(2)]
+        return reqs
+
+    def cut(self, requests, n_units_out: int, d_out, stream: int = 0):
+        """bf_vhist_cut: dedispersed units [request][n_units_out][freq][S][n_pol][ant] (packed bytes, device memory ``d_out``) of the
+        requests -- an iterable of (t0 in samples, row of the delay table), or a structured array with fields t0, dm -- asynchronously
+        on ``stream``.  Returns the int32 status of every request: 0 cut, 1 too old, 2 not pushed yet (its cells stay untouched)."""
+        import numpy as np
+
+        reqs = self._requests(requests)
+        status = np.full(len(reqs), -1, np.int32)
+        check(self._lib.bf_vhist_cut(self._c, _ptr(reqs), len(reqs), int(n_units_out), _ptr(d_out), _ptr(status), C.c_void_p(stream)))
+        return status
+
+    def cut_host(self, requests, n_units_out: int, host_out):
+        """bf_vhist_cut_host: the same cut on a queue of the stage's own, copied to ``host_out`` (host memory, pinned for an asynchronous
+        copy) and waited for there.  Returns the status array."""
+        import numpy as np
+
+        reqs = self._requests(requests)
+        status = np.full(len(reqs), -1, np.int32)
+        check(self._lib.bf_vhist_cut_host(self._c, _ptr(reqs), len(reqs), int(n_units_out), _ptr(host_out), _ptr(status)))
+        return status
 
 
 def event_dtype():

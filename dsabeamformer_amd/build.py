@@ -9,7 +9,8 @@ holds for the incoherent beam (csrc/ib/, docs/INCOHERENT_BEAM.md), the correlato
 solver (csrc/cal/, docs/CALIBRATION.md), the conditioning stage (csrc/cond/, docs/CONDITIONING.md), the voltage moments
 (csrc/sk/, docs/SPECTRAL_KURTOSIS.md), the full-Stokes follow-up beams (csrc/stokes/, docs/STOKES.md), the spatial null (csrc/null/,
 docs/NULLING.md), the stamp cut (csrc/stamp/, docs/EVENTS.md), the pulsar fold (csrc/psr/, docs/PULSAR_FOLDING.md), the periodicity
-search (csrc/ffa/, docs/PERIODICITY.md) and the pulse injector (csrc/inj/, docs/INJECTION.md).
+search (csrc/ffa/, docs/PERIODICITY.md), the pulse injector (csrc/inj/, docs/INJECTION.md) and the voltage cut (csrc/vcut/,
+docs/VOLTAGE_CUTS.md).
 """
 from __future__ import annotations
 
@@ -76,7 +77,8 @@ def sources() -> list[str]:
                   glob.glob(os.path.join(IB, "*.hip")) + glob.glob(os.path.join(CORR, "*.hip")) + glob.glob(os.path.join(CAL, "*.hip")) +
                   glob.glob(os.path.join(COND, "*.hip")) + glob.glob(os.path.join(SK, "*.hip")) +
                   glob.glob(os.path.join(STOKES, "*.hip")) + glob.glob(os.path.join(NULL, "*.hip")) + glob.glob(os.path.join(CUT, "*.hip")) +
-                  glob.glob(os.path.join(PSR, "*.hip")) + glob.glob(os.path.join(FFA, "*.hip")) + glob.glob(os.path.join(INJ, "*.hip"))
+                  glob.glob(os.path.join(PSR, "*.hip")) + glob.glob(os.path.join(FFA, "*.hip")) + glob.glob(os.path.join(INJ, "*.hip")) +
+                  glob.glob(os.path.join(VCUT, "*.hip"))
                   if os.path.abspath(p) not in [os.path.abspath(m) for m in MAINS.values()])
 
 
@@ -95,6 +97,7 @@ CUT = os.path.join(CSRC, "stamp")                   # device code of the stamp c
 PSR = os.path.join(CSRC, "psr")                     # device code of the pulsar fold: the same
 FFA = os.path.join(CSRC, "ffa")                     # device code of the periodicity search: the same
 INJ = os.path.join(CSRC, "inj")                     # device code of the pulse injector: the same
+VCUT = os.path.join(CSRC, "vcut")                   # device code of the voltage cut (bf_vhist_cut): the same
 
 
 def kernel_build_id() -> str:
@@ -124,7 +127,7 @@ def _headers() -> list[str]:
     return glob.glob(os.path.join(CSRC, "*.h*")) + glob.glob(os.path.join(CSRC, "*.inc")) + glob.glob(os.path.join(SPS, "*.h")) + glob.glob(os.path.join(IB, "*.h")) + \
         glob.glob(os.path.join(CORR, "*.h")) + glob.glob(os.path.join(CAL, "*.h")) + glob.glob(os.path.join(COND, "*.h")) + glob.glob(os.path.join(SK, "*.h")) + \
         glob.glob(os.path.join(STOKES, "*.h")) + glob.glob(os.path.join(NULL, "*.h")) + glob.glob(os.path.join(CUT, "*.h")) + glob.glob(os.path.join(PSR, "*.h")) + \
-        glob.glob(os.path.join(FFA, "*.h")) + glob.glob(os.path.join(INJ, "*.h")) + \
+        glob.glob(os.path.join(FFA, "*.h")) + glob.glob(os.path.join(INJ, "*.h")) + glob.glob(os.path.join(VCUT, "*.h")) + \
         glob.glob(os.path.join(ROOT, "include", "*.h*"))
 
 

@@ -147,6 +147,10 @@ int main(int argc, char* argv[])
     bf_evt_default_options(&evt_opt);
     int stamp_bins = 64, stamp_tbin = 0, stamp_fbin = 1;
     bool event_tol_given = false, event_veto_given = false, stamp_shape_given = false, stamp_flagged = false, long_bad = false;
+    // voltage cuts (docs/VOLTAGE_CUTS.md): --voltages FILE [--voltage-units N] [--voltage-history UNITS] [--voltage-flagged]
+    std::string voltages_path;
+    int voltage_units = 2, voltage_history = 0;
+    bool voltage_units_given = false, voltage_history_given = false, voltage_flagged = false, voltage_bad = false;
     // pulsar folding (docs/PULSAR_FOLDING.md): --fold f0[:f1[:phase0]] up to 4 times, --fold-dm dm (the k-th belongs to the k-th --fold),
     // --fold-bins n, --fold-rows rows_per_dump, --fold-out FILE
     struct fold_spec {
@@ -172,7 +176,7 @@ int main(int argc, char* argv[])
     std::vector<inject_spec> inj_bursts, inj_trains;
     std::string inj_path;
     bool inj_bad = false;
-    enum { kEvents = 1000, kEventTol, kEventVeto, kStamps, kStampShape, kStampFlagged, kFold, kFoldDm, kFoldBins, kFoldRows, kFoldOut, kFfa, kFfaSeg, kFfaDec, kFfaOct, kFfaWidths, kFfaSnr, kFfaOut, kFfaDetrend, kInject, kInjectTrain, kInjectOut };
+    enum { kEvents = 1000, kEventTol, kEventVeto, kStamps, kStampShape, kStampFlagged, kFold, kFoldDm, kFoldBins, kFoldRows, kFoldOut, kFfa, kFfaSeg, kFfaDec, kFfaOct, kFfaWidths, kFfaSnr, kFfaOut, kFfaDetrend, kInject, kInjectTrain, kInjectOut, kVoltages, kVoltageUnits, kVoltageHistory, kVoltageFlagged };
     static const option long_options[] = {{"events", required_argument, nullptr, kEvents},       {"event-tol", required_argument, nullptr, kEventTol},
                                           {"event-veto", required_argument, nullptr, kEventVeto}, {"stamps", required_argument, nullptr, kStamps},
                                           {"stamp-shape", required_argument, nullptr, kStampShape}, {"stamp-flagged", no_argument, nullptr, kStampFlagged},
@@ -185,6 +189,8 @@ int main(int argc, char* argv[])
                                           {"ffa-out", required_argument, nullptr, kFfaOut},       {"ffa-detrend", required_argument, nullptr, kFfaDetrend},
                                           {"inject", required_argument, nullptr, kInject},       {"inject-train", required_argument, nullptr, kInjectTrain},
                                           {"inject-out", required_argument, nullptr, kInjectOut},
+                                          {"voltages", required_argument, nullptr, kVoltages},   {"voltage-units", required_argument, nullptr, kVoltageUnits},
+                                          {"voltage-history", required_argument, nullptr, kVoltageHistory}, {"voltage-flagged", no_argument, nullptr, kVoltageFlagged},
                                           {nullptr, 0, nullptr, 0}};
     // a non-negative integer that fills its whole field; anything else marks the command line as malformed
     auto number = [&long_bad](const char* text, const char** end, int* out) {
@@ -313,6 +319,17 @@ int main(int argc, char* argv[])
             case kEvents: events_path = optarg; break;
             case kStamps: stamps_path = optarg; break;
             case kStampFlagged: stamp_flagged = true; break;
+            case kVoltages: voltages_path = optarg; break;
+            case kVoltageFlagged: voltage_flagged = true; break;
+            case kVoltageUnits:
+            case kVoltageHistory: {   // a whole number >= 1
+                char* e = nullptr;
+                const long v = strtol(optarg, &e, 10);
+                if (e == optarg || *e || v < 1 || v > 1000000000L || *optarg == '+' || *optarg == ' ') voltage_bad = true;
+                (arg == kVoltageUnits ? voltage_units : voltage_history) = (int)v;
+                (arg == kVoltageUnits ? voltage_units_given : voltage_history_given) = true;
+                break;
+            }
             case kEventTol: {   // T[,D]
                 const char* e = nullptr;
                 event_tol_given = true;
@@ -457,6 +474,11 @@ int main(int argc, char* argv[])
                              "                         [0: half the width] x channels in groups of FBIN [1, must divide the band], cut from the DM stage's ring\n"
                              "                         --events without -S, --stamps without --events, the others without their parent, or malformed\n"
                              "                         numbers: beam exits with a usage error\n"
+                             " --voltages FILE [--voltage-units N] [--voltage-history UNITS] [--voltage-flagged]   with --events: the dedispersed packed\n"
+                             "                         voltages under each unflagged event (--voltage-flagged: under flagged ones too), N [2] gemm-units in the\n"
+                             "                         input layout centred on the best member, cut from a history of UNITS gemm-units [what the search needs]\n"
+                             "                         kept on the device; not with -R; --voltages without --events, the others without --voltages, or a\n"
+                             "                         number < 1: beam exits with a usage error\n"
                              " --fold F0[:F1[:PHASE0]] [--fold-dm DM] [--fold-bins N] [--fold-rows ROWS] [--fold-out FILE]   with -M: the detected stream of\n"
                              "                         every beam folded at spin frequency F0 Hz, derivative F1 Hz/s [0] and phase PHASE0 turns [0] at the first row,\n"
                              "                         dedispersed at DM pc/cc [0] (the k-th --fold-dm belongs to the k-th --fold; up to 4 --fold), into N [64] phase\n"
@@ -561,6 +583,22 @@ int main(int argc, char* argv[])
     }
     if (stamps_path.empty() && (stamp_shape_given || stamp_flagged)) {
         fprintf(stderr, "beam: --stamp-shape / --stamp-flagged belong to the stamps: give --stamps FILE\n");
+        return EXIT_FAILURE;
+    }
+    if (voltage_bad) {
+        fprintf(stderr, "beam: --voltage-units N, --voltage-history UNITS: need a whole number >= 1\n");
+        return EXIT_FAILURE;
+    }
+    if (voltages_path.empty() && (voltage_units_given || voltage_history_given || voltage_flagged)) {
+        fprintf(stderr, "beam: --voltage-units / --voltage-history / --voltage-flagged belong to the voltage cuts: give --voltages FILE\n");
+        return EXIT_FAILURE;
+    }
+    if (!voltages_path.empty() && events_path.empty()) {
+        fprintf(stderr, "beam: --voltages cuts the voltages of the event builder's events: give --events FILE\n");
+        return EXIT_FAILURE;
+    }
+    if (!voltages_path.empty() && world > 1) {
+        fprintf(stderr, "beam: --voltages is not available in a sharded run (-R): a trigger is not sent to the ranks that hold the other channels\n");
         return EXIT_FAILURE;
     }
     if (!stamps_path.empty()) {   // the band is the production geometry's, whatever -R
@@ -974,6 +1012,7 @@ int main(int argc, char* argv[])
         std::unique_ptr<sps_file_sink> cand_sink;
         std::unique_ptr<event_file_sink> esink;
         std::unique_ptr<stamp_file_sink> tsink;
+        std::unique_ptr<voltage_file_sink> usink;
         int n_dm = 0, my_trials = 0;
         if (dm_max > 0.0) {
             std::vector<double> dms = dm_trials(0.0, dm_max);
@@ -1056,6 +1095,17 @@ int main(int argc, char* argv[])
                         return EXIT_FAILURE;
                     }
                     oopt.stamp_sink = tsink.get();
+                }
+                if (!voltages_path.empty()) {
+                    usink.reset(new voltage_file_sink(voltages_path.c_str(), pcfg, voltage_units, 0));
+                    if (!usink->is_open()) {
+                        fprintf(stderr, "beam: could not open %s\n", voltages_path.c_str());
+                        return EXIT_FAILURE;
+                    }
+                    oopt.vcut_sink = usink.get();
+                    oopt.vcut_units = voltage_units;
+                    oopt.vcut_history_units = voltage_history;
+                    oopt.vcut_flagged = voltage_flagged;
                 }
             }
         }
@@ -1234,6 +1284,7 @@ int main(int argc, char* argv[])
         if (ffa_out) std::cout << "Wrote " << ffa_out->get_candidates_written() << " periodicity candidates to " << ffa_path << std::endl;
         if (esink) std::cout << "Wrote " << esink->get_events_written() << " events to " << events_path << std::endl;
         if (tsink) std::cout << "Wrote " << tsink->get_stamps_written() << " stamps to " << stamps_path << std::endl;
+        if (usink) std::cout << "Wrote " << usink->get_cuts_written() << " voltage cuts to " << voltages_path << std::endl;
         if (vsink) std::cout << "Wrote " << vsink->get_dumps_written() << " visibility dumps of " << corr_blocks << " blocks to " << vis_path << std::endl;
         if (xsink) std::cout << "Wrote " << xsink->get_sets_written() << " sets of Stokes beams to " << stokes_path << std::endl;
         if (ksink) std::cout << "Wrote " << ksink->get_dumps_written() << " moment dumps of " << sk_blocks << " blocks to " << sk_path << std::endl;

@@ -739,6 +739,31 @@ int bfh_stamp_sink_destroy(bfh_stamp_sink* s)
     return BF_OK;
 }
 
+struct bfh_voltage_sink {
+    voltage_file_sink s;
+};
+int bfh_voltage_sink_create(const char* path, const bf_config* cfg, int units, int first_channel, bfh_voltage_sink** out)
+{
+    if (!path || !cfg || !out || units < 1 || first_channel < 0 || cfg->n_ant < 1 || cfg->n_freq < 1 || cfg->n_pol < 1 || cfg->n_avg < 1 ||
+        cfg->n_out_per_gemm < 1)
+        return BF_ERR_INVALID;
+    *out = nullptr;
+    std::unique_ptr<bfh_voltage_sink> s(new bfh_voltage_sink{voltage_file_sink(path, *cfg, units, first_channel)});
+    if (!s->s.is_open()) return BF_ERR_INVALID;
+    *out = s.release();
+    return BF_OK;
+}
+int bfh_voltage_sink_deliver(bfh_voltage_sink* s, uint64_t t0, int dm, int beam, int width, double snr, const void* data, size_t n_bytes)
+{
+    if (!s || !data) return BF_ERR_INVALID;
+    return s->s.deliver(t0, dm, beam, width, snr, static_cast<const uint8_t*>(data), n_bytes) ? BF_OK : BF_ERR_STATE;
+}
+int bfh_voltage_sink_destroy(bfh_voltage_sink* s)
+{
+    delete s;
+    return BF_OK;
+}
+
 struct bfh_psr_sink {
     psr_file_sink s;
     int n_psr, n_freq, n_bins, n_beams;

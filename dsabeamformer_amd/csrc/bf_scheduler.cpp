@@ -211,6 +211,7 @@ struct run_resources {
     bf_sk* sk = nullptr;
     bf_stokes* stokes = nullptr;
     bf_evt* evt = nullptr;
+    bf_vhist* vhist = nullptr;
     std::vector<void*> pinned;
     ~run_resources()
     {
@@ -218,6 +219,7 @@ struct run_resources {
         bf_corr_destroy(corr);
         bf_sk_destroy(sk);
         bf_stokes_destroy(stokes);
+        bf_vhist_destroy(vhist);
         bf_sps_destroy(sps);
         bf_evt_destroy(evt);
         bf_cond_destroy(cond);
@@ -512,6 +514,10 @@ int check_options(const bf_config& cfg, const observation_options& opt)
     if (opt.evt && (opt.stamp_bins < 1 || opt.stamp_tbin < 0 || opt.stamp_fbin < 1 || opt.stamp_max_per_deliver < 0 ||
                     (cfg.n_freq * (opt.comm ? opt.world : 1)) % opt.stamp_fbin != 0))
         return set_error(BF_ERR_INVALID, "run_observation: need stamp_bins >= 1, stamp_tbin >= 0, stamp_max_per_deliver >= 0 and stamp_fbin >= 1 dividing the band");
+    if (opt.vcut_sink && !opt.evt) return set_error(BF_ERR_INVALID, "run_observation: a vcut_sink needs evt");
+    if (opt.vcut_sink && opt.comm) return set_error(BF_ERR_INVALID, "run_observation: voltage cuts are not available on a sharded run");
+    if (opt.vcut_sink && (opt.vcut_units < 1 || opt.vcut_history_units < 0 || opt.vcut_max_per_deliver < 0))
+        return set_error(BF_ERR_INVALID, "run_observation: need vcut_units >= 1, vcut_history_units >= 0 and vcut_max_per_deliver >= 0");
     if (opt.cond_baseline < 0 || opt.cond_baseline > 64) return set_error(BF_ERR_INVALID, "run_observation: cond_baseline must be 0 (off) .. 64");
     if (opt.cond_baseline && !opt.dm_delays) return set_error(BF_ERR_INVALID, "run_observation: the conditioner needs the DM stage (dm_delays)");
     if (!opt.cond_baseline && (opt.cond_mask || opt.cond_auto_threshold != 0.0))
@@ -619,6 +625,13 @@ struct stamp_want {
     double snr;
 };
 
+// A voltage cut that is wanted: the request (samples, local trial index), and what the sink is told about the event it belongs to.
+struct vcut_want {
+    bf_vcut_request rq;
+    int beam, width, dm_global;
+    double snr;
+};
+
 struct dm_chunk {
     uint64_t block, first_t;
     int n_t;
@@ -667,6 +680,10 @@ struct production_run {
     float* stamp_host = nullptr;           // pinned: the stamps of one cut
     size_t stamp_batch = 0;                // requests one cut takes
     uint64_t events = 0, stamps = 0, stamps_dropped = 0, stamps_missed = 0, stamps_beyond_end = 0;
+    std::deque<vcut_want> vcut_pending;    // wanted, not yet cut: new ones, and those answered "not pushed yet"
+    uint8_t* vcut_host = nullptr;          // pinned: the units of one cut
+    size_t vcut_batch = 0, vcut_bytes = 0; // requests one cut takes; bytes of one request's units
+    uint64_t vcuts = 0, vcuts_dropped = 0, vcuts_missed = 0, vcuts_beyond_end = 0;
     uint64_t psr_rows_folded = 0, psr_dumps = 0;   // the pulsar folder: rows folded since the last dump; dumps delivered
     std::deque<uint64_t> psr_pending;              // the block behind whose last launch each uncollected dump was issued
     uint64_t ffa_times = 0, ffa_segments = 0, ffa_candidates = 0;   // the periodicity search: output times of the delivered chunks; segments collected
@@ -810,6 +827,7 @@ struct production_run {
                     const size_t stamp_floats = (size_t)(plan.n_freq_band / opt.stamp_fbin) * (size_t)opt.stamp_bins;
                     if ((rc = dev.alloc_pinned(stamp_batch * stamp_floats, &stamp_host)) != BF_OK) return rc;
                 }
+                if (opt.vcut_sink && (rc = create_voltage_history((int)n_buf)) != BF_OK) return rc;
             }
         }
         for (accum_tap* t : taps) {
@@ -842,6 +860,32 @@ struct production_run {
                 if (opt.comm && plan.is_root && !plan.dm_run && (rc = bf_block_gather_device(dev.h, q, opt.world, &unused)) != BF_OK) return rc;
                 if (opt.comm && plan.staged && plan.is_root && (rc = bf_block_gather_stage_device(dev.h, q, opt.world, &unused)) != BF_OK) return rc;
             }
+        return BF_OK;
+    }
+
+    // The voltage history (docs/VOLTAGE_CUTS.md): the delay table is the DM stage's row delays of this rank's trials in samples -- the
+    // ladder of the detected stream, nothing finer -- and the ring what bf_vhist_units_needed says, unless the caller sizes it.
+    int create_voltage_history(int n_buf)
+    {
+        const size_t n_del = (size_t)plan.dm_count * (size_t)cfg.n_freq;
+        std::vector<int32_t> delays(n_del);
+        const int32_t* rows = opt.dm_delays + (size_t)plan.dm_first * plan.n_freq_band;
+        for (size_t i = 0; i < n_del; i++) delays[i] = rows[i] * cfg.n_avg;
+        const int max_width = 1 << (opt.sps_widths - 1);
+        const int units = opt.vcut_history_units
+                              ? opt.vcut_history_units
+                              : bf_vhist_units_needed(&cfg, bf_dm_stream_max_delay(dev.dm), plan.dm_rows, n_buf, opt.evt->t_tol, max_width, opt.vcut_units);
+        int rc = bf_vhist_create(dev.h, delays.data(), plan.dm_count, units, &dev.vhist);
+        if (rc != BF_OK) return gpu_error(log, rc);
+        uint64_t oldest = 0, next = 0, cap = 0;
+        bf_vhist_history(dev.vhist, &oldest, &next, &cap);
+        vcut_bytes = (size_t)opt.vcut_units * (size_t)bf_bytes_per_gemm(&cfg);
+        log << "Voltage cuts: history of " << cap << " gemm-units (" << ((cap * (uint64_t)bf_bytes_per_gemm(&cfg)) >> 20) << " MiB), cuts of " << opt.vcut_units
+            << " units" << std::endl;
+        vcut_batch = (size_t)std::max(1, opt.vcut_max_per_deliver);
+        float* p = nullptr;
+        if ((rc = dev.alloc_pinned((vcut_batch * vcut_bytes + 3) / 4, &p)) != BF_OK) return rc;
+        vcut_host = reinterpret_cast<uint8_t*>(p);
         return BF_OK;
     }
 
@@ -925,6 +969,7 @@ struct production_run {
             rc = bf_stokes_push_block(dev.stokes, q, gpu_block, first, upl);
             if (rc == BF_OK) stokes_pending.emplace_back((uint64_t)block_index, (uint64_t)block_index * (uint64_t)n_units + (uint64_t)first);
         }
+        if (rc == BF_OK && dev.vhist) rc = bf_vhist_push_block(dev.vhist, q, gpu_block, first, upl);   // and the voltage history: a device copy of the units
         return rc == BF_OK ? BF_OK : gpu_error(log, rc);
     }
 
@@ -977,6 +1022,7 @@ struct production_run {
             log << "ERROR: event sink failed" << std::endl;
             return BF_ERR_STATE;
         }
+        if (opt.vcut_sink) want_voltage_cuts(n);
         if (!opt.stamp_sink) return BF_OK;
         std::vector<size_t> pick;
         for (size_t i = 0; i < n; i++)
@@ -992,6 +1038,61 @@ struct production_run {
             const int tbin = opt.stamp_tbin ? opt.stamp_tbin : std::max(1, b.width / 2);
             const uint64_t centre = b.t_start + (uint64_t)(b.width / 2), half = (uint64_t)opt.stamp_bins * (uint64_t)tbin / 2;
             stamp_pending.push_back({{centre > half ? centre - half : 0, b.dm - plan.dm_first, b.beam}, tbin, b.width, b.dm, b.snr});
+        }
+        return BF_OK;
+    }
+
+    // The stamps' selection rule for the voltage cuts of one feed's events: unflagged ones unless vcut_flagged, by snr descending, then
+    // event order, at most vcut_max_per_deliver; the rest are counted as dropped.  vcut_units units centred on the best member.
+    void want_voltage_cuts(size_t n)
+    {
+        std::vector<size_t> pick;
+        for (size_t i = 0; i < n; i++)
+            if (opt.vcut_flagged || !events_out[i].flags) pick.push_back(i);
+        std::stable_sort(pick.begin(), pick.end(), [&](size_t a, size_t b) { return events_out[a].best.snr > events_out[b].best.snr; });
+        const size_t cap = (size_t)opt.vcut_max_per_deliver;
+        if (pick.size() > cap) {
+            vcuts_dropped += pick.size() - cap;
+            pick.resize(cap);
+        }
+        const uint64_t S = (uint64_t)cfg.n_out_per_gemm * (uint64_t)cfg.n_avg;
+        for (size_t i : pick) {
+            const bf_sps_candidate& b = events_out[i].best;
+            const uint64_t centre = (b.t_start + (uint64_t)(b.width / 2)) * (uint64_t)cfg.n_avg, half = (uint64_t)opt.vcut_units * S / 2;
+            vcut_pending.push_back({{centre > half ? centre - half : 0, b.dm - plan.dm_first, 0}, b.beam, b.width, b.dm, b.snr});
+        }
+    }
+
+    // One round of voltage cuts over everything pending (vcut_batch requests at most per call): as cut_stamps.
+    int cut_voltages(bool last)
+    {
+        std::deque<vcut_want> todo;
+        todo.swap(vcut_pending);
+        while (!todo.empty()) {
+            std::vector<vcut_want> group;
+            while (!todo.empty() && group.size() < vcut_batch) {
+                group.push_back(todo.front());
+                todo.pop_front();
+            }
+            std::vector<bf_vcut_request> rq;
+            for (const vcut_want& w : group) rq.push_back(w.rq);
+            std::vector<int32_t> status(group.size(), -1);
+            const int rc = bf_vhist_cut_host(dev.vhist, rq.data(), (int)rq.size(), opt.vcut_units, vcut_host, status.data());
+            if (rc != BF_OK) return gpu_error(log, rc);
+            for (size_t i = 0; i < group.size(); i++) {
+                const vcut_want& w = group[i];
+                if (status[i] == 2) {   // not pushed yet: retried at the next deliver -- or, at the end of the run, never there
+                    if (last) vcuts_beyond_end++; else vcut_pending.push_back(w);
+                } else if (status[i] == 1) {
+                    vcuts_missed++;
+                } else {
+                    vcuts++;
+                    if (!opt.vcut_sink->deliver(w.rq.t0, w.dm_global, w.beam, w.width, w.snr, vcut_host + i * vcut_bytes, vcut_bytes)) {
+                        log << "ERROR: voltage sink failed at sample " << w.rq.t0 << std::endl;
+                        return BF_ERR_STATE;
+                    }
+                }
+            }
         }
         return BF_OK;
     }
@@ -1045,6 +1146,7 @@ struct production_run {
         int rc = bf_evt_flush(dev.evt, events_out.data(), events_out.size(), &n);
         if (rc != BF_OK) return gpu_error(log, rc);
         if ((rc = take_events(n)) != BF_OK) return rc;
+        if (opt.vcut_sink && (rc = cut_voltages(/*last=*/true)) != BF_OK) return rc;
         return opt.stamp_sink ? cut_stamps(/*last=*/true) : BF_OK;
     }
 
@@ -1097,6 +1199,8 @@ struct production_run {
         }
         if (opt.stamp_sink)   // one round of cuts per deliver, on the stage's own queue: the compute queues keep running
             if (int rc = cut_stamps(/*last=*/false)) return rc;
+        if (opt.vcut_sink)    // and one round of voltage cuts, on the history's own queue
+            if (int rc = cut_voltages(/*last=*/false)) return rc;
         for (accum_tap* t : taps)
             while (!t->pending.empty() && t->pending.front().second < blocks_analyzed) {   // (the collect waits for the dump's own copy)
                 const uint64_t first_block = t->pending.front().first;
@@ -1198,6 +1302,7 @@ int run_observation(const bf_config& cfg, const observation_options& opt, block_
     if ((rc = run.flush_events()) != BF_OK) return rc;
     if (opt.event_sink) opt.event_sink->close();
     if (opt.stamp_sink) opt.stamp_sink->close();
+    if (opt.vcut_sink) opt.vcut_sink->close();
     if (opt.sink) opt.sink->close();
     if (opt.dm_sink) opt.dm_sink->close();
     if (opt.sps_sink) opt.sps_sink->close();
@@ -1224,6 +1329,10 @@ int run_observation(const bf_config& cfg, const observation_options& opt, block_
         res->stamps_dropped = run.stamps_dropped;
         res->stamps_missed = run.stamps_missed;
         res->stamps_beyond_end = run.stamps_beyond_end;
+        res->vcuts = run.vcuts;
+        res->vcuts_dropped = run.vcuts_dropped;
+        res->vcuts_missed = run.vcuts_missed;
+        res->vcuts_beyond_end = run.vcuts_beyond_end;
         res->vis_dumps = run.corr.dumps;
         res->sk_dumps = run.sk.dumps;
         res->stokes_units = run.stokes_units;
@@ -1273,6 +1382,9 @@ int run_observation(const bf_config& cfg, const observation_options& opt, block_
                 << ", beyond the end of the run " << run.stamps_beyond_end;
         log << std::endl;
     }
+    if (run.dev.vhist)
+        log << "Voltage cuts: " << run.vcuts << " cuts of " << opt.vcut_units << " gemm-units, vcuts_dropped " << run.vcuts_dropped << ", vcuts_missed "
+            << run.vcuts_missed << ", beyond the end of the run " << run.vcuts_beyond_end << std::endl;
     return BF_OK;
 }
 

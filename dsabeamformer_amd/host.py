@@ -305,6 +305,27 @@ def read_stamp_file(path: str):
     return hdr, stamps
 
 
+def read_voltage_file(path: str):
+    """Parse a dsabf::voltage_file_sink file (docs/VOLTAGE_CUTS.md): returns (header dict, list of dict(t0, dm, beam, width, snr, data uint8
+    [UNITS][NFREQ][NOUT * NAVG][NPOL * NANT])), in the order the cuts were written."""
+    raw = open(path, "rb").read()
+    text = raw[:DETECTED_HEADER_BYTES].split(b"\0", 1)[0].decode()
+    hdr = dict(line.split(None, 1) for line in text.splitlines() if line.strip())
+    assert hdr["CONTENT"] == "voltages" and hdr["DTYPE"] == "packed4+4" and hdr["LAYOUT"] == "unit,freq,time,pol,ant"
+    shape = (int(hdr["UNITS"]), int(hdr["NFREQ"]), int(hdr["NOUT"]) * int(hdr["NAVG"]), int(hdr["NPOL"]) * int(hdr["NANT"]))
+    n, at, rec = int(np.prod(shape)), int(hdr["HDR_SIZE"]), int(hdr["RECORD_HEADER_BYTES"])
+    cuts = []
+    while at < len(raw):
+        t0 = int(np.frombuffer(raw, "<u8", 1, at)[0])
+        dm, beam, width = (int(v) for v in np.frombuffer(raw, "<i4", 3, at + 8))
+        snr = float(np.frombuffer(raw, "<f8", 1, at + 20)[0])
+        at += rec
+        cuts.append(dict(t0=t0, dm=dm, beam=beam, width=width, snr=snr, data=np.frombuffer(raw, np.uint8, n, at).reshape(shape)))
+        at += n
+    assert at == len(raw)
+    return hdr, cuts
+
+
 def read_dm_file(path: str):
     """Parse a dsabf::dm_file_sink file: returns (header dict, float32 array [n_dm][T][n_beams], list of (first_t, n_t) per
     chunk).  The chunks ([dm][t][beam] each) are joined along t; they follow each other without gaps."""

@@ -714,6 +714,58 @@ int bf_dm_stream_cut(bf_dm_stream *s, const bf_stamp_request *reqs, int n_req, i
 int bf_dm_stream_cut_host(bf_dm_stream *s, const bf_stamp_request *reqs, int n_req, int n_tau, int tbin, int fbin,
                           float *host_out, int32_t *status);
 
+/* ---- Voltage history: dedispersed voltage cuts (docs/VOLTAGE_CUTS.md) -----------------------------------------------------
+ * The reference keeps its packed voltages in a device ring of N_BLOCKS_ON_GPU blocks (src/beamformer.hh:124) that the H2D copy
+ * of src/beamformer.cu:425-431 refills slot by slot: the voltages under a pulse are gone a few blocks after it.  A bf_vhist is
+ * that ring generalised to a history of whole gemm-units deep enough to outlive the search, and a cut that leaves a burst as
+ * DEDISPERSED gemm-units in the input layout, so that bf_stokes_device, bf_correlate_device, bf_sk_device and
+ * bf_beamform_device run on it unchanged.  Opt-in: with no bf_vhist created nothing changes.  No arithmetic: bytes are moved.
+ * Geometry (the handle's bf_config): a SAMPLE is the n_pol consecutive columns of one time step, B = n_pol n_ant bytes (a
+ *   multiple of 4); a unit has S = n_out_per_gemm n_avg samples, [freq][S][n_pol][ant]: a channel of a unit is S B contiguous bytes.
+ * bf_vhist_create: delays[n_dm][n_freq] int32 >= 0 in SAMPLES (host; copied to the device), n_freq the handle's; a device ring of
+ *   cap_units >= history_units whole units, a plain allocation that wraps at unit granularity.  Sample s of the series, counted
+ *   from the first unit ever pushed, lies in unit s / S, physical unit (s / S) mod cap_units, at sample s % S.
+ * bf_vhist_push: n_units units at d_packed (device, 4-byte aligned) take the next unit positions, asynchronously on hip_stream (at
+ *   most two copies, because of the wrap).  bf_vhist_push_block: the units [first_unit, first_unit + n_units) of ring slot `slot` of
+ *   the handle (what bf_enqueue_block reads) on compute queue stream_idx, behind what that queue holds.  n_units > cap_units:
+ *   BF_ERR_INVALID.  bf_vhist_history: units [*oldest_unit, *next_unit) are readable; next_unit = units pushed, oldest_unit =
+ *   max(0, next_unit - cap_units).
+ * bf_vhist_cut, asynchronous on hip_stream: d_out (device, 4-byte aligned) [n_req][n_units_out][freq][S][n_pol][ant] packed bytes,
+ *     out[r][u][f][j][c][a] = v[t0_r + u S + j + delays[dm_r][f]][f][c][a];
+ *   request r needs samples [t0, t0 + n_units_out S + max_f delays[dm][f]).  status[r] (host, filled before the call returns, by
+ *   arithmetic alone): 0 cut, 1 a sample lies in a unit older than oldest_unit, 2 a sample is not pushed yet (1 wins where both
+ *   hold); a request with a non-zero status launches nothing and its cells stay untouched.  16-byte accesses where B % 16 == 0 and
+ *   d_out is 16-byte aligned, 4-byte ones otherwise.  bf_vhist_cut_host is the cut for a host consumer (run_observation): on a
+ *   queue of the stage's own, into a device buffer of the stage, copied to host_out (the same layout, pinned) and waited for THERE.
+ * Ordering: every push records an event behind its copy and behind the event of the push before it ("every unit < next_unit is in
+ *   place"), so pushes may alternate between queues; a cut waits for the newest one and records its own behind the cut before it; a
+ *   push queued after a cut waits for that before it writes.  While no cut has been issued a push waits for nothing new.
+ * BF_ERR_INVALID, nothing launched: NULL pointers, n_dm < 1, a negative delay, history_units < 1, dm or n_req out of range,
+ *   n_units_out < 1 (or n_freq n_units_out > 65535), d_out or d_packed not 4-byte aligned.  A handle that goes first releases the
+ *   device side; the stage then answers BF_ERR_STATE and can still be destroyed.  Every entry point leaves the caller's current
+ *   device as it found it.
+ * bf_vhist_units_needed: pure host arithmetic, no device (docs/VOLTAGE_CUTS.md section 3): the history_units with which a consumer
+ *   that cuts cut_units units around an event when it closes misses nothing -- rows of the detected stream = max_delay_rows +
+ *   3 dm_rows (the DM stage's own) + cut_units n_out_per_gemm / 2 + t_tol + max_width + (n_buf + 1) dm_rows, as whole units
+ *   (ceil(rows / n_out_per_gemm) + 1: a window may begin inside a unit), plus the n_gemms_per_block units of a block in flight.
+ *   0 where undefined (NULL, a geometry or a dm_rows < 1, a negative argument, cut_units < 1). */
+typedef struct bf_vhist bf_vhist;
+typedef struct bf_vcut_request {
+    uint64_t t0; /* samples, from the first unit ever pushed */
+    int32_t dm;  /* row of the stage's delay table */
+    int32_t pad;
+} bf_vcut_request;
+int bf_vhist_units_needed(const bf_config *cfg, int max_delay_rows, int dm_rows, int n_buf, int t_tol, int max_width,
+                          int cut_units);
+int bf_vhist_create(bf_handle *h, const int32_t *delays, int n_dm, int history_units, bf_vhist **out);
+int bf_vhist_destroy(bf_vhist *v);
+int bf_vhist_push(bf_vhist *v, const void *d_packed, int n_units, void *hip_stream);
+int bf_vhist_push_block(bf_vhist *v, int stream_idx, int slot, int first_unit, int n_units);
+int bf_vhist_history(const bf_vhist *v, uint64_t *oldest_unit, uint64_t *next_unit, uint64_t *cap_units);
+int bf_vhist_cut(bf_vhist *v, const bf_vcut_request *reqs, int n_req, int n_units_out, void *d_out, int32_t *status,
+                 void *hip_stream);
+int bf_vhist_cut_host(bf_vhist *v, const bf_vcut_request *reqs, int n_req, int n_units_out, void *host_out, int32_t *status);
+
 /* ---- Pulsar folding: phase-binned profiles of every beam (docs/PULSAR_FOLDING.md) -------------------------------------------
  * The reference stops at a DM-0 collapse copied to the host (src/beamformer.cu:498-510) and keeps nothing across blocks; the
  * search behind the DM stage looks at one push at a time.  A bf_psr integrates the detected rows x[row][freq][beam] (fp32, the

@@ -177,6 +177,15 @@ int bfh_stamp_sink_deliver(bfh_stamp_sink *s, uint64_t t0, int dm, int beam, int
                            int n_freq_out, int n_bins);
 int bfh_stamp_sink_destroy(bfh_stamp_sink *s);
 
+/* The voltage file sink on its own (docs/VOLTAGE_CUTS.md section 5; tests and host consumers, no device): dsabf::voltage_file_sink writes
+ * the 4096-byte header and one record per cut -- data: `units` gemm-units of cfg's geometry in the input layout, n_bytes =
+ * units * n_freq * n_out_per_gemm * n_avg * n_pol * n_ant; another size is refused with BF_ERR_STATE. */
+typedef struct bfh_voltage_sink bfh_voltage_sink;
+int bfh_voltage_sink_create(const char *path, const bf_config *cfg, int units, int first_channel, bfh_voltage_sink **out);
+int bfh_voltage_sink_deliver(bfh_voltage_sink *s, uint64_t t0, int dm, int beam, int width, double snr, const void *data,
+                             size_t n_bytes);
+int bfh_voltage_sink_destroy(bfh_voltage_sink *s);
+
 /* The fold file sink on its own (docs/PULSAR_FOLDING.md section 5; tests and host consumers, no device): dsabf::psr_file_sink
  * writes the 4096-byte header and one record per dump -- hits uint64 [n_psr][n_freq][n_bins], profile float64
  * [n_psr][n_freq][n_bins][n_beams], the shape given at creation. */

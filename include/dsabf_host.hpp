@@ -674,6 +674,58 @@ public:
     uint64_t get_stamps_written() const { return written; }
 };
 
+// ---- Voltage cuts of the search's events (include/dsabf.h: bf_vhist_*; docs/VOLTAGE_CUTS.md) ----------------------------------
+// With observation_options::vcut_sink set run_observation keeps a voltage history (bf_vhist) beside the handle, pushes every launch's
+// units into it and, of the events one feed closes, cuts the dedispersed voltages of (at most vcut_max_per_deliver of) them.
+// One cut: the request it was cut for (t0 in SAMPLES, the GLOBAL trial index), the best member's beam, width and S/N, and data: packed
+// bytes [n_units][n_freq][S][n_pol][n_ant] -- gemm-units in the input layout, n_bytes of them.
+struct voltage_sink {
+    virtual ~voltage_sink() {}
+    virtual bool deliver(uint64_t t0, int dm, int beam, int width, double snr, const uint8_t* data, size_t n_bytes) = 0;
+    virtual void close() {}
+};
+
+// File: the 4096-byte ASCII header (`KEY value` lines, NUL padded: CONTENT voltages, DTYPE packed4+4, NANT, NFREQ, NPOL, NAVG, NOUT, UNITS,
+// FIRST_CHANNEL, LAYOUT unit,freq,time,pol,ant), then one record per cut: uint64 t0; int32 dm, beam, width; double snr; the UNITS units.
+class voltage_file_sink : public voltage_sink {
+    FILE* fp = nullptr;
+    uint64_t written = 0;
+    size_t cut_bytes;
+
+public:
+    static constexpr size_t kHeaderBytes = 4096;
+    static constexpr size_t kRecordBytes = 28;
+    voltage_file_sink(const char* path, const bf_config& cfg, int units, int first_channel)
+        : fp(fopen(path, "wb")), cut_bytes((size_t)units * (size_t)cfg.n_freq * (size_t)cfg.n_out_per_gemm * (size_t)cfg.n_avg * (size_t)cfg.n_pol * (size_t)cfg.n_ant)
+    {
+        if (!fp) return;
+        char header[kHeaderBytes] = {0};
+        snprintf(header, sizeof header,
+                 "HDR_SIZE 4096\nCONTENT voltages\nDTYPE packed4+4\nNANT %d\nNFREQ %d\nNPOL %d\nNAVG %d\nNOUT %d\nUNITS %d\nFIRST_CHANNEL %d\n"
+                 "LAYOUT unit,freq,time,pol,ant\nRECORD_HEADER_BYTES 28\n",
+                 cfg.n_ant, cfg.n_freq, cfg.n_pol, cfg.n_avg, cfg.n_out_per_gemm, units, first_channel);
+        if (fwrite(header, 1, sizeof header, fp) != sizeof header) close();
+    }
+    ~voltage_file_sink() override { close(); }
+    voltage_file_sink(const voltage_file_sink&) = delete;
+    voltage_file_sink& operator=(const voltage_file_sink&) = delete;
+    bool is_open() const { return fp != nullptr; }
+    bool deliver(uint64_t t0, int dm, int beam, int width, double snr, const uint8_t* data, size_t n_bytes) override
+    {
+        if (!fp || n_bytes != cut_bytes) return false;
+        const int32_t ints[3] = {dm, beam, width};
+        if (fwrite(&t0, 8, 1, fp) != 1 || fwrite(ints, 4, 3, fp) != 3 || fwrite(&snr, 8, 1, fp) != 1 || fwrite(data, 1, n_bytes, fp) != n_bytes) return false;
+        written++;
+        return true;
+    }
+    void close() override
+    {
+        if (fp) fclose(fp);
+        fp = nullptr;
+    }
+    uint64_t get_cuts_written() const { return written; }
+};
+
 // ---- Pulsar folding behind the DM stage (include/dsabf.h: bf_psr_*, bf_dm_stream_attach_folder; docs/PULSAR_FOLDING.md) -------
 // With observation_options::n_psr > 0 run_observation creates a bf_psr next to the DM stage, attaches it, dumps whenever
 // psr_dump_rows rows or more have been folded (an incomplete integration at the end is dropped) and hands every collected dump to a psr_sink.
@@ -1108,6 +1160,17 @@ struct observation_options {
     int stamp_fbin = 1;
     bool stamp_flagged = false;
     int stamp_max_per_deliver = 16;
+    // Voltage cuts (docs/VOLTAGE_CUTS.md; vcut_sink needs evt, and so sps_widths > 0 and dm_delays; single-rank runs only): a bf_vhist is
+    // created beside the handle with the DM stage's row delays of this rank's trials, in samples (row delay x n_avg: the ladder of
+    // the detected stream, nothing finer), and a ring of vcut_history_units units (0: bf_vhist_units_needed).  Every launch's units are
+    // pushed on its queue behind the detect.  Of the events ONE FEED closes at most vcut_max_per_deliver -- by snr descending, then event
+    // order; flagged ones only with vcut_flagged -- get vcut_units dedispersed units centred on the best member; the rest count in
+    // observation_result::vcuts_dropped.
+    dsabf::voltage_sink* vcut_sink = nullptr;
+    int vcut_units = 2;
+    int vcut_history_units = 0;
+    bool vcut_flagged = false;
+    int vcut_max_per_deliver = 4;
     // Conditioning in front of the DM stage (docs/CONDITIONING.md; needs dm_delays): cond_baseline = pushes of the statistics' window
     // (1 .. 64), 0 = off.  A bf_cond is created next to the DM stage and attached to it: every pushed block is normalised per
     // (channel, beam), masked (cond_mask: host uint8 [cfg.n_freq * world], nonzero = masked, or NULL; cond_auto_threshold > 0 adds the
@@ -1187,6 +1250,10 @@ struct observation_result {
     uint64_t stamps_dropped = 0;    // events beyond stamp_max_per_deliver of their deliver
     uint64_t stamps_missed = 0;     // requests whose rows had left the ring (status 1)
     uint64_t stamps_beyond_end = 0; // requests whose window passes the last row of the run: still "not pushed yet" at the last cut
+    uint64_t vcuts = 0;             // voltage cuts handed to vcut_sink
+    uint64_t vcuts_dropped = 0;     // events beyond vcut_max_per_deliver of their feed
+    uint64_t vcuts_missed = 0;      // requests whose units had left the voltage history (status 1)
+    uint64_t vcuts_beyond_end = 0;  // requests whose window passes the last unit of the run: still "not pushed yet" at the last cut
     uint64_t vis_dumps = 0;         // integrations the correlator dumped (corr_blocks > 0)
     uint64_t sk_dumps = 0;          // integrations the moments stage dumped (sk_blocks > 0)
     uint64_t stokes_units = 0;      // gemm-units the Stokes stage delivered (stokes_beams non-empty)
