@@ -109,7 +109,7 @@ def kernel_build_id() -> str:
     h = hashlib.sha256(_stamp().encode())
     for p in sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.hpp")) + glob.glob(os.path.join(CSRC, "*.h")) +
                     glob.glob(os.path.join(CSRC, "*.inc"))):
-        if os.path.basename(p) == "bf_runtime_internal.h":   # host-only: the runtime's .cpp files share it, no .hip file includes it
+        if os.path.basename(p) in ("bf_runtime_internal.h", "bf_loop_internal.h"):   # host-only: .cpp files share them, no .hip file includes them
             continue
         h.update(os.path.basename(p).encode())
         h.update(open(p, "rb").read())
