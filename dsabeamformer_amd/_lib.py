@@ -278,6 +278,16 @@ SIGNATURES = {
     "bf_vhist_history": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "bf_vhist_cut": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bf_vhist_cut_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "bf_stokes_voltage_entries": (C.c_size_t, [C.POINTER(BfConfig), C.c_int]),
+    "bf_stokes_voltages_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "bf_cdd_sweep_samples": (C.c_double, [C.c_double, C.c_double, C.c_double]),
+    "bf_cdd_edge": (C.c_int, [C.c_double, C.POINTER(C.c_double), C.c_int, C.c_double]),
+    "bf_cdd_chirp": (C.c_int, [C.c_double, C.POINTER(C.c_double), C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p]),
+    "bf_cdd_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "bf_cdd_destroy": (C.c_int, [C.c_void_p]),
+    "bf_cdd_set_chirp": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "bf_cdd_voltages_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]),
+    "bf_cdd_stokes_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
     "bf_psr_model_from_spin": (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_double, C.c_int64, C.POINTER(BfPsrModel)]),
     "bf_psr_entries": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "bf_psr_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),

@@ -1064,6 +1064,11 @@ class StokesBeams(_Owner):
         """bf_stokes_device: the kernel alone into d_out (device int64, n_units * entries * 4), asynchronously on ``stream``."""
         check(self._lib.bf_stokes_device(self._c, _ptr(d_packed), int(n_units), _ptr(d_out), C.c_void_p(stream)))
 
+    def voltages(self, d_packed, n_units: int, d_out, stream: int = 0) -> None:
+        """bf_stokes_voltages_device: the beam samples themselves into d_out (device complex64 [freq][k][pol][n_units * S], the exact
+        integers as float32), asynchronously on ``stream`` and ordered as ``compute`` is (docs/COHERENT_DEDISPERSION.md section 1)."""
+        check(self._lib.bf_stokes_voltages_device(self._c, _ptr(d_packed), int(n_units), _ptr(d_out), C.c_void_p(stream)))
+
     def push(self, d_packed, n_units: int, stream: int = 0) -> None:
         check(self._lib.bf_stokes_push(self._c, _ptr(d_packed), int(n_units), C.c_void_p(stream)))
         self._pushed.append(self.n_sel)
@@ -1091,6 +1096,75 @@ class StokesBeams(_Owner):
         check(self._lib.bf_stokes_collect(self._c, _ptr(out), C.byref(n)))
         self._pushed.pop(0)
         return out[:n.value].copy()
+
+
+def _freqs(freq_ghz):
+    import numpy as np
+
+    f = np.ascontiguousarray(np.atleast_1d(freq_ghz), np.float64)
+    return f, f.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def cdd_sweep_samples(dm: float, f_ghz: float, bw_mhz: float) -> float:
+    """bf_cdd_sweep_samples: the dispersion sweep across one channel of width bw_mhz centred on f_ghz, in samples of 1 / bw_mhz us."""
+    return load().bf_cdd_sweep_samples(float(dm), float(f_ghz), float(bw_mhz))
+
+
+def cdd_edge(dm: float, freq_ghz, bw_mhz: float) -> int:
+    """bf_cdd_edge: the largest ceil(sweep) over the channels -- the samples a segment gives up on each side."""
+    f, p = _freqs(freq_ghz)
+    return check(load().bf_cdd_edge(float(dm), p, len(f), float(bw_mhz)))
+
+
+def cdd_chirp(dm: float, freq_ghz, bw_mhz: float, sideband: int, n_fft: int):
+    """bf_cdd_chirp: the table complex64 [n_chan][n_fft] of a CoherentDedisperser (the 1 / n_fft of the inverse transform included)."""
+    import numpy as np
+
+    f, p = _freqs(freq_ghz)
+    out = np.empty((len(f), max(int(n_fft), 0)), np.complex64)
+    check(load().bf_cdd_chirp(float(dm), p, len(f), float(bw_mhz), int(sideband), int(n_fft), _ptr(out)))
+    return out
+
+
+class CoherentDedisperser(_Owner):
+    """bf_cdd: coherent dedispersion of beam voltages by overlap-save FFT segments (include/dsabf.h, docs/COHERENT_DEDISPERSION.md).
+    ``chirp`` is complex64 [n_chan][n_fft] (cdd_chirp, or any table); the input of ``voltages`` and ``stokes`` is a device complex64
+    array [n_chan][K][2][n_time], what StokesBeams.voltages writes."""
+    _ptr_attr, _destroy = "_c", "bf_cdd_destroy"
+
+    def __init__(self, bf: Beamformer, n_chan: int, n_fft: int, n_edge: int, chirp):
+        self._lib = load()
+        self._c = C.c_void_p()
+        self._bf = bf
+        self.n_chan, self.n_fft, self.n_edge = int(n_chan), int(n_fft), int(n_edge)
+        check(self._lib.bf_cdd_create(bf._h, self.n_chan, self.n_fft, self.n_edge, _ptr(self._table(chirp)), C.byref(self._c)))
+
+    def _table(self, chirp):
+        import numpy as np
+
+        if chirp is None:
+            return None
+        table = np.ascontiguousarray(chirp, np.complex64)
+        if self.n_chan * self.n_fft > 0 and table.size != self.n_chan * self.n_fft:   # (a shape the library refuses: left to it)
+            raise ValueError("the chirp table has %d entries, not n_chan * n_fft = %d" % (table.size, self.n_chan * self.n_fft))
+        return table
+
+    @property
+    def n_valid(self) -> int:
+        """V = n_fft - 2 n_edge: the output samples of one segment."""
+        return self.n_fft - 2 * self.n_edge
+
+    def set_chirp(self, chirp) -> None:
+        """bf_cdd_set_chirp: waits for the stage's kernels in flight, uploads, returns when the table is in place."""
+        check(self._lib.bf_cdd_set_chirp(self._c, _ptr(self._table(chirp))))
+
+    def voltages(self, d_in, K: int, n_time: int, d_out, stream: int = 0) -> None:
+        """bf_cdd_voltages_device: the dedispersed series in the input's shape, asynchronously on ``stream``."""
+        check(self._lib.bf_cdd_voltages_device(self._c, _ptr(d_in), int(K), int(n_time), _ptr(d_out), C.c_void_p(stream)))
+
+    def stokes(self, d_in, K: int, n_time: int, n_int: int, d_out, stream: int = 0) -> None:
+        """bf_cdd_stokes_device: float32 [n_time / n_int][n_chan][K]{I, Q, U, V}; n_int divides n_valid and n_time."""
+        check(self._lib.bf_cdd_stokes_device(self._c, _ptr(d_in), int(K), int(n_time), int(n_int), _ptr(d_out), C.c_void_p(stream)))
 
 
 def sk_select(moments, M: int, centre: float | None = None, n_sigma: float | None = None, max_bad_fraction_ant: float | None = None,

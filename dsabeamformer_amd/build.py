@@ -9,8 +9,8 @@ holds for the incoherent beam (csrc/ib/, docs/INCOHERENT_BEAM.md), the correlato
 solver (csrc/cal/, docs/CALIBRATION.md), the conditioning stage (csrc/cond/, docs/CONDITIONING.md), the voltage moments
 (csrc/sk/, docs/SPECTRAL_KURTOSIS.md), the full-Stokes follow-up beams (csrc/stokes/, docs/STOKES.md), the spatial null (csrc/null/,
 docs/NULLING.md), the stamp cut (csrc/stamp/, docs/EVENTS.md), the pulsar fold (csrc/psr/, docs/PULSAR_FOLDING.md), the periodicity
-search (csrc/ffa/, docs/PERIODICITY.md), the pulse injector (csrc/inj/, docs/INJECTION.md) and the voltage cut (csrc/vcut/,
-docs/VOLTAGE_CUTS.md).
+search (csrc/ffa/, docs/PERIODICITY.md), the pulse injector (csrc/inj/, docs/INJECTION.md), the voltage cut (csrc/vcut/,
+docs/VOLTAGE_CUTS.md) and the coherent dedispersion stage (csrc/cdd/, docs/COHERENT_DEDISPERSION.md).
 """
 from __future__ import annotations
 
@@ -78,7 +78,7 @@ def sources() -> list[str]:
                   glob.glob(os.path.join(COND, "*.hip")) + glob.glob(os.path.join(SK, "*.hip")) +
                   glob.glob(os.path.join(STOKES, "*.hip")) + glob.glob(os.path.join(NULL, "*.hip")) + glob.glob(os.path.join(CUT, "*.hip")) +
                   glob.glob(os.path.join(PSR, "*.hip")) + glob.glob(os.path.join(FFA, "*.hip")) + glob.glob(os.path.join(INJ, "*.hip")) +
-                  glob.glob(os.path.join(VCUT, "*.hip"))
+                  glob.glob(os.path.join(VCUT, "*.hip")) + glob.glob(os.path.join(CDD, "*.hip"))
                   if os.path.abspath(p) not in [os.path.abspath(m) for m in MAINS.values()])
 
 
@@ -98,6 +98,7 @@ PSR = os.path.join(CSRC, "psr")                     # device code of the pulsar 
 FFA = os.path.join(CSRC, "ffa")                     # device code of the periodicity search: the same
 INJ = os.path.join(CSRC, "inj")                     # device code of the pulse injector: the same
 VCUT = os.path.join(CSRC, "vcut")                   # device code of the voltage cut (bf_vhist_cut): the same
+CDD = os.path.join(CSRC, "cdd")                     # device code of the coherent dedispersion stage: the same
 
 
 def kernel_build_id() -> str:
@@ -127,7 +128,7 @@ def _headers() -> list[str]:
     return glob.glob(os.path.join(CSRC, "*.h*")) + glob.glob(os.path.join(CSRC, "*.inc")) + glob.glob(os.path.join(SPS, "*.h")) + glob.glob(os.path.join(IB, "*.h")) + \
         glob.glob(os.path.join(CORR, "*.h")) + glob.glob(os.path.join(CAL, "*.h")) + glob.glob(os.path.join(COND, "*.h")) + glob.glob(os.path.join(SK, "*.h")) + \
         glob.glob(os.path.join(STOKES, "*.h")) + glob.glob(os.path.join(NULL, "*.h")) + glob.glob(os.path.join(CUT, "*.h")) + glob.glob(os.path.join(PSR, "*.h")) + \
-        glob.glob(os.path.join(FFA, "*.h")) + glob.glob(os.path.join(INJ, "*.h")) + glob.glob(os.path.join(VCUT, "*.h")) + \
+        glob.glob(os.path.join(FFA, "*.h")) + glob.glob(os.path.join(INJ, "*.h")) + glob.glob(os.path.join(VCUT, "*.h")) + glob.glob(os.path.join(CDD, "*.h")) + \
         glob.glob(os.path.join(ROOT, "include", "*.h*"))
 
 

@@ -151,6 +151,11 @@ int main(int argc, char* argv[])
     std::string voltages_path;
     int voltage_units = 2, voltage_history = 0;
     bool voltage_units_given = false, voltage_history_given = false, voltage_flagged = false, voltage_bad = false;
+    // coherent dedispersion of a --voltages file (docs/COHERENT_DEDISPERSION.md): --coherent V_FILE --coherent-out FILE [--coherent-fft N]
+    // [--coherent-int n] [--coherent-sideband +1|-1]; no observation is run
+    std::string coherent_path, coherent_out;
+    int coherent_fft = 0, coherent_int = 1, coherent_sideband = 1;
+    bool coherent_extra_given = false, coherent_bad = false;
     // pulsar folding (docs/PULSAR_FOLDING.md): --fold f0[:f1[:phase0]] up to 4 times, --fold-dm dm (the k-th belongs to the k-th --fold),
     // --fold-bins n, --fold-rows rows_per_dump, --fold-out FILE
     struct fold_spec {
@@ -176,7 +181,7 @@ int main(int argc, char* argv[])
     std::vector<inject_spec> inj_bursts, inj_trains;
     std::string inj_path;
     bool inj_bad = false;
-    enum { kEvents = 1000, kEventTol, kEventVeto, kStamps, kStampShape, kStampFlagged, kFold, kFoldDm, kFoldBins, kFoldRows, kFoldOut, kFfa, kFfaSeg, kFfaDec, kFfaOct, kFfaWidths, kFfaSnr, kFfaOut, kFfaDetrend, kInject, kInjectTrain, kInjectOut, kVoltages, kVoltageUnits, kVoltageHistory, kVoltageFlagged };
+    enum { kEvents = 1000, kEventTol, kEventVeto, kStamps, kStampShape, kStampFlagged, kFold, kFoldDm, kFoldBins, kFoldRows, kFoldOut, kFfa, kFfaSeg, kFfaDec, kFfaOct, kFfaWidths, kFfaSnr, kFfaOut, kFfaDetrend, kInject, kInjectTrain, kInjectOut, kVoltages, kVoltageUnits, kVoltageHistory, kVoltageFlagged, kCoherent, kCoherentOut, kCoherentFft, kCoherentInt, kCoherentSideband };
     static const option long_options[] = {{"events", required_argument, nullptr, kEvents},       {"event-tol", required_argument, nullptr, kEventTol},
                                           {"event-veto", required_argument, nullptr, kEventVeto}, {"stamps", required_argument, nullptr, kStamps},
                                           {"stamp-shape", required_argument, nullptr, kStampShape}, {"stamp-flagged", no_argument, nullptr, kStampFlagged},
@@ -191,6 +196,9 @@ int main(int argc, char* argv[])
                                           {"inject-out", required_argument, nullptr, kInjectOut},
                                           {"voltages", required_argument, nullptr, kVoltages},   {"voltage-units", required_argument, nullptr, kVoltageUnits},
                                           {"voltage-history", required_argument, nullptr, kVoltageHistory}, {"voltage-flagged", no_argument, nullptr, kVoltageFlagged},
+                                          {"coherent", required_argument, nullptr, kCoherent},   {"coherent-out", required_argument, nullptr, kCoherentOut},
+                                          {"coherent-fft", required_argument, nullptr, kCoherentFft}, {"coherent-int", required_argument, nullptr, kCoherentInt},
+                                          {"coherent-sideband", required_argument, nullptr, kCoherentSideband},
                                           {nullptr, 0, nullptr, 0}};
     // a non-negative integer that fills its whole field; anything else marks the command line as malformed
     auto number = [&long_bad](const char* text, const char** end, int* out) {
@@ -321,6 +329,18 @@ int main(int argc, char* argv[])
             case kStampFlagged: stamp_flagged = true; break;
             case kVoltages: voltages_path = optarg; break;
             case kVoltageFlagged: voltage_flagged = true; break;
+            case kCoherent: coherent_path = optarg; break;
+            case kCoherentOut: coherent_out = optarg; break;
+            case kCoherentFft:
+            case kCoherentInt:
+            case kCoherentSideband: {   // a whole number that fills its field
+                char* e = nullptr;
+                const long v = strtol(optarg, &e, 10);
+                if (e == optarg || *e || v < -1000000000L || v > 1000000000L || *optarg == ' ') coherent_bad = true;
+                (arg == kCoherentFft ? coherent_fft : arg == kCoherentInt ? coherent_int : coherent_sideband) = (int)v;
+                coherent_extra_given = true;
+                break;
+            }
             case kVoltageUnits:
             case kVoltageHistory: {   // a whole number >= 1
                 char* e = nullptr;
@@ -479,6 +499,14 @@ int main(int argc, char* argv[])
                              "                         input layout centred on the best member, cut from a history of UNITS gemm-units [what the search needs]\n"
                              "                         kept on the device; not with -R; --voltages without --events, the others without --voltages, or a\n"
                              "                         number < 1: beam exits with a usage error\n"
+                             " --coherent V_FILE --coherent-out FILE -M dm_max [-N n_dm] [-T tsamp_ms] [--coherent-fft N] [--coherent-int n]\n"
+                             "                         [--coherent-sideband +1|-1] [-A gains]   no observation: every cut of V_FILE (written with --voltages by a run\n"
+                             "                         with the same -M -N -T -g -p -d -A) coherently dedispersed at the DM of its trial, for its beam alone: the beam\n"
+                             "                         voltages, then overlap-save segments of N samples [the smallest power of two >= 256 whose quarter holds the\n"
+                             "                         dispersion sweep across a channel; 64 .. 4096 if given] through a chirp filter, then Stokes I, Q, U, V summed\n"
+                             "                         over n [1] samples, float32 [time][channel][4] per cut to FILE; a cut whose sweep needs more than 4096 samples\n"
+                             "                         or that is shorter than one segment is left out and counted; with -j / -k / -E, without --coherent-out or\n"
+                             "                         -M, the others without --coherent, or an N that is no power of two in range: a usage error\n"
                              " --fold F0[:F1[:PHASE0]] [--fold-dm DM] [--fold-bins N] [--fold-rows ROWS] [--fold-out FILE]   with -M: the detected stream of\n"
                              "                         every beam folded at spin frequency F0 Hz, derivative F1 Hz/s [0] and phase PHASE0 turns [0] at the first row,\n"
                              "                         dedispersed at DM pc/cc [0] (the k-th --fold-dm belongs to the k-th --fold; up to 4 --fold), into N [64] phase\n"
@@ -600,6 +628,34 @@ int main(int argc, char* argv[])
     if (!voltages_path.empty() && world > 1) {
         fprintf(stderr, "beam: --voltages is not available in a sharded run (-R): a trigger is not sent to the ranks that hold the other channels\n");
         return EXIT_FAILURE;
+    }
+    if (coherent_path.empty() && (!coherent_out.empty() || coherent_extra_given)) {
+        fprintf(stderr, "beam: --coherent-out / --coherent-fft / --coherent-int / --coherent-sideband belong to coherent dedispersion: give --coherent V_FILE\n");
+        return EXIT_FAILURE;
+    }
+    if (!coherent_path.empty()) {
+        if (junk_blocks >= 0 || !ring_key.empty() || !solve_vis.empty()) {
+            fprintf(stderr, "beam: --coherent runs no observation and no solver: leave out -j / -k / -E\n");
+            return EXIT_FAILURE;
+        }
+        if (coherent_out.empty()) {
+            fprintf(stderr, "beam: --coherent needs --coherent-out FILE (where the Stokes parameters go)\n");
+            return EXIT_FAILURE;
+        }
+        if (!(dm_max > 0.0)) {
+            fprintf(stderr, "beam: --coherent takes the DM of a cut from the ladder of the run that wrote it: give that run's -M dm_max (and -N, -T)\n");
+            return EXIT_FAILURE;
+        }
+        bool pow2 = false;
+        for (int n = 64; n <= 4096; n *= 2) pow2 = pow2 || coherent_fft == n;
+        if (coherent_bad || (coherent_fft != 0 && !pow2) || coherent_int < 1 || (coherent_sideband != 1 && coherent_sideband != -1)) {
+            fprintf(stderr, "beam: --coherent-fft N: a power of two 64 .. 4096; --coherent-int n: a whole number >= 1; --coherent-sideband: +1 or -1\n");
+            return EXIT_FAILURE;
+        }
+        if (!(tsamp_ms > 0.0)) {
+            fprintf(stderr, "beam: -T %g: the sample time must be positive\n", tsamp_ms);
+            return EXIT_FAILURE;
+        }
     }
     if (!stamps_path.empty()) {   // the band is the production geometry's, whatever -R
         bf_config band;
@@ -801,7 +857,24 @@ int main(int argc, char* argv[])
     }
     // -A: read before any device is touched; a DEBUG run has the DEBUG geometry, observation mode a rank's share of the production one
     std::vector<double> gains_layer;
-    if (!apply_gains.empty()) {
+    voltage_file_header coherent_header;   // --coherent: the geometry is the file's; read, with -A and -f, before any device is touched
+    if (!coherent_path.empty()) {
+        std::string why;
+        if (!read_voltage_header(coherent_path.c_str(), &coherent_header, &why)) {
+            fprintf(stderr, "beam: --coherent %s\n", why.c_str());
+            return EXIT_FAILURE;
+        }
+        if (!apply_gains.empty() &&
+            !read_gains_layer(apply_gains.c_str(), coherent_header.n_ant, coherent_header.n_freq, coherent_header.first_channel, &gains_layer, &why)) {
+            fprintf(stderr, "beam: -A %s\n", why.c_str());
+            return EXIT_FAILURE;
+        }
+        if (!ant_flags_path.empty() && !read_index_file(ant_flags_path.c_str(), coherent_header.n_ant, &ant_flags, &why)) {
+            fprintf(stderr, "beam: -f %s\n", why.c_str());
+            return EXIT_FAILURE;
+        }
+    }
+    if (!apply_gains.empty() && coherent_path.empty()) {
         const bool observe = junk_blocks >= 0 || !ring_key.empty();
         bf_config gcfg;
         bf_config_default(&gcfg, observe ? 0 : 1);
@@ -878,6 +951,38 @@ int main(int argc, char* argv[])
             }
             std::cout << "Wrote " << n_records << " null records to " << null_path << std::endl;
         }
+        return 0;
+    }
+
+    if (!coherent_path.empty()) {   // --coherent: a file of voltage cuts to coherently dedispersed Stokes parameters, no observation
+        bf_config pcfg;
+        bf_config_default(&pcfg, /*debug=*/0);
+        std::vector<antenna> pos((size_t)coherent_header.n_ant);
+        std::vector<beam_direction> dir((size_t)pcfg.n_beams);
+        if (!opt.positions || read_in_position_locations(opt.positions, coherent_header.n_ant, pos.data()) != 0) default_positions(coherent_header.n_ant, pos.data());
+        if (!opt.directions || read_in_beam_directions(opt.directions, pcfg.n_beams, dir.data()) != 0) default_directions(pcfg.n_beams, dir.data());
+        coherent_options copt;
+        copt.voltages_path = coherent_path.c_str();
+        copt.out_path = coherent_out.c_str();
+        copt.dm_max = dm_max;
+        copt.tsamp_ms = tsamp_ms;
+        copt.n_dm_cap = n_dm_cap;
+        copt.n_fft = coherent_fft;
+        copt.n_int = coherent_int;
+        copt.sideband = coherent_sideband;
+        copt.gpu = opt.gpu;
+        copt.device = opt.device;
+        copt.pos = pos.data();
+        copt.dir = dir.data();
+        copt.gains = gains_layer.empty() ? nullptr : gains_layer.data();
+        copt.ant_flags = gains_layer.empty() || ant_flags.empty() ? nullptr : ant_flags.data();
+        uint64_t n_written = 0, n_refused = 0;
+        const int crc = coherent_voltage_file(copt, &n_written, &n_refused, std::cout);
+        if (crc != BF_OK) {
+            fprintf(stderr, "GPUassert: %s (%d)\n", bf_last_error(), crc);
+            return EXIT_FAILURE;
+        }
+        std::cout << "Wrote " << n_written << " coherently dedispersed cuts to " << coherent_out << std::endl;
         return 0;
     }
 

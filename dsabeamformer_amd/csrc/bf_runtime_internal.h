@@ -94,7 +94,7 @@ struct bf_resources {
     void release();
 };
 
-// The base of the ten stage objects (bf_dm_stream, bf_sps, bf_cond, bf_corr, bf_sk, bf_stokes, bf_psr, bf_ffa, bf_inj, bf_vhist: opaque to callers, each defined in its own file).
+// The base of the eleven stage objects (bf_dm_stream, bf_sps, bf_cond, bf_corr, bf_sk, bf_stokes, bf_psr, bf_ffa, bf_inj, bf_vhist, bf_cdd: opaque to callers, each defined in its own file).
 struct bf_stage {
     bf_handle* h = nullptr;                 // NULL: the handle went first and took the device side with it
     const char* const noun;                 // "DM stage", "search stage", ...: the orphan check's message

@@ -250,6 +250,36 @@ int bf_stokes_device(bf_stokes* s, const void* d_packed, int n_units, int64_t* d
     return BF_OK;
 }
 
+size_t bf_stokes_voltage_entries(const bf_config* cfg, int n_sel)
+{
+    if (!cfg || cfg->n_freq <= 0 || cfg->n_out_per_gemm <= 0 || cfg->n_avg <= 0 || cfg->n_pol != 2 || n_sel < 1 || n_sel > BF_STOKES_MAX_BEAMS) return 0;
+    return (size_t)cfg->n_freq * (size_t)n_sel * 2 * (size_t)(cfg->n_out_per_gemm * cfg->n_avg);
+}
+
+// The beam samples before the products (docs/COHERENT_DEDISPERSION.md section 1): one more reader of the weights, ordered as bf_stokes_device.
+int bf_stokes_voltages_device(bf_stokes* s, const void* d_packed, int n_units, void* d_out, void* hip_stream)
+{
+    if (!s || !d_packed || !d_out) return fail(BF_ERR_INVALID, "NULL argument");
+    if (int rc = orphaned(s)) return rc;
+    if (n_units <= 0) return fail(BF_ERR_INVALID, "bf_stokes_voltages_device: n_units must be positive");
+    if (((uintptr_t)d_packed & 15) || ((uintptr_t)d_out & 7))
+        return fail(BF_ERR_INVALID, "misaligned device pointer: d_packed must be 16-byte and d_out 8-byte aligned");
+    const bf_config& cfg = s->h->cfg;
+    const int S = cfg.n_out_per_gemm * cfg.n_avg;
+    if ((long long)n_units * S > 0x7fffffffLL)
+        return fail(BF_ERR_INVALID, "bf_stokes_voltages_device: %d units of %d samples are a series of 2^31 samples or more", n_units, S);
+    if (!s->n_sel) return fail(BF_ERR_STATE, "bf_stokes_voltages_device: bf_stokes_set_weights has not been called");
+    ON_DEVICE(s->h);
+    hipStream_t q = as_stream(hip_stream);
+    HIP_TRY(hipStreamWaitEvent(q, s->gathered, 0));
+    HIP_TRY(dsabf::launch_stokes_voltages(cfg.n_ant, cfg.n_freq, S, s->n_sel, d_packed, n_units, s->d_w, (float*)d_out, s->h->n_cus, q));
+    if (s->direct_done) HIP_TRY(hipStreamWaitEvent(q, s->direct_done, 0));
+    hipEvent_t ev = s->direct_ev[s->n_direct++ % 2];
+    HIP_TRY(hipEventRecord(ev, q));
+    s->direct_done = ev;
+    return BF_OK;
+}
+
 int bf_stokes_push(bf_stokes* s, const void* d_packed, int n_units, void* hip_stream)
 {
     if (!s || !d_packed) return fail(BF_ERR_INVALID, "NULL argument");

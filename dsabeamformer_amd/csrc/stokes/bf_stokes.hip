@@ -45,7 +45,7 @@ struct StokesArgs {
     int S, K, n_int, T;               // samples per unit, beams, window, windows per unit
     int wps, spans;                   // windows per span (8; cooperative: 8 / gcd(n_int, 8)), spans per (unit, channel)
     long long items, per;             // spans of the launch, and of one workgroup
-    int mode;                         // kDirect, kPerWave or kCooperative
+    int mode;                         // kDirect, kPerWave, kCooperative or kVoltages
 };
 
 struct GatherArgs {
@@ -98,12 +98,14 @@ __device__ __forceinline__ void load_column(const uint8_t* p, bool valid, int n_
     }
 }
 
-enum { kDirect = 0, kPerWave = 1, kCooperative = 2 };   // n_int == 1; a span per wave; a span per workgroup
+// n_int == 1; a span per wave; a span per workgroup; the beam samples themselves (the work split of kDirect, out is float2
+// [f][k][pol][n_units S]: bf_stokes_voltages_device, docs/COHERENT_DEDISPERSION.md section 1)
+enum { kDirect = 0, kPerWave = 1, kCooperative = 2, kVoltages = 3 };
 
 template <int NKS, bool VEC, int MODE>
 __global__ __launch_bounds__(kThreads) void stokes_kernel(StokesArgs a)
 {
-    constexpr bool DIRECT = MODE == kDirect, COOP = MODE == kCooperative;
+    constexpr bool VOLT = MODE == kVoltages, DIRECT = MODE == kDirect || VOLT, COOP = MODE == kCooperative;
     constexpr int kStep = COOP ? kWaves : 1;              // tiles from one of a wave's tiles to its next
     __shared__ v4i wlds[NKS * 2 * 64];                    // [k-step][re, im][lane]
     __shared__ u64 image[DIRECT ? 1 : kWaves * kImage];   // per wave (cooperative: the first, for all): [window][beam column][I, Q, U, V]
@@ -184,8 +186,29 @@ __global__ __launch_bounds__(kThreads) void stokes_kernel(StokesArgs a)
                         acc_im = __builtin_amdgcn_mfma_i32_16x16x64_i8(a_re, b_wi, acc_im, 0, 0, 0);
                     }
                     // rows 4 g ... + 3 of the tile: the samples 8 (tile0 + tl) + 2 g + {0, 1} of the unit, each as (X, Y)
+                    if (VOLT) {   // two consecutive samples of X and of Y: 16 bytes each where the pair starts on an even element of memory
+                        const int j = 8 * (tile0 + tl) + 2 * g;
+                        if (j < a.S && k < a.K) {
+                            const size_t nt = (size_t)a.n_units * (size_t)a.S;
+                            float2* ox = reinterpret_cast<float2*>(a.out) + ((size_t)f * a.K + k) * 2 * nt + (size_t)u * a.S + j;
+                            float2* oy = ox + nt;
+                            const bool two = j + 1 < a.S;
+                            if (two && !((uintptr_t)ox & 15)) {
+                                *reinterpret_cast<float4*>(ox) = make_float4((float)acc_re[0], (float)acc_im[0], (float)acc_re[2], (float)acc_im[2]);
+                            } else {
+                                ox[0] = make_float2((float)acc_re[0], (float)acc_im[0]);
+                                if (two) ox[1] = make_float2((float)acc_re[2], (float)acc_im[2]);
+                            }
+                            if (two && !((uintptr_t)oy & 15)) {
+                                *reinterpret_cast<float4*>(oy) = make_float4((float)acc_re[1], (float)acc_im[1], (float)acc_re[3], (float)acc_im[3]);
+                            } else {
+                                oy[0] = make_float2((float)acc_re[1], (float)acc_im[1]);
+                                if (two) oy[1] = make_float2((float)acc_re[3], (float)acc_im[3]);
+                            }
+                        }
+                    }
 #pragma unroll
-                    for (int pr = 0; pr < 2; pr++) {
+                    for (int pr = 0; pr < 2 && !VOLT; pr++) {
                         const int xr = acc_re[2 * pr], xi = acc_im[2 * pr], yr = acc_re[2 * pr + 1], yi = acc_im[2 * pr + 1];
                         if (DIRECT) {
                             const int j = 8 * (tile0 + tl) + 2 * g + pr;
@@ -254,6 +277,8 @@ hipError_t launch_n(const StokesArgs& a, unsigned grid, hipStream_t s)
 {
     if (a.mode == kDirect)
         hipLaunchKernelGGL((stokes_kernel<NKS, VEC, kDirect>), dim3(grid), dim3(kThreads), 0, s, a);
+    else if (a.mode == kVoltages)
+        hipLaunchKernelGGL((stokes_kernel<NKS, VEC, kVoltages>), dim3(grid), dim3(kThreads), 0, s, a);
     else if (a.mode == kPerWave)
         hipLaunchKernelGGL((stokes_kernel<NKS, VEC, kPerWave>), dim3(grid), dim3(kThreads), 0, s, a);
     else
@@ -304,11 +329,31 @@ hipError_t launch_stokes_gather(const int8_t* d_w, const int* beams, int n_sel, 
     return hipGetLastError();
 }
 
+namespace {
+hipError_t launch_any(int n_ant, int n_freq, int n_cols, int n_sel, int n_int, const void* d_packed, int n_units, const int8_t* d_image,
+                      long long* d_out, int n_cus, hipStream_t s, bool voltages);
+}
+
 hipError_t launch_stokes(int n_ant, int n_freq, int n_cols, int n_sel, int n_int, const void* d_packed, int n_units, const int8_t* d_image,
                          long long* d_out, int n_cus, hipStream_t s)
 {
+    if ((uintptr_t)d_out & 15) return hipErrorInvalidValue;
+    return launch_any(n_ant, n_freq, n_cols, n_sel, n_int, d_packed, n_units, d_image, d_out, n_cus, s, false);
+}
+
+hipError_t launch_stokes_voltages(int n_ant, int n_freq, int n_cols, int n_sel, const void* d_packed, int n_units, const int8_t* d_image,
+                                  float* d_out, int n_cus, hipStream_t s)
+{
+    if (((uintptr_t)d_out & 7) || n_units <= 0 || (long long)n_units * n_cols > 0x7fffffffLL) return hipErrorInvalidValue;
+    return launch_any(n_ant, n_freq, n_cols, n_sel, 1, d_packed, n_units, d_image, reinterpret_cast<long long*>(d_out), n_cus, s, true);
+}
+
+namespace {
+hipError_t launch_any(int n_ant, int n_freq, int n_cols, int n_sel, int n_int, const void* d_packed, int n_units, const int8_t* d_image,
+                      long long* d_out, int n_cus, hipStream_t s, bool voltages)
+{
     if (n_freq <= 0 || n_units <= 0 || !d_packed || !d_image || !d_out || !stokes_supported(n_ant, 2, n_cols, n_sel, n_int) ||
-        ((uintptr_t)d_packed & 3) || ((uintptr_t)d_out & 15) || ((uintptr_t)d_image & 15))
+        ((uintptr_t)d_packed & 3) || ((uintptr_t)d_image & 15))
         return hipErrorInvalidValue;
     StokesArgs a;
     a.in = (const uint8_t*)d_packed;
@@ -326,7 +371,7 @@ hipError_t launch_stokes(int n_ant, int n_freq, int n_cols, int n_sel, int n_int
     a.spans = (a.T + a.wps - 1) / a.wps;
     a.items = (long long)n_freq * n_units * a.spans;
     const bool cooperative = n_int > 1 && a.items < cap;   // fewer waves than 8 per CU: a span per workgroup, and shorter spans
-    a.mode = n_int == 1 ? kDirect : cooperative ? kCooperative : kPerWave;
+    a.mode = voltages ? kVoltages : n_int == 1 ? kDirect : cooperative ? kCooperative : kPerWave;
     if (cooperative) {
         int gcd = 8;
         while (n_int % gcd) gcd >>= 1;
@@ -345,5 +390,6 @@ hipError_t launch_stokes(int n_ant, int n_freq, int n_cols, int n_sel, int n_int
     (void)hipGetLastError();
     return n_ant % 16 == 0 && ((uintptr_t)d_packed & 15) == 0 ? launch_v<true>(a, grid, s) : launch_v<false>(a, grid, s);
 }
+}  // namespace
 
 }  // namespace dsabf

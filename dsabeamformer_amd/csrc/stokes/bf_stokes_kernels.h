@@ -39,4 +39,10 @@ hipError_t launch_stokes_gather(const int8_t* d_w, const int* beams, int n_sel, 
 hipError_t launch_stokes(int n_ant, int n_freq, int n_cols, int n_sel, int n_int, const void* d_packed, int n_units, const int8_t* d_image,
                          long long* d_out, int n_cus, hipStream_t s);
 
+// The beam samples themselves, the work split of n_int = 1: d_out [freq][k][pol][n_units * n_cols]{re, im} float (8-byte aligned; the
+// exact integers of the accumulators, |.| <= 2^19), n_units * n_cols < 2^31.  16-byte stores where a lane's pair of samples starts on
+// a 16-byte address, 8-byte ones otherwise.
+hipError_t launch_stokes_voltages(int n_ant, int n_freq, int n_cols, int n_sel, const void* d_packed, int n_units, const int8_t* d_image,
+                                  float* d_out, int n_cus, hipStream_t s);
+
 }  // namespace dsabf

@@ -326,6 +326,33 @@ def read_voltage_file(path: str):
     return hdr, cuts
 
 
+COHERENT_LAYOUT = "time,freq,iquv"
+
+
+def read_coherent_file(path: str):
+    """Parse a `beam --coherent` file (docs/COHERENT_DEDISPERSION.md section 5): returns (header dict, list of dict(t0, dm, beam, width, snr,
+    dm_value, n_edge, n_fft, data float32 [NTIME / NINT][NFREQ][4] = {I, Q, U, V})), in the order of the voltage file's cuts."""
+    raw = open(path, "rb").read()
+    text = raw[:DETECTED_HEADER_BYTES].split(b"\0", 1)[0].decode()
+    hdr = dict(line.split(None, 1) for line in text.splitlines() if line.strip())
+    assert hdr["CONTENT"] == "coherent_stokes" and hdr["DTYPE"] == "float32" and hdr["LAYOUT"] == COHERENT_LAYOUT
+    shape = (int(hdr["NTIME"]) // int(hdr["NINT"]), int(hdr["NFREQ"]), 4)
+    n, at, rec = int(np.prod(shape)), int(hdr["HDR_SIZE"]), int(hdr["RECORD_HEADER_BYTES"])
+    assert rec == 44
+    cuts = []
+    while at < len(raw):
+        t0 = int(np.frombuffer(raw, "<u8", 1, at)[0])
+        dm, beam, width = (int(v) for v in np.frombuffer(raw, "<i4", 3, at + 8))
+        snr, dm_value = (float(v) for v in np.frombuffer(raw, "<f8", 2, at + 20))
+        n_edge, n_fft = (int(v) for v in np.frombuffer(raw, "<i4", 2, at + 36))
+        at += rec
+        cuts.append(dict(t0=t0, dm=dm, beam=beam, width=width, snr=snr, dm_value=dm_value, n_edge=n_edge, n_fft=n_fft,
+                         data=np.frombuffer(raw, "<f4", n, at).reshape(shape)))
+        at += 4 * n
+    assert at == len(raw)
+    return hdr, cuts
+
+
 def read_dm_file(path: str):
     """Parse a dsabf::dm_file_sink file: returns (header dict, float32 array [n_dm][T][n_beams], list of (first_t, n_t) per
     chunk).  The chunks ([dm][t][beam] each) are joined along t; they follow each other without gaps."""

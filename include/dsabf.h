@@ -766,6 +766,53 @@ int bf_vhist_cut(bf_vhist *v, const bf_vcut_request *reqs, int n_req, int n_unit
                  void *hip_stream);
 int bf_vhist_cut_host(bf_vhist *v, const bf_vcut_request *reqs, int n_req, int n_units_out, void *host_out, int32_t *status);
 
+/* ---- Coherent dedispersion: beam voltages and an FFT chirp filter (docs/COHERENT_DEDISPERSION.md) -----------------------------
+ * bf_vhist_cut aligns the channels of a burst by whole samples and bf_stokes_device forms Stokes parameters at every voltage
+ * sample, but the dispersion INSIDE a channel (tens of samples at the DMs of the search) stays.  The reference holds the beam
+ * voltages only as the GEMM's scratch d_C (src/beamformer.cu:178) and squares them away at once (src/beamformer.cuh:149-152), so
+ * it has nothing to dedisperse coherently.  Two pieces remove the smear; both are opt-in, and with neither used nothing changes.
+ * bf_stokes_voltages_device: the tied-array beam samples the Stokes kernel forms, kept instead of multiplied out.  n_units units
+ *   at d_packed (16-byte aligned, as for bf_stokes_device) -> d_out (device, 8-byte aligned) [freq][k][pol][n_units S]{re, im}
+ *   float32, S = n_out_per_gemm n_avg: time runs across the units, so a series is contiguous.  The values are the exact integers
+ *   n[u][f][2 j + pol][k] of docs/STOKES.md section 1 (|re|, |im| <= 2^19).  Ordered exactly as bf_stokes_device (behind the last
+ *   write of the weights; a later write waits for it).  bf_stokes_voltage_entries(cfg, K) = n_freq K 2 S complex samples per unit
+ *   (0 if undefined).  BF_ERR_INVALID, nothing launched: NULL pointers, n_units < 1, misalignment, n_units S >= 2^31;
+ *   BF_ERR_STATE before any weights.
+ * bf_cdd: the chirp filter.  Input x[chan][k][pol][n]{re, im} float32 (device, 8-byte aligned), n in [0, n_time) -- the layout
+ *   above, from anywhere.  bf_cdd_create: n_chan >= 1, an FFT length n_fft = 2^m with 6 <= m <= 12, an edge 0 <= n_edge <=
+ *   n_fft / 4, and a HOST table chirp[n_chan][n_fft]{re, im} float32 that is copied to the device.  With V = n_fft - 2 n_edge,
+ *   segment g = 0 ... ceil(n_time / V) - 1 reads the samples [g V - n_edge, g V - n_edge + n_fft), zero outside [0, n_time), and
+ *     y_g = IDFT( DFT(segment) * chirp[chan] )   (no other scale: the 1 / n_fft belongs to the table),
+ *   output sample g V + i = y_g[n_edge + i] for 0 <= i < V, g V + i < n_time (overlap-save).  float32 throughout, every operation
+ *   rounded on its own, in ONE operation order (docs section 2) that does not depend on K, n_chan, n_time or the segment; the
+ *   twiddle factors are a table computed on the host in double and rounded.
+ * bf_cdd_voltages_device: d_out in the input's shape.  bf_cdd_stokes_device: d_out[t][chan][k]{I, Q, U, V} float32, t < n_time /
+ *   n_int; per sample px = xr xr + xi xi, py likewise, uu = xr yr + xi yi, vv = xi yr - xr yi, I = px + py, Q = px - py, U = 2 uu,
+ *   V = 2 vv, summed over the window in ascending order of the samples (the first term is not added to a zero).  n_int must divide
+ *   both V and n_time.  Both are asynchronous on hip_stream and write every cell once.
+ * bf_cdd_set_chirp: waits for the stage's kernels in flight, uploads, returns when the table is in place.
+ * BF_ERR_INVALID, nothing launched: NULL pointers, n_fft not one of the seven lengths, n_edge out of range, K < 1, n_time < 1 or
+ *   >= 2^31, n_int < 1 or not dividing V and n_time, d_in or d_out not 8-byte aligned, more than 2^31 - 1 (segment, channel, beam)
+ *   workgroups.  A handle that goes first: BF_ERR_STATE, and the stage can still be destroyed.
+ * Host helpers, plain double, no device, with the dispersion constant 4.15 ms GHz^2 of dm_delays:
+ *   bf_cdd_sweep_samples(dm, f_ghz, bw_mhz) = 4.15e3 dm ((f - bw/2000)^-2 - (f + bw/2000)^-2) bw_mhz: the sweep across a channel of
+ *     width bw_mhz centred on f_ghz, in samples of 1 / bw_mhz microseconds.
+ *   bf_cdd_edge: the largest ceil(sweep) over the channels (negative: an error code).
+ *   bf_cdd_chirp fills out[n_chan][n_fft]{re, im}: for bin j, nu = sideband (j < N/2 ? j : j - N) bw_mhz / N MHz, F = 1000 f MHz,
+ *     phi = 2 pi 4.15e9 dm nu^2 / (F^2 (F + nu)), out = (cos phi, sin phi) / N rounded to float32.  sideband = +1 or -1: whether
+ *     baseband frequency rises with sky frequency. */
+typedef struct bf_cdd bf_cdd;
+size_t bf_stokes_voltage_entries(const bf_config *cfg, int n_sel);
+int bf_stokes_voltages_device(bf_stokes *s, const void *d_packed, int n_units, void *d_out, void *hip_stream);
+double bf_cdd_sweep_samples(double dm, double f_ghz, double bw_mhz);
+int bf_cdd_edge(double dm, const double *freq_ghz, int n_chan, double bw_mhz);
+int bf_cdd_chirp(double dm, const double *freq_ghz, int n_chan, double bw_mhz, int sideband, int n_fft, float *out);
+int bf_cdd_create(bf_handle *h, int n_chan, int n_fft, int n_edge, const float *chirp, bf_cdd **out);
+int bf_cdd_destroy(bf_cdd *c);
+int bf_cdd_set_chirp(bf_cdd *c, const float *chirp);
+int bf_cdd_voltages_device(bf_cdd *c, const void *d_in, int K, int64_t n_time, void *d_out, void *hip_stream);
+int bf_cdd_stokes_device(bf_cdd *c, const void *d_in, int K, int64_t n_time, int n_int, void *d_out, void *hip_stream);
+
 /* ---- Pulsar folding: phase-binned profiles of every beam (docs/PULSAR_FOLDING.md) -------------------------------------------
  * The reference stops at a DM-0 collapse copied to the host (src/beamformer.cu:498-510) and keeps nothing across blocks; the
  * search behind the DM stage looks at one push at a time.  A bf_psr integrates the detected rows x[row][freq][beam] (fp32, the

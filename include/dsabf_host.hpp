@@ -726,6 +726,38 @@ public:
     uint64_t get_cuts_written() const { return written; }
 };
 
+// ---- Coherent dedispersion of a file of voltage cuts (include/dsabf.h: bf_stokes_voltages_device, bf_cdd_*; `beam --coherent`;
+// docs/COHERENT_DEDISPERSION.md section 5) ---------------------------------------------------------------------------------------
+struct voltage_file_header {
+    int n_ant = 0, n_freq = 0, n_pol = 0, n_avg = 0, n_out = 0, units = 0, first_channel = 0;
+    size_t record_bytes = 0, n_records = 0;   // packed bytes of one cut; whole records in the file
+};
+// The header of a voltage_file_sink file.  false + *why if it is not one (two polarisations).  No device is touched.
+bool read_voltage_header(const char* path, voltage_file_header* out, std::string* why);
+// The smallest power of two >= 256 with n_edge <= N / 4; 0 if none <= 4096 exists.
+int coherent_fft_length(int n_edge);
+struct coherent_options {
+    const char* voltages_path = nullptr;   // in: a voltage_file_sink file
+    const char* out_path = nullptr;        // out
+    double dm_max = 0.0, tsamp_ms = 0.131;  // -M, -T of the run that wrote the cuts: its ladder, and n_avg voltage samples per tsamp
+    int n_dm_cap = 0;                      // -N of that run
+    int n_fft = 0;                         // 0: per record, coherent_fft_length of its edge
+    int n_int = 1, sideband = 1;
+    int gpu = 0, device = 0;
+    const antenna* pos = nullptr;          // [NANT] and [n_beams]: the weights the run would use
+    const beam_direction* dir = nullptr;
+    const double* gains = nullptr;         // -A: a layer [freq][ant]{re, im}, or NULL
+    const uint8_t* ant_flags = nullptr;
+};
+constexpr size_t coherent_file_header_bytes = 4096;
+constexpr size_t coherent_record_header_bytes = 44;
+// Every record of the voltage file: its `beam` as the one follow-up beam, the DM of its global trial, the edge of bf_cdd_edge over the
+// file's channels, then bf_stokes_voltages_device -> bf_cdd_stokes_device.  Writes the 4096-byte ASCII header (CONTENT coherent_stokes,
+// DTYPE float32, NFREQ, FIRST_CHANNEL, NFFT (0: chosen per record), NINT, SIDEBAND, NTIME, LAYOUT time,freq,iquv) and per record
+// uint64 t0; int32 dm, beam, width; double snr; double dm_value; int32 n_edge, n_fft; float32 [NTIME / NINT][NFREQ]{I, Q, U, V}.
+// A record with no FFT length <= 4096 for its edge, or shorter than one segment, is left out and counted in the log line.
+int coherent_voltage_file(const coherent_options& o, uint64_t* n_written, uint64_t* n_refused, std::ostream& log);
+
 // ---- Pulsar folding behind the DM stage (include/dsabf.h: bf_psr_*, bf_dm_stream_attach_folder; docs/PULSAR_FOLDING.md) -------
 // With observation_options::n_psr > 0 run_observation creates a bf_psr next to the DM stage, attaches it, dumps whenever
 // psr_dump_rows rows or more have been folded (an incomplete integration at the end is dropped) and hands every collected dump to a psr_sink.
