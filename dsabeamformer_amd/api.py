@@ -293,7 +293,8 @@ class Beamformer(_Owner):
         check(self._lib.bf_set_switch(self._h, name.encode(), int(value)))
 
     def counter(self, name: str) -> int:
-        """bf_get_counter: "fused_launches", "queued_units", "dm_ring_stages", "fold_stream"."""
+        """bf_get_counter: "fused_launches", "queued_units", "dm_ring_stages", "fold_stream"; "dm_wide_groups" / "dm_wide_mask": the
+        trial groups the shared-window DM kernel took in the most recent DM launch (these two wait for that launch's stream)."""
         v = C.c_uint64()
         check(self._lib.bf_get_counter(self._h, name.encode(), C.byref(v)))
         return int(v.value)

@@ -83,8 +83,12 @@ int bf_get_counter(const bf_handle* h, const char* name, uint64_t* value)
         *value = n;
     } else if (!strcmp(name, "fold_stream"))       // 1: the antenna-fold launch of this handle is fused16_fold_stream_kernel (whole chunk spans)
         *value = dsabf::fold_streams(h->geom) ? 1 : 0;
-    else
-        return fail(BF_ERR_INVALID, "unknown counter \"%s\" (fused_launches, queued_units, dm_ring_stages, fold_stream)", name);
+    else if (!strcmp(name, "dm_wide_groups") || !strcmp(name, "dm_wide_mask")) {   // the groups the shared-window kernel took in the most recent DM launch
+        uint64_t groups = 0, mask = 0;
+        if (int rc = dm_wide_taken(h, &groups, &mask)) return rc;
+        *value = !strcmp(name, "dm_wide_groups") ? groups : mask;
+    } else
+        return fail(BF_ERR_INVALID, "unknown counter \"%s\" (fused_launches, queued_units, dm_ring_stages, fold_stream, dm_wide_groups, dm_wide_mask)", name);
     return BF_OK;
 }
 

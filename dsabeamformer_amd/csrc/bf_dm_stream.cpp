@@ -93,6 +93,7 @@ void bf_dm_stream::release_device()
     set_link<bf_ffa>(this, ffa, nullptr);
     set_link<bf_inj>(this, inj, nullptr);
     res.wait();
+    if (h && h->dm_last.owner == this) h->dm_last = {};   // (the scratch of the handle's most recent DM launch goes with res)
     if (mapped0) (void)hipMemUnmap(d_buf, phys_bytes);
     if (mapped1) (void)hipMemUnmap(reinterpret_cast<char*>(d_buf) + phys_bytes, phys_bytes);
     if (phys_created) (void)hipMemRelease(phys);   // (the addresses go back to nobody: ring_address_space)
@@ -186,6 +187,7 @@ static hipError_t dm_scratch(bf_handle* h, hipStream_t s, int** out)
         if (e != hipSuccess) return e;
         for (auto& sc : h->dm_scratch) (void)hipFree(sc.second);   // (the handle's bf_dm_streams own their scratch: untouched)
         h->dm_scratch.clear();
+        if (!h->dm_last.owner) h->dm_last = {};
     }
     int* p = nullptr;
     hipError_t e = hipMalloc((void**)&p, dsabf::kDmScratchBytes);
@@ -198,6 +200,46 @@ static hipError_t dm_scratch(bf_handle* h, hipStream_t s, int** out)
     h->dm_scratch.emplace_back(s, p);
     *out = p;
     return hipSuccess;
+}
+
+// Which kernel ran.  The shared-window kernel decides per trial group ON THE DEVICE whether it takes it, and leaves the verdicts in
+// the launch's scratch for dedisperse_dm_kernel; both give the same bits, so nothing else shows which of them computed a group.
+// This notes, behind a launch_dedisperse_dm that succeeded, what bf_get_counter needs to read the verdicts later.  `wide` restates the gate of
+// launch_dedisperse_dm (bf_kernels.hip: the switch, dm_wide_supported, 16-byte alignment of series and output, a series below
+// 4 GiB): a launch that fails it never writes the flags, and what the scratch then holds belongs to an earlier launch.
+// TWO COPIES OF ONE CONDITION: whoever changes the gate in bf_kernels.hip changes it here.  (The launcher is device code under the
+// kernel build id and does not say what it launched; having it return that is the follow-up that removes this copy.  Until then
+// tests/test_gpu_dm_paths.py holds the two together gate by gate: the switch in every case, the channel limit in
+// test_cap_by_channels[1025], both alignments in test_gates against flags an aligned call left behind; the 4 GiB gate is untested.)
+static void dm_note_launch(bf_handle* h, const dsabf::Geometry& g, const float* d_series, int n_t, int n_dm, int n_t_out, const float* d_out,
+                           const int* flags, hipStream_t s, const bf_stage* owner)
+{
+    bf_handle::dm_launch& r = h->dm_last;
+    r.flags = flags;
+    r.n_g = n_dm > 0 ? (n_dm + dsabf::kDwTrials - 1) / dsabf::kDwTrials : 0;
+    r.stream = s;
+    r.owner = owner;
+    r.wide = n_dm > 0 && n_t_out > 0 && flags && dsabf::dm_wide_supported(g, n_dm) && g.dm_wide && !((uintptr_t)d_series & 15) &&
+             !((uintptr_t)d_out & 15) && (size_t)n_t * g.n_freq * g.n_beams * sizeof(float) < ((size_t)1 << 32);
+}
+
+// The counters "dm_wide_groups" and "dm_wide_mask": waits for the stream of the handle's most recent DM launch and reads that
+// launch's flags.  A launch the wide kernel was no part of reports 0 without touching the device.
+int dsabf::rt::dm_wide_taken(const bf_handle* h, uint64_t* groups, uint64_t* mask)
+{
+    *groups = *mask = 0;
+    const bf_handle::dm_launch& r = h->dm_last;
+    if (!r.wide || r.n_g <= 0) return BF_OK;
+    ON_DEVICE(h);
+    std::vector<int> taken((size_t)r.n_g, 0);
+    HIP_TRY(hipStreamSynchronize(r.stream));
+    HIP_TRY(hipMemcpy(taken.data(), r.flags, taken.size() * sizeof(int), hipMemcpyDeviceToHost));
+    for (int g = 0; g < r.n_g; g++) {
+        if (!taken[(size_t)g]) continue;
+        ++*groups;
+        if (g < 64) *mask |= (uint64_t)1 << g;
+    }
+    return BF_OK;
 }
 
 extern "C" {
@@ -221,7 +263,9 @@ int bf_dedisperse_dm_band_device(bf_handle* h, const float* d_series, int n_t, i
     g.n_freq = n_freq_total;
     int* flags = nullptr;
     HIP_TRY(dm_scratch(h, as_stream(hip_stream), &flags));
+    h->dm_last = {};   // (a launch that fails half-way leaves nothing to report)
     HIP_TRY(dsabf::launch_dedisperse_dm(g, d_series, n_t, d_delays, n_dm, n_t_out, d_out, flags, as_stream(hip_stream)));
+    dm_note_launch(h, g, d_series, n_t, n_dm, n_t_out, d_out, flags, as_stream(hip_stream), nullptr);
     return BF_OK;
 }
 
@@ -485,8 +529,10 @@ int bf_dm_stream_push(bf_dm_stream* s, const float* d_rows, int n_rows, float* h
     if (n_out > 0) {
         dsabf::Geometry g = h->geom;
         g.n_freq = s->n_freq;
+        h->dm_last = {};
         HIP_TRY(dsabf::launch_dedisperse_dm(g, s->d_buf + start * s->row_floats, (int)n_t, s->d_delays, s->n_dm, n_out, s->d_out[set],
                                             s->d_flags[set], q));
+        dm_note_launch(h, g, s->d_buf + start * s->row_floats, (int)n_t, s->n_dm, n_out, s->d_out[set], s->d_flags[set], q, s);
         if (host_out)
             HIP_TRY(hipMemcpyAsync(host_out, s->d_out[set], (size_t)s->n_dm * n_out * h->cfg.n_beams * sizeof(float), hipMemcpyDeviceToHost, q));
         // the search reads the chunk where it lies, on this queue and BEFORE `done` below: only that event keeps push j + 3 out of set j % 3

@@ -301,6 +301,7 @@ int bf_destroy(bf_handle* h)
     if (h->t1) (void)hipEventDestroy(h->t1);
     for (void* p : std::initializer_list<void*>{h->d_wimage, h->d_wimage_p, h->d_wimage_f, h->d_flag, h->d_data, h->d_out, h->d_ded}) (void)hipFree(p);
     for (bf_stage* st : h->stages) stage_release(st);   // a stage that outlives its handle is left empty, not dangling
+    h->dm_last = {};
     for (auto& sc : h->dm_scratch) (void)hipFree(sc.second);
     for (auto& b : h->qbuf)
         for (float* p : {b.out_blk, b.full_blk, b.stage_blk, b.ded_blk}) (void)hipFree(p);

@@ -36,6 +36,16 @@ struct bf_handle {
     // wide kernel takes + a 512-byte row of zeros).  The wide kernel writes the flags and the per-thread-window kernel reads
     // them later on the same stream: calls on one stream are ordered by the stream, calls on different streams must not share.
     std::vector<std::pair<hipStream_t, int*>> dm_scratch;
+    // The most recent DM launch of this handle -- bf_dedisperse_dm*_device, or a push of a bf_dm_stream that launched -- for
+    // bf_get_counter "dm_wide_groups" / "dm_wide_mask" (bf_dm_stream.cpp, dm_wide_taken).  Cleared wherever the scratch can go
+    // away: the eviction in dm_scratch(), the release of the stage that owns it, bf_destroy.
+    struct dm_launch {
+        const int* flags = nullptr;             // the scratch the launch used: its first n_g ints are this launch's verdicts
+        int n_g = 0;                            // trial groups of the launch
+        hipStream_t stream = nullptr;           // the stream it was issued on
+        bool wide = false;                      // the shared-window kernel was launched (false: nothing wrote the flags)
+        const struct bf_stage* owner = nullptr; // the DM stage whose scratch it is; NULL: one of dm_scratch above
+    } dm_last;
     bool force_general = false;   // bf_set_switch("paired", 0): never select the conjugate-pair kernel (nor the antenna-fold kernel)
     bool no_fold = false;         // bf_set_switch("fold", 0): never select the antenna-fold kernel
     bool dm_ring = true;          // bf_set_switch("dm_ring", 0): the next bf_dm_stream_create takes the linear buffer (test switch)
@@ -186,6 +196,8 @@ bf_stage* as_stage(struct bf_psr* p);                   // bf_psr.cpp
 bf_stage* as_stage(struct bf_ffa* s);                   // bf_ffa.cpp
 bf_stage* as_stage(struct bf_inj* s);                   // bf_inj.cpp
 void dm_stream_drop(struct bf_dm_stream* dm, bf_stage* attached);   // bf_dm_stream.cpp: `attached` is going away
+// bf_get_counter "dm_wide_groups" / "dm_wide_mask" (bf_dm_stream.cpp): the trial groups the shared-window kernel took in h->dm_last
+int dm_wide_taken(const bf_handle* h, uint64_t* groups, uint64_t* mask);
 int sps_check_attach(const struct bf_sps* s, const bf_handle* h, int n_dm, int max_rows);            // bf_dm_stream_attach_search's conditions
 int sps_max_in_flight(const struct bf_sps* s);
 int cond_check_attach(const struct bf_cond* c, const bf_handle* h, int n_freq_total, int max_rows);  // bf_dm_stream_attach_conditioner's conditions

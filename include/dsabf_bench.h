@@ -58,7 +58,12 @@ int bf_set_switch(bf_handle *h, const char *name, int value);
  * "queued_units" = gemm-units bf_enqueue_gemm_unit has queued and not launched yet, "dm_ring_stages" = live DM stages of the handle
  * whose buffer is the twice-mapped ring (a device without virtual-memory management gives them the linear buffer instead),
  * "fold_stream" = 1 if the handle's antenna-fold launch is fused16_fold_stream_kernel (gemm-units of whole 128-sample chunk spans;
- * 256 for a 64-sample window), 0 if it is fused16_fold_kernel or no fold kernel at all (bf_handle_variant_key names the family). */
+ * 256 for a 64-sample window), 0 if it is fused16_fold_kernel or no fold kernel at all (bf_handle_variant_key names the family),
+ * "dm_wide_groups" = how many groups of 32 trials the shared-window DM kernel took in the handle's most recent DM launch
+ * (bf_dedisperse_dm*_device, or a bf_dm_stream_push that emitted rows), "dm_wide_mask" = bit g set if it took group g < 64; the groups
+ * it left ran the per-thread-window kernel (same bits).  These two wait for the stream of that launch (which must still exist) and
+ * read its flags; they are 0, without touching the device, if the launch did not include the shared-window kernel at all ("dm_wide" 0,
+ * more than 1024 channels, a series or output that is not 16-byte aligned, a series of 4 GiB or more). */
 int bf_get_counter(const bf_handle *h, const char *name, uint64_t *value);
 int bf_kernel_name(const bf_handle *h, char *buf, size_t buflen); /* which fused kernel this geometry runs */
 /* The same answers WITHOUT a handle or a device: which kernel and launch shape a configuration would run for n_units gemm-units

@@ -2,12 +2,17 @@
 (the tight pin of a2 / a3 / a8), calibrated (non-conjugate-symmetric) weights through the general kernel at production
 size, events on a handle's device, the block-wide DM-0 collapse.  Every call goes through the C-ABI of libdsabf.so."""
 import os
+import sys
 
 import numpy as np
 import pytest
 
 import bench
-from conftest import NOTEBOOK_INTEGER_TOL
+from conftest import NOTEBOOK_INTEGER_TOL, ROOT
+
+sys.path.insert(0, os.path.join(ROOT, "tests", "support"))
+
+import dm_paths  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -249,6 +254,10 @@ def test_shared_window_dm_kernel_bit_exact(torch, bfmod, orc, case, monkeypatch)
         n_t, n_f, n_b, n_dm = 20, 4, 4, 3
         delays = np.array([[0, 0, 0, 0], [2, 1, 1, 0], [5, 3, 2, 0]])
     delays = np.ascontiguousarray(delays.astype(np.int32))
+    # which kernel will run, predicted from the delays alone (tests/support/dm_paths.py) -- and it is what the cases above say
+    fits = dm_paths.wide_fits(delays)
+    assert fits.tolist() == {"fine_64": [True, True], "ragged_beams_trials": [True, True], "mixed_groups": [True, False, True],
+                             "negative_and_tail": [True, True], "tiny": [True]}[case]
     series = (rng.random((n_t, n_f, n_b), dtype=np.float32) * 1e4).astype(np.float32)
     bf = bfmod.Beamformer(bfmod.debug_config(n_beams=n_b, n_freq=n_f))
     d_series, d_delays = torch.from_numpy(series).cuda(), torch.from_numpy(delays).cuda()
@@ -260,6 +269,8 @@ def test_shared_window_dm_kernel_bit_exact(torch, bfmod, orc, case, monkeypatch)
             bf.set_switch("dm_wide", 0 if mode == "thread" else 1)   # per handle (bf_set_switch): never the environment mid-process
             d_out = torch.full((n_dm, n_t_out, n_b), float("nan"), dtype=torch.float32, device="cuda")
             bf.dedisperse_dm(d_series, n_t, d_delays, n_dm, n_t_out, d_out, s)
+            assert bf.counter("dm_wide_mask") == (dm_paths.mask_of(fits) if mode == "shared" else 0), (case, n_t_out, mode)
+            assert bf.counter("dm_wide_groups") == (int(fits.sum()) if mode == "shared" else 0)
             torch.cuda.synchronize()
             got[mode] = d_out.cpu().numpy()
         bf.set_switch("dm_wide", 1)

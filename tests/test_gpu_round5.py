@@ -5,7 +5,11 @@ import sys
 import numpy as np
 import pytest
 
-from conftest import sweep
+from conftest import ROOT, sweep
+
+sys.path.insert(0, os.path.join(ROOT, "tests", "support"))
+
+import dm_paths  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -207,9 +211,13 @@ def test_dm_stream_chunks_are_the_whole_series_call_bit_for_bit(torch, bfmod, or
         n_t, n_f, n_b, n_dm, max_rows = 210, 48, 256, 40, 32
         delays = _pulse_delays(n_dm, n_f, 45)
     else:                                   # group 0 fits a window, group 1 is far too coarse (per-thread kernel), group 2 fits
-        n_t, n_f, n_b, n_dm, max_rows = 260, 32, 132, 96, 40
-        step = np.concatenate([np.full(32, 0.4), np.full(32, 2.5), np.full(32, 0.4)])
+        # (a step of 4: group 1 spans 124 rows, more than any window holds; at 2.5 it spans 77 + 16, which FITS the 102 rows of 32 channels)
+        # (n_t: the ring holds max_delay + 3 max_rows = 153 + 120 rows and a little more; the series must run well past its seam)
+        n_t, n_f, n_b, n_dm, max_rows = 360, 32, 132, 96, 40
+        step = np.concatenate([np.full(32, 0.4), np.full(32, 4.0), np.full(32, 0.4)])
         delays = np.ascontiguousarray((np.cumsum(step)[:, None] * np.linspace(1.0, 0.05, n_f)[None, :]).astype(np.int32))
+    fits = dm_paths.wide_fits(delays)      # what the shared-window kernel will take, predicted from the delays alone
+    assert fits.tolist() == ([True, True] if shape == "fine_ladder" else [True, False, True])
     D = int(delays.max())
     series = (rng.random((n_t, n_f, n_b), dtype=np.float32) * 1e3).astype(np.float32)
     k_true, t0 = n_dm // 2, 70                                  # a pulse dispersed at trial k_true, arriving at t0 in channel 0
@@ -221,14 +229,18 @@ def test_dm_stream_chunks_are_the_whole_series_call_bit_for_bit(torch, bfmod, or
     d_series = torch.from_numpy(series).cuda()
     streams = [torch.cuda.Stream(), torch.cuda.Stream()]
     row_bytes = n_f * n_b * 4
-    # ring: the stage's buffer mapped twice back to back (nothing ever moves; the ring here holds 141 / 173 rows: a window wraps
-    # around its end every few pushes) -- or the linear buffer whose carry slides (what a device without VMM gets)
+    # ring: the stage's buffer mapped twice back to back (nothing ever moves; the ring here holds 140 / 280 rows of the
+    # 210 / 360: the windows of the later pushes wrap around its end, asserted below against the capacity the stage reports) -- or the linear buffer whose carry slides (what a device without VMM gets)
     for wide, feed, ring in ((1, "copy", 1), (0, "copy", 0), (1, "reserve", 1), (0, "mixed", 1), (1, "mixed", 0), (0, "reserve", 0)):
         bf.set_switch("dm_wide", wide)
         bf.set_switch("dm_ring", ring)
         dm = api.DmStream(bf, delays, n_f, max_rows)
         assert bf.counter("dm_ring_stages") == ring            # an MI355X really gives the stage the twice-mapped ring
         assert dm.max_delay == D
+        cap_rows = dm.history()[2]
+        print("%s ring %d: the stage's buffer holds %d rows, the series has %d" % (shape, ring, cap_rows, n_t))
+        if ring:                                               # the series runs past the ring's seam by more than a whole push
+            assert D + 3 * max_rows <= cap_rows <= n_t - max_rows, (shape, cap_rows, n_t)
         host = torch.full((n_dm * max_rows * n_b,), float("nan"), dtype=torch.float32).pin_memory()
         parts, at, pushed, k = [], 0, 0, 0
         sizes = [max_rows, 1, 7, max_rows, 3, 19, 2, max_rows, max_rows - 1, 11]
@@ -248,6 +260,9 @@ def test_dm_stream_chunks_are_the_whole_series_call_bit_for_bit(torch, bfmod, or
                 src = dst
             first, n_out = dm.push(src, n, host, st.cuda_stream)
             assert first == at and n_out == max(0, pushed + n - D) - max(0, pushed - D)
+            if n_out:                                                               # which kernel ran: the groups predicted, or none of them
+                assert bf.counter("dm_wide_mask") == (dm_paths.mask_of(fits) if wide else 0), (shape, wide, feed, ring, k)
+                assert bf.counter("dm_wide_groups") == (int(fits.sum()) if wide else 0)
             st.synchronize()
             if n_out:
                 parts.append(host[:n_dm * n_out * n_b].numpy().reshape(n_dm, n_out, n_b).copy())
