@@ -288,6 +288,15 @@ SIGNATURES = {
     "bf_cdd_set_chirp": (C.c_int, [C.c_void_p, C.c_void_p]),
     "bf_cdd_voltages_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]),
     "bf_cdd_stokes_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
+    "bf_rm_lambda2": (C.c_double, [C.c_double]),
+    "bf_rm_resolution": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "bf_rm_table": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
+    "bf_rm_rmsf": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p]),
+    "bf_rm_refine": (C.c_int, [C.c_void_p, C.c_size_t, C.c_double, C.c_double, C.c_int, C.c_double, C.c_void_p]),
+    "bf_rm_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "bf_rm_destroy": (C.c_int, [C.c_void_p]),
+    "bf_rm_set_table": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bf_rm_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bf_psr_model_from_spin": (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_double, C.c_int64, C.POINTER(BfPsrModel)]),
     "bf_psr_entries": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "bf_psr_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),

@@ -1168,6 +1168,111 @@ class CoherentDedisperser(_Owner):
         check(self._lib.bf_cdd_stokes_device(self._c, _ptr(d_in), int(K), int(n_time), int(n_int), _ptr(d_out), C.c_void_p(stream)))
 
 
+def rm_peak_dtype():
+    """bf_rm_peak: the 32-byte record FaradaySynthesis.run writes per (row, beam)."""
+    import numpy as np
+
+    dt = np.dtype([("p", np.int32), ("pow_lo", np.float32), ("pow_pk", np.float32), ("pow_hi", np.float32), ("re", np.float32),
+                   ("im", np.float32), ("isum", np.float32), ("zero", np.int32)])
+    assert dt.itemsize == 32
+    return dt
+
+
+def rm_fit_dtype():
+    """bf_rm_fit: what rm_refine makes of a record."""
+    import numpy as np
+
+    return np.dtype([("rm", np.float64), ("pa", np.float64), ("lin", np.float64), ("frac", np.float64)])
+
+
+def _channels(freq_ghz, w):
+    import numpy as np
+
+    f, fp = _freqs(freq_ghz)
+    wt = np.ascontiguousarray(np.broadcast_to(np.asarray(1.0 if w is None else w, np.float64), f.shape))
+    return f, fp, wt, wt.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def rm_lambda2(f_ghz: float) -> float:
+    """bf_rm_lambda2: (0.299792458 / f_ghz)^2 in m^2."""
+    return load().bf_rm_lambda2(float(f_ghz))
+
+
+def rm_resolution(freq_ghz, w=None):
+    """bf_rm_resolution: (fwhm, phi_max) in rad / m^2 of the unmasked channels (w None: all ones)."""
+    f, fp, wt, wp = _channels(freq_ghz, w)
+    fwhm, phi_max = C.c_double(), C.c_double()
+    check(load().bf_rm_resolution(fp, wp, len(f), C.byref(fwhm), C.byref(phi_max)))
+    return fwhm.value, phi_max.value
+
+
+def rm_table(freq_ghz, w, phi0: float, dphi: float, n_phi: int):
+    """bf_rm_table: (rot complex64 [n_phi][n_chan] = r + i s, wn float32 [n_chan], lambda0_2) of a FaradaySynthesis."""
+    import numpy as np
+
+    f, fp, wt, wp = _channels(freq_ghz, w)
+    rot, wn, l0 = np.empty((max(int(n_phi), 0), len(f)), np.complex64), np.empty(len(f), np.float32), C.c_double()
+    check(load().bf_rm_table(fp, wp, len(f), float(phi0), float(dphi), int(n_phi), _ptr(rot), _ptr(wn), C.byref(l0)))
+    return rot, wn, l0.value
+
+
+def rm_rmsf(freq_ghz, w, phi0: float, dphi: float, n_phi: int):
+    """bf_rm_rmsf: the rotation measure spread function on the grid, complex128 [n_phi]."""
+    import numpy as np
+
+    f, fp, wt, wp = _channels(freq_ghz, w)
+    out = np.empty(max(int(n_phi), 0), np.complex128)
+    check(load().bf_rm_rmsf(fp, wp, len(f), float(phi0), float(dphi), int(n_phi), _ptr(out)))
+    return out
+
+
+def rm_refine(peaks, phi0: float, dphi: float, n_phi: int, lambda0_2: float):
+    """bf_rm_refine: the parabola through the three powers of every record -> a structured array of rm_fit_dtype in ``peaks``'s shape."""
+    import numpy as np
+
+    pk = np.ascontiguousarray(peaks, rm_peak_dtype())
+    fits = np.empty(pk.shape, rm_fit_dtype())
+    check(load().bf_rm_refine(_ptr(pk), pk.size, float(phi0), float(dphi), int(n_phi), float(lambda0_2), _ptr(fits)))
+    return fits
+
+
+class FaradaySynthesis(_Owner):
+    """bf_rm: rotation-measure synthesis of Stokes beams on the f32 matrix instructions (include/dsabf.h, docs/FARADAY.md).  ``rot`` is
+    complex64 [n_phi][n_chan] and ``wn`` float32 [n_chan] (rm_table, or any table); the input of ``run`` is a device float32 array
+    [n_rows][n_chan][K][4], what CoherentDedisperser.stokes writes."""
+    _ptr_attr, _destroy = "_c", "bf_rm_destroy"
+
+    def __init__(self, bf: Beamformer, n_chan: int, n_phi: int, rot, wn):
+        self._lib = load()
+        self._c = C.c_void_p()
+        self._bf = bf
+        self.n_chan, self.n_phi = int(n_chan), int(n_phi)
+        r, n = self._tables(rot, wn)
+        check(self._lib.bf_rm_create(bf._h, self.n_chan, self.n_phi, _ptr(r), _ptr(n), C.byref(self._c)))
+
+    def _tables(self, rot, wn):
+        import numpy as np
+
+        r = None if rot is None else np.ascontiguousarray(rot, np.complex64)
+        n = None if wn is None else np.ascontiguousarray(wn, np.float32)
+        if self.n_chan * self.n_phi > 0:   # (a shape the library refuses: left to it)
+            if r is not None and r.size != self.n_chan * self.n_phi:
+                raise ValueError("the table has %d entries, not n_phi * n_chan = %d" % (r.size, self.n_chan * self.n_phi))
+            if n is not None and n.size != self.n_chan:
+                raise ValueError("wn has %d entries, not n_chan = %d" % (n.size, self.n_chan))
+        return r, n
+
+    def set_table(self, rot, wn) -> None:
+        """bf_rm_set_table: waits for the stage's kernels in flight, uploads, returns when the table is in place."""
+        r, n = self._tables(rot, wn)
+        check(self._lib.bf_rm_set_table(self._c, _ptr(r), _ptr(n)))
+
+    def run(self, d_stokes, K: int, n_rows: int, base=None, spec=None, peaks=None, stream: int = 0) -> None:
+        """bf_rm_device: spec complex64 [n_rows][K][n_phi] and / or peaks [n_rows][K] records of rm_peak_dtype (32 bytes each), device
+        arrays, asynchronously on ``stream``; base: an optional device float32 [n_chan][K][4] subtracted from every row."""
+        check(self._lib.bf_rm_device(self._c, _ptr(d_stokes), int(K), int(n_rows), _ptr(base), _ptr(spec), _ptr(peaks), C.c_void_p(stream)))
+
+
 def sk_select(moments, M: int, centre: float | None = None, n_sigma: float | None = None, max_bad_fraction_ant: float | None = None,
               max_bad_fraction_chan: float | None = None):
     """bf_sk_select (host only): moments int64 [freq][pol][ant][2] over ``M`` columns per polarisation -> (sk float64 [freq][pol][ant],

@@ -10,7 +10,8 @@ solver (csrc/cal/, docs/CALIBRATION.md), the conditioning stage (csrc/cond/, doc
 (csrc/sk/, docs/SPECTRAL_KURTOSIS.md), the full-Stokes follow-up beams (csrc/stokes/, docs/STOKES.md), the spatial null (csrc/null/,
 docs/NULLING.md), the stamp cut (csrc/stamp/, docs/EVENTS.md), the pulsar fold (csrc/psr/, docs/PULSAR_FOLDING.md), the periodicity
 search (csrc/ffa/, docs/PERIODICITY.md), the pulse injector (csrc/inj/, docs/INJECTION.md), the voltage cut (csrc/vcut/,
-docs/VOLTAGE_CUTS.md) and the coherent dedispersion stage (csrc/cdd/, docs/COHERENT_DEDISPERSION.md).
+docs/VOLTAGE_CUTS.md), the coherent dedispersion stage (csrc/cdd/, docs/COHERENT_DEDISPERSION.md) and the Faraday synthesis stage
+(csrc/rm/, docs/FARADAY.md).
 """
 from __future__ import annotations
 
@@ -78,7 +79,7 @@ def sources() -> list[str]:
                   glob.glob(os.path.join(COND, "*.hip")) + glob.glob(os.path.join(SK, "*.hip")) +
                   glob.glob(os.path.join(STOKES, "*.hip")) + glob.glob(os.path.join(NULL, "*.hip")) + glob.glob(os.path.join(CUT, "*.hip")) +
                   glob.glob(os.path.join(PSR, "*.hip")) + glob.glob(os.path.join(FFA, "*.hip")) + glob.glob(os.path.join(INJ, "*.hip")) +
-                  glob.glob(os.path.join(VCUT, "*.hip")) + glob.glob(os.path.join(CDD, "*.hip"))
+                  glob.glob(os.path.join(VCUT, "*.hip")) + glob.glob(os.path.join(CDD, "*.hip")) + glob.glob(os.path.join(RM, "*.hip"))
                   if os.path.abspath(p) not in [os.path.abspath(m) for m in MAINS.values()])
 
 
@@ -99,6 +100,7 @@ FFA = os.path.join(CSRC, "ffa")                     # device code of the periodi
 INJ = os.path.join(CSRC, "inj")                     # device code of the pulse injector: the same
 VCUT = os.path.join(CSRC, "vcut")                   # device code of the voltage cut (bf_vhist_cut): the same
 CDD = os.path.join(CSRC, "cdd")                     # device code of the coherent dedispersion stage: the same
+RM = os.path.join(CSRC, "rm")                       # device code of the Faraday synthesis stage: the same
 
 
 def kernel_build_id() -> str:
@@ -129,6 +131,7 @@ def _headers() -> list[str]:
         glob.glob(os.path.join(CORR, "*.h")) + glob.glob(os.path.join(CAL, "*.h")) + glob.glob(os.path.join(COND, "*.h")) + glob.glob(os.path.join(SK, "*.h")) + \
         glob.glob(os.path.join(STOKES, "*.h")) + glob.glob(os.path.join(NULL, "*.h")) + glob.glob(os.path.join(CUT, "*.h")) + glob.glob(os.path.join(PSR, "*.h")) + \
         glob.glob(os.path.join(FFA, "*.h")) + glob.glob(os.path.join(INJ, "*.h")) + glob.glob(os.path.join(VCUT, "*.h")) + glob.glob(os.path.join(CDD, "*.h")) + \
+        glob.glob(os.path.join(RM, "*.h")) + \
         glob.glob(os.path.join(ROOT, "include", "*.h*"))
 
 

@@ -189,6 +189,12 @@ struct options {
         int fft = 0, n_int = 1, sideband = 1;
         bool given = false, bad = false;
     } coherent;
+    struct {   // --faraday C_FILE --faraday-out FILE [--faraday-phi lo:hi:n] [--faraday-window rows] [-F mask_file]
+        std::string path, out;
+        double phi_lo = 0.0, phi_hi = 0.0;
+        int n_phi = 0, window = 0;   // 0: the default grid; 0: the record's search width
+        bool given = false, phi_given = false, bad = false;
+    } faraday;
     struct {   // --fold f0[:f1[:phase0]] (up to 4) [--fold-dm dm, the k-th for the k-th --fold] [--fold-bins n] [--fold-rows rows] [--fold-out FILE]
         std::vector<fold_spec> pulsars;
         std::vector<double> dms;
@@ -417,7 +423,7 @@ void extended_usage()
 // ---------------------------------------------------------------------------------------------------------------------------------
 int parse(int argc, char* argv[], options& o)
 {
-    enum { kEvents = 1000, kEventTol, kEventVeto, kStamps, kStampShape, kStampFlagged, kFold, kFoldDm, kFoldBins, kFoldRows, kFoldOut, kFfa, kFfaSeg, kFfaDec, kFfaOct, kFfaWidths, kFfaSnr, kFfaOut, kFfaDetrend, kInject, kInjectTrain, kInjectOut, kVoltages, kVoltageUnits, kVoltageHistory, kVoltageFlagged, kCoherent, kCoherentOut, kCoherentFft, kCoherentInt, kCoherentSideband };
+    enum { kEvents = 1000, kEventTol, kEventVeto, kStamps, kStampShape, kStampFlagged, kFold, kFoldDm, kFoldBins, kFoldRows, kFoldOut, kFfa, kFfaSeg, kFfaDec, kFfaOct, kFfaWidths, kFfaSnr, kFfaOut, kFfaDetrend, kInject, kInjectTrain, kInjectOut, kVoltages, kVoltageUnits, kVoltageHistory, kVoltageFlagged, kCoherent, kCoherentOut, kCoherentFft, kCoherentInt, kCoherentSideband, kFaraday, kFaradayOut, kFaradayPhi, kFaradayWindow };
     static const option long_options[] = {{"events", required_argument, nullptr, kEvents},       {"event-tol", required_argument, nullptr, kEventTol},
                                           {"event-veto", required_argument, nullptr, kEventVeto}, {"stamps", required_argument, nullptr, kStamps},
                                           {"stamp-shape", required_argument, nullptr, kStampShape}, {"stamp-flagged", no_argument, nullptr, kStampFlagged},
@@ -435,6 +441,8 @@ int parse(int argc, char* argv[], options& o)
                                           {"coherent", required_argument, nullptr, kCoherent},   {"coherent-out", required_argument, nullptr, kCoherentOut},
                                           {"coherent-fft", required_argument, nullptr, kCoherentFft}, {"coherent-int", required_argument, nullptr, kCoherentInt},
                                           {"coherent-sideband", required_argument, nullptr, kCoherentSideband},
+                                          {"faraday", required_argument, nullptr, kFaraday},     {"faraday-out", required_argument, nullptr, kFaradayOut},
+                                          {"faraday-phi", required_argument, nullptr, kFaradayPhi}, {"faraday-window", required_argument, nullptr, kFaradayWindow},
                                           {nullptr, 0, nullptr, 0}};
     const char* end = nullptr;
     int arg = 0;
@@ -529,6 +537,20 @@ int parse(int argc, char* argv[], options& o)
                 if (!whole(optarg, -1000000000L, 1000000000L, " ", arg == kCoherentFft ? &o.coherent.fft : arg == kCoherentInt ? &o.coherent.n_int : &o.coherent.sideband, &end) || *end)
                     o.coherent.bad = true;
                 o.coherent.given = true;
+                break;
+            case kFaraday: o.faraday.path = optarg; break;
+            case kFaradayOut: o.faraday.out = optarg; break;
+            case kFaradayPhi: {   // lo:hi:n, n a whole number
+                double v[3] = {0.0, 0.0, 0.0};
+                if (reals(optarg, 3, /*finite=*/true, v) != 3 || v[2] != std::floor(v[2]) || std::fabs(v[2]) > 1e9) o.faraday.bad = true;
+                o.faraday.phi_lo = v[0], o.faraday.phi_hi = v[1], o.faraday.n_phi = o.faraday.bad ? 0 : (int)v[2];
+                o.faraday.given = o.faraday.phi_given = true;
+                break;
+            }
+            case kFaradayWindow:
+                if (!whole(optarg, -1000000000L, 1000000000L, "+ ", &o.faraday.window, &end) || *end) o.faraday.bad = true;
+                if (!o.faraday.bad && o.faraday.window < 1) o.faraday.window = -1;
+                o.faraday.given = true;
                 break;
             case 's': o.sources = optarg; break;                 // :77-89
             case 'g': o.run.gpu = atoi(optarg); break;           // :92-100
@@ -681,10 +703,26 @@ int check(options& o, inputs* in)
             return refuse("--coherent-fft N: a power of two 64 .. 4096; --coherent-int n: a whole number >= 1; --coherent-sideband: +1 or -1");
         if (!(o.dm.tsamp_ms > 0.0)) return refuse("-T %g: the sample time must be positive", o.dm.tsamp_ms);
     }
+    // (the mode's refusals end in its synopsis: the texts of -h and -H are recorded byte for byte and do not list it)
+    static const char* const synopsis = "usage: beam --faraday C_FILE --faraday-out FILE [--faraday-phi LO:HI:N] [--faraday-window ROWS] [-F mask_file] [-g gpu] [-D device]";
+    if (o.faraday.path.empty() && (!o.faraday.out.empty() || o.faraday.given))
+        return refuse("--faraday-out / --faraday-phi / --faraday-window belong to Faraday synthesis: give --faraday C_FILE\n      %s", synopsis);
+    if (!o.faraday.path.empty()) {
+        if (o.observe() || !o.solve.vis.empty() || !o.coherent.path.empty())
+            return refuse("--faraday runs no observation, no solver and no dedispersion: leave out -j / -k / -E / --coherent\n      %s", synopsis);
+        if (o.dm.on() || o.sps.on || o.cond.given || !o.solve.apply.empty() || !o.null.path.empty())
+            return refuse("--faraday takes nothing from the DM stage, the search, the conditioner or the weights: leave out -M / -S / -n / -A / -Z\n      %s", synopsis);
+        if (o.faraday.out.empty()) return refuse("--faraday needs --faraday-out FILE (where the spectra and peaks go)\n      %s", synopsis);
+        if (o.faraday.bad) return refuse("--faraday-phi LO:HI:N: three numbers, N whole; --faraday-window ROWS: a whole number\n      %s", synopsis);
+        if (o.faraday.n_phi > 4096) return refuse("--faraday-phi: N = %d; at most 4096 depths\n      %s", o.faraday.n_phi, synopsis);
+        if (o.faraday.phi_given && (o.faraday.n_phi < 1 || o.faraday.phi_hi < o.faraday.phi_lo || (o.faraday.n_phi == 1 && o.faraday.phi_hi != o.faraday.phi_lo)))
+            return refuse("--faraday-phi %g:%g:%d: an empty grid; LO <= HI and N >= 1 (N = 1: LO = HI)\n      %s", o.faraday.phi_lo, o.faraday.phi_hi, o.faraday.n_phi, synopsis);
+        if (o.faraday.window < 0) return refuse("--faraday-window: at least 1 row\n      %s", synopsis);
+    }
     if (!o.evt.stamps_path.empty() && band.n_freq % o.evt.stamp_fbin != 0)
         return refuse("--stamp-shape: FBIN %d does not divide the band's %d channels", o.evt.stamp_fbin, band.n_freq);
     if (o.sps.on && (o.sps.widths < 1 || o.sps.widths > 8)) return refuse("-B %d: n_widths must be 1 .. 8", o.sps.widths);
-    const bool cond_extra = o.cond.zero_dm || o.cond.auto_given || !o.cond.mask_path.empty();
+    const bool cond_extra = o.cond.zero_dm || o.cond.auto_given || (!o.cond.mask_path.empty() && o.faraday.path.empty());   // (--faraday's -F is its own)
     if ((o.cond.given || cond_extra) && !o.dm.on()) return refuse("-n / -z / -U / -F (conditioner) require the DM stage: give -M dm_max");
     if (!o.cond.given && cond_extra) return refuse("-z / -U / -F belong to the conditioner: give -n baseline_pushes");
     if (o.cond.given && (o.cond.pushes < 1 || o.cond.pushes > 64)) return refuse("-n %d: baseline_pushes must be 1 .. 64", o.cond.pushes);
@@ -774,6 +812,8 @@ int load(const options& o, inputs* in)
         if (!o.solve.apply.empty() && !read_gains_layer(o.solve.apply.c_str(), vh.n_ant, vh.n_freq, vh.first_channel, &in->gains, &why)) return refuse("-A %s", why.c_str());
         if (int rc = load_ant_flags(o, vh.n_ant, in)) return rc;
     }
+    if (coherent_file_header fh; !o.faraday.path.empty() && !read_coherent_header(o.faraday.path.c_str(), &fh, &why))   // (only whether it is one: the mode reads it itself)
+        return refuse("--faraday %s", why.c_str());
     if (!o.solve.apply.empty() && !coherent) {
         if (!read_gains_layer(o.solve.apply.c_str(), n_ant, n_freq, first, &in->gains, &why)) return refuse("-A %s", why.c_str());
         if (int rc = load_ant_flags(o, n_ant, in)) return rc;
@@ -858,6 +898,27 @@ int run_coherent(const options& o, const inputs& in)
     const int rc = coherent_voltage_file(copt, &n_written, &n_refused, std::cout);
     if (rc != BF_OK) return gpu_assert(rc);
     std::cout << "Wrote " << n_written << " coherently dedispersed cuts to " << o.coherent.out << std::endl;
+    return 0;
+}
+
+// --faraday: a file of coherently dedispersed Stokes parameters to rotation-measure spectra, fits and peaks
+int run_faraday(const options& o, const inputs& in)
+{
+    faraday_options fopt;
+    fopt.coherent_path = o.faraday.path.c_str();
+    fopt.out_path = o.faraday.out.c_str();
+    fopt.n_phi = o.faraday.n_phi;
+    fopt.phi_lo = o.faraday.phi_lo;
+    fopt.phi_hi = o.faraday.phi_hi;
+    fopt.window = o.faraday.window;
+    fopt.chan_mask = in.cond_mask.empty() ? nullptr : in.cond_mask.data();
+    fopt.n_mask = (int)in.cond_mask.size();
+    fopt.gpu = o.run.gpu;
+    fopt.device = o.run.device;
+    uint64_t n_written = 0, n_left_out = 0;
+    const int rc = faraday_coherent_file(fopt, &n_written, &n_left_out, std::cout);
+    if (rc != BF_OK) return gpu_assert(rc);
+    std::cout << "Wrote " << n_written << " Faraday records to " << o.faraday.out << std::endl;
     return 0;
 }
 
@@ -1354,6 +1415,7 @@ int main(int argc, char* argv[])
 
     if (!o.solve.vis.empty()) return run_solve(o, in);
     if (!o.coherent.path.empty()) return run_coherent(o, in);
+    if (!o.faraday.path.empty()) return run_faraday(o, in);
     if (o.observe()) return run_observe(o, in);
     return run_debug(o, in);
 }

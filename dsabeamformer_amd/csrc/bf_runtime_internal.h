@@ -1,5 +1,5 @@
 // bf_runtime_internal.h -- what the C-ABI runtime's translation units share (bf_runtime.cpp, bf_queues.cpp, bf_dm_stream.cpp,
-// bf_sps.cpp, bf_cond.cpp, bf_accum.cpp, bf_corr.cpp, bf_sk.cpp, bf_stokes.cpp, bf_psr.cpp, bf_ffa.cpp, bf_inj.cpp, bf_evt.cpp, bf_vhist.cpp, bf_bench_abi.cpp): the handle, the base of its stages,
+// bf_sps.cpp, bf_cond.cpp, bf_accum.cpp, bf_corr.cpp, bf_sk.cpp, bf_stokes.cpp, bf_psr.cpp, bf_ffa.cpp, bf_inj.cpp, bf_evt.cpp, bf_vhist.cpp, bf_cdd.cpp, bf_rm.cpp, bf_bench_abi.cpp): the handle, the base of its stages,
 // the accumulator stage under the correlator and the voltage moments, the error string, the device scope.
 // Host-only and not installed: no .hip / .hpp file includes it.
 #pragma once
@@ -104,7 +104,7 @@ struct bf_resources {
     void release();
 };
 
-// The base of the eleven stage objects (bf_dm_stream, bf_sps, bf_cond, bf_corr, bf_sk, bf_stokes, bf_psr, bf_ffa, bf_inj, bf_vhist, bf_cdd: opaque to callers, each defined in its own file).
+// The base of the twelve stage objects (bf_dm_stream, bf_sps, bf_cond, bf_corr, bf_sk, bf_stokes, bf_psr, bf_ffa, bf_inj, bf_vhist, bf_cdd, bf_rm: opaque to callers, each defined in its own file).
 struct bf_stage {
     bf_handle* h = nullptr;                 // NULL: the handle went first and took the device side with it
     const char* const noun;                 // "DM stage", "search stage", ...: the orphan check's message

@@ -353,6 +353,34 @@ def read_coherent_file(path: str):
     return hdr, cuts
 
 
+def read_faraday_file(path: str):
+    """Parse a `beam --faraday` file (docs/FARADAY.md section 5): returns (header dict, list of dict(the coherent record's t0, dm, beam,
+    width, snr, dm_value, n_edge, n_fft; lo, w; rm, pa, lin, frac; spec complex64 [NPHI]; peaks [1 + NROWS] records of bf_rm_peak)),
+    in the order of the coherent file's records."""
+    raw = open(path, "rb").read()
+    text = raw[:DETECTED_HEADER_BYTES].split(b"\0", 1)[0].decode()
+    hdr = dict(line.split(None, 1) for line in text.splitlines() if line.strip())
+    assert hdr["CONTENT"] == "faraday" and hdr["DTYPE"] == "float32"
+    n_phi, n_rows, at, rec = int(hdr["NPHI"]), int(hdr["NROWS"]), int(hdr["HDR_SIZE"]), int(hdr["RECORD_HEADER_BYTES"])
+    assert rec == 84
+    peak = np.dtype([("p", "<i4"), ("pow_lo", "<f4"), ("pow_pk", "<f4"), ("pow_hi", "<f4"), ("re", "<f4"), ("im", "<f4"), ("isum", "<f4"), ("zero", "<i4")])
+    records = []
+    while at < len(raw):
+        t0 = int(np.frombuffer(raw, "<u8", 1, at)[0])
+        dm, beam, width = (int(v) for v in np.frombuffer(raw, "<i4", 3, at + 8))
+        snr, dm_value = (float(v) for v in np.frombuffer(raw, "<f8", 2, at + 20))
+        n_edge, n_fft, lo, w = (int(v) for v in np.frombuffer(raw, "<i4", 4, at + 36))
+        rm, pa, lin, frac = (float(v) for v in np.frombuffer(raw, "<f8", 4, at + 52))
+        at += rec
+        spec = np.frombuffer(raw, "<c8", n_phi, at)
+        at += 8 * n_phi
+        records.append(dict(t0=t0, dm=dm, beam=beam, width=width, snr=snr, dm_value=dm_value, n_edge=n_edge, n_fft=n_fft, lo=lo, w=w, rm=rm, pa=pa,
+                            lin=lin, frac=frac, spec=spec, peaks=np.frombuffer(raw, peak, 1 + n_rows, at)))
+        at += 32 * (1 + n_rows)
+    assert at == len(raw)
+    return hdr, records
+
+
 def read_dm_file(path: str):
     """Parse a dsabf::dm_file_sink file: returns (header dict, float32 array [n_dm][T][n_beams], list of (first_t, n_t) per
     chunk).  The chunks ([dm][t][beam] each) are joined along t; they follow each other without gaps."""

@@ -813,6 +813,57 @@ int bf_cdd_set_chirp(bf_cdd *c, const float *chirp);
 int bf_cdd_voltages_device(bf_cdd *c, const void *d_in, int K, int64_t n_time, void *d_out, void *hip_stream);
 int bf_cdd_stokes_device(bf_cdd *c, const void *d_in, int K, int64_t n_time, int n_int, void *d_out, void *hip_stream);
 
+/* ---- Faraday synthesis: rotation-measure spectra and peaks of Stokes beams (docs/FARADAY.md) -----------------------------------
+ * The reference squares its beam voltages away at once (src/beamformer.cuh:149-152) and keeps total power only, so it has no linear
+ * polarisation to derotate; behind bf_cdd_stokes_device this project has Q and U per channel.  A bf_rm evaluates
+ *     F(phi_p) = sum_c wn_c (Q_c + i U_c) exp(-2 i phi_p (lambda_c^2 - lambda_0^2))
+ * for every row and follow-up beam on a grid of Faraday depths and finds the peak of |F|^2.  Opt-in: with no stage nothing changes.
+ * Input s[t][chan][k]{I, Q, U, V} float32 (device), t < n_rows, k < K -- what bf_cdd_stokes_device writes, from anywhere; optionally a
+ *   baseline base[chan][k]{I, Q, U, V} float32 (device).  Finite values; NaN and Inf are outside the contract but fault nothing.
+ * Tables, HOST arrays copied to the device: rot[p][c]{r, s} float32 = wn_c (cos, -sin)(2 phi_p (lambda_c^2 - lambda_0^2)) and
+ *   wn[c] float32 = w_c / sum w  (bf_rm_table, or any table).  No sine or cosine runs on the device.
+ * ONE operation order, whatever K, n_rows and the launch shape (docs section 2), float32:
+ *   per cell q = Q - base.Q, u = U - base.U, i = I - base.I (one subtraction each; none without a baseline);
+ *   F_re: acc = fmaf(q_c, r_pc, acc), acc = fmaf(u_c, -s_pc, acc) over ascending c from +0; F_im: fmaf(q_c, s_pc, acc), fmaf(u_c, r_pc, acc);
+ *   pow[p] = F_re F_re + F_im F_im (two products, one addition, each rounded);  isum: acc = fmaf(i_c, wn[c], acc) from +0;
+ *   the peak: the smallest p whose pow[p] is the maximum.
+ * bf_rm_device, asynchronous on hip_stream, every cell written once; either output may be NULL, not both:
+ *   d_spec[t][k][p]{re, im} float32;  d_peaks[t][k]: one bf_rm_peak (32 bytes), pow_lo / pow_hi the powers at p -+ 1 (0 outside the
+ *   grid), re / im = F at the peak.  With d_spec NULL the spectrum never goes to memory.
+ * bf_rm_set_table: waits for the stage's kernels in flight, uploads, returns when the table is in place.
+ * BF_ERR_INVALID, nothing launched: NULL stage, handle or table, n_chan or n_phi outside 1 ... 4096, K < 1, n_rows < 1 or
+ *   n_rows K >= 2^31, both outputs NULL, a device pointer not 8-byte aligned (16-byte aligned ones take 16-byte accesses).  A handle
+ *   that goes first: BF_ERR_STATE, and the stage can still be destroyed.  The caller's current device is left as found.
+ * Host helpers, plain double, no device (w_c >= 0, a zero masks a channel):
+ *   bf_rm_lambda2(f_ghz) = (0.299792458 / f_ghz)^2 m^2;  lambda_0^2 = sum w_c lambda_c^2 / sum w_c.
+ *   bf_rm_resolution: fwhm = 2 sqrt 3 / (max - min lambda^2 of the unmasked channels), phi_max = sqrt 3 / the largest |lambda^2
+ *     step| between neighbouring channels of the list (Brentjens & de Bruyn 2005, eqs. 61 and 63).
+ *   bf_rm_table fills rot[n_phi][n_chan]{r, s} and wn[n_chan] for phi_p = phi0 + p dphi, and *lambda0_2 (may be NULL).
+ *   bf_rm_rmsf: out[n_phi]{re, im} double = sum_c wn_c exp(-2 i phi_p (lambda_c^2 - lambda_0^2)).
+ *   bf_rm_refine, per record: delta = 0.5 (lo - hi) / (lo - 2 pk + hi) (0 at a grid end or a zero denominator), rm = phi0 +
+ *     (p + delta) dphi, pa = 0.5 atan2(im, re) - rm lambda_0^2 wrapped into [-pi/2, pi/2), lin = sqrt(pk), frac = lin / isum
+ *     (0 where isum <= 0). */
+typedef struct bf_rm bf_rm;
+typedef struct bf_rm_peak {
+    int32_t p;
+    float pow_lo, pow_pk, pow_hi, re, im, isum;
+    int32_t zero;
+} bf_rm_peak;
+typedef struct bf_rm_fit {
+    double rm, pa, lin, frac;
+} bf_rm_fit;
+double bf_rm_lambda2(double f_ghz);
+int bf_rm_resolution(const double *freq_ghz, const double *w, int n_chan, double *fwhm, double *phi_max);
+int bf_rm_table(const double *freq_ghz, const double *w, int n_chan, double phi0, double dphi, int n_phi, float *rot, float *wn,
+                double *lambda0_2);
+int bf_rm_rmsf(const double *freq_ghz, const double *w, int n_chan, double phi0, double dphi, int n_phi, double *out);
+int bf_rm_refine(const bf_rm_peak *peaks, size_t n, double phi0, double dphi, int n_phi, double lambda0_2, bf_rm_fit *fits);
+int bf_rm_create(bf_handle *h, int n_chan, int n_phi, const float *rot, const float *wn, bf_rm **out);
+int bf_rm_destroy(bf_rm *s);
+int bf_rm_set_table(bf_rm *s, const float *rot, const float *wn);
+int bf_rm_device(bf_rm *s, const void *d_stokes, int K, int64_t n_rows, const void *d_base, void *d_spec, void *d_peaks,
+                 void *hip_stream);
+
 /* ---- Pulsar folding: phase-binned profiles of every beam (docs/PULSAR_FOLDING.md) -------------------------------------------
  * The reference stops at a DM-0 collapse copied to the host (src/beamformer.cu:498-510) and keeps nothing across blocks; the
  * search behind the DM stage looks at one push at a time.  A bf_psr integrates the detected rows x[row][freq][beam] (fp32, the

@@ -758,6 +758,36 @@ constexpr size_t coherent_record_header_bytes = 44;
 // A record with no FFT length <= 4096 for its edge, or shorter than one segment, is left out and counted in the log line.
 int coherent_voltage_file(const coherent_options& o, uint64_t* n_written, uint64_t* n_refused, std::ostream& log);
 
+// ---- Faraday synthesis of a file of coherently dedispersed Stokes parameters (include/dsabf.h: bf_rm_*; `beam --faraday`;
+// docs/FARADAY.md section 5) -----------------------------------------------------------------------------------------------------
+struct coherent_file_header {
+    int n_freq = 0, first_channel = 0, n_time = 0, n_int = 0, n_avg = 0;
+    size_t n_rows = 0, n_records = 0;   // rows of one record (n_time / n_int); whole records in the file
+};
+// The header of a coherent_voltage_file file.  false + *why if it is not one, or does not end with a whole record.  No device is touched.
+bool read_coherent_header(const char* path, coherent_file_header* out, std::string* why);
+struct faraday_options {
+    const char* coherent_path = nullptr;   // in: a coherent_voltage_file file
+    const char* out_path = nullptr;        // out
+    int n_phi = 0;                         // 0: the default grid, +-phi_max of bf_rm_resolution in steps of fwhm / 8, at most 4096 depths
+    double phi_lo = 0.0, phi_hi = 0.0;     // n_phi > 0: phi_p = phi_lo + p (phi_hi - phi_lo) / (n_phi - 1)
+    int window = 0;                        // rows of the on-pulse window; 0: the record's search width in rows of the file, at least 1
+    const uint8_t* chan_mask = nullptr;    // [n_mask], indexed by the channel of the whole band: non-zero masks it (weight 0), or NULL
+    int n_mask = 0;
+    int gpu = 0, device = 0;
+};
+constexpr size_t faraday_file_header_bytes = 4096;
+constexpr size_t faraday_record_header_bytes = 84;
+constexpr int faraday_min_baseline_rows = 8;
+// Every record of the file, on the host in double: the series sum_c I[t][c], a boxcar of w rows over it and its FIRST maximum [lo, lo +
+// w); the baseline = the mean of the rows outside [lo - w, lo + 2 w) in ascending order, rounded to float32 (a record with fewer than 8
+// such rows is left out and counted); row 0 = the mean of the window's rows, rounded to float32.  Then ONE bf_rm_device call over the
+// 1 + n_rows rows (row 0, then the file's) with that baseline.  Writes the 4096-byte ASCII header (CONTENT faraday, DTYPE float32, NFREQ,
+// FIRST_CHANNEL, NROWS, NPHI, PHI0, DPHI, LAMBDA0_2, FWHM, PHI_MAX, RECORD_HEADER_BYTES 84) and per record uint64 t0; int32 dm, beam,
+// width; double snr, dm_value; int32 n_edge, n_fft (the coherent record's header), int32 lo, w; double rm, pa, lin, frac (bf_rm_refine
+// of row 0); float32 [NPHI]{re, im} (row 0's spectrum); bf_rm_peak [1 + NROWS].  On any failure the output file is removed again.
+int faraday_coherent_file(const faraday_options& o, uint64_t* n_written, uint64_t* n_left_out, std::ostream& log);
+
 // ---- Pulsar folding behind the DM stage (include/dsabf.h: bf_psr_*, bf_dm_stream_attach_folder; docs/PULSAR_FOLDING.md) -------
 // With observation_options::n_psr > 0 run_observation creates a bf_psr next to the DM stage, attaches it, dumps whenever
 // psr_dump_rows rows or more have been folded (an incomplete integration at the end is dropped) and hands every collected dump to a psr_sink.
