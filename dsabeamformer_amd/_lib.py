@@ -370,6 +370,7 @@ SIGNATURES = {
     "bf_dm_stream_reserve": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_void_p]),
     "bf_variant_key": (C.c_int, [C.POINTER(BfConfig), C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
     "bf_handle_variant_key": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_size_t]),
+    "bf_stage_launches": (C.c_int, [C.c_char_p, C.c_size_t, C.c_int]),
     # ---- include/dsabf_host.h ----
     "bfh_default_positions": (C.c_int, [C.c_int, C.c_void_p]),
     "bfh_default_directions": (C.c_int, [C.c_int, C.c_void_p]),

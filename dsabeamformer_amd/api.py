@@ -45,6 +45,14 @@ def variant_key(cfg: BfConfig, paired: bool, write_c: bool = False) -> str:
     return buf.value.decode()
 
 
+def stage_launches(clear: bool = False) -> list[str]:
+    """The stage kernels the calling thread launched most recently (at most 32, oldest first), as their demangled symbols spell
+    them -- "cdd_kernel<9, true>", "corr_kernel" (bf_stage_launches: the launchers' own record); ``clear`` empties the record."""
+    buf = C.create_string_buffer(32 * 64 + 1)
+    check(load().bf_stage_launches(buf, len(buf), int(clear)))
+    return buf.value.decode().split("\n")[:-1]
+
+
 def _ptr(x) -> C.c_void_p:
     """Accept ints, ctypes pointers, numpy arrays (host) and torch tensors (device or host)."""
     if x is None:

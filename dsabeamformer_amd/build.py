@@ -79,7 +79,8 @@ def sources() -> list[str]:
                   glob.glob(os.path.join(COND, "*.hip")) + glob.glob(os.path.join(SK, "*.hip")) +
                   glob.glob(os.path.join(STOKES, "*.hip")) + glob.glob(os.path.join(NULL, "*.hip")) + glob.glob(os.path.join(CUT, "*.hip")) +
                   glob.glob(os.path.join(PSR, "*.hip")) + glob.glob(os.path.join(FFA, "*.hip")) + glob.glob(os.path.join(INJ, "*.hip")) +
-                  glob.glob(os.path.join(VCUT, "*.hip")) + glob.glob(os.path.join(CDD, "*.hip")) + glob.glob(os.path.join(RM, "*.hip"))
+                  glob.glob(os.path.join(VCUT, "*.hip")) + glob.glob(os.path.join(CDD, "*.hip")) + glob.glob(os.path.join(RM, "*.hip")) +
+                  glob.glob(os.path.join(REC, "*.cpp"))
                   if os.path.abspath(p) not in [os.path.abspath(m) for m in MAINS.values()])
 
 
@@ -101,6 +102,7 @@ INJ = os.path.join(CSRC, "inj")                     # device code of the pulse i
 VCUT = os.path.join(CSRC, "vcut")                   # device code of the voltage cut (bf_vhist_cut): the same
 CDD = os.path.join(CSRC, "cdd")                     # device code of the coherent dedispersion stage: the same
 RM = os.path.join(CSRC, "rm")                       # device code of the Faraday synthesis stage: the same
+REC = os.path.join(CSRC, "rec")                     # host code: the stage launchers' record of what they launched (no device code)
 
 
 def kernel_build_id() -> str:
@@ -131,7 +133,7 @@ def _headers() -> list[str]:
         glob.glob(os.path.join(CORR, "*.h")) + glob.glob(os.path.join(CAL, "*.h")) + glob.glob(os.path.join(COND, "*.h")) + glob.glob(os.path.join(SK, "*.h")) + \
         glob.glob(os.path.join(STOKES, "*.h")) + glob.glob(os.path.join(NULL, "*.h")) + glob.glob(os.path.join(CUT, "*.h")) + glob.glob(os.path.join(PSR, "*.h")) + \
         glob.glob(os.path.join(FFA, "*.h")) + glob.glob(os.path.join(INJ, "*.h")) + glob.glob(os.path.join(VCUT, "*.h")) + glob.glob(os.path.join(CDD, "*.h")) + \
-        glob.glob(os.path.join(RM, "*.h")) + \
+        glob.glob(os.path.join(RM, "*.h")) + glob.glob(os.path.join(REC, "*.h")) + \
         glob.glob(os.path.join(ROOT, "include", "*.h*"))
 
 

@@ -16,6 +16,7 @@
 //              the fly.  No scratch memory, so concurrent solves on any queues share nothing.
 // calw_kernel: the elementwise weight correction, one workgroup per (channel, antenna) row of the weight array.
 #include "bf_cal_kernels.h"
+#include "../rec/bf_launch_record.h"
 
 #pragma clang fp contract(off)
 
@@ -308,6 +309,7 @@ hipError_t launch_solve_gains(int n_ant, int n_freq, int n_pol, const long long*
         if (e != hipSuccess) return e;
     }
     (void)hipGetLastError();
+    record_launch(resident ? "solve_kernel<true>" : "solve_kernel<false>");
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kThreads), lds, s, a);
     return hipGetLastError();
 }
@@ -329,6 +331,7 @@ hipError_t launch_calibrate_weights(int n_ant, int n_freq, int n_beams, const in
     a.n_beams = n_beams;
     a.mode = mode;
     (void)hipGetLastError();
+    record_launch("calw_kernel");
     hipLaunchKernelGGL(calw_kernel, dim3((unsigned)grid), dim3(kCalwThreads), 0, s, a);
     return hipGetLastError();
 }

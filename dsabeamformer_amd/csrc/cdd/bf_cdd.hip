@@ -11,6 +11,7 @@
 // LDS: element p of a polarisation lives at float2 index p + (p >> 5) -- one float2 of padding per 32, so that the stride-8 ... stride-
 // 2048 accesses of the passes do not meet in one bank (ds_read_b64 banks on 64 dwords).  16.5 N bytes per workgroup: 66 KiB at N = 4096.
 #include "bf_cdd_kernels.h"
+#include "../rec/bf_launch_record.h"
 
 #include <cmath>
 
@@ -201,10 +202,13 @@ __global__ __launch_bounds__(cdd_threads(M)) void cdd_kernel(CddArgs a)
 template <int M>
 hipError_t launch_m(const CddArgs& a, bool stokes, unsigned grid, hipStream_t s)
 {
-    if (stokes)
+    if (stokes) {
+        record_launchf("cdd_kernel<%d, true>", M);
         hipLaunchKernelGGL((cdd_kernel<M, true>), dim3(grid), dim3(cdd_threads(M)), 0, s, a);
-    else
+    } else {
+        record_launchf("cdd_kernel<%d, false>", M);
         hipLaunchKernelGGL((cdd_kernel<M, false>), dim3(grid), dim3(cdd_threads(M)), 0, s, a);
+    }
     return hipGetLastError();
 }
 

@@ -10,6 +10,7 @@
 // The library is built with -ffp-contract=off and the pragma below says so again: NO fused multiply-add anywhere in this file, one
 // rounding per written operation.  Plain C++ with vector loads and stores; no inline assembly, no atomics.
 #include "bf_cond_kernels.h"
+#include "../rec/bf_launch_record.h"
 
 #pragma clang fp contract(off)
 
@@ -277,15 +278,20 @@ __global__ __launch_bounds__(kCellThreads) void cond_apply_kernel(float* __restr
 hipError_t launch_cond_push(float* d_rows, int n_rows, int n_freq, int n_beams, const CondBuffers& buf, int window, int cur_set, int n_sets,
                             uint64_t n_window, bool zero_dm, double k_auto, hipStream_t stream)
 {
+    record_launch("cond_totals_kernel");
     cond_totals_kernel<<<dim3((unsigned)n_freq), dim3(kTotalsThreads), 0, stream>>>(d_rows, n_rows, n_freq, n_beams, buf, window, cur_set, n_sets,
                                                                                     (double)n_window);
+    record_launch("cond_summary_kernel");
     cond_summary_kernel<<<dim3(1), dim3(kSummaryThreads), 0, stream>>>(n_freq, buf, k_auto);
     const size_t n_threads = (size_t)((n_rows + kApplyRows - 1) / kApplyRows) * n_beams;
     const dim3 grid((unsigned)((n_threads + kCellThreads - 1) / kCellThreads));
-    if (zero_dm)
+    if (zero_dm) {
+        record_launch("cond_apply_kernel<true>");
         cond_apply_kernel<true><<<grid, dim3(kCellThreads), 0, stream>>>(d_rows, n_rows, n_freq, n_beams, buf.mr32, buf.mask, buf.params);
-    else
+    } else {
+        record_launch("cond_apply_kernel<false>");
         cond_apply_kernel<false><<<grid, dim3(kCellThreads), 0, stream>>>(d_rows, n_rows, n_freq, n_beams, buf.mr32, buf.mask, buf.params);
+    }
     return hipGetLastError();
 }
 

@@ -19,6 +19,7 @@
 // The next chunk's global loads are issued before the MFMAs of the current one.  Columns past the end and antennas past n_ant are
 // zero bytes.  Epilogue: int32 -> int64, stored or added (accumulate) with plain vector stores.
 #include "bf_corr_kernels.h"
+#include "../rec/bf_launch_record.h"
 
 namespace dsabf {
 
@@ -211,6 +212,7 @@ hipError_t launch_correlate(int n_ant, int n_freq, int n_pol, int n_cols, const 
     const long long grid = (long long)((n_freq + 7) / 8) * 8 * n_pol * (a.n_super * (a.n_super + 1) / 2);
     if (grid > 0x7FFFFFFFll) return hipErrorInvalidValue;
     (void)hipGetLastError();
+    record_launch("corr_kernel");
     hipLaunchKernelGGL(corr_kernel, dim3((unsigned)grid), dim3(kThreads), 0, s, a);
     return hipGetLastError();
 }

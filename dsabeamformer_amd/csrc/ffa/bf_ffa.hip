@@ -15,6 +15,7 @@
 // index i * 512 + j: "larger value, or equal value and smaller index" is a total order, so the result does not depend on the
 // order of the merges (lane, wave-shuffle, workgroup).
 #include "bf_ffa_kernels.h"
+#include "../rec/bf_launch_record.h"
 
 namespace dsabf {
 
@@ -317,6 +318,7 @@ hipError_t launch_search_octave(const float* y, int L, int p_lo, int p_hi, int n
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
+    record_launchf("ffa_search_kernel<%d>", K);
     hipLaunchKernelGGL(kern, dim3((unsigned)n_beams, (unsigned)n_dm), dim3(kThreads), lds, stream, y, L, p_lo, p_hi, cap, n_dm, n_beams, peaks, stats);
     return hipGetLastError();
 }
@@ -336,6 +338,7 @@ hipError_t launch_ffa_decimate(const float* d_chunk, int n_dm, int n_t, int n_be
     if (last_start >= n_t || in_seg < 0 || pos0 + in_seg > n_seg) return hipErrorInvalidValue;
     (void)hipGetLastError();
     const dim3 grid((unsigned)((n_beams + 4 * kBeamLanes - 1) / (4 * kBeamLanes)), (unsigned)((n_groups + kGroupLanes - 1) / kGroupLanes), (unsigned)n_dm);
+    record_launch("ffa_decimate_kernel");
     hipLaunchKernelGGL(ffa_decimate_kernel, grid, dim3(kDecThreads), 0, stream, d_chunk, n_t, n_beams, tdec, c0, g0, n_groups, carry_in,
                        carry_out, y0, n_seg, pos0);
     return hipGetLastError();
@@ -354,6 +357,7 @@ hipError_t launch_ffa_detrend(float* y0, int n_dm, int n_beams, int n_seg, int b
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(ffa_detrend_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
+    record_launch("ffa_detrend_kernel");
     hipLaunchKernelGGL(ffa_detrend_kernel, dim3((unsigned)n_beams, (unsigned)n_dm), dim3(kThreads), lds, stream, y0, n_seg, lb, 1.0f / (float)blk,
                        (win - 1) / 2);
     return hipGetLastError();
@@ -376,6 +380,7 @@ hipError_t launch_ffa_search(float* slot, int n_dm, int n_beams, int n_seg, int 
         float* y = slot + ffa_octave_offset(o, n_seg, n_db);
         if (o > 0) {
             const size_t n = n_db * (size_t)L;
+            record_launch("ffa_octave_kernel");
             hipLaunchKernelGGL(ffa_octave_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream,
                                reinterpret_cast<const float2*>(slot + ffa_octave_offset(o - 1, n_seg, n_db)), y, n);
             if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;

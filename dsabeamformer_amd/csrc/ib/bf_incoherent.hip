@@ -14,6 +14,7 @@
 // x256 fits int32; it is shifted out BEFORE the lanes of the group are summed (the group's total may reach 2^24).  Integer sums:
 // the result does not depend on L, W or the launch.  No LDS, no atomics: lane 0 of a group stores its output.
 #include "bf_incoherent.h"
+#include "../rec/bf_launch_record.h"
 
 namespace dsabf {
 
@@ -60,6 +61,7 @@ hipError_t launch(const void* d_packed, float* d_out, long long n_spans, size_t 
 {
     // a group per span up to 8 workgroups per CU; beyond that the groups stride on to further spans
     const long long per_block = kThreads / L, want = (n_spans + per_block - 1) / per_block, cap = (long long)(n_cus > 0 ? n_cus : 256) * 8;
+    record_launchf("incoherent_kernel<%d, %s>", L, sizeof(W) == 16 ? "HIP_vector_type<unsigned int, 4u> " : "unsigned int");
     hipLaunchKernelGGL((incoherent_kernel<L, W>), dim3((unsigned)(want < cap ? want : cap)), dim3(kThreads), 0, s, (const uint8_t*)d_packed, d_out,
                        n_spans, (int)(span_bytes / sizeof(W)), n_out, n_freq, stride);
     return hipGetLastError();

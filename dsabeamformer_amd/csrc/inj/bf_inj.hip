@@ -9,6 +9,7 @@
 // The multiply and the add are two roundings (__fmul_rn, __fadd_rn), in the order of the argument arrays: ascending id.
 // No atomics, no LDS, nothing carried from one launch to the next.
 #include "bf_inj_kernels.h"
+#include "../rec/bf_launch_record.h"
 
 namespace dsabf {
 
@@ -135,10 +136,10 @@ hipError_t launch_inj_bursts(float* rows, int n_rows, const InjBurstArgs& a, int
     const dim3 grid = inj_grid(max_span, a.n_freq, a.n_beams);
     (void)hipGetLastError();   // clear what earlier, unrelated calls left behind: return this launch's own status
     switch (a.n) {
-        case 1: inj_burst_kernel<1><<<grid, 64, 0, stream>>>(rows, n_rows, a); break;
-        case 2: inj_burst_kernel<2><<<grid, 64, 0, stream>>>(rows, n_rows, a); break;
-        case 3: inj_burst_kernel<3><<<grid, 64, 0, stream>>>(rows, n_rows, a); break;
-        case 4: inj_burst_kernel<4><<<grid, 64, 0, stream>>>(rows, n_rows, a); break;
+        case 1: record_launch("inj_burst_kernel<1>"); inj_burst_kernel<1><<<grid, 64, 0, stream>>>(rows, n_rows, a); break;
+        case 2: record_launch("inj_burst_kernel<2>"); inj_burst_kernel<2><<<grid, 64, 0, stream>>>(rows, n_rows, a); break;
+        case 3: record_launch("inj_burst_kernel<3>"); inj_burst_kernel<3><<<grid, 64, 0, stream>>>(rows, n_rows, a); break;
+        case 4: record_launch("inj_burst_kernel<4>"); inj_burst_kernel<4><<<grid, 64, 0, stream>>>(rows, n_rows, a); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
@@ -151,10 +152,10 @@ hipError_t launch_inj_trains(float* rows, const InjTrainArgs& a, hipStream_t str
     const dim3 grid = inj_grid(a.row_hi - a.row_lo, a.n_freq, a.n_beams);
     (void)hipGetLastError();
     switch (a.n) {
-        case 1: inj_train_kernel<1><<<grid, 64, 0, stream>>>(rows, a); break;
-        case 2: inj_train_kernel<2><<<grid, 64, 0, stream>>>(rows, a); break;
-        case 3: inj_train_kernel<3><<<grid, 64, 0, stream>>>(rows, a); break;
-        case 4: inj_train_kernel<4><<<grid, 64, 0, stream>>>(rows, a); break;
+        case 1: record_launch("inj_train_kernel<1>"); inj_train_kernel<1><<<grid, 64, 0, stream>>>(rows, a); break;
+        case 2: record_launch("inj_train_kernel<2>"); inj_train_kernel<2><<<grid, 64, 0, stream>>>(rows, a); break;
+        case 3: record_launch("inj_train_kernel<3>"); inj_train_kernel<3><<<grid, 64, 0, stream>>>(rows, a); break;
+        case 4: record_launch("inj_train_kernel<4>"); inj_train_kernel<4><<<grid, 64, 0, stream>>>(rows, a); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

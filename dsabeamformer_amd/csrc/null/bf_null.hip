@@ -17,6 +17,7 @@
 //              No scratch memory, so concurrent solves on any queues share nothing.
 // null_apply_kernel: the projection of the weights, one workgroup per channel, one thread per beam column.
 #include "bf_null_kernels.h"
+#include "../rec/bf_launch_record.h"
 
 #pragma clang fp contract(off)
 
@@ -478,6 +479,7 @@ hipError_t launch_null_solve(int n_ant, int n_freq, int n_pol, const long long* 
         if (e != hipSuccess) return e;
     }
     (void)hipGetLastError();
+    record_launch(resident ? "null_solve_kernel<true>" : "null_solve_kernel<false>");
     hipLaunchKernelGGL(kern, dim3((unsigned)n_freq), dim3(kThreads), lds, s, a);
     return hipGetLastError();
 }
@@ -501,6 +503,7 @@ hipError_t launch_null_weights(int n_ant, int n_freq, int n_beams, const int8_t*
     a.n_null = n_null;
     a.mode = mode;
     (void)hipGetLastError();
+    record_launch("null_apply_kernel");
     hipLaunchKernelGGL(null_apply_kernel, dim3((unsigned)n_freq), dim3(kApplyThreads), 0, s, a);
     return hipGetLastError();
 }

@@ -9,6 +9,7 @@
 // The rows come in batches of kBatch independent loads in front of the dependent adds: with one wave per (channel, 64 beams) that
 // is the parallelism the memory system sees.
 #include "bf_psr_kernels.h"
+#include "../rec/bf_launch_record.h"
 
 namespace dsabf {
 
@@ -87,10 +88,10 @@ hipError_t launch_psr_fold(const float* rows, int n_rows, const PsrFoldArgs& a, 
     const dim3 grid((unsigned)a.n_freq, (unsigned)((a.n_beams + block - 1) / block));
     (void)hipGetLastError();   // clear what earlier, unrelated calls left behind: return this launch's own status
     switch (a.n_psr) {
-        case 1: psr_fold_kernel<1><<<grid, block, 0, stream>>>(rows, n_rows, a); break;
-        case 2: psr_fold_kernel<2><<<grid, block, 0, stream>>>(rows, n_rows, a); break;
-        case 3: psr_fold_kernel<3><<<grid, block, 0, stream>>>(rows, n_rows, a); break;
-        case 4: psr_fold_kernel<4><<<grid, block, 0, stream>>>(rows, n_rows, a); break;
+        case 1: record_launch("psr_fold_kernel<1>"); psr_fold_kernel<1><<<grid, block, 0, stream>>>(rows, n_rows, a); break;
+        case 2: record_launch("psr_fold_kernel<2>"); psr_fold_kernel<2><<<grid, block, 0, stream>>>(rows, n_rows, a); break;
+        case 3: record_launch("psr_fold_kernel<3>"); psr_fold_kernel<3><<<grid, block, 0, stream>>>(rows, n_rows, a); break;
+        case 4: record_launch("psr_fold_kernel<4>"); psr_fold_kernel<4><<<grid, block, 0, stream>>>(rows, n_rows, a); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

@@ -14,6 +14,7 @@
 // four waves (LDS), of the passes (a running record in LDS); then the lanes that hold depth p - 1, p, p + 1 of a row write their part
 // of its record.  Nothing but the 32-byte record goes to memory when no spectrum is asked for.
 #include "bf_rm_kernels.h"
+#include "../rec/bf_launch_record.h"
 
 #include <climits>
 
@@ -267,12 +268,16 @@ hipError_t launch_rm(const RmLaunch& l, hipStream_t s)
     a.peaks16 = ((uintptr_t)l.peaks & 15) == 0;
     const unsigned grid = (unsigned)(((long long)a.M + kRmRows - 1) / kRmRows);   // (64 bits: M + 31 can pass 2^31)
     (void)hipGetLastError();
-    if (l.spec && l.peaks)
+    if (l.spec && l.peaks) {
+        record_launch("rm_kernel<true, true>");
         hipLaunchKernelGGL((rm_kernel<true, true>), dim3(grid), dim3(kThreads), 0, s, a);
-    else if (l.peaks)
+    } else if (l.peaks) {
+        record_launch("rm_kernel<false, true>");
         hipLaunchKernelGGL((rm_kernel<false, true>), dim3(grid), dim3(kThreads), 0, s, a);
-    else
+    } else {
+        record_launch("rm_kernel<true, false>");
         hipLaunchKernelGGL((rm_kernel<true, false>), dim3(grid), dim3(kThreads), 0, s, a);
+    }
     return hipGetLastError();
 }
 

@@ -18,6 +18,7 @@
 // atomics, and the image's non-zero entries go to the output with 64-bit global atomics.  accumulate == false is a memset of the
 // output in front of the kernel, on the same queue.
 #include "bf_sk_kernels.h"
+#include "../rec/bf_launch_record.h"
 
 namespace dsabf {
 
@@ -154,6 +155,7 @@ hipError_t launch(SkArgs a, int n_cus, hipStream_t s)
     const long long want = (a.items + 3) / 4, cap = (long long)(n_cus > 0 ? n_cus : 256) * 4;
     const long long groups = want < cap ? want : cap;
     a.per = (a.items + groups - 1) / groups;
+    record_launchf("moments_kernel<%s>", sizeof(W) == 16 ? "HIP_vector_type<unsigned int, 4u> " : "unsigned int");
     hipLaunchKernelGGL((moments_kernel<W>), dim3((unsigned)((a.items + a.per - 1) / a.per)), dim3(kThreads), 0, s, a);
     return hipGetLastError();
 }

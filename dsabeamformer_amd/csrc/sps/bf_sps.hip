@@ -15,6 +15,7 @@
 // sps_finish_kernel: combines the tiles' records in ascending tile order (a later tile wins only with a LARGER value: ties keep
 // the first time), sums the tiles' statistics, and writes the tail for the next push.
 #include "bf_sps_kernels.h"
+#include "../rec/bf_launch_record.h"
 
 namespace dsabf {
 
@@ -246,6 +247,7 @@ hipError_t launch_tile(const float* d_chunk, int n_dm, int n_t, int n_beams, uin
 {
     constexpr int ROWS = kT + (1 << (K - 1)) - 1;
     const dim3 grid((unsigned)((n_beams + 4 * kBeamLanes - 1) / (4 * kBeamLanes)), (unsigned)sps_tiles(n_t), (unsigned)n_dm);
+    record_launchf("sps_tile_kernel<%d>", K);
     hipLaunchKernelGGL(sps_tile_kernel<K>, grid, dim3(kThreads), ROWS * kBeamLanes * sizeof(float4), stream, d_chunk, buf.tail_in, n_dm, n_t,
                        n_beams, (unsigned long long)seen, buf.part_peaks, buf.part_stats);
     return hipGetLastError();
@@ -272,6 +274,7 @@ hipError_t launch_sps_push(const float* d_chunk, int n_dm, int n_t, int n_beams,
     if (e != hipSuccess) return e;
     const int H = sps_halo(n_widths);
     const size_t items = (size_t)(n_widths + 1) * n_dm * n_beams + (size_t)n_dm * H * (n_beams / 4);
+    record_launch("sps_finish_kernel");
     hipLaunchKernelGGL(sps_finish_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, stream, d_chunk, buf.tail_in, buf.tail_out,
                        buf.part_peaks, buf.part_stats, buf.peaks, buf.stats, sps_tiles(n_t), n_dm, n_t, n_beams, n_widths, H);
     return hipGetLastError();

@@ -9,6 +9,7 @@
 // the delay loads are scalar.  The window starts at a physical row < cap_rows and runs on through the ring's second mapping: no
 // wrap test in the loop.  Row offsets are 64-bit.
 #include "bf_stamp_kernels.h"
+#include "../rec/bf_launch_record.h"
 
 namespace dsabf {
 
@@ -66,6 +67,7 @@ hipError_t launch_stamp_cut(const float* ring, size_t row_floats, int n_freq, in
     const int n_g = n_freq / fbin;
     const dim3 block(kStampLanes, kStampGroups);
     const dim3 grid((unsigned)(((size_t)n_tau + kStampLanes - 1) / kStampLanes), (unsigned)((n_g + kStampGroups - 1) / kStampGroups), (unsigned)n_items);
+    record_launch("stamp_cut_kernel");
     hipLaunchKernelGGL(stamp_cut_kernel, grid, block, 0, stream, ring, row_floats, n_freq, n_beams, d_delays, batch, n_tau, tbin, fbin, out);
     return hipGetLastError();
 }

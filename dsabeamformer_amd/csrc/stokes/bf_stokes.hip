@@ -25,6 +25,7 @@
 // sum to the wave's own int64 image of the span's windows in LDS (LDS atomics: the four lane groups of a beam meet there); at the end
 // of the span the wave stores the image with plain 8-byte vector stores and zeroes it.  Every output cell is written exactly once.
 #include "bf_stokes_kernels.h"
+#include "../rec/bf_launch_record.h"
 
 namespace dsabf {
 
@@ -275,14 +276,19 @@ __global__ __launch_bounds__(kThreads) void stokes_kernel(StokesArgs a)
 template <int NKS, bool VEC>
 hipError_t launch_n(const StokesArgs& a, unsigned grid, hipStream_t s)
 {
-    if (a.mode == kDirect)
+    if (a.mode == kDirect) {
+        record_launchf("stokes_kernel<%d, %s, %d>", NKS, VEC ? "true" : "false", (int)kDirect);
         hipLaunchKernelGGL((stokes_kernel<NKS, VEC, kDirect>), dim3(grid), dim3(kThreads), 0, s, a);
-    else if (a.mode == kVoltages)
+    } else if (a.mode == kVoltages) {
+        record_launchf("stokes_kernel<%d, %s, %d>", NKS, VEC ? "true" : "false", (int)kVoltages);
         hipLaunchKernelGGL((stokes_kernel<NKS, VEC, kVoltages>), dim3(grid), dim3(kThreads), 0, s, a);
-    else if (a.mode == kPerWave)
+    } else if (a.mode == kPerWave) {
+        record_launchf("stokes_kernel<%d, %s, %d>", NKS, VEC ? "true" : "false", (int)kPerWave);
         hipLaunchKernelGGL((stokes_kernel<NKS, VEC, kPerWave>), dim3(grid), dim3(kThreads), 0, s, a);
-    else
+    } else {
+        record_launchf("stokes_kernel<%d, %s, %d>", NKS, VEC ? "true" : "false", (int)kCooperative);
         hipLaunchKernelGGL((stokes_kernel<NKS, VEC, kCooperative>), dim3(grid), dim3(kThreads), 0, s, a);
+    }
     return hipGetLastError();
 }
 
@@ -325,6 +331,7 @@ hipError_t launch_stokes_gather(const int8_t* d_w, const int* beams, int n_sel, 
     const size_t n = stokes_weight_bytes(n_ant, n_freq);
     const size_t blocks = (n + kThreads - 1) / kThreads;
     (void)hipGetLastError();
+    record_launch("stokes_gather_kernel");
     hipLaunchKernelGGL(stokes_gather_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(kThreads), 0, s, a);
     return hipGetLastError();
 }

@@ -13,6 +13,7 @@
 // offsets are 64-bit; offsets inside a run are 32-bit (S B < 2^31).
 // Plain C++, vector loads and stores, no LDS, no atomics; every output byte is written exactly once and nothing else is written.
 #include "bf_vcut_kernels.h"
+#include "../rec/bf_launch_record.h"
 
 namespace dsabf {
 
@@ -71,10 +72,13 @@ hipError_t launch_vcut(const VcutRing& ring, const int32_t* d_delays, const Vcut
     const bool vec = ring.B % 16 == 0 && ((uintptr_t)out & 15) == 0;
     const uint32_t run_bytes = ring.S * ring.B, piece = (uint32_t)kThreads * kUnroll * (vec ? 16 : 4);
     const dim3 grid((unsigned)((run_bytes + piece - 1) / piece), (unsigned)(ring.n_freq * (uint32_t)n_units_out), (unsigned)n_items);
-    if (vec)
+    if (vec) {
+        record_launch("vcut_kernel<unsigned int __vector(4)>");
         hipLaunchKernelGGL(vcut_kernel<v4u>, grid, dim3(kThreads), 0, stream, ring, d_delays, batch, n_units_out, out);
-    else
+    } else {
+        record_launch("vcut_kernel<unsigned int>");
         hipLaunchKernelGGL(vcut_kernel<uint32_t>, grid, dim3(kThreads), 0, stream, ring, d_delays, batch, n_units_out, out);
+    }
     return hipGetLastError();
 }
 

@@ -81,6 +81,15 @@ int bf_launch_plan(const bf_config *cfg, int paired, int n_units, int n_cus, int
  * detect mode>; bf_variant_key knows nothing of the antenna symmetry and never names it. */
 int bf_variant_key(const bf_config *cfg, int paired, int write_c, char *buf, size_t buflen);
 int bf_handle_variant_key(const bf_handle *h, int write_c, char *buf, size_t buflen);
+/* The same question for the STAGE kernels (csrc/<stage>/: sps, ib, corr, cal, cond, sk, stokes, null, stamp, psr, ffa, inj, vcut, cdd,
+ * rm), asked after the fact: their launchers pick among templates on antenna count, FFT length, alignment, width count and the chip's
+ * CU count, and every launch site records the kernel it is about to launch, spelled as the demangled symbol spells it --
+ * "cdd_kernel<9, true>", "stokes_kernel<2, true, 1>", "vcut_kernel<unsigned int>", "corr_kernel".  The record is a ring of the CALLING
+ * THREAD's most recent 32 names (a launch pays one pointer store or a short snprintf; no lock, no allocation).  bf_stage_launches
+ * copies them into buf, oldest first, each followed by '\n', NUL-terminated ("" if nothing was launched); clear != 0 empties the ring
+ * afterwards.  BF_ERR_INVALID, ring untouched: buf NULL or too small (32 * 64 + 1 bytes always suffice).  A name says that the launch
+ * was issued, not that it completed.  (tests/test_gpu_stage_census.py, tools/census.py::stage_compiled) */
+int bf_stage_launches(char *buf, size_t buflen, int clear);
 
 #ifdef __cplusplus
 }

@@ -101,9 +101,12 @@ def _run_voltages(torch, stage, packed, n_units, want, case, shift_words=0):
 
 DESC16 = list(range(31, 15, -1))
 # (n_ant, beams, n_avg, n_out, n_freq, n_units): S = n_avg * n_out = 1, 3 (odd: the 8-byte tail store), 8, 24, 256
+# 128, 132, 192 and 252 antennas: with 4 / 12, 64, 68 and 256 every (k-steps, 16-byte loads) pair of stokes_kernel runs its voltages mode
 VOLTAGE_CASES = [(4, [0], 1, 1, 1, 1), (4, [31, 0, 7], 1, 3, 3, 3), (12, [5], 1, 3, 1, 1), (12, DESC16, 8, 1, 3, 3), (12, [9, 3, 31], 8, 3, 1, 3),
                  (68, [31, 0, 15], 1, 3, 3, 1), (68, DESC16, 8, 3, 1, 3), (68, [1], 16, 16, 1, 1), (64, DESC16, 16, 16, 3, 1), (64, [31], 1, 1, 1, 3),
-                 (64, [2, 31, 0], 8, 1, 3, 3), (256, DESC16, 1, 3, 1, 3), (256, [0, 16, 31], 8, 3, 3, 1), (256, [31], 16, 16, 1, 3)]
+                 (64, [2, 31, 0], 8, 1, 3, 3), (256, DESC16, 1, 3, 1, 3), (256, [0, 16, 31], 8, 3, 3, 1), (256, [31], 16, 16, 1, 3),
+                 (128, DESC16, 8, 3, 1, 3), (128, [7], 1, 1, 3, 1), (132, [31, 0, 15], 1, 3, 3, 3), (132, DESC16, 8, 1, 1, 1),
+                 (192, [0, 16, 31], 8, 3, 3, 1), (192, [4], 1, 3, 1, 3), (252, DESC16, 1, 1, 3, 3), (252, [9, 3, 31], 8, 3, 1, 1)]
 
 
 def test_beam_voltages_to_the_bit(torch, bfmod):
@@ -111,7 +114,7 @@ def test_beam_voltages_to_the_bit(torch, bfmod):
     shape; an output that is only 8-byte aligned; the all-byte-codes scene with the weight extremes; the 2^19 bound."""
     from dsabeamformer_amd import api
 
-    for lst, idx in (((4, 12, 68, 64, 256), 0), ((1, 3), 4), ((1, 3), 5)):
+    for lst, idx in (((4, 12, 68, 64, 128, 132, 192, 252, 256), 0), ((1, 3), 4), ((1, 3), 5)):
         assert {c[idx] for c in VOLTAGE_CASES} == set(lst), idx
     assert {len(c[1]) for c in VOLTAGE_CASES} == {1, 3, 16} and {c[2] * c[3] for c in VOLTAGE_CASES} == {1, 3, 8, 24, 256}
     rng = np.random.default_rng(20261021)
@@ -127,7 +130,10 @@ def test_beam_voltages_to_the_bit(torch, bfmod):
         stage.set_weights(w, beams)
         assert bf._lib.bf_stokes_voltage_entries(cfg, len(beams)) * n_units == want.size, case
         for shift in (0, 2):                                                     # 16-byte aligned, and 8-byte aligned only
+            api.stage_launches(clear=True)
             _run_voltages(torch, stage, packed, n_units, want, (case, shift), shift)
+            name = "stokes_kernel<%d, %s, 3>" % ((n_ant + 63) // 64, "true" if n_ant % 16 == 0 else "false")   # mode 3: the voltages
+            assert name in api.stage_launches(), (case, api.stage_launches())
         stage.close()
         bf.close()
     # every byte code at every byte position of a lane's word, weights from the extremes of int8 (the scene of tests/test_gpu_stokes.py)
@@ -188,7 +194,8 @@ def _run_cdd(torch, stage, x, n_int, want, case, shift_words=0):
 
 
 def test_every_fft_length_and_edge_to_the_bit(torch, bfmod, handle):
-    """N 64, 128, 256, 1024, 4096; n_edge 0, 1, N / 4; n_time 1, V - 1, V, V + 1, 2 V, 3 V + 5 and an odd length (every second series
+    """N 64, 128, 256, 512, 1024, 2048, 4096 (every cdd_kernel<log2 N, *>; 512 and 2048 behind the others, which keep their inputs);
+    n_edge 0, 1, N / 4; n_time 1, V - 1, V, V + 1, 2 V, 3 V + 5 and an odd length (every second series
     starts on an address that is 8-byte aligned only); 1 and 3 channels with a row of their own each; K 1, 3, 16; both outputs, n_int
     1, 2, V wherever it divides; full-scale integers, and an impulse at the first, the last and a seam sample."""
     from dsabeamformer_amd import api
@@ -197,14 +204,14 @@ def test_every_fft_length_and_edge_to_the_bit(torch, bfmod, handle):
     t0, n_cases, n_words = time.perf_counter(), 0, 0
     shapes = [(1, 1), (3, 3), (1, 16), (3, 1)]                                   # (n_chan, K), taken in turn
     turn = 0
-    for n in (64, 128, 256, 1024, 4096):
+    for n in (64, 128, 256, 1024, 4096, 512, 2048):
         for n_edge in (0, 1, n // 4):
             v = n - 2 * n_edge
             lengths = [1, v - 1, v, v + 1, 2 * v, 3 * v + 5]
             lengths.append(3 * v + 5 + (3 * v + 5) % 2 + 1)                      # and one that is certainly odd
             assert any(t % 2 for t in lengths) and all(t >= 1 for t in lengths)
             for n_time in lengths:
-                n_chan, K = shapes[turn % 4] if n <= 1024 else shapes[turn % 2]  # (the longest transforms at the two smaller shapes)
+                n_chan, K = shapes[turn % 4] if n <= 1024 else shapes[turn % 2]  # (the two longest transforms at the two smaller shapes)
                 turn += 1
                 table = _random_table(rng, n_chan, n)
                 stage = api.CoherentDedisperser(handle, n_chan, n, n_edge, table)
@@ -220,13 +227,17 @@ def test_every_fft_length_and_edge_to_the_bit(torch, bfmod, handle):
                     assert y.shape == x.shape and np.isfinite(y.view(np.float32)).all()
                     case = (n, n_edge, n_time, n_chan, K, name)
                     for shift in ((0, 2) if name == "full scale" else (0,)):
+                        api.stage_launches(clear=True)
                         _run_cdd(torch, stage, x, 0, y, case + ("voltages", shift), shift)
+                        assert set(api.stage_launches()) == {"cdd_kernel<%d, false>" % (n.bit_length() - 1)}, (case, api.stage_launches())
                     for n_int in (1, 2, v):
                         if n_time % n_int:
                             continue
                         want = co.stokes(y, n_int)
                         assert want.shape == (n_time // n_int, n_chan, K, 4)
+                        api.stage_launches(clear=True)
                         _run_cdd(torch, stage, x, n_int, want, case + ("stokes", n_int), 2 if n_int == 2 else 0)
+                        assert set(api.stage_launches()) == {"cdd_kernel<%d, true>" % (n.bit_length() - 1)}, (case, api.stage_launches())
                         n_words += want.size
                     n_cases += 1
                     n_words += 2 * y.size
@@ -241,7 +252,7 @@ def test_accuracy_against_fp64(torch, bfmod, handle):
     from dsabeamformer_amd import api
 
     rng = np.random.default_rng(5)
-    for n in (64, 128, 256, 1024, 4096):
+    for n in (64, 128, 256, 1024, 4096, 512, 2048):
         table = _random_table(rng, 2, n)
         x = _full_scale(rng, (2, 3, 2, 4 * n))
         stage = api.CoherentDedisperser(handle, 2, n, 0, table)

@@ -105,16 +105,19 @@ def run_pushes(torch, hip, cond, orc, x, sizes):
 
 SIZES = [1, 31, 32, 33, 65, 100]      # below, at and above a segment; two segments and one row; three and a ragged fourth
 # (n_beams, n_freq_total, baseline_pushes, zero_dm, what): every n_beams (below a wave, ragged below and above one, four per lane),
-# every n_freq_total, the window of 1, 2 and 3 pushes under 12 pushes (it wraps), zero-DM on and off
+# every n_freq_total, the window of 1, 2 and 3 pushes under 12 pushes (it wraps), zero-DM on and off.  260 and 516 beams: cond_totals_kernel
+# walks the beams 256 at a time -- a second trip of 4 live lanes, and three trips (a lane of the zero-DM sums owns 9 beams); BASELINE config
+# 5 has 512 beams.
 CASES = [(4, 1, 1, True, "plain"), (4, 3, 2, False, "dead"), (4, 40, 3, True, "static"), (4, 300, 2, True, "dead"),
          (60, 1, 3, False, "plain"), (60, 3, 1, True, "dead"), (60, 40, 2, True, "all_masked"), (60, 300, 3, False, "static"),
          (64, 1, 2, True, "dead_cell"), (64, 3, 3, True, "static"), (64, 40, 1, False, "dead"), (64, 300, 2, True, "plain"),
          (68, 1, 1, False, "all_masked"), (68, 3, 2, True, "plain"), (68, 40, 3, True, "dead"), (68, 300, 1, False, "dead"),
          (256, 1, 3, True, "plain"), (256, 3, 1, False, "all_masked"), (256, 40, 2, False, "plain"), (256, 40, 3, True, "dead"),
-         (256, 300, 3, True, "dead"), (256, 3, 2, True, "dead")]
+         (256, 300, 3, True, "dead"), (256, 3, 2, True, "dead"),
+         (260, 3, 2, True, "dead"), (260, 1, 3, False, "plain"), (516, 3, 1, True, "dead_cell"), (516, 1, 2, False, "dead")]
 
 
-@pytest.mark.sweep_cap(24)
+@pytest.mark.sweep_cap(26)
 @pytest.mark.parametrize("case", CASES, ids=lambda c: "b%d-f%d-w%d-%s-%s" % (c[0], c[1], c[2], "zdm" if c[3] else "nozdm", c[4]))
 def test_every_shape_to_the_bit(torch, bfmod, hip, case):
     """Output and mask of every push equal the oracle's, bit for bit.  "dead": a constant channel and an all-zero one (both masked:
@@ -123,7 +126,7 @@ def test_every_shape_to_the_bit(torch, bfmod, hip, case):
     from dsabeamformer_amd import api
 
     n_b, n_f, window, zero_dm, what = case
-    assert len(CASES) <= 24
+    assert len(CASES) <= 26 and {260, 516} <= {c[0] for c in CASES}
     rng = np.random.default_rng(1000 * n_b + 10 * n_f + window)
     T = sum(SIZES)
     x = band(rng, T, n_f, n_b)

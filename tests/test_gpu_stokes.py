@@ -82,23 +82,36 @@ SHAPE_CASES = [(4, [0], 1, 1, 1, 1, 1), (4, [31, 0, 7], 1, 3, 1, 3, 3), (4, [5],
                (64, DESC16, 16, 8, 16, 3, 3), (64, [31], 16, 8, 1, 1, 1), (64, [0, 31, 1], 16, 3, 3, 3, 1), (64, [2, 1, 0], 1, 8, 2, 1, 3),
                (68, [31, 0, 15], 16, 1, 8, 3, 1), (68, DESC16, 8, 3, 24, 1, 3), (100, [1], 16, 3, 2, 3, 3), (100, [30, 31, 0], 1, 1, 1, 1, 1),
                (132, DESC16, 16, 1, 16, 1, 3), (132, [4, 2, 9], 8, 3, 3, 3, 1), (256, [31], 16, 8, "S", 3, 1), (256, DESC16, 1, 3, 1, 1, 3),
-               (256, [0, 16, 31], 16, 3, 8, 3, 3)]
+               (256, [0, 16, 31], 16, 3, 8, 3, 3),
+               # every (k-steps, 16-byte loads) pair of stokes_kernel with n_int 1 (direct) and with a cooperative n_int: 80 ... 128 and 144 ... 192
+               # antennas with n_ant % 16 == 0 are two and three steps on 16-byte loads, 196 ... 252 four steps on 4-byte loads; 128 antennas on
+               # BASELINE's windows (n_avg 16 and 1); 132 with n_int 1 (three steps, 4-byte loads, direct)
+               (128, DESC16, 16, 8, 16, 3, 1), (128, [31, 0, 7], 1, 8, 1, 3, 3), (80, [0, 31, 1], 1, 3, 1, 1, 1), (112, [5], 8, 3, 3, 1, 3),
+               (144, DESC16, 1, 8, 1, 1, 3), (144, [9], 16, 3, 8, 3, 1), (192, [31, 0, 15], 16, 1, 2, 3, 3), (192, DESC16, 1, 3, 1, 3, 1),
+               (196, [2], 8, 3, 24, 1, 3), (196, [0, 16, 31], 1, 8, 1, 3, 1), (252, DESC16, 16, 8, "S", 1, 1), (252, [31], 1, 1, 1, 3, 3),
+               (132, [7, 0, 31], 1, 8, 1, 3, 1)]
 # More spans than one round of workgroups holds (8 workgroups per CU on 256 CUs, 4 waves each: 8192): n_int = 1 at 64 antennas has 16 spans
 # per unit and channel (3 * 172 * 16 = 8256); n_int = 16 at 4 antennas one (3 * 2800 = 8400).  Ranges are cut by the cap and cross channels.
 # Launches with fewer spans than 8 waves per CU (2048 on 256 CUs) and n_int > 1 are cooperative -- a span per workgroup: every case of
-# SHAPE_CASES with n_int > 1.  The last four cases have 2100 spans or more and n_int 16, 3, 2 and S: a span per wave.
+# SHAPE_CASES with n_int > 1.  Every case behind the first has 2100 spans or more and n_int > 1 -- 16, 3, 2 and S: a span per wave.  The last
+# four: two, three and four steps on 16-byte loads and four steps on 4-byte loads (128, 192, 256 and 252 antennas), one span per unit and channel.
 LARGE_CASES = [(64, [31, 0, 7], 16, 8, 1, 3, 172), (4, [3, 31], 16, 8, 16, 3, 2800),
-               (64, [0, 31, 5], 16, 8, 16, 3, 700), (20, [9, 3, 31], 8, 3, 3, 3, 700), (68, [2, 1, 0], 1, 8, 2, 1, 2100), (132, [31], 16, 1, "S", 3, 700)]
+               (64, [0, 31, 5], 16, 8, 16, 3, 700), (20, [9, 3, 31], 8, 3, 3, 3, 700), (68, [2, 1, 0], 1, 8, 2, 1, 2100), (132, [31], 16, 1, "S", 3, 700),
+               (128, [0, 31, 5], 1, 8, 2, 3, 700), (192, [9, 3, 31], 1, 3, 3, 3, 700), (252, [2], 1, 8, 8, 1, 2100), (256, [31, 16, 0], 16, 1, 16, 3, 700)]
 
 
 def test_every_shape_to_the_bit(torch, bfmod):
     """bf_stokes_device against the oracle on random bytes (every code) and random weights over all of int8."""
     from dsabeamformer_amd import api
 
-    for lst, idx in (((4, 16, 20, 64, 68, 100, 132, 256), 0), ((1, 8, 16), 2), ((1, 3, 8), 3), ((1, 3), 5), ((1, 3), 6)):
+    for lst, idx in (((4, 16, 20, 64, 68, 80, 100, 112, 128, 132, 144, 192, 196, 252, 256), 0), ((1, 8, 16), 2), ((1, 3, 8), 3), ((1, 3), 5), ((1, 3), 6)):
         assert {c[idx] for c in SHAPE_CASES} == set(lst), idx
     assert {len(c[1]) for c in SHAPE_CASES} == {1, 3, 16} and {c[4] for c in SHAPE_CASES} >= {1, 2, 3, 8, 16, "S"}
     assert any(0 in c[1] for c in SHAPE_CASES) and any(31 in c[1] for c in SHAPE_CASES)
+    for group in ((80, 112, 128), (144, 192), (196, 252)):   # direct and cooperative, 1 / 3 / 16 beams at every new class of antenna counts
+        mine = [c for c in SHAPE_CASES if c[0] in group]
+        assert {len(c[1]) for c in mine} == {1, 3, 16} and any(c[4] == 1 for c in mine) and any(c[4] != 1 for c in mine), group
+    assert {(c[0], c[2]) for c in SHAPE_CASES} >= {(128, 16), (128, 1)} and {c[0] for c in LARGE_CASES[-4:]} == {128, 192, 252, 256}
     rng = np.random.default_rng(20261019)
     t0, n = time.perf_counter(), 0
     for case in SHAPE_CASES + LARGE_CASES:
@@ -112,7 +125,12 @@ def test_every_shape_to_the_bit(torch, bfmod):
         stage = api.StokesBeams(bf, n_int)
         stage.set_weights(w, beams)
         assert stage.entries * n_units * 4 == want.size, case
+        api.stage_launches(clear=True)
         _compare(_run(torch, stage, packed, n_units, want.shape), want, case)
+        # which stokes_kernel<k-steps, 16-byte loads, mode> the launcher took: mode 0 direct, 1 a span per wave, 2 cooperative
+        name = "stokes_kernel<%d, %s, %d>" % ((n_ant + 63) // 64, "true" if n_ant % 16 == 0 else "false",
+                                              0 if n_int == 1 else 1 if case in LARGE_CASES else 2)
+        assert [k for k in api.stage_launches() if k.startswith("stokes_kernel<")] == [name], (case, api.stage_launches())
         stage.close()
         bf.close()
         n += want.size

@@ -44,11 +44,56 @@ def compiled(lib_path: str | None = None) -> set[str]:
     return out
 
 
-def other_kernels(lib_path: str | None = None) -> list[str]:
-    """The library's kernels that are not instantiations of the two fused templates (one each: nothing to select)."""
+def _stubs(lib_path: str | None = None) -> set[str]:
+    """Every `__device_stub__` kernel of the library as its demangled symbol spells it, without the argument list:
+    "corr_kernel", "cdd_kernel<9, true>", "vcut_kernel<unsigned int __vector(4)>", "moments_kernel<HIP_vector_type<unsigned int, 4u> >"."""
     lib_path = lib_path or os.path.join(ROOT, "dsabeamformer_amd", "libdsabf.so")
     txt = subprocess.check_output(["nm", "-C", lib_path], text=True)
-    return sorted({m.group(1) for m in re.finditer(r"__device_stub__([a-z_0-9]+)\(", txt)})
+    out = set()
+    for m in re.finditer(r"__device_stub__([A-Za-z_0-9]+)", txt):
+        i = m.end()
+        if txt[i] == "<":   # the template arguments: to the matching '>' (they may hold '<', '>' and parentheses of their own)
+            depth = 0
+            while True:
+                depth += {"<": 1, ">": -1}.get(txt[i], 0)
+                i += 1
+                if depth == 0:
+                    break
+        assert txt[i] == "(", txt[m.start():i + 40]
+        out.add(txt[m.end() - len(m.group(1)):i])
+    return out
+
+
+# The stages whose device code lives in a directory of its own under csrc/ (dsabeamformer_amd/build.py): their launchers pick among
+# template instantiations on antenna count, FFT length, alignment, width count and the chip's CU count.
+STAGE_DIRS = ("sps", "ib", "corr", "cal", "cond", "sk", "stokes", "null", "stamp", "psr", "ffa", "inj", "vcut", "cdd", "rm")
+
+
+def stage_sources() -> list[str]:
+    csrc = os.path.join(ROOT, "dsabeamformer_amd", "csrc")
+    return sorted(os.path.join(csrc, d, f) for d in STAGE_DIRS for f in os.listdir(os.path.join(csrc, d)) if f.endswith(".hip"))
+
+
+def stage_kernel_names() -> set[str]:
+    """The `__global__` functions defined under csrc/<stage>/, without template arguments."""
+    names = set()
+    for path in stage_sources():
+        names |= set(re.findall(r"__global__\s+(?:__launch_bounds__\([^\n]*?\)\s+)?void\s+([A-Za-z_0-9]+)\s*\(", open(path).read()))
+    return names
+
+
+def stage_compiled(lib_path: str | None = None) -> set[str]:
+    """Every kernel instantiation of the library whose source is under one of STAGE_DIRS, as demangled names.  The launchers record
+    exactly these spellings (include/dsabf_bench.h: bf_stage_launches); tests/support/stage_census.py has one row for each, and
+    tests/test_gpu_stage_census.py launches every row against the stage's oracle."""
+    base = stage_kernel_names()
+    return {k for k in _stubs(lib_path) if k.split("<")[0] in base}
+
+
+def other_kernels(lib_path: str | None = None) -> list[str]:
+    """The library's kernels that are neither instantiations of the two fused templates nor stage kernels (stage_compiled())."""
+    stage = stage_compiled(lib_path)
+    return sorted(k for k in _stubs(lib_path) if k not in stage and not re.match(r"fused(?:16|g)_kernel<", k))
 
 
 def interleaved(key: str, n_beams: int) -> bool:
@@ -139,7 +184,7 @@ def main() -> int:
     print("# fusedg_kernel<16-byte rows, detect mode, stage-parity store>;  detect mode 0 canonical, 1 fast, 2 contracted")
     print("# compiled %d, reachable over the contract %d, compiled but unreachable %d, reachable but not compiled %d"
           % (len(comp), len(reach), len(comp - set(reach)), len(set(reach) - comp)))
-    print("# other kernels (one instantiation each): " + ", ".join(other_kernels()))
+    print("# other kernels of csrc/ itself: " + ", ".join(other_kernels()))
     print("# %-52s %-22s %5s %7s  smallest geometry that selects it" % ("instantiation", "translation unit", "vgprs", "scratch"))
     for key in sorted(comp | set(reach)):
         r, g = res.get(key, {}), reach.get(key)
@@ -147,6 +192,10 @@ def main() -> int:
                                                                             "paired" if g["paired"] else "general", " (bf_gemm_device)" if g["write_c"] else "")) if g else "UNREACHABLE"
         print("%-54s %-22s %5s %7s  %s%s" % (key, r.get("unit", "?"), r.get("vgprs", "?") if not r.get("agprs") else "%d+%d" % (r["vgprs"], r["agprs"]),
                                             r.get("scratch", "?"), geo, "" if key in comp else "  NOT COMPILED"))
+    stage = stage_compiled()
+    print("# stage kernels (csrc/<stage>/; launched one by one by tests/test_gpu_stage_census.py: profiles/stage_census_gpu.txt): %d" % len(stage))
+    for key in sorted(stage):
+        print("#   " + key)
     return 0 if comp == set(reach) else 1
 
 
