@@ -1153,7 +1153,10 @@ int plan_dm_stage(observation& ob)
         oopt.gather_root = BF_GATHER_ROOT_ALL;
         oopt.dm_split_trials = true;
         dm_trial_share(ob.n_dm, o.shard.world, ob.rank, &ob.my_first, &ob.my_trials);
-        std::cout << "Shard " << ob.rank << " dedisperses trials " << ob.my_first << " .. " << ob.my_first + ob.my_trials - 1 << std::endl;
+        if (ob.my_trials > 0)
+            std::cout << "Shard " << ob.rank << " dedisperses trials " << ob.my_first << " .. " << ob.my_first + ob.my_trials - 1 << std::endl;
+        else   // (more shards than trials: this one beamforms and sends its channels, and runs no DM-side stage)
+            std::cout << "Shard " << ob.rank << " dedisperses no trials: the ladder has " << ob.n_dm << ", fewer than the " << o.shard.world << " shards" << std::endl;
     }
     ob.my_dmax = largest(ob.my_first, ob.my_trials);
     ob.dm_here = ob.my_trials > 0 && (!ob.comm || ob.rank == 0 || oopt.dm_split_trials);

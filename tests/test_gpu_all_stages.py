@@ -5,9 +5,15 @@ lines are theirs, in the loop's order.  Then the lab switch that turns block lau
 stages that need block launches refuse it before anything is launched."""
 import os
 import subprocess
+import sys
 
 import numpy as np
 import pytest
+
+from conftest import ROOT
+
+sys.path.insert(0, os.path.join(ROOT, "tests", "support"))
+from dm_side import closing_lines, sorted_records  # noqa: E402  (shared with tests/test_gpu_trial_split.py)
 
 pytestmark = pytest.mark.gpu
 
@@ -25,12 +31,6 @@ VOLTAGE_FILES = ("vis.bin", "sk.bin", "stokes.bin", "det.bin")
 # the closing lines of run_observation, in its order; and which run has the same line
 CLOSING = [("DM stage:", "b"), ("Conditioner:", "b"), ("Incoherent beam:", "b"), ("Correlator:", "c"), ("Voltage moments:", "c"), ("Stokes beams:", "c"),
            ("Injector:", "b"), ("Pulsar folder:", "b"), ("Periodicity search:", "b"), ("Single-pulse search:", "b"), ("Events:", "b"), ("Voltage cuts:", "b")]
-
-
-def closing_lines(stdout):
-    """What run_observation prints behind its closing report ("Synchronized" ends that), without the driver's own "Wrote ..." lines."""
-    lines = stdout.splitlines()
-    return [l for l in lines[lines.index("Synchronized") + 1:] if not l.startswith("Wrote ")]
 
 
 @pytest.fixture(scope="module")
@@ -55,10 +55,7 @@ def test_every_file_of_the_full_run_is_the_file_of_a_partial_run(runs):
             assert got == want and (len(got) > 4096 or not n.endswith(".bin")), n   # (a binary file: more than its header)
     # the cuts: a retried one lands a deliver later, and when a deliver comes depends on the clock -- the same records in any order
     for n, read, key in (("st.bin", host.read_stamp_file, ("t0", "dm", "beam", "tbin", "width", "snr")), ("v.bin", host.read_voltage_file, ("t0", "dm", "beam", "width", "snr"))):
-        records = {}
-        for run in ("a", "b"):
-            hdr, recs = read(os.path.join(runs[run][0], n))
-            records[run] = (hdr, sorted((tuple(r[k] for k in key), r["data"].tobytes()) for r in recs))
+        records = {run: sorted_records(os.path.join(runs[run][0], n), read, key) for run in ("a", "b")}
         assert len(records["a"][1]) >= 1, n
         assert records["a"] == records["b"], n
     for n in ("cands.txt", "ev.txt", "ffa.txt"):   # the run is one at which the search stages find something

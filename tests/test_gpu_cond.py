@@ -14,6 +14,7 @@ from conftest import ROOT
 sys.path.insert(0, os.path.join(ROOT, "tests", "support"))
 import cond_oracle  # noqa: E402
 import cond_scenario  # noqa: E402
+import dm_side  # noqa: E402
 import sps_oracle  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -442,9 +443,7 @@ def test_beam_cli_n_z(tmp_path):
     production geometry (the window of 3 wraps at the fourth).  The -w file keeps the RAW stream; the oracle conditions it block by
     block (window 3, zero-DM, automatic mask, the file's static mask), and the oracle's dedispersion of that over the driver's delays
     must be the -W file bit for bit; the masked count the driver prints under -v is the oracle's for the last block."""
-    import oracle as orc
-
-    from dsabeamformer_amd import build, host
+    from dsabeamformer_amd import build
 
     n_an, tsamp = 4, 0.02
     raw_file, dm_file, mask_file = tmp_path / "raw.bin", tmp_path / "dm.bin", tmp_path / "mask.txt"
@@ -452,22 +451,15 @@ def test_beam_cli_n_z(tmp_path):
     r = subprocess.run([build.BEAM, "-j", str(25 + n_an), "-M", "40", "-N", "4", "-T", str(tsamp), "-n", "3", "-z", "-U", "5", "-F", str(mask_file), "-v",
                         "-w", str(raw_file), "-W", str(dm_file)], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr
-    hdr, data, chunks = host.read_dm_file(str(dm_file))
-    _, det = host.read_detected_file(str(raw_file))                 # [gemm][output][f][b]: rows in time order
-    n_f, n_b = det.shape[2], det.shape[3]
-    raw = det.reshape(-1, n_f, n_b)
+    raw = dm_side.read_rows(raw_file)                                # [gemm][output][f][b]: rows in time order
+    n_f, n_b = raw.shape[1], raw.shape[2]
     assert raw.shape[0] % n_an == 0 and (n_f, n_b) == (256, 256)
-    rows = raw.shape[0] // n_an
     # what `beam -M 40 -N 4 -T 0.02` computes (csrc/beam_main.cpp): the notebook's ladder, evenly picked
-    dms = host.dm_trials(dm_max=40.0)
-    dms = np.array([dms[int(i * (len(dms) - 1) / 3)] for i in range(4)])
-    freq = np.array([host.channel_frequency(0, ch) for ch in range(n_f)], np.float32)
-    delays = host.dm_delays(dms, freq, float(freq[0]), tsamp)
+    _, _, delays = dm_side.beam_ladder(40.0, 4, n_f, tsamp)
     static = np.zeros(n_f, np.uint8)
     static[[7, 200]] = 1
-    c = cond_oracle.Conditioner(n_f, n_b, 3, True, 5.0, static)
-    cooked = np.concatenate([c.push(raw[k * rows:(k + 1) * rows]) for k in range(n_an)])
-    want = orc.dedisperse_dm(cooked, delays, raw.shape[0] - int(delays.max()))
-    assert data.shape == want.shape and np.array_equal(bits(data), bits(want))
+    # (the conditioning push by push and the comparison: tests/support/dm_side.py, shared with tests/test_gpu_trial_split.py)
+    cooked, c = dm_side.conditioned_rows(raw, raw.shape[0] // n_an, 3, True, 5.0, static)
+    dm_side.check_dm_file(dm_file, cooked, delays)
     assert ("Conditioner: %d of %d channels masked in the last push" % (int(c.mask.sum()), n_f)) in r.stdout, r.stdout[-2000:]
     assert c.mask[7] and c.mask[200] and not c.mask.all()

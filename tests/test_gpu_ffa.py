@@ -14,6 +14,7 @@ import pytest
 from conftest import ROOT
 
 sys.path.insert(0, os.path.join(ROOT, "tests", "support"))
+import dm_side  # noqa: E402
 import ffa_oracle  # noqa: E402
 import sps_oracle  # noqa: E402
 from ffa_stage import PARITY_CASES, case_cfg, case_input, check_segment, run_stage, same_candidates  # noqa: E402
@@ -365,18 +366,9 @@ def test_beam_cli_writes_the_candidates_the_oracle_finds_in_its_dm_file(tmp_path
     assert r.returncode == 0, r.stdout + r.stderr
     hdr, data, chunks = host.read_dm_file(str(dm_file))
     assert data.shape[0] == 8 and sum(n for _, n in chunks) == data.shape[1]
+    # (the comparison itself: tests/support/dm_side.py, shared with the trial-split runs of tests/test_gpu_trial_split.py)
+    head, want, n_every = dm_side.check_ffa(ffa_file, r.stdout, data, cfg, thr)
     n_segs = data.shape[1] // 128
-    assert n_segs >= 2
-    every = [c for s in ffa_oracle.Search(data, *cfg, threshold=-np.inf).segments() for c in s["cands"]]
-    snr = np.array([c[10] for c in every])
-    assert np.all(np.abs(snr - thr) > 1e-7 * thr)
-    want = [c for c in every if c[10] >= thr]
     print("periodicity candidates recomputed from dm.bin: %d of %d series x %d segments" % (len(want), data.shape[0] * data.shape[2], n_segs))
-    assert 1 <= len(want) < len(every)
-    assert ("%d segments of 64 samples, %d candidates" % (n_segs, len(want))) in r.stdout and ("Wrote %d periodicity candidates" % len(want)) in r.stdout
-    head, rows = ffa_oracle.read_candidates(str(ffa_file))
+    assert n_segs >= 2 and 1 <= len(want) < n_every
     assert head["p_lo"] == "8" and head["p_hi"] == "13" and head["n_seg"] == "64" and head["tdec"] == "2" and head["n_oct"] == "2" and head["n_widths"] == "2"
-    assert len(rows) == len(want)
-    for got, w in zip(rows, want):
-        assert got[:10] == w[:10] and got[11] == w[11], (got, w)
-        assert abs(got[10] - w[10]) <= 1e-9 * abs(w[10])

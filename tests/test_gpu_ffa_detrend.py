@@ -13,6 +13,7 @@ import pytest
 from conftest import ROOT
 
 sys.path.insert(0, os.path.join(ROOT, "tests", "support"))
+import dm_side  # noqa: E402
 import ffa_detrend_oracle as det  # noqa: E402
 import ffa_oracle  # noqa: E402
 import sps_oracle  # noqa: E402
@@ -303,17 +304,10 @@ def test_beam_cli_with_ffa_detrend_writes_what_the_oracle_finds_in_its_dm_file(t
     hdr, data, chunks = host.read_dm_file(str(dm_file))
     n_segs = data.shape[1] // 128
     assert data.shape[0] == 8 and n_segs >= 2
-    every = [c for s in det.Search(data, *cfg, 8, 5, threshold=-np.inf).segments() for c in s["cands"]]
-    snr = np.array([c[10] for c in every])
-    assert np.all(np.abs(snr - thr) > 1e-7 * thr)
-    want = [c for c in every if c[10] >= thr]
-    assert 1 <= len(want) < len(every)
-    head, rows = ffa_oracle.read_candidates(str(ffa_file))
+    # (the comparison itself: tests/support/dm_side.py, shared with the trial-split runs of tests/test_gpu_trial_split.py)
+    head, want, n_every = dm_side.check_ffa(ffa_file, r.stdout, data, cfg, thr, detrend=(8, 5))
+    assert 1 <= len(want) < n_every
     assert head["detrend"] == "8:5" and head["n_seg"] == "64" and head["tdec"] == "2"
-    assert len(rows) == len(want) and ("Wrote %d periodicity candidates" % len(want)) in r.stdout
-    for got, w in zip(rows, want):
-        assert got[:10] == w[:10] and got[11] == w[11], (got, w)
-        assert abs(got[10] - w[10]) <= 1e-9 * abs(w[10])
     # out of range: refused by bf_ffa_set_detrend, with its message
     r = subprocess.run([build.BEAM, "-j", "33", "-M", "250", "-N", "8", "--ffa", "8:13", "--ffa-seg", "64", "--ffa-detrend", "128:5"], capture_output=True,
                        text=True, timeout=300)

@@ -16,6 +16,7 @@ from conftest import ROOT
 
 sys.path.insert(0, os.path.join(ROOT, "tests", "support"))
 import cond_oracle  # noqa: E402
+import dm_side  # noqa: E402
 import inj_cases  # noqa: E402
 import inj_oracle  # noqa: E402
 import sps_oracle  # noqa: E402
@@ -478,8 +479,7 @@ def test_beam_injects_and_finds_the_burst(tmp_path, orc):
     from dsabeamformer_amd import api, build, host
 
     raw_file, cand_file, truth_file = tmp_path / "raw.bin", tmp_path / "cands.txt", tmp_path / "truth.txt"
-    dms = host.dm_trials(dm_max=40.0)
-    dms = np.array([dms[int(i * (len(dms) - 1) / 3)] for i in range(4)])             # what `beam -M 40 -N 4` picks
+    dms, freq, ladder = dm_side.beam_ladder(40.0, 4, 256, BEAM_TSAMP)                # what `beam -M 40 -N 4 -T 0.02` picks
     dm = float(dms[2])
     r = subprocess.run([build.BEAM, "-j", "27", "-M", "40", "-N", "4", "-T", str(BEAM_TSAMP), "-S", "8", "-B", "5", "-w", str(raw_file), "-C", str(cand_file),
                         "--inject", "%d:%.17g:%d:%.17g:1:%d" % (BEAM_T0, dm, BEAM_BEAM, BEAM_FLUENCE, BEAM_W),
@@ -496,13 +496,9 @@ def test_beam_injects_and_finds_the_burst(tmp_path, orc):
     t0, trial, beam, W, t_lo, t_hi = int(lines[0][2]), int(lines[0][4]), int(lines[0][5]), int(lines[0][8]), int(lines[0][9]), int(lines[0][10])
     assert (t0, beam, W, t_lo, t_hi) == (BEAM_T0, BEAM_BEAM, BEAM_W, BEAM_T0, BEAM_T0 + BEAM_W - 1)
     assert float(lines[0][3]) == dm and float(lines[0][6]) == BEAM_FLUENCE and float(lines[0][7]) == 1.0
-    _, det = host.read_detected_file(str(raw_file))
-    n_f, n_b = det.shape[2], det.shape[3]
-    raw = det.reshape(-1, n_f, n_b)
+    raw = dm_side.read_rows(raw_file)
     rows = raw.shape[0] // 2
-    assert (raw.shape[0], n_f, n_b) == (512, 256, 256)
-    freq = np.array([host.channel_frequency(0, ch) for ch in range(n_f)], np.float32)
-    ladder = host.dm_delays(dms, freq, float(freq[0]), BEAM_TSAMP)
+    assert raw.shape == (512, 256, 256)
     delay = host.dm_delays(np.array([dm]), freq, float(freq[0]), BEAM_TSAMP)[0]
     assert trial == api.Injector.nearest_trial(ladder, delay) == inj_oracle.nearest_trial(ladder, delay) == 2
     truth = [(t_lo, t_hi, trial, beam)]
@@ -514,24 +510,15 @@ def test_beam_injects_and_finds_the_burst(tmp_path, orc):
         return [c for at in (0, rows) for c in search.push(max(0, at + rows - D) - max(0, at - D))["cands"]]
 
     assert list(inj_oracle.match(truth, _as_records(chain(raw)), t_tol=2, dm_tol=1)) == [-1]
-    prof = api.Injector.burst_profile(n_f, W, (W - 1) / 2.0, 1.0, BEAM_FLUENCE)     # the table the driver made: the same helper
-    resp = np.zeros(n_b, np.float32)
-    resp[beam] = 1.0
-    m = api.PulsarFolder.model_from_spin(TRAIN_F0, row_seconds=BEAM_TSAMP * 1e-3)
-    t_prof = np.zeros((n_f, TRAIN_BINS), np.float32)
-    t_prof[:, :max(1, round(TRAIN_DUTY * TRAIN_BINS))] = TRAIN_AMP
-    t_resp = np.zeros(n_b, np.float32)
-    t_resp[TRAIN_BEAM] = 1.0
-    train = ((m.phase0, m.dphase, m.ddphase, m.epoch_row), host.dm_delays(np.array([float(dms[1])]), freq, float(freq[0]), BEAM_TSAMP)[0], t_prof, t_resp, 0, None)
-    want = chain(inj_oracle.inject(raw, [(t0, delay, prof, resp)], [train], cuts=[rows, rows]))
+    # (the tables the driver made, with the same helpers, and inj_oracle over them: tests/support/dm_side.py, shared with
+    #  tests/test_gpu_trial_split.py)
+    want = chain(dm_side.injected_rows(raw, rows, freq, BEAM_TSAMP, [(t0, dm, beam, BEAM_FLUENCE, 1.0, W)],
+                                       [(TRAIN_F0, float(dms[1]), TRAIN_BEAM, TRAIN_AMP, TRAIN_DUTY, TRAIN_BINS)]))
     best = inj_oracle.match(truth, _as_records(want), t_tol=0, dm_tol=0)
     print("chain:", len(want), "candidates,", sum(c[2] == TRAIN_BEAM for c in want), "of them in the train's beam; the burst's:", want[best[0]] if best[0] >= 0 else None)
     assert best[0] >= 0 and want[best[0]][5] >= 8.0
     # ---- the driver found the same
-    tab = [l.split() for l in open(cand_file).read().splitlines()[1:]]
-    got = np.zeros(len(tab), api._candidate_dtype())
-    for i, f in enumerate(("t_start", "dm", "beam", "width", "snr", "peak")):
-        got[f] = [row[i] for row in tab]
+    got = dm_side.read_candidates(cand_file)
     sps_oracle.assert_candidates_equal(got, want, rtol=1e-9)
     assert list(api.Injector.match(truth, got)) == list(best)
 
@@ -541,18 +528,10 @@ def test_beam_shards_inject_the_whole_band_redundantly(tmp_path):
     processes: the band is gathered to both, the six trials are split, and BOTH ranks inject the whole band where they dedisperse it.
     Each writes the same truth to truth.txt.<rank> (the trial numbered over the whole ladder); the rank that owns trial 4 finds the
     burst there, the other rank's trials hold nothing that matches it at dm_tol 0."""
-    from test_gpu_multirank import FAKE, SUPPORT
+    from dsabeamformer_amd import api, build
 
-    from dsabeamformer_amd import api, build, host
-
-    src = os.path.join(SUPPORT, "fake_rccl.cpp")
-    if not os.path.exists(FAKE) or os.path.getmtime(FAKE) < os.path.getmtime(src):
-        obj = os.path.join(SUPPORT, "fake_rccl.o")
-        subprocess.check_call([build.HIPCC, "-O2", "-std=c++17", "-fPIC", "-c", src, "-o", obj])
-        cxx = os.path.join(os.path.dirname(os.path.realpath(build.HIPCC)), "..", "lib", "llvm", "bin", "clang++")
-        subprocess.check_call([cxx if os.path.exists(cxx) else "g++", "-shared", "-fPIC", "-o", FAKE, obj, "-lpthread", "-lrt"])
-    dms = host.dm_trials(dm_max=40.0)
-    dms = np.array([dms[int(i * (len(dms) - 1) / 5)] for i in range(6)])             # what `beam -M 40 -N 6` picks
+    FAKE = dm_side.fake_rccl()                                                       # (built here if no test has built it yet)
+    dms, _, _ = dm_side.beam_ladder(40.0, 6, 256, BEAM_TSAMP)                        # what `beam -M 40 -N 6` picks
     cands, truth_file = tmp_path / "cands.txt", tmp_path / "truth.txt"
     cmd = lambda rk: [build.BEAM, "-j", "27", "-D", "0", "-M", "40", "-N", "6", "-T", str(BEAM_TSAMP), "-R", "2", "-r", str(rk), "-I", str(tmp_path / "id"),  # noqa: E731
                       "-X", "-S", "8", "-B", "5", "-C", str(cands), "--inject", "%d:%.17g:%d:%.17g:1:%d" % (BEAM_T0, float(dms[4]), BEAM_BEAM, BEAM_FLUENCE, BEAM_W),
@@ -568,10 +547,7 @@ def test_beam_shards_inject_the_whole_band_redundantly(tmp_path):
     for rk in (0, 1):
         assert ("Shard %d dedisperses trials %d .. %d" % (rk, 3 * rk, 3 * rk + 2)) in outs[rk]
         assert "Injector: 1 bursts and 0 trains added to the rows in front of the DM stage, 1 kernels launched" in outs[rk], outs[rk]
-        tab = [l.split() for l in open(str(cands) + ".%d" % rk).read().splitlines()[1:]]
-        got = np.zeros(len(tab), api._candidate_dtype())
-        for i, f in enumerate(("t_start", "dm", "beam", "width", "snr", "peak")):
-            got[f] = [row[i] for row in tab]
+        got = dm_side.read_candidates(str(cands) + ".%d" % rk)
         best = api.Injector.match(truth, got)
         print("rank %d: %d candidates, the burst's: %s" % (rk, len(got), got[best[0]] if best[0] >= 0 else None))
         assert (best[0] >= 0) == (rk == 1)

@@ -17,6 +17,7 @@ from conftest import ROOT
 
 sys.path.insert(0, os.path.join(ROOT, "tests", "support"))
 import cond_oracle  # noqa: E402
+import dm_side  # noqa: E402
 import psr_oracle  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -411,18 +412,11 @@ def test_beam_cli_fold(tmp_path):
                        capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr
     assert "Pulsar folder: 2 pulsars, 16 bins, 2 dumps" in r.stdout, r.stdout[-2000:]
-    _, det = host.read_detected_file(str(raw_file))                 # [gemm][output][f][b]: rows in time order
-    n_f, n_b = det.shape[2], det.shape[3]
-    raw = det.reshape(-1, n_f, n_b)
+    raw = dm_side.read_rows(raw_file)                                # [gemm][output][f][b]: rows in time order
     assert raw.shape[0] == 2 * dump_rows
-    header, recs = psr_oracle.read_file(str(fold_file))
-    assert [int(header[k]) for k in ("NPSR", "NFREQ", "NBINS", "NBEAMS")] == [2, n_f, n_bins, n_b]
-    assert [(q["first_row"], q["n_rows"]) for q in recs] == [(0, dump_rows), (dump_rows, dump_rows)]
-    freq = np.array([host.channel_frequency(0, ch) for ch in range(n_f)], np.float32)
+    # (the comparison itself: tests/support/dm_side.py, shared with the trial-split runs of tests/test_gpu_trial_split.py)
+    _, freq, _ = dm_side.beam_ladder(40.0, 4, raw.shape[1], tsamp)
     delays = host.dm_delays(np.array([25.0, 0.0]), freq, float(freq[0]), tsamp)
-    assert delays.shape == (2, n_f) and delays[0].max() > 0 and not delays[1].any()
-    models = [psr_oracle.model_from_spin(31.7, -0.4, 0.3, tsamp * 1e-3), psr_oracle.model_from_spin(1200.0, 0.0, 0.0, tsamp * 1e-3)]
-    for q in recs:
-        assert int(q["hits"].sum()) == 2 * n_f * dump_rows and q["hits"].shape == (2, n_f, n_bins)
-        want_prof, want_hits = psr_oracle.fold(raw[q["first_row"]:q["first_row"] + dump_rows], models, delays, n_bins, first_row=q["first_row"])
-        assert np.array_equal(q["hits"], want_hits) and np.array_equal(bits(q["profile"]), bits(want_prof))
+    assert delays.shape == (2, raw.shape[1]) and delays[0].max() > 0 and not delays[1].any()
+    recs = dm_side.check_folds(fold_file, raw, freq, tsamp, [(31.7, -0.4, 0.3), (1200.0, 0.0, 0.0)], [25.0, 0.0], n_bins, dump_rows)
+    assert [(q["first_row"], q["n_rows"]) for q in recs] == [(0, dump_rows), (dump_rows, dump_rows)]

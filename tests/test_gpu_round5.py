@@ -350,40 +350,23 @@ def test_observation_loop_with_the_dm_stage_streams_a_pulse_across_block_boundar
     assert np.array_equal(a, b)
 
 
-def _beam_ladder(host, dm_max, n_cap, n_freq, tsamp_ms):
-    """What `beam -M dm_max -N n_cap -T tsamp_ms` computes (csrc/beam_main.cpp): the notebook's ladder, evenly picked."""
-    dms = host.dm_trials(dm_max=dm_max)
-    if len(dms) > n_cap:
-        dms = np.array([dms[int(i * (len(dms) - 1) / (n_cap - 1))] for i in range(n_cap)])
-    freq = np.array([host.channel_frequency(0, c) for c in range(n_freq)], np.float32)
-    return dms, host.dm_delays(dms, freq, float(freq[0]), tsamp_ms)
-
-
 def test_beam_cli_dm_stage_single_gpu_and_two_loopback_ranks(orc, tmp_path):
     """`beam -j 27 -M 40 -N 6 -T 0.02 -W dm.bin` (25 burn-in reads + 2 analysed blocks of the production geometry) on one GPU,
     and the same sub-band as `-R 2` shard processes (loopback stand-in for RCCL p2p): the gather root dedisperses the GATHERED
     band.  Each file is bit-equal to orc.dedisperse_dm over the whole detected series the run produced, ascending f over all
     256 channels -- one GPU or two.  With -X the band goes to every rank and the TRIALS are split across the shards; that run has
     the single-pulse search on (-S -B -C): every shard's candidates are the oracle's over its own file."""
-    from test_gpu_multirank import FAKE, SUPPORT  # noqa: F401  (built by that module's fixture; build here if it has not run)
     import subprocess
 
     from dsabeamformer_amd import build, host
 
     import dsabeamformer_amd as bfm
 
-    if SUPPORT not in sys.path:
-        sys.path.insert(0, SUPPORT)
-    import sps_oracle
+    import dm_side
 
-    src = os.path.join(SUPPORT, "fake_rccl.cpp")
-    if not os.path.exists(FAKE) or os.path.getmtime(FAKE) < os.path.getmtime(src):
-        obj = os.path.join(SUPPORT, "fake_rccl.o")
-        subprocess.check_call([build.HIPCC, "-O2", "-std=c++17", "-fPIC", "-c", src, "-o", obj])
-        cxx = os.path.join(os.path.dirname(os.path.realpath(build.HIPCC)), "..", "lib", "llvm", "bin", "clang++")
-        subprocess.check_call([cxx if os.path.exists(cxx) else "g++", "-shared", "-fPIC", "-o", FAKE, obj, "-lpthread", "-lrt"])
+    FAKE = dm_side.fake_rccl()                              # (built here if no test has built it yet)
     n_an, tsamp = 2, 0.02                                   # analysed blocks; a sample time that makes DM 40 span ~45 rows
-    dms, delays = _beam_ladder(host, 40.0, 6, 256, tsamp)
+    dms, _, delays = dm_side.beam_ladder(40.0, 6, 256, tsamp)   # what `beam -M 40 -N 6 -T 0.02` computes
     D = int(delays.max())
     assert len(dms) == 6 and 20 < D < 256
     pos, dirs = host.default_positions(64), host.default_directions(256)
@@ -441,30 +424,14 @@ def test_beam_cli_dm_stage_single_gpu_and_two_loopback_ranks(orc, tmp_path):
             assert all(p.returncode == 0 for p in procs), "\n".join(outs)
             for rk in (0, 1):
                 assert ("Shard %d dedisperses trials %d .. %d" % (rk, 3 * rk, 3 * rk + 2)) in outs[rk]
-                mine = np.ascontiguousarray(delays[3 * rk:3 * rk + 3])
-                d_r = int(mine.max())
-                hdr, got, chunks = host.read_dm_file(str(outx) + ".%d" % rk)
-                assert int(hdr["N_DM"]) == 3 and int(hdr["DM_FIRST_TRIAL"]) == 3 * rk and int(hdr["MAX_DELAY"]) == d_r
-                assert np.array_equal(got, orc.dedisperse_dm(series, mine, T - d_r)), rk
-                # the candidates, recomputed from this rank's file: the same chunk boundaries, the driver's window of 8 chunks and
-                # 64-sample minimum (the oracle's defaults), trial numbers from the plan's dm_first
-                search = sps_oracle.Search(got, 4, dm_first=3 * rk, threshold=thr)
-                want = [c for _, n in chunks for c in search.push(n)["cands"]]
+                # (both comparisons: tests/support/dm_side.py, shared with the runs of tests/test_gpu_trial_split.py) -- the header names
+                # the share and its own largest delay, the file is the oracle's over ITS trials; the candidates are recomputed from this
+                # rank's file: the same chunk boundaries, the driver's window of 8 chunks and 64-sample minimum (the oracle's defaults),
+                # trial numbers from the plan's dm_first, no S/N on the threshold, every trial numbered over the whole ladder
+                hdr, got, chunks = dm_side.check_dm_file(str(outx) + ".%d" % rk, series, delays, 3 * rk, 3)
+                cand, want = dm_side.check_candidates(str(candx) + ".%d" % rk, outs[rk], got, chunks, 4, thr, 3 * rk)
                 print("rank %d: candidates recomputed from dm_x.bin.%d: %d of %d records" % (rk, rk, len(want), 3 * 256 * len(chunks)))
                 assert 1 <= len(want) < 3 * 256 * len(chunks)
-                every = sps_oracle.Search(got, 4, dm_first=3 * rk, threshold=-np.inf)
-                snr = np.array([c[5] for _, n in chunks for c in every.push(n)["cands"]])
-                assert np.all(np.abs(snr - thr) > 1e-7 * thr)                          # no S/N on the threshold: 100 x the tolerance below
-                assert ("Single-pulse search: boxcar widths 1 .. 8, %d candidates" % len(want)) in outs[rk], outs[rk]
-                assert ("Wrote %d candidates to %s.%d" % (len(want), candx, rk)) in outs[rk]
-                lines = open(str(candx) + ".%d" % rk).read().splitlines()
-                assert lines[0].startswith("#") and len(lines) == 1 + len(want)
-                tab = np.array([l.split() for l in lines[1:]])
-                cand = np.zeros(len(want), [("t_start", np.uint64), ("dm", np.int32), ("beam", np.int32), ("width", np.int32), ("peak", np.float32), ("snr", np.float64)])
-                for i, f in enumerate(("t_start", "dm", "beam", "width", "snr", "peak")):
-                    cand[f] = tab[:, i].astype(cand.dtype[f])
-                sps_oracle.assert_candidates_equal(cand, want, rtol=1e-9)
-                assert np.all((cand["dm"] >= 3 * rk) & (cand["dm"] < 3 * rk + 3))      # numbered over the whole ladder
             assert not os.path.exists(str(candx))                  # (one file per shard, none without a rank)
             assert int(delays[:3].max()) < D                       # (rank 0's window really is the shorter one)
 

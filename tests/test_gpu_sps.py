@@ -10,6 +10,7 @@ import pytest
 from conftest import ROOT
 
 sys.path.insert(0, os.path.join(ROOT, "tests", "support"))
+import dm_side  # noqa: E402
 import sps_oracle  # noqa: E402
 from sps_stage import run_stage as _run_stage  # noqa: E402
 from test_sps_cpu import series_for  # noqa: E402
@@ -269,15 +270,7 @@ def test_beam_cli_writes_the_candidates_the_oracle_finds_in_its_dm_file(tmp_path
     assert r.returncode == 0, r.stdout + r.stderr
     hdr, data, chunks = host.read_dm_file(str(dm_file))
     assert data.shape[0] == 8 and len(chunks) == 8 and sum(n for _, n in chunks) == data.shape[1]
-    orc = sps_oracle.Search(data, 6, threshold=thr)
-    want = [c for _, n in chunks for c in orc.push(n)["cands"]]
+    # (the comparison itself: tests/support/dm_side.py, shared with the trial-split runs of tests/test_gpu_trial_split.py)
+    got, want = dm_side.check_candidates(cand_file, r.stdout, data, chunks, 6, thr)
     print("candidates recomputed from dm.bin:", len(want))
-    assert 1 <= len(want) <= 5000
-    assert ("Single-pulse search: boxcar widths 1 .. 32, %d candidates" % len(want)) in r.stdout and ("Wrote %d candidates" % len(want)) in r.stdout
-    lines = open(cand_file).read().splitlines()
-    assert lines[0].startswith("#") and len(lines) == 1 + len(want)
-    tab = np.array([l.split() for l in lines[1:]])
-    got = np.zeros(len(want), [("t_start", np.uint64), ("dm", np.int32), ("beam", np.int32), ("width", np.int32), ("peak", np.float32), ("snr", np.float64)])
-    for i, f in enumerate(("t_start", "dm", "beam", "width", "snr", "peak")):
-        got[f] = tab[:, i].astype(got.dtype[f])
-    sps_oracle.assert_candidates_equal(got, want, rtol=1e-9)
+    assert 1 <= len(got) == len(want) <= 5000

@@ -12,6 +12,7 @@ from conftest import ROOT
 
 sys.path.insert(0, os.path.join(ROOT, "tests", "support"))
 import cond_oracle  # noqa: E402
+import dm_side  # noqa: E402
 import stamp_oracle as so  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -405,10 +406,7 @@ def test_beam_cli_events_and_stamps_end_to_end(tmp_path):
     stamps_dropped included); every stamp is bit-equal to the stamp oracle over the rows of det.bin."""
     import subprocess
 
-    import evt_oracle as eo
-    import oracle as orc
-
-    from dsabeamformer_amd import api, build, host
+    from dsabeamformer_amd import build
 
     names = ("det.bin", "dm.bin", "cands.txt", "ev.txt", "st.bin")
     det_file, dm_file, cand_file, ev_file, st_file = (str(tmp_path / n) for n in names)
@@ -416,52 +414,15 @@ def test_beam_cli_events_and_stamps_end_to_end(tmp_path):
                         "--events", ev_file, "--stamps", st_file], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr
     opts = dict(max_width=32, ib_beam=255)
-    tab = np.loadtxt(cand_file, ndmin=2)
-    cands = eo.candidates([(int(v[0]), int(v[1]), int(v[2]), int(v[3]), v[4], v[5]) for v in tab])
-    want = eo.events(cands, **opts)
-    got = host.read_event_file(ev_file)
+    # (the comparisons themselves: tests/support/dm_side.py, shared with the trial-split runs of tests/test_gpu_trial_split.py)
+    cands, want = dm_side.check_events(ev_file, cand_file, **opts)
     print("candidates", len(cands), "events", len(want))
     assert len(want) >= 1
-    eo.assert_events_equal(by_best_key(got), want, snr_rtol=1e-9)
-    # the events of every deliver: the builder replayed over the chunks of dm.bin (a candidate is reported with the END of its boxcar)
-    _, data, chunks = host.read_dm_file(dm_file)
-    t_end = cands["t_start"].astype(np.int64) + cands["width"] - 1
-    picked, dropped, n_events = [], 0, 0
-    with api.EventBuilder(**opts) as eb:
-        feeds = [eb.feed(cands[(t_end >= first_t) & (t_end < first_t + n_t)], first_t + n_t) for first_t, n_t in chunks] + [eb.flush()]
-    for ev in feeds:
-        n_events += len(ev)
-        pick = [e for e in ev if not e["flags"]]
-        pick = sorted(pick, key=lambda e: -float(e["best"]["snr"]))              # (stable: ties stay in event order)
-        dropped += max(0, len(pick) - 16)
-        picked += pick[:16]
-    assert n_events == len(want)
-    # the rows the ring held: det.bin (there is no conditioner), and the driver's ladder -- checked against dm.bin below
-    _, det = host.read_detected_file(det_file)
-    series = np.ascontiguousarray(det.reshape(-1, det.shape[2], det.shape[3]))
-    dms = host.dm_trials(dm_max=250.0)
-    dms = np.array([dms[int(i * (len(dms) - 1) / 7)] for i in range(8)])
-    freq = np.array([host.channel_frequency(0, ch) for ch in range(series.shape[1])], np.float32)
-    delays = host.dm_delays(dms, freq, float(freq[0]), 0.131)
-    # a window that passes the last row the run produced cannot be cut: arithmetic on the request, nothing the run reports
-    def request(e):
-        b = e["best"]
-        tbin = max(1, int(b["width"]) // 2)
-        return max(0, int(b["t_start"]) + int(b["width"]) // 2 - 64 * tbin // 2), int(b["dm"]), int(b["beam"]), tbin, int(b["width"])
-    beyond = [e for e in picked if request(e)[0] + so.span(delays, request(e)[1], 64, request(e)[3]) > series.shape[0]]
-    picked = [e for e in picked if request(e)[0] + so.span(delays, request(e)[1], 64, request(e)[3]) <= series.shape[0]]
-    assert ("Events: %d events, stamps %d, stamps_dropped %d, stamps_missed 0, beyond the end of the run %d" % (len(want), len(picked), dropped, len(beyond))) \
-        in r.stdout, r.stdout[-1500:]
-    hdr, stamps = host.read_stamp_file(st_file)
-    print("stamps", len(stamps), "dropped", dropped)
-    assert len(stamps) == len(picked) >= 1 and (hdr["NFREQ_OUT"], hdr["NBINS"], hdr["FBIN"]) == ("256", "64", "1")
-    key = lambda t0, dm, beam, tbin, width: (int(t0), int(dm), int(beam), int(tbin), int(width))   # noqa: E731
-    want_keys = [key(*request(e)) for e in picked]
-    assert sorted(key(s["t0"], s["dm"], s["beam"], s["tbin"], s["width"]) for s in stamps) == sorted(want_keys)
-    assert np.array_equal(bits(data), bits(orc.dedisperse_dm(series, delays, series.shape[0] - int(delays.max()))))
-    for s in stamps:
-        assert np.array_equal(bits(s["data"]), bits(so.stamp(series, delays, s["t0"], s["dm"], s["beam"], 64, s["tbin"], 1))), key(*[s[k] for k in ("t0", "dm", "beam", "tbin", "width")])
-
-
-def by_best_key(events):
-    return sorted(events, key=lambda e: (int(e["best"]["t_start"]), int(e["best"]["dm"]), int(e["best"]["beam"])))
+    # the rows the ring held: det.bin (there is no conditioner), and the driver's ladder -- dm.bin is the oracle's over both
+    series = dm_side.read_rows(det_file)
+    _, _, delays = dm_side.beam_ladder(250.0, 8, series.shape[1], 0.131)
+    _, data, chunks = dm_side.check_dm_file(dm_file, series, delays)
+    # the events of every deliver (the builder replayed over the chunks of dm.bin), the selection rule, the closing line, every stamp
+    stamps = dm_side.check_stamps(st_file, r.stdout, cands, chunks, len(want), series, delays, **opts)
+    print("stamps", len(stamps))
+    assert len(stamps) >= 1
