@@ -1,11 +1,46 @@
-// bf_accum.cpp -- the accumulator stage under the correlator and the voltage moments (bf_accum_stage, bf_runtime_internal.h): one int64
-// accumulator on the device that pushes add to and a dump snapshots and zeroes.  This file owns the accumulator, orders its pushes and
-// dumps whatever queues they come on, and keeps the result sets; what a kind of stage computes is its bf_accum_kind (bf_corr.cpp, bf_sk.cpp).
+// bf_accum.cpp -- the snapshot-and-zero accumulator (bf_accumulator, bf_runtime_internal.h): bytes on the device that pushes add to and a
+// dump copies out and zeroes, ordered by a bf_chain whatever queues they come on, the snapshots in a bf_result_ring.  The pulsar folder
+// (bf_psr.cpp) holds one; so does the accumulator stage under the correlator and the voltage moments (bf_accum_stage), whose entry points
+// are here too: what a kind of stage computes is its bf_accum_kind (bf_corr.cpp, bf_sk.cpp).
 #include <cstring>
 #include <memory>
 #include <string>
 
 #include "bf_runtime_internal.h"
+
+void bf_accumulator::create(bf_resources& res, size_t bytes_, int max_in_flight)
+{
+    bytes = bytes_;
+    res.dev(&d_acc, bytes, true);
+    chain.create(res);
+    ring.create(res, max_in_flight);
+    for (auto& r : ring.sets) res.host(&r.h_acc, bytes);
+}
+
+int bf_accumulator::dump(uint64_t record0, uint64_t record1)
+{
+    snapshot& r = ring.next();
+    HIP_TRY(chain.wait(ring.copy_q));
+    HIP_TRY(hipMemcpyAsync(r.h_acc, d_acc, bytes, hipMemcpyDeviceToHost, ring.copy_q));
+    HIP_TRY(hipMemsetAsync(d_acc, 0, bytes, ring.copy_q));
+    HIP_TRY(hipEventRecord(r.copied, ring.copy_q));
+    chain.adopt(r.copied);
+    r.record[0] = record0;
+    r.record[1] = record1;
+    ring.issued();
+    return BF_OK;
+}
+
+int bf_accumulator::collect(const char** h_acc, uint64_t record[2])
+{
+    HIP_TRY(ring.wait_oldest());
+    const snapshot& r = ring.oldest();
+    *h_acc = r.h_acc;
+    record[0] = r.record[0];
+    record[1] = r.record[1];
+    ring.collected();
+    return BF_OK;
+}
 
 // "bf_corr" + "_push": the entry point's name, as the messages carry it
 static std::string entry(const bf_accum_stage* s, const char* suffix) { return std::string(s->kind.abi) + suffix; }
@@ -14,11 +49,9 @@ static std::string entry(const bf_accum_stage* s, const char* suffix) { return s
 static int push_impl(bf_accum_stage* s, const void* d_packed, int n_units, hipStream_t q)
 {
     bf_handle* h = s->h;
-    if (s->last) HIP_TRY(hipStreamWaitEvent(q, s->last, 0));
-    if (int rc = s->kind.launch(h, d_packed, n_units, s->d_acc, true, q)) return rc;
-    hipEvent_t ev = s->push_done[s->n_push++ % 2];
-    HIP_TRY(hipEventRecord(ev, q));
-    s->last = ev;
+    HIP_TRY(s->acc.chain.wait(q));
+    if (int rc = s->kind.launch(h, d_packed, n_units, reinterpret_cast<long long*>(s->acc.d_acc), true, q)) return rc;
+    HIP_TRY(s->acc.chain.extend(q));
     s->columns += (uint64_t)n_units * (uint64_t)h->cfg.n_out_per_gemm * (uint64_t)h->cfg.n_avg;
     return BF_OK;
 }
@@ -34,23 +67,12 @@ int dsabf::rt::accum_init(bf_accum_stage* fresh, bf_handle* h, int max_in_flight
     if (int rc = s->kind.check_create(h)) return rc;
     ON_DEVICE(h);
     s->h = h;
-    s->max_in_flight = max_in_flight;
-    s->n_int64 = 2 * s->kind.entries(&h->cfg);
-    const size_t bytes = s->n_int64 * sizeof(long long);
-    bf_resources& res = s->res;
-    res.dev(&s->d_acc, bytes, true);
-    res.queue(&s->copy_q);
-    for (auto& ev : s->push_done) res.event(&ev);
-    s->sets.resize((size_t)max_in_flight);
-    for (auto& r : s->sets) {
-        res.host(&r.h_acc, bytes);
-        res.event(&r.copied);
-    }
-    res.device_sync();
+    s->acc.create(s->res, 2 * s->kind.entries(&h->cfg) * sizeof(long long), max_in_flight);
+    s->res.device_sync();
     return stage_adopt(keep.release(), who.c_str());
 }
 
-int dsabf::rt::accum_pending(const bf_accum_stage* s) { return s ? (int)(s->n_dump - s->n_collected) : fail(BF_ERR_INVALID, "the stage is NULL"); }
+int dsabf::rt::accum_pending(const bf_accum_stage* s) { return s ? s->acc.ring.pending() : fail(BF_ERR_INVALID, "the stage is NULL"); }
 
 int dsabf::rt::accum_push(bf_accum_stage* s, const void* d_packed, int n_units, void* hip_stream)
 {
@@ -80,19 +102,11 @@ int dsabf::rt::accum_dump(bf_accum_stage* s)
 {
     if (!s) return fail(BF_ERR_INVALID, "the stage is NULL");
     if (int rc = orphaned(s)) return rc;
-    if (s->n_dump - s->n_collected >= (uint64_t)s->max_in_flight)
-        return fail(BF_ERR_STATE, "%s_dump: %d dumps are uncollected (max_in_flight): %s_collect first", s->kind.abi, s->max_in_flight, s->kind.abi);
+    if (!s->acc.ring.room())
+        return fail(BF_ERR_STATE, "%s_dump: %d dumps are uncollected (max_in_flight): %s_collect first", s->kind.abi, s->acc.ring.max_in_flight, s->kind.abi);
     ON_DEVICE(s->h);
-    bf_accum_stage::result_set& r = s->sets[s->n_dump % s->max_in_flight];
-    if (s->last) HIP_TRY(hipStreamWaitEvent(s->copy_q, s->last, 0));
-    const size_t bytes = s->n_int64 * sizeof(long long);
-    HIP_TRY(hipMemcpyAsync(r.h_acc, s->d_acc, bytes, hipMemcpyDeviceToHost, s->copy_q));
-    HIP_TRY(hipMemsetAsync(s->d_acc, 0, bytes, s->copy_q));
-    HIP_TRY(hipEventRecord(r.copied, s->copy_q));
-    s->last = r.copied;
-    r.columns = s->columns;
+    if (int rc = s->acc.dump(s->columns)) return rc;
     s->columns = 0;
-    s->n_dump++;
     return BF_OK;
 }
 
@@ -100,12 +114,12 @@ int dsabf::rt::accum_collect(bf_accum_stage* s, int64_t* out, uint64_t* n_column
 {
     if (!s || !out) return fail(BF_ERR_INVALID, "NULL argument");
     if (int rc = orphaned(s)) return rc;
-    if (s->n_collected == s->n_dump) return fail(BF_ERR_STATE, "%s_collect: no dump is pending", s->kind.abi);
+    if (!s->acc.ring.pending()) return fail(BF_ERR_STATE, "%s_collect: no dump is pending", s->kind.abi);
     ON_DEVICE(s->h);
-    bf_accum_stage::result_set& r = s->sets[s->n_collected % s->max_in_flight];
-    HIP_TRY(hipEventSynchronize(r.copied));
-    std::memcpy(out, r.h_acc, s->n_int64 * sizeof(long long));
-    if (n_columns_per_pol) *n_columns_per_pol = r.columns;
-    s->n_collected++;   // (the set is free from here on)
+    const char* h_acc = nullptr;
+    uint64_t record[2];
+    if (int rc = s->acc.collect(&h_acc, record)) return rc;
+    std::memcpy(out, h_acc, s->acc.bytes);
+    if (n_columns_per_pol) *n_columns_per_pol = record[0];
     return BF_OK;
 }

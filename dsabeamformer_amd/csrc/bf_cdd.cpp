@@ -1,6 +1,6 @@
 // bf_cdd.cpp -- coherent dedispersion of beam voltages (include/dsabf.h: bf_cdd_*; contract and measurements:
 // docs/COHERENT_DEDISPERSION.md).  The device code is csrc/cdd/bf_cdd.hip; this file checks the bounds, owns a stage's twiddle and
-// chirp tables, orders the uploads of a new chirp against the kernels in flight, and holds the host helpers (sweep, edge, chirp).
+// chirp tables, orders the uploads of a new chirp against the kernels in flight (a bf_chain: bf_runtime_internal.h), and holds the host helpers (sweep, edge, chirp).
 #include <cmath>
 #include <new>
 
@@ -15,9 +15,7 @@ struct bf_cdd : bf_stage {
     float* h_chirp = nullptr;   // pinned: where bf_cdd_set_chirp builds the rows (free again when that call returns)
     hipStream_t copy_q = nullptr;
     hipEvent_t uploaded = nullptr;               // end of the last upload: every kernel waits for it
-    hipEvent_t done_ev[2] = {nullptr, nullptr};
-    hipEvent_t done = nullptr;                   // fires when EVERY kernel issued so far has run (each joins the one before it)
-    uint64_t n_launch = 0;
+    bf_chain kernels;                            // its end fires when EVERY kernel issued so far has run (each joins the one before it)
 };
 
 static const double kDispersion = 4.15;   // ms GHz^2 per pc cm^-3: the constant of dm_delays (bf_geometry.cpp)
@@ -26,7 +24,7 @@ static int upload(bf_cdd* c, const float* chirp)
 {
     const size_t row = (size_t)c->n_fft * 2;
     for (int f = 0; f < c->n_chan; f++) dsabf::cdd_permute_row_host(chirp + f * row, c->n_fft, c->h_chirp + f * row);
-    if (c->done) HIP_TRY(hipStreamWaitEvent(c->copy_q, c->done, 0));
+    HIP_TRY(c->kernels.wait(c->copy_q));
     HIP_TRY(hipMemcpyAsync(c->d_chirp, c->h_chirp, (size_t)c->n_chan * row * sizeof(float), hipMemcpyHostToDevice, c->copy_q));
     HIP_TRY(hipEventRecord(c->uploaded, c->copy_q));
     HIP_TRY(hipEventSynchronize(c->uploaded));
@@ -54,11 +52,8 @@ static int run(bf_cdd* c, const void* d_in, int K, long long n_time64, int n_int
     HIP_TRY(hipStreamWaitEvent(q, c->uploaded, 0));
     dsabf::CddLaunch l = {d_in, d_out, c->d_tw, c->d_chirp, c->n_chan, K, n_time, c->n_fft, c->n_edge, n_int};
     HIP_TRY(dsabf::launch_cdd(l, q));
-    // one event for all launches: behind this kernel the queue joins the launch before it (the kernel itself is not held up)
-    if (c->done) HIP_TRY(hipStreamWaitEvent(q, c->done, 0));
-    hipEvent_t ev = c->done_ev[c->n_launch++ % 2];
-    HIP_TRY(hipEventRecord(ev, q));
-    c->done = ev;
+    // one chain for all launches: behind this kernel the queue joins the launch before it (the kernel itself is not held up)
+    HIP_TRY(c->kernels.join(q));
     return BF_OK;
 }
 
@@ -126,7 +121,7 @@ int bf_cdd_create(bf_handle* h, int n_chan, int n_fft, int n_edge, const float* 
     res.host(&c->h_chirp, table > (size_t)n_fft * sizeof(float) ? table : (size_t)n_fft * sizeof(float));
     res.queue(&c->copy_q);
     res.event(&c->uploaded);
-    for (auto& ev : c->done_ev) res.event(&ev);
+    c->kernels.create(res);
     if (int rc = stage_adopt(c, "bf_cdd_create")) return rc;
     auto fill = [&]() -> int {
         dsabf::cdd_twiddles_host(n_fft, c->h_chirp);   // (through the pinned buffer, before the chirp takes it)

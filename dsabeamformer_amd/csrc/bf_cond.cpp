@@ -1,6 +1,6 @@
 // bf_cond.cpp -- conditioning of the detected stream in front of the DM stage (include/dsabf.h: bf_cond_*; contract, ordering and
 // measurements: docs/CONDITIONING.md).  The device code is csrc/cond/bf_cond.hip; this file owns the stage's memory, keeps the
-// window's row counts and orders the pushes.
+// window's row counts and orders the pushes (a bf_chain: bf_runtime_internal.h).
 #include <algorithm>
 #include <deque>
 #include <new>
@@ -15,10 +15,7 @@ struct bf_cond : bf_stage {
     double k_auto = 0.0;                  // auto_threshold * 1.4826, formed once, here, in fp64
     dsabf::CondBuffers buf{};
     uint8_t* d_static = nullptr;          // the caller's mask (buf.static_mask)
-    // Push j runs behind done[(j - 1) % 2], whatever queue that ran on, and records done[j % 2]: the pushes share the ring of
-    // totals, the per-cell and per-channel scratch and the mask.
-    hipEvent_t done[2] = {nullptr, nullptr};
-    uint64_t n_push = 0;
+    bf_chain pushes;                      // the pushes share the ring of totals, the per-cell and per-channel scratch and the mask
     std::deque<int> rows_in_window;       // row counts of the pushes in the window, oldest first
     void attached() override { rows_in_window.clear(); }   // attached, in mid-stream or not: the window starts empty there
 };
@@ -78,7 +75,7 @@ int bf_cond_create(bf_handle* h, int n_freq_total, int max_rows_per_push, const 
     res.dev(&c->d_static, F, true);
     res.dev(&c->buf.mask, (F + 3) / 4 * 4, true);   // (whole dwords: a host mirror may copy it as such)
     res.dev(&c->buf.params, sizeof(dsabf::CondParams));
-    for (hipEvent_t& ev : c->done) res.event(&ev);
+    c->pushes.create(res);
     res.device_sync();
     c->buf.static_mask = c->d_static;
     if (int rc = stage_adopt(c, "bf_cond_create")) return rc;
@@ -95,7 +92,7 @@ int bf_cond_set_mask(bf_cond* c, const uint8_t* host_mask)
     bf_handle* h = c->h;
     ON_DEVICE(h);
     // the push in flight still reads the old mask: wait for it, then copy (a blocking call: masks change rarely)
-    if (c->n_push) HIP_TRY(hipEventSynchronize(c->done[(c->n_push - 1) % 2]));
+    if (c->pushes.end) HIP_TRY(hipEventSynchronize(c->pushes.end));
     HIP_TRY(hipMemcpy(c->d_static, host_mask, (size_t)c->n_freq, hipMemcpyHostToDevice));
     return BF_OK;
 }
@@ -109,16 +106,15 @@ int bf_cond_push(bf_cond* c, float* d_rows, int n_rows, void* hip_stream)
     ON_DEVICE(h);
     hipStream_t q = as_stream(hip_stream);
     // behind the push before this one, whatever queue it ran on: the window, the scratch and the mask are shared
-    if (c->n_push) HIP_TRY(hipStreamWaitEvent(q, c->done[(c->n_push - 1) % 2], 0));
+    HIP_TRY(c->pushes.wait(q));
     const int n_sets = (int)std::min<size_t>(c->rows_in_window.size() + 1, (size_t)c->window);
     uint64_t n_window = (uint64_t)n_rows;
     for (size_t i = c->rows_in_window.size() + 1 - (size_t)n_sets; i < c->rows_in_window.size(); i++) n_window += (uint64_t)c->rows_in_window[i];
-    HIP_TRY(dsabf::launch_cond_push(d_rows, n_rows, c->n_freq, c->n_beams, c->buf, c->window, (int)(c->n_push % (uint64_t)c->window), n_sets, n_window,
+    HIP_TRY(dsabf::launch_cond_push(d_rows, n_rows, c->n_freq, c->n_beams, c->buf, c->window, (int)(c->pushes.n % (uint64_t)c->window), n_sets, n_window,
                                     c->zero_dm, c->k_auto, q));
-    HIP_TRY(hipEventRecord(c->done[c->n_push % 2], q));
+    HIP_TRY(c->pushes.extend(q));
     c->rows_in_window.push_back(n_rows);
     while (c->rows_in_window.size() > (size_t)c->window) c->rows_in_window.pop_front();
-    c->n_push++;
     return BF_OK;
 }
 

@@ -1,7 +1,7 @@
 // bf_ffa.cpp -- the periodicity search behind the DM trials (include/dsabf.h: bf_ffa_*; contract, ordering and measurements:
 // docs/PERIODICITY.md).  The device code is csrc/ffa/bf_ffa.hip; this file owns the series and the carried decimation state, cuts
-// every push at the segment boundaries, orders the pushes whatever queues they come on, keeps the result sets and selects the
-// candidates.
+// every push at the segment boundaries, orders the pushes whatever queues they come on (a bf_chain), keeps the result sets (a
+// bf_result_ring: bf_runtime_internal.h) and selects the candidates.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -13,7 +13,7 @@
 
 struct bf_ffa : bf_stage {
     bf_ffa() : bf_stage("periodicity stage") {}
-    int n_dm = 0, dm_first = 0, tdec = 0, n_seg = 0, n_oct = 0, p_lo = 0, p_hi = 0, n_widths = 0, max_t = 0, max_in_flight = 0, n_beams = 0;
+    int n_dm = 0, dm_first = 0, tdec = 0, n_seg = 0, n_oct = 0, p_lo = 0, p_hi = 0, n_widths = 0, max_t = 0, n_beams = 0;
     double threshold = 0;
     int det_blk = 0, det_win = 0;   // bf_ffa_set_detrend: samples per block and blocks per median window; det_blk == 0: off
     // Two series slots: segment s is decimated into slot s % 2 and searched there while the samples behind it go to the other one.
@@ -24,19 +24,14 @@ struct bf_ffa : bf_stage {
     float* d_carry[2] = {nullptr, nullptr};
     uint64_t n_in = 0;        // input samples the stage has been given
     uint64_t seg_first = 0;   // first_row of the segment in progress (set by the push that brings its first sample)
-    // Pushes share the slots and the carry, so each waits for the one before it, whatever queue that came on.
-    hipEvent_t push_done[2] = {nullptr, nullptr};
-    hipEvent_t last = nullptr;
-    uint64_t n_push = 0;
-    struct result_set {
+    bf_chain pushes;          // the pushes share the slots and the carry; pushes.n is j above
+    struct result_set : bf_result_set {
         bf_ffa_peak *d_peaks = nullptr, *h_peaks = nullptr;
         bf_ffa_stat *d_stats = nullptr, *h_stats = nullptr;
-        hipEvent_t kernels_done = nullptr, copied = nullptr;
+        hipEvent_t kernels_done = nullptr;
         uint64_t first_row = 0;
     };
-    std::vector<result_set> sets;   // segment s leaves its records in set s % max_in_flight
-    hipStream_t copy_q = nullptr;
-    uint64_t n_searched = 0, n_collected = 0;
+    bf_result_ring<result_set> ring;   // one issue per segment searched
     std::vector<bf_ffa_peak> last_peaks;
     std::vector<bf_ffa_stat> last_stats;
     uint64_t last_first_row = 0;
@@ -63,10 +58,9 @@ int dsabf::rt::ffa_check_push(const bf_ffa* s, int n_t)
 {
     if (n_t < 1 || n_t > s->max_t) return fail(BF_ERR_INVALID, "n_t must be 1 .. %d (max_t_per_push)", s->max_t);
     const uint64_t completes = (s->n_in + (uint64_t)n_t) / s->seg_rows() - s->n_in / s->seg_rows();
-    const uint64_t pending = s->n_searched - s->n_collected;
-    if (completes && pending + completes > (uint64_t)s->max_in_flight)
+    if (completes && !s->ring.room(completes))
         return fail(BF_ERR_STATE, "bf_ffa_push: %llu segments are uncollected and this push completes %llu more (max_in_flight %d): bf_ffa_collect first",
-                    (unsigned long long)pending, (unsigned long long)completes, s->max_in_flight);
+                    (unsigned long long)s->ring.pending(), (unsigned long long)completes, s->ring.max_in_flight);
     return BF_OK;
 }
 
@@ -124,7 +118,6 @@ int bf_ffa_create(bf_handle* h, int n_dm, int dm_first, int tdec, int n_seg, int
     s->p_hi = p_hi;
     s->n_widths = n_widths;
     s->max_t = max_t_per_push;
-    s->max_in_flight = max_in_flight;
     s->threshold = threshold;
     s->n_beams = h->cfg.n_beams;
     const size_t n_db = s->n_db(), n_rec = s->n_rec();
@@ -134,16 +127,14 @@ int bf_ffa_create(bf_handle* h, int n_dm, int dm_first, int tdec, int n_seg, int
         res.dev(&s->d_slot[k], slot_floats * sizeof(float));
         res.dev(&s->d_carry[k], n_db * sizeof(float));
     }
-    res.queue(&s->copy_q);
-    for (hipEvent_t& ev : s->push_done) res.event(&ev);
-    s->sets.resize((size_t)max_in_flight);
-    for (auto& r : s->sets) {
+    s->pushes.create(res);
+    s->ring.create(res, max_in_flight);
+    for (auto& r : s->ring.sets) {
         res.dev(&r.d_peaks, n_rec * sizeof(bf_ffa_peak));
         res.dev(&r.d_stats, n_db * sizeof(bf_ffa_stat));
         res.host(&r.h_peaks, n_rec * sizeof(bf_ffa_peak));
         res.host(&r.h_stats, n_db * sizeof(bf_ffa_stat));
         res.event(&r.kernels_done);
-        res.event(&r.copied);
     }
     if (int rc = stage_adopt(s, "bf_ffa_create")) return rc;
     *out = s;
@@ -162,7 +153,7 @@ int bf_ffa_set_detrend(bf_ffa* s, int blk, int win)
     }
     if (!s) return fail(BF_ERR_INVALID, "the stage is NULL");
     if (int rc = orphaned(s)) return rc;
-    if (s->n_push) return fail(BF_ERR_STATE, "bf_ffa_set_detrend: the stage has taken a push; the detrend is set before the first");
+    if (s->pushes.n) return fail(BF_ERR_STATE, "bf_ffa_set_detrend: the stage has taken a push; the detrend is set before the first");
     if (blk != 0 && s->n_seg % blk) return fail(BF_ERR_INVALID, "bf_ffa_set_detrend: n_seg %d is no multiple of blk %d", s->n_seg, blk);
     s->det_blk = blk;
     s->det_win = blk ? win : 0;
@@ -177,7 +168,7 @@ int bf_ffa_detrend(const bf_ffa* s, int* blk, int* win)
     return BF_OK;
 }
 
-int bf_ffa_pending(const bf_ffa* s) { return s ? (int)(s->n_searched - s->n_collected) : fail(BF_ERR_INVALID, "the stage is NULL"); }
+int bf_ffa_pending(const bf_ffa* s) { return s ? s->ring.pending() : fail(BF_ERR_INVALID, "the stage is NULL"); }
 
 int bf_ffa_push(bf_ffa* s, const float* d_chunk, int n_t, uint64_t first_t, void* hip_stream)
 {
@@ -187,9 +178,9 @@ int bf_ffa_push(bf_ffa* s, const float* d_chunk, int n_t, uint64_t first_t, void
     if ((uintptr_t)d_chunk & 15) return fail(BF_ERR_INVALID, "misaligned device pointer: d_chunk must be 16-byte aligned");
     ON_DEVICE(s->h);
     hipStream_t q = as_stream(hip_stream);
-    if (s->last) HIP_TRY(hipStreamWaitEvent(q, s->last, 0));
-    const float* carry_in = s->d_carry[s->n_push % 2];
-    float* carry_out = s->d_carry[(s->n_push + 1) % 2];
+    HIP_TRY(s->pushes.wait(q));
+    const float* carry_in = s->d_carry[s->pushes.n % 2];
+    float* carry_out = s->d_carry[(s->pushes.n + 1) % 2];
     const int c0 = (int)(s->n_in % (uint64_t)s->tdec);                     // samples the group in progress already holds
     const uint64_t dec0 = s->n_in / (uint64_t)s->tdec;                     // decimated samples in front of this push
     const int n_complete = (int)(((uint64_t)c0 + (uint64_t)n_t) / (uint64_t)s->tdec);
@@ -211,20 +202,18 @@ int bf_ffa_push(bf_ffa* s, const float* d_chunk, int n_t, uint64_t first_t, void
         g += cnt + (with_open ? 1 : 0);
         if (closes) {
             if (s->det_blk) HIP_TRY(dsabf::launch_ffa_detrend(slot, s->n_dm, s->n_beams, s->n_seg, s->det_blk, s->det_win, q));
-            bf_ffa::result_set& r = s->sets[s->n_searched % (uint64_t)s->max_in_flight];
+            bf_ffa::result_set& r = s->ring.next();
             HIP_TRY(dsabf::launch_ffa_search(slot, s->n_dm, s->n_beams, s->n_seg, s->n_oct, s->p_lo, s->p_hi, s->n_widths, r.d_peaks, r.d_stats, q));
             HIP_TRY(hipEventRecord(r.kernels_done, q));
-            HIP_TRY(hipStreamWaitEvent(s->copy_q, r.kernels_done, 0));
-            HIP_TRY(hipMemcpyAsync(r.h_peaks, r.d_peaks, s->n_rec() * sizeof(bf_ffa_peak), hipMemcpyDeviceToHost, s->copy_q));
-            HIP_TRY(hipMemcpyAsync(r.h_stats, r.d_stats, s->n_db() * sizeof(bf_ffa_stat), hipMemcpyDeviceToHost, s->copy_q));
-            HIP_TRY(hipEventRecord(r.copied, s->copy_q));
+            HIP_TRY(hipStreamWaitEvent(s->ring.copy_q, r.kernels_done, 0));
+            HIP_TRY(hipMemcpyAsync(r.h_peaks, r.d_peaks, s->n_rec() * sizeof(bf_ffa_peak), hipMemcpyDeviceToHost, s->ring.copy_q));
+            HIP_TRY(hipMemcpyAsync(r.h_stats, r.d_stats, s->n_db() * sizeof(bf_ffa_stat), hipMemcpyDeviceToHost, s->ring.copy_q));
+            HIP_TRY(hipEventRecord(r.copied, s->ring.copy_q));
             r.first_row = s->seg_first;
-            s->n_searched++;
+            s->ring.issued();
         }
     }
-    hipEvent_t ev = s->push_done[s->n_push++ % 2];
-    HIP_TRY(hipEventRecord(ev, q));
-    s->last = ev;
+    HIP_TRY(s->pushes.extend(q));
     s->n_in += (uint64_t)n_t;
     return BF_OK;
 }
@@ -236,14 +225,14 @@ int bf_ffa_collect(bf_ffa* s, bf_ffa_candidate* out, size_t max_out, size_t* n_o
     if (max_out < s->n_db())
         return fail(BF_ERR_INVALID, "bf_ffa_collect: room for %zu candidates, a segment can give n_dm * n_beams = %zu", max_out, s->n_db());
     if (int rc = orphaned(s)) return rc;
-    if (s->n_collected == s->n_searched) return fail(BF_ERR_STATE, "bf_ffa_collect: no segment is pending");
+    if (!s->ring.pending()) return fail(BF_ERR_STATE, "bf_ffa_collect: no segment is pending");
     ON_DEVICE(s->h);
-    bf_ffa::result_set& r = s->sets[s->n_collected % (uint64_t)s->max_in_flight];
-    HIP_TRY(hipEventSynchronize(r.copied));
+    HIP_TRY(s->ring.wait_oldest());
+    const bf_ffa::result_set& r = s->ring.oldest();
     s->last_peaks.assign(r.h_peaks, r.h_peaks + s->n_rec());
     s->last_stats.assign(r.h_stats, r.h_stats + s->n_db());
     s->last_first_row = r.first_row;
-    s->n_collected++;   // (the set is free from here on)
+    s->ring.collected();
     return bf_ffa_select(s->last_peaks.data(), s->last_stats.data(), s->tdec, s->n_seg, s->n_oct, s->p_lo, s->p_hi, s->n_widths, s->n_dm, s->n_beams,
                          s->last_first_row, s->seg_rows(), s->dm_first, s->threshold, out, max_out, n_out);
 }

@@ -1,7 +1,7 @@
 // bf_psr.cpp -- the pulsar folder (include/dsabf.h: bf_psr_*; contract, ordering and measurements: docs/PULSAR_FOLDING.md).  The
-// device code is csrc/psr/bf_psr.hip; this file owns the accumulators, orders the pushes and dumps whatever queues they come on (the
-// event chain of bf_accum.cpp, on fp64 cells), keeps the result sets, and holds the two host helpers (the model from a spin
-// frequency, the per-beam S/N of a folded profile).
+// device code is csrc/psr/bf_psr.hip; this file folds the pushes into a bf_accumulator (bf_runtime_internal.h: it orders the pushes and
+// dumps whatever queues they come on and keeps the snapshots), and holds the two host helpers (the model from a spin frequency, the
+// per-beam S/N of a folded profile).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -13,30 +13,16 @@
 
 struct bf_psr : bf_stage {
     bf_psr() : bf_stage("pulsar folder") {}
-    int n_freq = 0, n_beams = 0, max_rows = 0, n_bins = 0, n_psr = 0, max_in_flight = 0;
+    int n_freq = 0, n_beams = 0, max_rows = 0, n_bins = 0, n_psr = 0;
     bf_psr_model model[dsabf::kPsrMaxPulsars] = {};
     int32_t delay_min[dsabf::kPsrMaxPulsars] = {}, delay_max[dsabf::kPsrMaxPulsars] = {};
     int32_t* d_delays = nullptr;       // [n_psr][n_freq]
-    // The integration in progress, one allocation: n_prof doubles [k][f][bin][beam], then n_hits uint64 [k][f][bin].  Every push adds
-    // to it, a dump copies it out and zeroes it.
-    char* d_acc = nullptr;
+    // The integration in progress, one allocation: n_prof doubles [k][f][bin][beam], then n_hits uint64 [k][f][bin].  A dump's record
+    // is {first_row, n_rows}.
+    bf_accumulator acc;
     size_t n_prof = 0, n_hits = 0;
     uint64_t pushed = 0;               // rows the stage has been given
     uint64_t first_row = 0;            // first row of the integration in progress
-    // Pushes and dumps share d_acc, so each waits for the one before it, whatever queue that was issued on: `last` is the event
-    // behind the most recent kernel (push_done, two taking turns) or behind the most recent dump's copy and memset (its set's).
-    hipEvent_t push_done[2] = {nullptr, nullptr};
-    hipEvent_t last = nullptr;
-    uint64_t n_push = 0;
-    struct result_set {
-        char* h_acc = nullptr;         // pinned
-        hipEvent_t copied = nullptr;
-        uint64_t first_row = 0, n_rows = 0;
-    };
-    std::vector<result_set> sets;      // dump j leaves its snapshot in set j % max_in_flight
-    hipStream_t copy_q = nullptr;
-    uint64_t n_dump = 0, n_collected = 0;
-    size_t acc_bytes() const { return n_prof * sizeof(double) + n_hits * sizeof(uint64_t); }
 };
 
 bf_stage* dsabf::rt::as_stage(bf_psr* p) { return p; }
@@ -129,7 +115,6 @@ int bf_psr_create(bf_handle* h, int n_freq_total, int max_rows_per_push, int n_b
     p->max_rows = max_rows_per_push;
     p->n_bins = n_bins;
     p->n_psr = n_psr;
-    p->max_in_flight = max_in_flight;
     for (int k = 0; k < n_psr; k++) {
         p->model[k] = models[k];
         const int32_t* d = delays + (size_t)k * n_freq_total;
@@ -139,16 +124,9 @@ int bf_psr_create(bf_handle* h, int n_freq_total, int max_rows_per_push, int n_b
     p->n_prof = bf_psr_entries(n_psr, n_freq_total, n_bins, p->n_beams);
     p->n_hits = p->n_prof / (size_t)p->n_beams;
     bf_resources& res = p->res;
-    res.dev(&p->d_acc, p->acc_bytes(), true);
+    p->acc.create(res, p->n_prof * sizeof(double) + p->n_hits * sizeof(uint64_t), max_in_flight);
     res.dev(&p->d_delays, (size_t)n_psr * n_freq_total * sizeof(int32_t));
     if (res.err == hipSuccess) res.err = hipMemcpy(p->d_delays, delays, (size_t)n_psr * n_freq_total * sizeof(int32_t), hipMemcpyHostToDevice);
-    res.queue(&p->copy_q);
-    for (hipEvent_t& ev : p->push_done) res.event(&ev);
-    p->sets.resize((size_t)max_in_flight);
-    for (auto& r : p->sets) {
-        res.host(&r.h_acc, p->acc_bytes());
-        res.event(&r.copied);
-    }
     res.device_sync();
     if (int rc = stage_adopt(p, "bf_psr_create")) return rc;
     *out = p;
@@ -171,18 +149,16 @@ int bf_psr_push(bf_psr* p, const float* d_rows, int n_rows, void* hip_stream)
         a.osc[k] = {m.phase0, m.dphase, m.ddphase, (int64_t)((__int128)p->pushed - (__int128)m.epoch_row)};
     }
     a.delays = p->d_delays;
-    a.profile = reinterpret_cast<double*>(p->d_acc);
-    a.hits = reinterpret_cast<unsigned long long*>(p->d_acc + p->n_prof * sizeof(double));
+    a.profile = reinterpret_cast<double*>(p->acc.d_acc);
+    a.hits = reinterpret_cast<unsigned long long*>(p->acc.d_acc + p->n_prof * sizeof(double));
     a.n_psr = p->n_psr;
     a.n_freq = p->n_freq;
     a.n_bins = p->n_bins;
     a.n_beams = p->n_beams;
     // behind whatever used the accumulators last, and the new end of that chain
-    if (p->last) HIP_TRY(hipStreamWaitEvent(q, p->last, 0));
+    HIP_TRY(p->acc.chain.wait(q));
     HIP_TRY(dsabf::launch_psr_fold(d_rows, n_rows, a, q));
-    hipEvent_t ev = p->push_done[p->n_push++ % 2];
-    HIP_TRY(hipEventRecord(ev, q));
-    p->last = ev;
+    HIP_TRY(p->acc.chain.extend(q));
     p->pushed += (uint64_t)n_rows;
     return BF_OK;
 }
@@ -193,19 +169,11 @@ int bf_psr_dump(bf_psr* p, void* hip_stream)
     (void)hip_stream;
     if (!p) return fail(BF_ERR_INVALID, "the stage is NULL");
     if (int rc = orphaned(p)) return rc;
-    if (p->n_dump - p->n_collected >= (uint64_t)p->max_in_flight)
-        return fail(BF_ERR_STATE, "bf_psr_dump: %d dumps are uncollected (max_in_flight): bf_psr_collect first", p->max_in_flight);
+    if (!p->acc.ring.room())
+        return fail(BF_ERR_STATE, "bf_psr_dump: %d dumps are uncollected (max_in_flight): bf_psr_collect first", p->acc.ring.max_in_flight);
     ON_DEVICE(p->h);
-    bf_psr::result_set& r = p->sets[p->n_dump % p->max_in_flight];
-    if (p->last) HIP_TRY(hipStreamWaitEvent(p->copy_q, p->last, 0));
-    HIP_TRY(hipMemcpyAsync(r.h_acc, p->d_acc, p->acc_bytes(), hipMemcpyDeviceToHost, p->copy_q));
-    HIP_TRY(hipMemsetAsync(p->d_acc, 0, p->acc_bytes(), p->copy_q));
-    HIP_TRY(hipEventRecord(r.copied, p->copy_q));
-    p->last = r.copied;
-    r.first_row = p->first_row;
-    r.n_rows = p->pushed - p->first_row;
+    if (int rc = p->acc.dump(p->first_row, p->pushed - p->first_row)) return rc;
     p->first_row = p->pushed;
-    p->n_dump++;
     return BF_OK;
 }
 
@@ -213,19 +181,19 @@ int bf_psr_collect(bf_psr* p, double* profile, uint64_t* hits, uint64_t* first_r
 {
     if (!p || !profile || !hits) return fail(BF_ERR_INVALID, "NULL argument");
     if (int rc = orphaned(p)) return rc;
-    if (p->n_collected == p->n_dump) return fail(BF_ERR_STATE, "bf_psr_collect: no dump is pending");
+    if (!p->acc.ring.pending()) return fail(BF_ERR_STATE, "bf_psr_collect: no dump is pending");
     ON_DEVICE(p->h);
-    bf_psr::result_set& r = p->sets[p->n_collected % p->max_in_flight];
-    HIP_TRY(hipEventSynchronize(r.copied));
-    std::memcpy(profile, r.h_acc, p->n_prof * sizeof(double));
-    std::memcpy(hits, r.h_acc + p->n_prof * sizeof(double), p->n_hits * sizeof(uint64_t));
-    if (first_row) *first_row = r.first_row;
-    if (n_rows) *n_rows = r.n_rows;
-    p->n_collected++;   // (the set is free from here on)
+    const char* h_acc = nullptr;
+    uint64_t record[2];
+    if (int rc = p->acc.collect(&h_acc, record)) return rc;
+    std::memcpy(profile, h_acc, p->n_prof * sizeof(double));
+    std::memcpy(hits, h_acc + p->n_prof * sizeof(double), p->n_hits * sizeof(uint64_t));
+    if (first_row) *first_row = record[0];
+    if (n_rows) *n_rows = record[1];
     return BF_OK;
 }
 
-int bf_psr_pending(const bf_psr* p) { return p ? (int)(p->n_dump - p->n_collected) : fail(BF_ERR_INVALID, "the stage is NULL"); }
+int bf_psr_pending(const bf_psr* p) { return p ? p->acc.ring.pending() : fail(BF_ERR_INVALID, "the stage is NULL"); }
 
 // median of v[0 .. n) (n >= 1), which it sorts ascending
 static double median_sorted(std::vector<double>& v)

@@ -1,6 +1,6 @@
 // bf_rm.cpp -- Faraday synthesis of Stokes beams (include/dsabf.h: bf_rm_*; contract and measurements: docs/FARADAY.md).
 // The device code is csrc/rm/bf_rm.hip; this file checks the bounds, owns a stage's tables, orders the upload of a new table against
-// the kernels in flight, and holds the host helpers (lambda^2, resolution, table, RMSF, the fit of a peak record).
+// the kernels in flight (a bf_chain: bf_runtime_internal.h), and holds the host helpers (lambda^2, resolution, table, RMSF, the fit of a peak record).
 #include <cmath>
 #include <new>
 #include <vector>
@@ -16,9 +16,7 @@ struct bf_rm : bf_stage {
     float* h_table = nullptr;   // pinned: the table, then wn
     hipStream_t copy_q = nullptr;
     hipEvent_t uploaded = nullptr;               // end of the last upload: every kernel waits for it
-    hipEvent_t done_ev[2] = {nullptr, nullptr};
-    hipEvent_t done = nullptr;                   // fires when EVERY kernel issued so far has run (each joins the one before it)
-    uint64_t n_launch = 0;
+    bf_chain kernels;                            // its end fires when EVERY kernel issued so far has run (each joins the one before it)
 };
 
 static const double kLight = 0.299792458;   // m GHz
@@ -28,7 +26,7 @@ static int upload(bf_rm* s, const float* rot, const float* wn)
     const size_t floats = dsabf::rm_table_floats(s->n_chan, s->n_phi);
     dsabf::rm_permute_table_host(rot, s->n_chan, s->n_phi, s->h_table);
     for (int c = 0; c < s->n_chan; c++) s->h_table[floats + c] = wn[c];
-    if (s->done) HIP_TRY(hipStreamWaitEvent(s->copy_q, s->done, 0));
+    HIP_TRY(s->kernels.wait(s->copy_q));
     HIP_TRY(hipMemcpyAsync(s->d_table, s->h_table, floats * sizeof(float), hipMemcpyHostToDevice, s->copy_q));
     HIP_TRY(hipMemcpyAsync(s->d_wn, s->h_table + floats, (size_t)s->n_chan * sizeof(float), hipMemcpyHostToDevice, s->copy_q));
     HIP_TRY(hipEventRecord(s->uploaded, s->copy_q));
@@ -177,7 +175,7 @@ int bf_rm_create(bf_handle* h, int n_chan, int n_phi, const float* rot, const fl
     res.host(&s->h_table, (floats + n_chan) * sizeof(float));
     res.queue(&s->copy_q);
     res.event(&s->uploaded);
-    for (auto& ev : s->done_ev) res.event(&ev);
+    s->kernels.create(res);
     if (int rc = stage_adopt(s, "bf_rm_create")) return rc;
     if (int rc = upload(s, rot, wn)) {
         stage_destroy(s);
@@ -213,11 +211,8 @@ int bf_rm_device(bf_rm* s, const void* d_stokes, int K, int64_t n_rows, const vo
     HIP_TRY(hipStreamWaitEvent(q, s->uploaded, 0));
     dsabf::RmLaunch l = {d_stokes, d_base, s->d_table, s->d_wn, d_spec, d_peaks, s->n_chan, s->n_phi, K, (int)n_rows};
     HIP_TRY(dsabf::launch_rm(l, q));
-    // one event for all launches: behind this kernel the queue joins the launch before it (the kernel itself is not held up)
-    if (s->done) HIP_TRY(hipStreamWaitEvent(q, s->done, 0));
-    hipEvent_t ev = s->done_ev[s->n_launch++ % 2];
-    HIP_TRY(hipEventRecord(ev, q));
-    s->done = ev;
+    // one chain for all launches: behind this kernel the queue joins the launch before it (the kernel itself is not held up)
+    HIP_TRY(s->kernels.join(q));
     return BF_OK;
 }
 

@@ -1,6 +1,7 @@
 // bf_runtime_internal.h -- what the C-ABI runtime's translation units share (bf_runtime.cpp, bf_queues.cpp, bf_dm_stream.cpp,
 // bf_sps.cpp, bf_cond.cpp, bf_accum.cpp, bf_corr.cpp, bf_sk.cpp, bf_stokes.cpp, bf_psr.cpp, bf_ffa.cpp, bf_inj.cpp, bf_evt.cpp, bf_vhist.cpp, bf_cdd.cpp, bf_rm.cpp, bf_bench_abi.cpp): the handle, the base of its stages,
-// the accumulator stage under the correlator and the voltage moments, the error string, the device scope.
+// the event chain and the ring of result sets that order the stages' work (bf_chain, bf_result_ring), the snapshot-and-zero accumulator on
+// top of both (bf_accumulator) and the accumulator stage under the correlator and the voltage moments, the error string, the device scope.
 // Host-only and not installed: no .hip / .hpp file includes it.
 #pragma once
 #include "../../include/dsabf.h"
@@ -117,6 +118,81 @@ struct bf_stage {
     virtual void attached() {}                          // a DM stage has just become the feeder
 };
 
+// The event chain: an operation on memory that a stage shares waits for the one before it, whatever queue that came on, and then is
+// the new end of the chain.  Two events take turns, so the event being recorded is never the one the queue has just been told to wait
+// for.  A push is wait(q), kernel, extend(q); a kernel that must not be held up is kernel, join(q).
+struct bf_chain {
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    hipEvent_t end = nullptr;          // behind the most recent link (hipEventSynchronize on it: everything so far has run); NULL: the chain is empty
+    uint64_t n = 0;                    // links recorded on `ev`
+    void create(bf_resources& res) { for (auto& e : ev) res.event(&e); }
+    hipError_t wait(hipStream_t q) const { return end ? hipStreamWaitEvent(q, end, 0) : hipSuccess; }   // an empty chain holds nothing up
+    hipError_t extend(hipStream_t q)   // what q holds now is the new end
+    {
+        hipEvent_t e = ev[n++ % 2];
+        const hipError_t rc = hipEventRecord(e, q);
+        if (rc == hipSuccess) end = e;
+        return rc;
+    }
+    void adopt(hipEvent_t theirs) { end = theirs; }    // an event someone else has recorded (a result set's `copied`, behind a dump) is the new end
+    hipError_t join(hipStream_t q)     // behind what q holds now, q waits for the end and then is the end
+    {
+        const hipError_t rc = wait(q);
+        return rc == hipSuccess ? extend(q) : rc;
+    }
+};
+
+// The ring of result sets: issue j leaves its results in set j % max_in_flight, on the stage's own copy queue, and the sets are
+// collected oldest first.  `Set` is the stage's own and derives from bf_result_set; the ring makes the queue and the `copied` events,
+// the stage adds its buffers and further events per set.  The refusals ("... are uncollected", "no ... is pending") are the stage's words.
+struct bf_result_set {
+    hipEvent_t copied = nullptr;       // behind the set's last copy, on copy_q
+};
+template <class Set> struct bf_result_ring {
+    std::vector<Set> sets;
+    hipStream_t copy_q = nullptr;
+    int max_in_flight = 0;
+    uint64_t n_issued = 0, n_collected = 0;
+    void create(bf_resources& res, int max_in_flight_)
+    {
+        max_in_flight = max_in_flight_;
+        res.queue(&copy_q);
+        sets.resize((size_t)max_in_flight);
+        for (auto& r : sets) res.event(&r.copied);
+    }
+    int pending() const { return (int)(n_issued - n_collected); }
+    bool room(uint64_t n = 1) const { return n_issued - n_collected + n <= (uint64_t)max_in_flight; }
+    Set& next() { return sets[n_issued % (uint64_t)max_in_flight]; }            // the set the next issue uses
+    Set& newest() { return sets[(n_issued - 1) % (uint64_t)max_in_flight]; }    // the set before that one (n_issued > 0)
+    void issued() { n_issued++; }
+    Set& oldest() { return sets[n_collected % (uint64_t)max_in_flight]; }       // the oldest uncollected set (pending() > 0)
+    hipError_t wait_oldest()
+    {
+        Set& r = oldest();
+        return hipEventSynchronize(r.copied);
+    }
+    void collected() { n_collected++; }   // (the set is free from here on)
+};
+
+// The snapshot-and-zero accumulator under bf_accum_stage and the pulsar folder (bf_accum.cpp): bytes on the device that pushes add
+// to, the chain that orders the pushes and dumps, and the ring of pinned snapshots.  A push is the stage's own: chain.wait(q), its
+// kernel into d_acc, chain.extend(q).  The callers refuse a dump without room and a collect with nothing pending, in their own words.
+struct bf_accumulator {
+    char* d_acc = nullptr;             // the integration in progress: every push adds to it, a dump copies it out and zeroes it
+    size_t bytes = 0;
+    bf_chain chain;
+    struct snapshot : bf_result_set {
+        char* h_acc = nullptr;         // pinned
+        uint64_t record[2] = {0, 0};   // the caller's record of the integration
+    };
+    bf_result_ring<snapshot> ring;
+    void create(bf_resources& res, size_t bytes_, int max_in_flight);   // (zeroes d_acc: the create ends with res.device_sync())
+    // On copy_q (the dump never holds a caller's queue): behind the end of the chain, the copy out and the memset; the set's `copied` is the new end.
+    int dump(uint64_t record0, uint64_t record1 = 0);
+    // Waits for the oldest snapshot and frees its set: *h_acc and record[] are good until the next dump.
+    int collect(const char** h_acc, uint64_t record[2]);
+};
+
 // What differs between the two kinds of accumulator stage, the correlator (bf_corr.cpp) and the voltage moments (bf_sk.cpp).
 struct bf_accum_kind {
     const char* noun;                              // bf_stage::noun
@@ -127,27 +203,12 @@ struct bf_accum_kind {
     int (*launch)(bf_handle* h, const void* d_packed, int n_units, long long* d_acc, bool accumulate, hipStream_t q);
 };
 
-// The base of bf_corr and bf_sk (bf_accum.cpp): the accumulator, the chain of events that orders its pushes and dumps, the result sets.
+// The base of bf_corr and bf_sk (bf_accum.cpp): a bf_accumulator of two int64 per cell, pushed through its kind's launch.
 struct bf_accum_stage : bf_stage {
     const bf_accum_kind& kind;
     explicit bf_accum_stage(const bf_accum_kind& k) : bf_stage(k.noun), kind(k) {}
-    int max_in_flight = 0;
-    size_t n_int64 = 0;                // 2 * kind.entries
-    long long* d_acc = nullptr;        // the integration in progress: every push adds to it, a dump copies it out and zeroes it
+    bf_accumulator acc;                // two int64 per cell of kind.entries
     uint64_t columns = 0;              // columns per polarisation pushed since the last dump
-    // Pushes and dumps share d_acc, so each waits for the one before it, whatever queue that was issued on: `last` is the event
-    // behind the most recent kernel (push_done, two taking turns) or behind the most recent dump's copy and memset (its set's).
-    hipEvent_t push_done[2] = {nullptr, nullptr};
-    hipEvent_t last = nullptr;
-    uint64_t n_push = 0;
-    struct result_set {
-        long long* h_acc = nullptr;    // pinned
-        hipEvent_t copied = nullptr;
-        uint64_t columns = 0;
-    };
-    std::vector<result_set> sets;      // dump j leaves its snapshot in set j % max_in_flight
-    hipStream_t copy_q = nullptr;
-    uint64_t n_dump = 0, n_collected = 0;
 };
 
 // (hidden: shared by the runtime's translation units, not exported from libdsabf.so)

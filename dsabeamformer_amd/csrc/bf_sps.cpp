@@ -1,5 +1,6 @@
 // bf_sps.cpp -- single-pulse search behind the DM stage (include/dsabf.h: bf_sps_*; contract and measurements: docs/SINGLE_PULSE.md).
-// The device code is csrc/sps/bf_sps.hip; this file owns the stage's memory, orders its pushes and selects the candidates.
+// The device code is csrc/sps/bf_sps.hip; this file owns the stage's memory, orders its pushes (each behind the kernels of the one
+// before it), keeps the result sets (a bf_result_ring: bf_runtime_internal.h) and selects the candidates.
 #include <cmath>
 #include <cstring>
 #include <deque>
@@ -10,7 +11,7 @@
 
 struct bf_sps : bf_stage {
     bf_sps() : bf_stage("search stage") {}
-    int n_dm = 0, dm_first = 0, n_widths = 0, halo = 0, max_t = 0, max_in_flight = 0, baseline = 0, n_beams = 0;
+    int n_dm = 0, dm_first = 0, n_widths = 0, halo = 0, max_t = 0, baseline = 0, n_beams = 0;
     uint64_t min_samples = 0;
     double threshold = 0;
     // The last `halo` = 2^(K-1) - 1 samples of every (trial, beam), [n_dm][halo][n_beams], zeros where the stream had none yet.
@@ -18,18 +19,16 @@ struct bf_sps : bf_stage {
     float* d_tail[2] = {nullptr, nullptr};
     bf_sps_peak* d_part_peaks = nullptr;   // per-tile records of the push that is running (pushes run one after the other)
     bf_sps_stat* d_part_stats = nullptr;
-    // Push j leaves its records in set j % max_in_flight: on the device, then -- on the stage's own copy queue, so that the queue
+    // Push j = ring.n_issued leaves its records in set j % max_in_flight: on the device, then -- on the stage's own copy queue, so that the queue
     // the chunk came from goes on as soon as the kernels have read it -- in pinned host memory.
-    struct result_set {
+    struct result_set : bf_result_set {
         bf_sps_peak *d_peaks = nullptr, *h_peaks = nullptr;
         bf_sps_stat *d_stats = nullptr, *h_stats = nullptr;
-        hipEvent_t kernels_done = nullptr, copied = nullptr;
+        hipEvent_t kernels_done = nullptr;
         uint64_t first_t = 0;
         int n_t = 0;
     };
-    std::vector<result_set> sets;
-    hipStream_t copy_q = nullptr;
-    uint64_t n_push = 0, n_collected = 0;
+    bf_result_ring<result_set> ring;
     uint64_t seen = 0;                     // samples of the series in front of the next push
     // the push last collected (bf_sps_last_records) and the statistics of the last `baseline` collected pushes, oldest first
     std::vector<bf_sps_peak> last_peaks;
@@ -52,7 +51,7 @@ int dsabf::rt::sps_check_attach(const bf_sps* s, const bf_handle* h, int n_dm, i
     return BF_OK;
 }
 
-int dsabf::rt::sps_max_in_flight(const bf_sps* s) { return s->max_in_flight; }
+int dsabf::rt::sps_max_in_flight(const bf_sps* s) { return s->ring.max_in_flight; }
 
 extern "C" {
 
@@ -76,7 +75,6 @@ int bf_sps_create(bf_handle* h, int n_dm, int dm_first, int n_widths, int max_t_
     s->n_widths = n_widths;
     s->halo = dsabf::sps_halo(n_widths);
     s->max_t = max_t_per_push;
-    s->max_in_flight = max_in_flight;
     s->baseline = baseline_pushes;
     s->min_samples = (uint64_t)min_samples;
     s->threshold = threshold;
@@ -87,15 +85,13 @@ int bf_sps_create(bf_handle* h, int n_dm, int dm_first, int n_widths, int max_t_
     for (int k = 0; k < 2 && tail_bytes; k++) res.dev(&s->d_tail[k], tail_bytes, true);
     res.dev(&s->d_part_peaks, tiles * n_rec * sizeof(bf_sps_peak));
     res.dev(&s->d_part_stats, tiles * n_db * sizeof(bf_sps_stat));
-    res.queue(&s->copy_q);
-    s->sets.resize((size_t)max_in_flight);
-    for (auto& r : s->sets) {
+    s->ring.create(res, max_in_flight);
+    for (auto& r : s->ring.sets) {
         res.dev(&r.d_peaks, n_rec * sizeof(bf_sps_peak));
         res.dev(&r.d_stats, n_db * sizeof(bf_sps_stat));
         res.host(&r.h_peaks, n_rec * sizeof(bf_sps_peak));
         res.host(&r.h_stats, n_db * sizeof(bf_sps_stat));
         res.event(&r.kernels_done);
-        res.event(&r.copied);
     }
     res.device_sync();
     if (int rc = stage_adopt(s, "bf_sps_create")) return rc;
@@ -105,34 +101,35 @@ int bf_sps_create(bf_handle* h, int n_dm, int dm_first, int n_widths, int max_t_
 
 int bf_sps_destroy(bf_sps* s) { return stage_destroy(s); }
 
-int bf_sps_pending(const bf_sps* s) { return s ? (int)(s->n_push - s->n_collected) : BF_ERR_INVALID; }
+int bf_sps_pending(const bf_sps* s) { return s ? s->ring.pending() : BF_ERR_INVALID; }
 
 int bf_sps_push(bf_sps* s, const float* d_chunk, int n_t, uint64_t first_t, void* hip_stream)
 {
     if (!s || !d_chunk) return fail(BF_ERR_INVALID, "NULL argument");
     if (n_t <= 0 || n_t > s->max_t) return fail(BF_ERR_INVALID, "n_t must be 1 .. %d (max_t_per_push)", s->max_t);
     if (int rc = orphaned(s)) return rc;
-    if (s->n_push - s->n_collected >= (uint64_t)s->max_in_flight)
-        return fail(BF_ERR_STATE, "bf_sps_push: %d pushes are uncollected (max_in_flight): bf_sps_collect first", s->max_in_flight);
+    if (!s->ring.room())
+        return fail(BF_ERR_STATE, "bf_sps_push: %d pushes are uncollected (max_in_flight): bf_sps_collect first", s->ring.max_in_flight);
     bf_handle* h = s->h;
     ON_DEVICE(h);
     hipStream_t q = as_stream(hip_stream);
-    bf_sps::result_set& r = s->sets[s->n_push % s->max_in_flight];
+    const uint64_t j = s->ring.n_issued;
+    bf_sps::result_set& r = s->ring.next();
     // behind the kernels of the push before this one, whatever queue they ran on: they wrote the tail this one reads, and the
     // per-tile records are shared
-    if (s->n_push) HIP_TRY(hipStreamWaitEvent(q, s->sets[(s->n_push - 1) % s->max_in_flight].kernels_done, 0));
-    dsabf::SpsBuffers buf{s->d_tail[s->n_push % 2], s->d_tail[(s->n_push + 1) % 2], s->d_part_peaks, s->d_part_stats, r.d_peaks, r.d_stats};
+    if (j) HIP_TRY(hipStreamWaitEvent(q, s->ring.newest().kernels_done, 0));
+    dsabf::SpsBuffers buf{s->d_tail[j % 2], s->d_tail[(j + 1) % 2], s->d_part_peaks, s->d_part_stats, r.d_peaks, r.d_stats};
     HIP_TRY(dsabf::launch_sps_push(d_chunk, s->n_dm, n_t, s->n_beams, s->n_widths, s->seen, buf, q));
     HIP_TRY(hipEventRecord(r.kernels_done, q));
-    HIP_TRY(hipStreamWaitEvent(s->copy_q, r.kernels_done, 0));
+    HIP_TRY(hipStreamWaitEvent(s->ring.copy_q, r.kernels_done, 0));
     const size_t n_db = (size_t)s->n_dm * s->n_beams;
-    HIP_TRY(hipMemcpyAsync(r.h_peaks, r.d_peaks, s->n_widths * n_db * sizeof(bf_sps_peak), hipMemcpyDeviceToHost, s->copy_q));
-    HIP_TRY(hipMemcpyAsync(r.h_stats, r.d_stats, n_db * sizeof(bf_sps_stat), hipMemcpyDeviceToHost, s->copy_q));
-    HIP_TRY(hipEventRecord(r.copied, s->copy_q));
+    HIP_TRY(hipMemcpyAsync(r.h_peaks, r.d_peaks, s->n_widths * n_db * sizeof(bf_sps_peak), hipMemcpyDeviceToHost, s->ring.copy_q));
+    HIP_TRY(hipMemcpyAsync(r.h_stats, r.d_stats, n_db * sizeof(bf_sps_stat), hipMemcpyDeviceToHost, s->ring.copy_q));
+    HIP_TRY(hipEventRecord(r.copied, s->ring.copy_q));
     r.first_t = first_t;
     r.n_t = n_t;
     s->seen += (uint64_t)n_t;
-    s->n_push++;
+    s->ring.issued();
     return BF_OK;
 }
 
@@ -143,16 +140,16 @@ int bf_sps_collect(bf_sps* s, bf_sps_candidate* out, size_t max_out, size_t* n_o
     const size_t n_db = (size_t)s->n_dm * s->n_beams;
     if (max_out < n_db) return fail(BF_ERR_INVALID, "bf_sps_collect: room for %zu candidates, a push can give n_dm * n_beams = %zu", max_out, n_db);
     if (int rc = orphaned(s)) return rc;
-    if (s->n_collected == s->n_push) return fail(BF_ERR_STATE, "bf_sps_collect: no push is pending");
+    if (!s->ring.pending()) return fail(BF_ERR_STATE, "bf_sps_collect: no push is pending");
     bf_handle* h = s->h;
     ON_DEVICE(h);
-    bf_sps::result_set& r = s->sets[s->n_collected % s->max_in_flight];
-    HIP_TRY(hipEventSynchronize(r.copied));
+    HIP_TRY(s->ring.wait_oldest());
+    const bf_sps::result_set& r = s->ring.oldest();
     s->last_peaks.assign(r.h_peaks, r.h_peaks + s->n_widths * n_db);
     s->last_stats.assign(r.h_stats, r.h_stats + n_db);
     s->last_first_t = r.first_t;
     s->last_n_t = r.n_t;
-    s->n_collected++;   // (the set is free from here on)
+    s->ring.collected();
     s->window.emplace_back(r.n_t, s->last_stats);
     while (s->window.size() > (size_t)s->baseline) s->window.pop_front();
     uint64_t n = 0;

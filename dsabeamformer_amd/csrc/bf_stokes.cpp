@@ -1,6 +1,6 @@
 // bf_stokes.cpp -- full-Stokes follow-up beams (include/dsabf.h: bf_stokes_*; contract and measurements: docs/STOKES.md).  The device
-// code is csrc/stokes/bf_stokes.hip; this file checks the bounds, owns a stage's compact weights and result sets, and orders its weight
-// gathers, pushes and copies (the copy pattern is the correlator's dump: the caller's queue is held for the kernel only).
+// code is csrc/stokes/bf_stokes.hip; this file checks the bounds, owns a stage's compact weights and result sets (a bf_result_ring:
+// bf_runtime_internal.h), and orders its weight gathers, pushes and copies on two bf_chains (the caller's queue is held for the kernel only).
 #include <cstring>
 #include <new>
 
@@ -9,29 +9,22 @@
 
 struct bf_stokes : bf_stage {
     bf_stokes() : bf_stage("Stokes stage") {}
-    int n_int = 0, max_in_flight = 0;
+    int n_int = 0;
     int n_sel = 0;                     // 0: no weights yet
     int cap_sel = 0;                   // beams the result sets are sized for: the largest selection so far
     int8_t* d_w = nullptr;             // the compact weights (ONE copy: a gather waits for the pushes in flight, docs/STOKES.md section 2)
     int8_t* h_w = nullptr;             // pinned: where bf_stokes_set_weights builds them
     // Whatever writes d_w (a gather, an upload) waits for the write before it and for every kernel that may still read d_w, whichever
-    // queues those were issued on; whatever reads it waits for the last write.  Events alternate, as in bf_sk.
-    hipEvent_t gather_ev[2] = {nullptr, nullptr};
-    hipEvent_t gathered = nullptr;     // end of the last gather (an event never recorded holds nothing up): every later kernel waits for it
-    uint64_t n_gather = 0;
-    hipEvent_t direct_ev[2] = {nullptr, nullptr};
-    hipEvent_t direct_done = nullptr;  // fires when EVERY bf_stokes_device kernel issued so far has run (each joins the one before it)
-    uint64_t n_direct = 0;
-    struct result_set {
+    // queues those were issued on; whatever reads it waits for the last write.
+    bf_chain gathers;                  // the writes of d_w: every later kernel waits for its end
+    bf_chain direct;                   // its end fires when EVERY bf_stokes_device / _voltages_device kernel issued so far has run (each joins the one before it)
+    struct result_set : bf_result_set {
         long long* d_out = nullptr;    // n_gemms_per_block units of entries at cap_sel beams (allocated by the first set_weights)
         long long* h_out = nullptr;    // pinned, the same size
-        hipEvent_t computed = nullptr; // the kernel, on the caller's queue
-        hipEvent_t copied = nullptr;   // the D2H copy, on copy_q
+        hipEvent_t computed = nullptr; // the kernel, on the caller's queue (`copied`: the D2H copy)
         int n_units = 0, n_sel = 0;
     };
-    std::vector<result_set> sets;      // push j uses set j % max_in_flight
-    hipStream_t copy_q = nullptr;
-    uint64_t n_push = 0, n_collected = 0;
+    bf_result_ring<result_set> ring;   // one issue per push
 };
 
 static size_t entries(const bf_config& cfg, int n_sel, int n_int)
@@ -66,8 +59,8 @@ static int check_push(const bf_stokes* s, const void* d_packed, int n_units, con
     if (n_units > s->h->cfg.n_gemms_per_block)
         return fail(BF_ERR_INVALID, "%s: %d gemm-units; a result set holds the %d of a block", who, n_units, s->h->cfg.n_gemms_per_block);
     if (!s->n_sel) return fail(BF_ERR_STATE, "%s: bf_stokes_set_weights has not been called", who);
-    if (s->n_push - s->n_collected >= (uint64_t)s->max_in_flight)
-        return fail(BF_ERR_STATE, "%s: %d result sets are uncollected (max_in_flight): bf_stokes_collect first", who, s->max_in_flight);
+    if (!s->ring.room())
+        return fail(BF_ERR_STATE, "%s: %d result sets are uncollected (max_in_flight): bf_stokes_collect first", who, s->ring.max_in_flight);
     return BF_OK;
 }
 
@@ -82,17 +75,17 @@ static int launch(const bf_stokes* s, const void* d_packed, int n_units, long lo
 // One push, already checked: the kernel on the caller's queue behind the last gather, its copy on the stage's own queue.
 static int push_impl(bf_stokes* s, const void* d_packed, int n_units, hipStream_t q)
 {
-    bf_stokes::result_set& r = s->sets[s->n_push % s->max_in_flight];
-    HIP_TRY(hipStreamWaitEvent(q, s->gathered, 0));
+    bf_stokes::result_set& r = s->ring.next();
+    HIP_TRY(s->gathers.wait(q));
     if (int rc = launch(s, d_packed, n_units, r.d_out, q)) return rc;
     HIP_TRY(hipEventRecord(r.computed, q));
-    HIP_TRY(hipStreamWaitEvent(s->copy_q, r.computed, 0));
+    HIP_TRY(hipStreamWaitEvent(s->ring.copy_q, r.computed, 0));
     const size_t bytes = (size_t)n_units * entries(s->h->cfg, s->n_sel, s->n_int) * 4 * sizeof(long long);
-    HIP_TRY(hipMemcpyAsync(r.h_out, r.d_out, bytes, hipMemcpyDeviceToHost, s->copy_q));
-    HIP_TRY(hipEventRecord(r.copied, s->copy_q));
+    HIP_TRY(hipMemcpyAsync(r.h_out, r.d_out, bytes, hipMemcpyDeviceToHost, s->ring.copy_q));
+    HIP_TRY(hipEventRecord(r.copied, s->ring.copy_q));
     r.n_units = n_units;
     r.n_sel = s->n_sel;
-    s->n_push++;
+    s->ring.issued();
     return BF_OK;
 }
 
@@ -100,18 +93,23 @@ static int push_impl(bf_stokes* s, const void* d_packed, int n_units, hipStream_
 // bf_stokes_device launches' (an event never recorded, or long fired, holds nothing up).
 static int wait_for_weight_users(bf_stokes* s, hipStream_t q)
 {
-    HIP_TRY(hipStreamWaitEvent(q, s->gathered, 0));
-    for (auto& r : s->sets) HIP_TRY(hipStreamWaitEvent(q, r.computed, 0));
-    if (s->direct_done) HIP_TRY(hipStreamWaitEvent(q, s->direct_done, 0));
+    HIP_TRY(s->gathers.wait(q));
+    for (auto& r : s->ring.sets) HIP_TRY(hipStreamWaitEvent(q, r.computed, 0));
+    HIP_TRY(s->direct.wait(q));
+    return BF_OK;
+}
+
+// The tail of the two direct entry points, behind their kernel (which is not held up): q joins the direct launch before it.
+static int direct_launched(bf_stokes* s, hipStream_t q)
+{
+    HIP_TRY(s->direct.join(q));
     return BF_OK;
 }
 
 // The write of the weights just queued on `q` is the new last one.
 static int weights_written(bf_stokes* s, hipStream_t q, int n_sel)
 {
-    hipEvent_t ev = s->gather_ev[++s->n_gather % 2];
-    HIP_TRY(hipEventRecord(ev, q));
-    s->gathered = ev;
+    HIP_TRY(s->gathers.extend(q));
     s->n_sel = n_sel;
     return BF_OK;
 }
@@ -121,9 +119,9 @@ static int weights_written(bf_stokes* s, hipStream_t q, int n_sel)
 static int ensure_sets(bf_stokes* s, int n_sel, const char* who)
 {
     if (n_sel <= s->cap_sel) return BF_OK;
-    if (s->n_push != s->n_collected)
+    if (s->ring.pending())
         return fail(BF_ERR_STATE, "%s: %d beams are more than any selection before (%d), so the result sets grow: collect the %d pending ones first", who,
-                    n_sel, s->cap_sel, (int)(s->n_push - s->n_collected));
+                    n_sel, s->cap_sel, s->ring.pending());
     bf_resources& res = s->res;
     auto drop = [](std::vector<void*>& list, void* p) {
         for (size_t i = 0; i < list.size(); i++)
@@ -134,13 +132,13 @@ static int ensure_sets(bf_stokes* s, int n_sel, const char* who)
         return false;
     };
     s->cap_sel = 0;
-    for (auto& r : s->sets) {   // (nothing is pending: every kernel and copy into them has run)
+    for (auto& r : s->ring.sets) {   // (nothing is pending: every kernel and copy into them has run)
         if (r.d_out && drop(res.device, r.d_out)) (void)hipFree(r.d_out);
         if (r.h_out && drop(res.pinned, r.h_out)) (void)hipHostFree(r.h_out);
         r.d_out = r.h_out = nullptr;
     }
     const size_t bytes = (size_t)s->h->cfg.n_gemms_per_block * entries(s->h->cfg, n_sel, s->n_int) * 4 * sizeof(long long);
-    for (auto& r : s->sets) {
+    for (auto& r : s->ring.sets) {
         res.dev(&r.d_out, bytes);
         res.host(&r.h_out, bytes);
     }
@@ -176,20 +174,14 @@ int bf_stokes_create(bf_handle* h, int n_int, int max_in_flight, bf_stokes** out
     if (!s) return fail(BF_ERR_DEVICE, "out of host memory");
     s->h = h;
     s->n_int = n_int;
-    s->max_in_flight = max_in_flight;
     const size_t w_bytes = dsabf::stokes_weight_bytes(h->cfg.n_ant, h->cfg.n_freq);
     bf_resources& res = s->res;
     res.dev(&s->d_w, w_bytes);
     res.host(&s->h_w, w_bytes);
-    for (auto& ev : s->gather_ev) res.event(&ev);
-    for (auto& ev : s->direct_ev) res.event(&ev);
-    s->gathered = s->gather_ev[0];
-    res.queue(&s->copy_q);
-    s->sets.resize((size_t)max_in_flight);
-    for (auto& r : s->sets) {
-        res.event(&r.computed);
-        res.event(&r.copied);
-    }
+    s->gathers.create(res);
+    s->direct.create(res);
+    s->ring.create(res, max_in_flight);
+    for (auto& r : s->ring.sets) res.event(&r.computed);
     if (int rc = stage_adopt(s, "bf_stokes_create")) return rc;
     *out = s;
     return BF_OK;
@@ -197,7 +189,7 @@ int bf_stokes_create(bf_handle* h, int n_int, int max_in_flight, bf_stokes** out
 
 int bf_stokes_destroy(bf_stokes* s) { return stage_destroy(s); }
 
-int bf_stokes_pending(const bf_stokes* s) { return s ? (int)(s->n_push - s->n_collected) : fail(BF_ERR_INVALID, "the stage is NULL"); }
+int bf_stokes_pending(const bf_stokes* s) { return s ? s->ring.pending() : fail(BF_ERR_INVALID, "the stage is NULL"); }
 
 int bf_stokes_set_weights(bf_stokes* s, const int8_t* w_host, const int* beams, int n_sel)
 {
@@ -209,10 +201,10 @@ int bf_stokes_set_weights(bf_stokes* s, const int8_t* w_host, const int* beams, 
     if (int rc = ensure_sets(s, n_sel, "bf_stokes_set_weights")) return rc;
     // (h_w is free: this call returns only after its copy has run)
     dsabf::stokes_gather_host(w_host, beams, n_sel, cfg.n_ant, cfg.n_freq, cfg.n_beams, s->h_w);
-    if (int rc = wait_for_weight_users(s, s->copy_q)) return rc;
-    HIP_TRY(hipMemcpyAsync(s->d_w, s->h_w, dsabf::stokes_weight_bytes(cfg.n_ant, cfg.n_freq), hipMemcpyHostToDevice, s->copy_q));
-    if (int rc = weights_written(s, s->copy_q, n_sel)) return rc;
-    HIP_TRY(hipEventSynchronize(s->gathered));
+    if (int rc = wait_for_weight_users(s, s->ring.copy_q)) return rc;
+    HIP_TRY(hipMemcpyAsync(s->d_w, s->h_w, dsabf::stokes_weight_bytes(cfg.n_ant, cfg.n_freq), hipMemcpyHostToDevice, s->ring.copy_q));
+    if (int rc = weights_written(s, s->ring.copy_q, n_sel)) return rc;
+    HIP_TRY(hipEventSynchronize(s->gathers.end));
     return BF_OK;
 }
 
@@ -240,14 +232,9 @@ int bf_stokes_device(bf_stokes* s, const void* d_packed, int n_units, int64_t* d
     if (!s->n_sel) return fail(BF_ERR_STATE, "bf_stokes_device: bf_stokes_set_weights has not been called");
     ON_DEVICE(s->h);
     hipStream_t q = as_stream(hip_stream);
-    HIP_TRY(hipStreamWaitEvent(q, s->gathered, 0));
+    HIP_TRY(s->gathers.wait(q));
     if (int rc = launch(s, d_packed, n_units, (long long*)d_out, q)) return rc;
-    // one event for all of these launches: behind this kernel the queue joins the launch before it (the kernel itself is not held up)
-    if (s->direct_done) HIP_TRY(hipStreamWaitEvent(q, s->direct_done, 0));
-    hipEvent_t ev = s->direct_ev[s->n_direct++ % 2];
-    HIP_TRY(hipEventRecord(ev, q));
-    s->direct_done = ev;
-    return BF_OK;
+    return direct_launched(s, q);
 }
 
 size_t bf_stokes_voltage_entries(const bf_config* cfg, int n_sel)
@@ -271,13 +258,9 @@ int bf_stokes_voltages_device(bf_stokes* s, const void* d_packed, int n_units, v
     if (!s->n_sel) return fail(BF_ERR_STATE, "bf_stokes_voltages_device: bf_stokes_set_weights has not been called");
     ON_DEVICE(s->h);
     hipStream_t q = as_stream(hip_stream);
-    HIP_TRY(hipStreamWaitEvent(q, s->gathered, 0));
+    HIP_TRY(s->gathers.wait(q));
     HIP_TRY(dsabf::launch_stokes_voltages(cfg.n_ant, cfg.n_freq, S, s->n_sel, d_packed, n_units, s->d_w, (float*)d_out, s->h->n_cus, q));
-    if (s->direct_done) HIP_TRY(hipStreamWaitEvent(q, s->direct_done, 0));
-    hipEvent_t ev = s->direct_ev[s->n_direct++ % 2];
-    HIP_TRY(hipEventRecord(ev, q));
-    s->direct_done = ev;
-    return BF_OK;
+    return direct_launched(s, q);
 }
 
 int bf_stokes_push(bf_stokes* s, const void* d_packed, int n_units, void* hip_stream)
@@ -308,13 +291,13 @@ int bf_stokes_collect(bf_stokes* s, int64_t* out, int* n_units)
 {
     if (!s || !out) return fail(BF_ERR_INVALID, "NULL argument");
     if (int rc = orphaned(s)) return rc;
-    if (s->n_collected == s->n_push) return fail(BF_ERR_STATE, "bf_stokes_collect: no push is pending");
+    if (!s->ring.pending()) return fail(BF_ERR_STATE, "bf_stokes_collect: no push is pending");
     ON_DEVICE(s->h);
-    bf_stokes::result_set& r = s->sets[s->n_collected % s->max_in_flight];
-    HIP_TRY(hipEventSynchronize(r.copied));
+    HIP_TRY(s->ring.wait_oldest());
+    const bf_stokes::result_set& r = s->ring.oldest();
     std::memcpy(out, r.h_out, (size_t)r.n_units * entries(s->h->cfg, r.n_sel, s->n_int) * 4 * sizeof(long long));
     if (n_units) *n_units = r.n_units;
-    s->n_collected++;   // (the set is free from here on)
+    s->ring.collected();
     return BF_OK;
 }
 

@@ -168,7 +168,7 @@ def test_dump_in_mid_stream(torch, bfmod):
     folder = api.PulsarFolder(bf, n_f, 64, n_bins, models, delays, max_in_flight=2)
     with pytest.raises(bfmod.DsabfError) as e:
         folder.collect()
-    assert e.value.code == BF_ERR_STATE
+    assert e.value.code == BF_ERR_STATE and str(e.value) == "libdsabf error -4: bf_psr_collect: no dump is pending"
     cuts = cuts_of(split, SIZES)
     push_all(torch, folder, d_x, row_bytes, cuts, streams)
     folder.dump(streams[1].cuda_stream)
@@ -176,20 +176,58 @@ def test_dump_in_mid_stream(torch, bfmod):
     push_all(torch, folder, d_x, row_bytes, cuts2, streams[::-1])
     folder.dump(streams[0].cuda_stream)
     assert folder.pending == 2
-    with pytest.raises(bfmod.DsabfError, match="max_in_flight") as e:
+    with pytest.raises(bfmod.DsabfError) as e:
         folder.dump()
     assert e.value.code == BF_ERR_STATE
+    assert str(e.value) == "libdsabf error -4: bf_psr_dump: 2 dumps are uncollected (max_in_flight): bf_psr_collect first"
     for (want_prof, want_hits), first, n in zip(want, (0, split), (split, n_rows - split)):
         prof, hits, first_row, got_rows = folder.collect()
         assert (first_row, got_rows) == (first, n)
         assert np.array_equal(hits, want_hits) and np.array_equal(bits(prof), bits(want_prof))
     assert folder.pending == 0
-    with pytest.raises(bfmod.DsabfError, match="no dump is pending") as e:
+    with pytest.raises(bfmod.DsabfError) as e:
         folder.collect()
-    assert e.value.code == BF_ERR_STATE
+    assert e.value.code == BF_ERR_STATE and str(e.value) == "libdsabf error -4: bf_psr_collect: no dump is pending"
     folder.dump()                                       # an integration of no rows: zeros
     prof, hits, first_row, got_rows = folder.collect()
     assert (first_row, got_rows) == (n_rows, 0) and not hits.any() and not bits(prof).any()
+    folder.close()
+    bf.close()
+
+
+def test_a_refused_dump_queues_and_zeroes_nothing(torch, bfmod):
+    """max_in_flight 1 at the smallest shape of SHAPES (one pulsar, 2 bins, 1 channel, 4 beams): push, dump, and a second dump while the
+    first is uncollected is refused with the whole message; after the collect, the next rows pushed on ANOTHER queue, dumped and
+    collected are the oracle's fold of exactly those rows -- the refused dump copied nothing, zeroed nothing and did not move first_row."""
+    from dsabeamformer_amd import api
+
+    n_b, n_f, n_bins, n_rows, split = 4, 1, 2, 120, 71
+    rng = np.random.default_rng(53)
+    x = wide(rng, (n_rows, n_f, n_b))
+    models = models_for(1, n_bins, n_rows, "fast")
+    delays = np.zeros((1, n_f), np.int32)
+    want = [order_matters(x[:split], models, delays, n_bins, 0), order_matters(x[split:], models, delays, n_bins, split)]
+    bf = bfmod.Beamformer(bfmod.debug_config(n_beams=n_b, n_freq=8))
+    streams = [torch.cuda.Stream(), torch.cuda.Stream()]
+    d_x = torch.from_numpy(x).cuda()
+    torch.cuda.synchronize()
+    row_bytes = n_f * n_b * 4
+    folder = api.PulsarFolder(bf, n_f, 64, n_bins, models, delays, max_in_flight=1)
+    push_all(torch, folder, d_x, row_bytes, cuts_of(split, [64, 7]), streams[:1])
+    folder.dump()
+    with pytest.raises(bfmod.DsabfError) as e:
+        folder.dump()
+    assert e.value.code == BF_ERR_STATE and folder.pending == 1
+    assert str(e.value) == "libdsabf error -4: bf_psr_dump: 1 dumps are uncollected (max_in_flight): bf_psr_collect first"
+    prof, hits, first_row, got_rows = folder.collect()
+    assert (first_row, got_rows) == (0, split)
+    assert np.array_equal(hits, want[0][1]) and np.array_equal(bits(prof), bits(want[0][0]))
+    push_all(torch, folder, d_x, row_bytes, [(split + at, n) for at, n in cuts_of(n_rows - split, [33, 16])], streams[1:])
+    folder.dump()
+    prof, hits, first_row, got_rows = folder.collect()
+    assert (first_row, got_rows) == (split, n_rows - split) and int(hits.sum()) == (n_rows - split) * n_f
+    assert np.array_equal(hits, want[1][1]) and np.array_equal(bits(prof), bits(want[1][0]))
+    assert folder.pending == 0
     folder.close()
     bf.close()
 

@@ -237,6 +237,7 @@ def test_pushes_on_two_queues_without_synchronisation(torch, bfmod):
     with pytest.raises(bfmod.DsabfError) as e:
         stage.collect()
     assert e.value.code == BF_ERR_STATE and stage.pending == 0
+    assert str(e.value) == "libdsabf error -4: bf_sk_collect: no dump is pending"
     refused = 0
     for c in counts:
         if c is None:
@@ -244,6 +245,7 @@ def test_pushes_on_two_queues_without_synchronisation(torch, bfmod):
                 with pytest.raises(bfmod.DsabfError) as e:
                     stage.dump()
                 assert e.value.code == BF_ERR_STATE and stage.pending == 2
+                assert str(e.value) == "libdsabf error -4: bf_sk_dump: 2 dumps are uncollected (max_in_flight): bf_sk_collect first"
                 refused += 1
                 mom, n_columns = stage.collect()                                 # the oldest: make room, then dump
                 lo, hi = groups.pop(0)

@@ -197,9 +197,10 @@ def test_back_pressure_lifetime_and_detaching(torch, bfmod, fine_ladder):
     st = torch.cuda.Stream()
     sps.push(chunks[0], 30, 0, st.cuda_stream)
     sps.push(chunks[1], 30, 30, st.cuda_stream)
-    with pytest.raises(bfmod.DsabfError, match="uncollected") as e:
+    with pytest.raises(bfmod.DsabfError) as e:
         sps.push(chunks[2], 30, 60, st.cuda_stream)
     assert e.value.code == BF_ERR_STATE and sps.pending == 2
+    assert str(e.value) == "libdsabf error -4: bf_sps_push: 2 pushes are uncollected (max_in_flight): bf_sps_collect first"
     out = np.zeros(4, api._candidate_dtype())
     import ctypes as C
     n_out = C.c_size_t()
@@ -233,9 +234,11 @@ def test_back_pressure_lifetime_and_detaching(torch, bfmod, fine_ladder):
 
     assert push(32) == (0, 0) and small.pending == 0                                # nothing emitted yet: no search push
     assert push(32) == (0, 64 - D) and small.pending == 1
-    with pytest.raises(bfmod.DsabfError, match="uncollected") as e:
+    with pytest.raises(bfmod.DsabfError) as e:
         push(8)
     assert e.value.code == BF_ERR_STATE and pushed == 64
+    assert str(e.value) == ("libdsabf error -4: bf_dm_stream_push: the attached search stage has 1 uncollected pushes (max_in_flight): "
+                            "bf_sps_collect first")
     small.collect()
     assert push(8) == (64 - D, 8) and small.pending == 1
     small.collect()

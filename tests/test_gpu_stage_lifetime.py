@@ -214,7 +214,8 @@ def test_a_correlator_and_a_moments_stage_on_one_handle_keep_their_own_state(tor
         stage.push_block(1, 1, 0, n_u)
     with pytest.raises(bfmod.DsabfError) as e:
         corr.dump()
-    assert e.value.code == BF_ERR_STATE and "bf_corr_dump" in str(e.value) and "uncollected" in str(e.value), str(e.value)
+    assert e.value.code == BF_ERR_STATE, str(e.value)
+    assert str(e.value) == "libdsabf error -4: bf_corr_dump: 1 dumps are uncollected (max_in_flight): bf_corr_collect first"
     assert corr.pending == 1 and sk.pending == 0
     vis, n_columns = corr.collect()                                              # makes room for the correlator's second dump
     assert n_columns == cols and np.array_equal(vis, want_vis[0])

@@ -246,10 +246,11 @@ def test_refusals_launch_nothing(torch, bfmod):
     d_in, d_w = torch.from_numpy(packed).cuda(), torch.from_numpy(w).cuda()
     d_out = torch.full((5 * 8 * 3 * 16 * 4,), SENTINEL, dtype=torch.int64, device="cuda")
 
-    def refused(code, call):
+    def refused(code, call, msg=None):
         with pytest.raises(bfmod.DsabfError) as e:
             call()
         assert e.value.code == code, (e.value.code, str(e.value))
+        assert msg is None or str(e.value) == "libdsabf error %d: %s" % (code, msg), str(e.value)
 
     mono = bfmod.Beamformer(_cfg(bfmod, 64, 2, 4, n_pol=1))                      # n_pol != 2
     refused(BF_ERR_INVALID, lambda: api.StokesBeams(mono, 1))
@@ -274,12 +275,14 @@ def test_refusals_launch_nothing(torch, bfmod):
     refused(BF_ERR_INVALID, lambda: stage.compute(d_in, 0, d_out))
     refused(BF_ERR_INVALID, lambda: stage.compute(d_in.data_ptr() + 4, 1, d_out))
     refused(BF_ERR_INVALID, lambda: stage.compute(d_in, 1, d_out.data_ptr() + 8))
-    refused(BF_ERR_STATE, stage.collect)
+    refused(BF_ERR_STATE, stage.collect, "bf_stokes_collect: no push is pending")
     assert stage.pending == 0
     stage.push(d_in, 1)
     stage.push(d_in, 1)
-    refused(BF_ERR_STATE, lambda: stage.push(d_in, 1))                           # max_in_flight uncollected sets
-    refused(BF_ERR_STATE, lambda: stage.set_weights(w, [3, 1, 2]))               # more beams than before: the sets would grow under the pending ones
+    refused(BF_ERR_STATE, lambda: stage.push(d_in, 1),                           # max_in_flight uncollected sets
+            "bf_stokes_push: 2 result sets are uncollected (max_in_flight): bf_stokes_collect first")
+    refused(BF_ERR_STATE, lambda: stage.set_weights(w, [3, 1, 2]),               # more beams than before: the sets would grow under the pending ones
+            "bf_stokes_set_weights: 3 beams are more than any selection before (2), so the result sets grow: collect the 2 pending ones first")
     assert stage.pending == 2
     want = so.stokes(packed[:1], w, [3, 1], 2, so.geometry(cfg))
     for _ in range(2):
@@ -390,6 +393,7 @@ def test_pushes_on_two_queues_and_the_in_flight_limit(torch, bfmod):
             with pytest.raises(bfmod.DsabfError) as e:
                 stage.push(d_in.data_ptr() + at * per_unit, c, streams[k % 2].cuda_stream)
             assert e.value.code == BF_ERR_STATE and stage.pending == 2
+            assert str(e.value) == "libdsabf error -4: bf_stokes_push: 2 result sets are uncollected (max_in_flight): bf_stokes_collect first"
             refused += 1
             lo, hi = queued.pop(0)
             _compare(stage.collect(), want[lo:hi], (lo, hi))
